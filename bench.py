@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py - Mpixels/s of the fused remap on BASELINE.json's configs, with the roofline of its kernel.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c3|c5|c4shard|c5shard] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c3|c5|c4shard|c5shard] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up (plan, frame pool), warms up, times K steps, writes what the last step computed if --dump-outputs is
+given, and prints the line: metric, value (Mpx/s, wall clock over the K steps), ms_per_step and the config.  Everything
+else described below (per-launch HIP events, roofline, the other configs, CPU baseline, ...) runs only with --full.
 
 ``--gpus N`` with N > 1 and no RANK in the environment makes this script START the N ranks itself
 (``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...``) before
@@ -23,7 +27,7 @@ independent (frames shard, nothing pixel-sized crosses xGMI); the only collectiv
 parameter block from rank 0 and the barriers / max-reduce that bracket the timed region.  Rank 0 prints ONE
 JSON line.
 
-At N = 1 the line also carries ``configs``: c1, c3, c5, c4shard and c5shard measured in the SAME process right after the
+With --full, at N = 1 the line also carries ``configs``: c1, c3, c5, c4shard and c5shard measured in the SAME process right after the
 headline (plan, frame pool beyond the Infinity Cache, HIP-event timed launches, algorithmic / must-move bytes from the plan's own
 index map checked against the reference's figure), plus ``single_image_ms`` (a new geometry's warm plan + first frame) and
 ``faithful_kernel_ms`` (the float64 chain, what a deferred plan runs) for the headline config - so that one driver-run line shows
@@ -127,8 +131,16 @@ def parse_args():
     ap.add_argument("--no-live-traffic", action="store_true", help="roofline.traffic from the committed PMC pass (profiles/traffic_*.json) instead of two rocprofv3 --pmc child runs of this script")
     ap.add_argument("--flavour-probe", action="store_true", help="(child mode) print {plan_create_warm_ms, single_image_ms, faithful_kernel_ms} of --config for the math flavour this process loads (PB_MATH_FLAVOUR) and exit")
     ap.add_argument("--explain", action="store_true", help="also print the VERBOSE record (every figure with its workload text, timing protocol and notes) to stderr")
-    ap.add_argument("--detail", default=None, help="write the verbose record to this file (default: gpurun_out/bench_detail.json when gpurun_out/ exists)")
-    return ap.parse_args()
+    ap.add_argument("--detail", default=None, help="write the verbose record to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-launch HIP events and the roofline, the other configs, math flavours, host path, sharded "
+                         "workloads, CPU baseline, live PMC traffic (the --no-* options trim this); without it a run times the steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/*.npy (float32 / float64, a fixed seeded sample, at most 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -424,7 +436,7 @@ def live_traffic(args, batch, kernel_prefix, timeout_s=180):
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="pb_pmc_", dir="/tmp")
         cmd = [exe, "--kernel-trace", "--pmc", ctr, "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__), "--config", args.config,
-               "--sampling", args.sampling, "--batch", str(batch), "--steps", "12", "--warmup", "2", "--no-cpu-baseline", "--no-configs", "--no-events", "--no-live-traffic"]
+               "--sampling", args.sampling, "--batch", str(batch), "--steps", "12", "--warmup", "2"]  # (a plain run: the timed launches and nothing else)
         if args.budget:
             cmd += ["--budget", str(args.budget)]
         try:
@@ -730,12 +742,13 @@ def compact_line(full):
     c = full["config"]
     out["config"] = {"workload": c["workload"], "name": c["name"], "frames_per_launch": c["frames_per_launch"], "frames_resident_per_gpu": c["frames_resident_per_gpu"],
                      "streams": c["streams"], "sampling": c["sampling"].split(",")[0].split(" ")[0], "parallelism": f"dp{full['n_gpus']}"}
-    r = full["roofline"]
-    out["roofline"] = {k: r[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "copy_ceiling_gbs", "frac_of_copy_ceiling", "algorithmic_bytes_per_launch",
-                                         "must_move_bytes_per_launch", "attainable_frac", "kernel_ms_mean", "kernel_ms_median", "kernel_ms_p10", "kernel_ms_p90", "window_budget")}
-    out["roofline"]["traffic_live"] = r.get("traffic_live", False)
-    if "frac_unamortised" in r:
-        out["roofline"]["frac_unamortised"] = {k: r["frac_unamortised"][k] for k in ("single_image", "faithful_kernel", "break_even_frames")}
+    r = full.get("roofline")  # (--full only)
+    if r:
+        out["roofline"] = {k: r[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "copy_ceiling_gbs", "frac_of_copy_ceiling", "algorithmic_bytes_per_launch",
+                                             "must_move_bytes_per_launch", "attainable_frac", "kernel_ms_mean", "kernel_ms_median", "kernel_ms_p10", "kernel_ms_p90", "window_budget")}
+        out["roofline"]["traffic_live"] = r.get("traffic_live", False)
+        if "frac_unamortised" in r:
+            out["roofline"]["frac_unamortised"] = {k: r["frac_unamortised"][k] for k in ("single_image", "faithful_kernel", "break_even_frames")}
     for k in ("plan_create_ms", "plan_create_warm_ms", "plan_bilinear_prepare_ms", "first_frame_ms", "single_image_ms", "faithful_kernel_ms"):
         if k in full:
             out[k] = full[k]
@@ -803,6 +816,34 @@ def copy_ceiling_gbs(lib, nat, device, stream) -> float:
     lib.pb_event_destroy(e1)
     del a, b
     return 2 * n / (best * 1e-3) / 1e9
+
+
+DUMP_SAMPLES = 1 << 22  # values of the output sampled into output_sample.npy (float32; with its float64 index: 48 MB)
+DUMP_ROW_GROUPS = 1 << 18  # at most this many row sums (x 3 channels, float64: 6 MB), so the dump stays under 64 MB at any batch
+
+
+def dump_outputs(out_dir, out, device):
+    """--dump-outputs: what the last timed step handed back (`out`: the launch's uint8 frames, B x H x W x 3) as .npy files that two builds can
+    be compared by, from the same arguments:
+        output_sample.npy        float32, DUMP_SAMPLES values (every value when the output is smaller) at fixed positions drawn with seed 0
+        output_sample_index.npy  float64, those positions in the flattened output (sorted)
+        output_row_sums.npy      float64, R x 3: every output value summed along its row, per channel - R = B x H rows, or, past
+                                 DUMP_ROW_GROUPS rows, R groups of the same number of consecutive rows (each value counted once)"""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    flat = out.reshape(-1)
+    n = flat.numel()
+    idx = np.arange(n) if n <= DUMP_SAMPLES else np.unique(np.random.default_rng(0).integers(0, n, DUMP_SAMPLES))
+    vals = flat[torch.from_numpy(idx).to(device)].float().cpu().numpy()
+    rows = out.reshape(-1, out.shape[-2], out.shape[-1]).sum(dim=1, dtype=torch.float64)  # (B x H) x 3
+    group = -(-rows.shape[0] // DUMP_ROW_GROUPS)
+    if group > 1:
+        pad = (-rows.shape[0]) % group
+        rows = torch.cat([rows, rows.new_zeros(pad, rows.shape[1])]).reshape(-1, group, rows.shape[1]).sum(dim=1)
+    np.save(os.path.join(out_dir, "output_sample.npy"), vals)
+    np.save(os.path.join(out_dir, "output_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "output_row_sums.npy"), rows.cpu().numpy())
 
 
 def flavour_probe(args):
@@ -913,14 +954,13 @@ def main():
     torch.cuda.synchronize(device)
     plan_create_ms = (time.perf_counter() - t0) * 1e3  # cold: the first plan of the process also loads the code object
     warm_times = []
-    for _ in range(3):  # what every further geometry costs: thresholds, models, certification, tables - best of three like the other configs'
+    for _ in range(3 if args.full else 0):  # what every further geometry costs: thresholds, models, certification, tables - best of three like the other configs'
         t0 = time.perf_counter()  # (each destroyed before the next: from the second on its tables come out of the library's block cache)
         warm = nat.Plan(d, rots, s, budget=budget)
         torch.cuda.synchronize(device)
         warm_times.append((time.perf_counter() - t0) * 1e3)
         del warm
         torch.cuda.synchronize(device)
-    plan_create_warm_ms = min(warm_times)
     sh, sw, dh, dw = s.height, s.width, d.height, d.width
     mpx_per_frame = dh * dw / 1e6
 
@@ -954,15 +994,16 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(device)
 
-    torch.cuda.synchronize(device)
-    t0 = time.perf_counter()
-    step(0)
-    torch.cuda.synchronize(device)
-    first_frame_ms = (time.perf_counter() - t0) * 1e3
+    if args.full:
+        torch.cuda.synchronize(device)
+        t0 = time.perf_counter()
+        step(0)
+        torch.cuda.synchronize(device)
+        first_frame_ms = (time.perf_counter() - t0) * 1e3
     for k in range(args.warmup):
         step(k)
     K = args.steps
-    use_events = not args.no_events
+    use_events = args.full and not args.no_events
     ev = []
     # an event pair costs a few microseconds on the stream, so one pair brackets a GROUP of consecutive
     # launches (same stream, back to back): the kernel duration is still measured live inside the timed
@@ -990,6 +1031,9 @@ def main():
     torch.cuda.synchronize(device)
     dt = time.perf_counter() - t0
     sync_all()
+    if args.dump_outputs and rank == 0:
+        last = ((K - 1) % groups_in_pool) * batch
+        dump_outputs(args.dump_outputs, dsts[last : last + batch], device)
 
     t = torch.tensor([dt], dtype=torch.float64, device=coll_device)
     if dist.is_initialized():
@@ -1008,27 +1052,6 @@ def main():
     if rank == 0:
         frames_total = world * K * batch
         value = frames_total * mpx_per_frame / dt_max
-        launch_ms = float(np.mean(durs)) if durs else dt_max / K * 1e3
-        alg_frame, must_frame = byte_accounting(plan, (sh, sw), device)
-        pins = json.load(open(os.path.join(ROOT, "tests", "golden", "full.json")))
-        ref_alg = int(pins[cfg["pin"]]["algorithmic_bytes"])
-        if alg_frame != ref_alg:
-            raise SystemExit(f"bench.py: algorithmic bytes from the plan's index map ({alg_frame}) differ from the reference's ({ref_alg})")
-        if bilinear:  # four taps of 3 bytes per in-bounds sample instead of one (must-move: the same lines, give or take a rim)
-            alg_frame += 3 * ((alg_frame - 3 * dh * dw) // 3) * 3
-        alg_launch = alg_frame * batch
-        achieved = alg_launch / (launch_ms * 1e-3) / 1e9
-        ceiling = copy_ceiling_gbs(lib, nat, device, sts[0])
-        info = plan.info()
-        traffic, traffic_src = (None, "bilinear run: the committed PMC passes are the nearest kernel's") if bilinear else traffic_for(args.config, info)
-        if world == 1 and not args.no_live_traffic:
-            kern = ("pb_bilinear_double_hot_kernel" if cfg["src"][0] == "double" else "pb_bilinear_hot_kernel") if bilinear else ("pb_hot_double_kernel" if cfg["src"][0] == "double" else "pb_hot_win_kernel")
-            live, live_src = live_traffic(args, batch, kern)
-            if live is not None:
-                committed = traffic
-                traffic, traffic_src = live, live_src + (f"; committed pass (profiles/): {committed}" if committed else "")
-            else:
-                traffic_src = f"{traffic_src}; live pass failed: {live_src}"
         line = {
             "metric": "Mpixels/s remapped, 8K equirect->equidistant" if cfg["pin"] == "c2" else f"Mpixels/s remapped ({args.config})",
             "value": round(value, 1),
@@ -1052,7 +1075,31 @@ def main():
                 "parallelism": f"frames sharded over {world} GPU(s); RCCL broadcast of the parameter block only",
             },
             "plan_create_ms": round(plan_create_ms, 3),
-            "plan_create_warm_ms": round(plan_create_warm_ms, 3),
+        }
+    if rank == 0 and args.full:
+        launch_ms = float(np.mean(durs)) if durs else dt_max / K * 1e3
+        alg_frame, must_frame = byte_accounting(plan, (sh, sw), device)
+        pins = json.load(open(os.path.join(ROOT, "tests", "golden", "full.json")))
+        ref_alg = int(pins[cfg["pin"]]["algorithmic_bytes"])
+        if alg_frame != ref_alg:
+            raise SystemExit(f"bench.py: algorithmic bytes from the plan's index map ({alg_frame}) differ from the reference's ({ref_alg})")
+        if bilinear:  # four taps of 3 bytes per in-bounds sample instead of one (must-move: the same lines, give or take a rim)
+            alg_frame += 3 * ((alg_frame - 3 * dh * dw) // 3) * 3
+        alg_launch = alg_frame * batch
+        achieved = alg_launch / (launch_ms * 1e-3) / 1e9
+        ceiling = copy_ceiling_gbs(lib, nat, device, sts[0])
+        info = plan.info()
+        traffic, traffic_src = (None, "bilinear run: the committed PMC passes are the nearest kernel's") if bilinear else traffic_for(args.config, info)
+        if world == 1 and not args.no_live_traffic:
+            kern = ("pb_bilinear_double_hot_kernel" if cfg["src"][0] == "double" else "pb_bilinear_hot_kernel") if bilinear else ("pb_hot_double_kernel" if cfg["src"][0] == "double" else "pb_hot_win_kernel")
+            live, live_src = live_traffic(args, batch, kern)
+            if live is not None:
+                committed = traffic
+                traffic, traffic_src = live, live_src + (f"; committed pass (profiles/): {committed}" if committed else "")
+            else:
+                traffic_src = f"{traffic_src}; live pass failed: {live_src}"
+        line.update({
+            "plan_create_warm_ms": round(min(warm_times), 3),
             "plan_timing": {k: round(v, 3) for k, v in plan.timing().items()},
             "first_frame_ms": round(first_frame_ms, 3),
             "roofline": {
@@ -1079,10 +1126,11 @@ def main():
                 "window_budget": info["window_budget"],
                 "plan": info,
             },
-        }
+        })
+    if rank == 0:
         line["ranks_seen"] = dist.get_world_size() if dist.is_initialized() else 1
         line["collective_backend"] = (dist.get_backend() if dist.is_initialized() else None)
-        if world == 1 and not bilinear and not args.no_configs and args.config == "c2":
+        if args.full and world == 1 and not bilinear and not args.no_configs and args.config == "c2":
             # the other BASELINE configs, same process, same box, seconds: one driver-run line shows every kernel
             try:
                 line["graph_replay_ms_per_frame"] = round(graph_replay_ms(lib, nat, plan, srcs, dsts, sbytes, dbytes, pool, device), 5)
@@ -1134,7 +1182,7 @@ def main():
     # with shard_range, 8 frames per launch; aggregate Mpx/s over all ranks; every rank's first output frame is re-made by rank 0
     # from the same frame index and must be byte-identical (SURVEY 8 e's acceptance check)
     sharded = None
-    if not bilinear and not args.no_configs and args.config == "c2":
+    if args.full and not bilinear and not args.no_configs and args.config == "c2":
         import hashlib
 
         try:
@@ -1186,20 +1234,19 @@ def main():
             sharded["collective_backend"] = dist.get_backend() if dist.is_initialized() else None
             sharded["collective"] = "one broadcast of the 90-double parameter block per workload (RCCL when the backend is nccl); no pixel crosses a link"
             line["sharded"] = sharded
-        if world == 1 and not args.no_cpu_baseline and not bilinear:  # (the CPU leg times the reference's nearest sampler)
+        if args.full and world == 1 and not args.no_cpu_baseline and not bilinear:  # (the CPU leg times the reference's nearest sampler)
             if numa_cpus and cpus_as_found:
                 os.sched_setaffinity(0, cpus_as_found)  # (the CPU legs run where the host would have put them: the pin is the GPU path's)
             line["cpu_baseline"] = cpu_baseline(cfg, mpx_per_frame)
             extra = cpu_baseline_all_cores(args.config, mpx_per_frame)
             if extra:
                 line["cpu_baseline"]["all_cores"] = extra
-        detail = args.detail or (os.path.join(ROOT, "gpurun_out", "bench_detail.json") if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else None)
-        if detail:
+        if args.detail:
             try:
-                with open(detail, "w") as fh:
+                with open(args.detail, "w") as fh:
                     json.dump(line, fh, indent=1)
             except OSError as exc:
-                print(f"bench.py: could not write {detail}: {exc}", file=sys.stderr)
+                print(f"bench.py: could not write {args.detail}: {exc}", file=sys.stderr)
         if args.explain:
             print(json.dumps(line), file=sys.stderr, flush=True)
         text = json.dumps(compact_line(line), separators=(",", ":"))

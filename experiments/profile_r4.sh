@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_r4; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 run() {  # tag, bench args...
   tag=$1; shift
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw_${tag}_stats -- python3 $R/bench.py "$@" --steps 60 --warmup 10 --no-cpu-baseline --no-configs > $O/${tag}_bench.json 2> $O/${tag}_stats.err || return 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw_${tag}_stats -- python3 $R/bench.py --full "$@" --steps 60 --warmup 10 --no-cpu-baseline --no-configs > $O/${tag}_bench.json 2> $O/${tag}_stats.err || return 1
   cp $(ls $O/raw_${tag}_stats/*/*kernel_stats.csv | head -1) $O/${tag}_kernel_stats.csv
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/raw_${tag}_$c -- python3 $R/bench.py "$@" --steps 12 --warmup 2 --no-cpu-baseline --no-configs --no-events > /dev/null 2> $O/${tag}_$c.err || return 1

@@ -6,9 +6,9 @@ export PB_LIB_PATH=$R/build/libphotonbend_hip_diag.so
 for rep in 1 2 3; do
   for c in c3 c1; do
     for k in 0 1; do
-      l=$(PB_XCD_BY_SRC=$k timeout -k 10 120 python3 bench.py --config $c --steps 80 --warmup 10 --no-cpu-baseline --no-configs 2>>$O/err.log | tail -1)
+      l=$(PB_XCD_BY_SRC=$k timeout -k 10 120 python3 bench.py --full --config $c --steps 80 --warmup 10 --no-cpu-baseline --no-configs 2>>$O/err.log | tail -1)
       echo "time $c by_src=$k $(echo "$l" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["roofline"]["kernel_ms_per_frame"])')" | tee -a $O/xcd.log
-      l=$(PB_XCD_BY_SRC=$k timeout -k 10 120 python3 bench.py --config $c --batch 8 --steps 40 --warmup 5 --no-cpu-baseline --no-configs 2>>$O/err.log | tail -1)
+      l=$(PB_XCD_BY_SRC=$k timeout -k 10 120 python3 bench.py --full --config $c --batch 8 --steps 40 --warmup 5 --no-cpu-baseline --no-configs 2>>$O/err.log | tail -1)
       echo "time8 $c by_src=$k $(echo "$l" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["roofline"]["kernel_ms_per_frame"])')" | tee -a $O/xcd.log
     done
   done

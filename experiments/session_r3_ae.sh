@@ -1,7 +1,7 @@
 #!/bin/bash
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r3ae; mkdir -p $O
 timeout -k 10 600 python -m pytest tests/test_hip_plan.py -x -q -m gpu > $O/tests.log 2>&1; echo "tests rc $?"; tail -2 $O/tests.log
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
 python - <<'PY'
 import json
 j = json.loads(open('gpurun_out/r3ae/bench.json').read().strip().splitlines()[-1])

@@ -3,8 +3,8 @@
 # launch-table error path), then the default bench line with its `configs` block, then bench under PB_FORCE_DIST=1 (RCCL, world 1)
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r3h; mkdir -p $O
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/tests.log 2>&1; echo "tests rc $?"; tail -4 $O/tests.log
-timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?"
-PB_FORCE_DIST=1 timeout -k 10 600 python bench.py --no-cpu-baseline --no-configs --steps 50 > $O/bench_rccl.json 2> $O/bench_rccl.err; echo "bench rccl rc $?"
+timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?"
+PB_FORCE_DIST=1 timeout -k 10 600 python bench.py --full --no-cpu-baseline --no-configs --steps 50 > $O/bench_rccl.json 2> $O/bench_rccl.err; echo "bench rccl rc $?"
 python - <<'PY'
 import json
 for f in ('bench_default','bench_rccl'):

@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r3i; mkdir -p $O
 timeout -k 10 900 python -m pytest tests -m gpu -x -q -s > $O/tests.log 2>&1; echo "tests rc $?"; tail -3 $O/tests.log
 grep -h "identity\|differ\|\[maps D_pano_chain\|\[maps C_alter\|\[maps D_photo_rot" $O/tests.log | cut -c1-230 | head -40
-timeout -k 10 600 python bench.py --no-cpu-baseline --steps 50 > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
+timeout -k 10 600 python bench.py --full --no-cpu-baseline --steps 50 > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
 python - <<'PY'
 import json
 j=json.loads(open('gpurun_out/r3i/bench.json').read().strip().splitlines()[-1])

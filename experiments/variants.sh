@@ -5,7 +5,7 @@ O=gpurun_out/$1; shift; mkdir -p $O
 for spec in "$@"; do
   set -- $spec; ex=$1; bud=$2; cfg=$3; shift 3
   tag=${cfg}_e${ex}_b${bud}$(echo "$*" | tr -d ' -')
-  PB_EXP=$ex timeout -k 10 200 python bench.py --config $cfg --budget $bud --steps 120 --warmup 10 --no-cpu-baseline "$@" > $O/$tag.json 2> $O/$tag.err || echo "FAILED $tag"
+  PB_EXP=$ex timeout -k 10 200 python bench.py --full --config $cfg --budget $bud --steps 120 --warmup 10 --no-cpu-baseline "$@" > $O/$tag.json 2> $O/$tag.err || echo "FAILED $tag"
   python3 - <<PY
 import json
 try:

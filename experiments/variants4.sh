@@ -5,7 +5,7 @@ O=gpurun_out/$1; shift; mkdir -p $O
 for spec in "$@"; do
   set -- $spec; envs=$1; bud=$2; cfg=$3; shift 3
   e2=${envs//\/root\/repo\/experiments\//}; tag=${cfg}_${e2//[,=.]/_}_b${bud}$(echo "$*" | tr -d ' -')
-  env $(echo $envs | tr ',' ' ') timeout -k 10 200 python bench.py --config $cfg --budget $bud --steps 120 --warmup 10 --no-cpu-baseline "$@" > $O/$tag.json 2> $O/$tag.err || echo "FAILED $tag"
+  env $(echo $envs | tr ',' ' ') timeout -k 10 200 python bench.py --full --config $cfg --budget $bud --steps 120 --warmup 10 --no-cpu-baseline "$@" > $O/$tag.json 2> $O/$tag.err || echo "FAILED $tag"
   python3 - <<PY
 import json
 try:

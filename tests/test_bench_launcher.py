@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 def _run(extra_env, gpus):
     env = dict(os.environ, PB_DIST_BACKEND="gloo", PB_SHARD_FRAMES="8", **extra_env)
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "8", "--warmup", "2", "--no-cpu-baseline"],
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--full"],
                           env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
 
 
