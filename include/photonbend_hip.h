@@ -232,6 +232,30 @@ int pb_remap_u8v(const pb_plan* plan, const uint8_t* const* src_dev, uint8_t* co
 int pb_remap_bilinear_u8(const pb_plan* plan, const uint8_t* src_dev, uint8_t* dst_dev, int n_frames,
                          size_t src_frame_stride, size_t dst_frame_stride, void* stream);
 
+/* SUPERSAMPLED REMAPPING (ABI 5, additive).  Output pixel (i, j) is, per channel, the round-half-to-even mean of the n x n block
+ * S[n i : n i + n, n j : n j + n] of S = the remap of the n x destination: the same kind and lens with image (n H, n W) and, for a camera,
+ * magnitude n x (a double fisheye's magnitude = height / 2 scales by itself); n in {2, 4}, a power of two, so its f_distance is exactly
+ * n x f_distance.  In integers (N = n^2, k = log2 N): q = sum >> k, r = sum & (N - 1), out = q + (r > N/2 || (r == N/2 && (q & 1))).
+ *   pb_remap_ss_u8        `plan` is an ordinary plan of the n x destination (dimensions divisible by n); dst receives (H, W, 3) frames.
+ *                         interpolation: PB_INTERP_NEAREST (pb_remap_u8's samples) or PB_INTERP_BILINEAR (pb_remap_bilinear_u8's).  Prepared
+ *                         single-source plans in nearest mode (AUTO / FAST, 16-byte aligned frames) take the FUSED kernel: one launch per
+ *                         batch, the n x n blocks reduced in registers, only the H x W output stored.  Everything else (double-fisheye
+ *                         sources, bilinear mode, deferred plans, PB_MODE_FAITHFUL / PB_MODE_FAST_DIRECT, unaligned frames, PB_SS_GENERIC)
+ *                         takes the GENERIC path: frame by frame, the n x remap into `workspace_dev`, then pb_box_reduce.  Never allocates,
+ *                         never synchronises (graph-capture safe): the caller provides the workspace.
+ *   pb_remap_ss_workspace the workspace bytes a call needs: 0 when the fused kernel takes it (source pointer and stride - a packed frame's
+ *                         size when 0 - multiples of 16 bytes), else one n x frame.
+ *   pb_box_reduce         the generic kernel on its own: (n_frames, n height, n width, channels) samples of sample_bytes (1 or 2) bytes ->
+ *                         (n_frames, height, width, channels), tightly packed.
+ * n outside {2, 4}, indivisible dimensions and n x frames beyond the projection limit (n^2 h w < 2^29) are PB_ERR_INVALID. */
+#define PB_INTERP_NEAREST 0
+#define PB_INTERP_BILINEAR 1
+#define PB_SS_GENERIC 1u
+int pb_remap_ss_workspace(const pb_plan* plan, int n, int interpolation, unsigned flags, size_t* bytes);
+int pb_remap_ss_u8(const pb_plan* plan, int n, int interpolation, const uint8_t* src_dev, uint8_t* dst_dev, int n_frames, size_t src_frame_stride,
+                   size_t dst_frame_stride, void* workspace_dev, size_t workspace_bytes, unsigned flags, void* stream);
+int pb_box_reduce(const void* src_dev, void* dst_dev, int height, int width, int channels, int sample_bytes, int n, int n_frames, void* stream);
+
 /* Integer coordinate map: for camera / pano sources idx_dev is int32 [H*W], the
  * linear source pixel index (row * src_width + col) or -1 where the output is
  * black.  For a double source idx_dev is int32 [2][H*W] (left-eye index, then

@@ -41,6 +41,7 @@ class HostPipe:
         self._stage = []  # [pinned uint8 ndarray, Event or None]
         self._dev = OrderedDict()  # (slot, nbytes) -> DeviceArray
         self._ring = {}  # nbytes -> idle DeviceArrays of remap_frames
+        self._ws_idle = None  # the supersampled generic path's workspace between calls (at most one kept: the largest)
         self._k = 0
 
     # -- device buffers kept between calls (hipMalloc of a 100 MB frame costs about a millisecond) ------------------------
@@ -68,6 +69,22 @@ class HostPipe:
         idle.extend(bufs[: max(0, 4 - len(idle))])  # (at most four per size stay)
         for key in [k for k in self._ring if k != nbytes][1:]:  # (and two sizes)
             del self._ring[key]
+
+    # -- the supersampled generic path's workspace (one n x frame): checked out for one call, like the ring, so that a streamed batch
+    #    and a single frame of the same thread never share one; at most one idle buffer stays
+    def take_workspace(self, nbytes: int):
+        ws = self._ws_idle
+        if not nbytes:
+            return None
+        if ws is not None and ws.nbytes >= nbytes:
+            self._ws_idle = None
+            return ws
+        return DeviceArray((int(nbytes),), np.uint8)
+
+    def give_workspace(self, ws) -> None:
+        """Returns a workspace whose work has completed."""
+        if ws is not None and (self._ws_idle is None or ws.nbytes > self._ws_idle.nbytes):
+            self._ws_idle = ws
 
     def _staging(self):
         """The next page-locked staging chunk, free of its previous DMA."""
@@ -124,32 +141,56 @@ def pipe_for(device: int | None = None) -> HostPipe:
     return p
 
 
-def remap_ndarray(plan: nat.Plan, image: np.ndarray, interpolation: str = "nearest", device: int | None = None) -> np.ndarray:
-    """One frame: uint8 (h, w, 3) ndarray -> fresh uint8 (H, W, 3) ndarray (upload, ONE kernel launch, download)."""
+def _out_shape(plan, supersample: int) -> tuple:
+    """(H, W) of a result: the plan's destination, or its n x n block grid (Plan.out_shape) when supersampled."""
+    if nat.check_supersample(supersample) == 1:
+        return plan.dst.height, plan.dst.width
+    return plan.out_shape(supersample)
+
+
+def _ss_kw(supersample: int, ws=None) -> dict:
+    """Plan.launch's supersample arguments - passed only when supersampling, so that n = 1 is exactly the plain launch."""
+    return {} if supersample == 1 else {"supersample": supersample, "workspace": ws}
+
+
+def _ss_bytes(plan, supersample: int, interpolation: str, src_ptr: int) -> int:
+    return 0 if supersample == 1 else plan.supersample_workspace_bytes(supersample, interpolation, src_ptr=src_ptr)
+
+
+def remap_ndarray(plan: nat.Plan, image: np.ndarray, interpolation: str = "nearest", device: int | None = None, supersample: int = 1) -> np.ndarray:
+    """One frame: uint8 (h, w, 3) ndarray -> fresh uint8 (H, W, 3) ndarray (upload, ONE kernel launch, download).  ``supersample`` n: `plan`
+    is the n x destination's and the result (H / n, W / n, 3) holds the n x n block means (``Plan.launch``)."""
+    oh, ow = _out_shape(plan, supersample)
     nat.require_gpu()
     pipe = pipe_for(device)
     with nat.on_device(pipe.device):
         d_in = pipe.device_buffer("in", image.nbytes)
-        d_out = pipe.device_buffer("out", 3 * plan.dst.height * plan.dst.width)
+        d_out = pipe.device_buffer("out", 3 * oh * ow)
+        ws = pipe.take_workspace(_ss_bytes(plan, supersample, interpolation, d_in.data_ptr()))
         pipe.upload(image, d_in)
-        plan.launch(d_in.data_ptr(), d_out.data_ptr(), 1, pipe.stream.handle, interpolation)
-        out = pipe.download(d_out, (plan.dst.height, plan.dst.width, 3), np.uint8)
+        plan.launch(d_in.data_ptr(), d_out.data_ptr(), 1, pipe.stream.handle, interpolation, **_ss_kw(supersample, ws))
+        out = pipe.download(d_out, (oh, ow, 3), np.uint8)
         pipe.stream.sync()
+        pipe.give_workspace(ws)
     return out
 
 
-def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, interpolation: str = "nearest") -> Iterator[np.ndarray]:
+def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, interpolation: str = "nearest",
+                 supersample: int = 1) -> Iterator[np.ndarray]:
     """Streams host-resident frames through one plan: while frame k + 1 uploads on the H2D stream, the remap kernel of frame k stores its
     output over PCIe straight into frame k's result ndarray (page-locked, device-visible), through `depth` rotating device input
-    buffers.  Yields uint8 (H, W, 3) ndarrays in order (page-locked, recycled when dropped)."""
+    buffers.  Yields uint8 (H, W, 3) ndarrays in order (page-locked, recycled when dropped).  ``supersample`` n: `plan` is the n x
+    destination's, the results are (H / n, W / n, 3) block means - the fused kernel stores only those over PCIe."""
+    oh, ow = _out_shape(plan, supersample)
     nat.require_gpu()
     depth = max(2, int(depth))
     dev = nat.current_device()
     pipe = pipe_for(dev)
     sh = (plan.src.height, plan.src.width, 3)
-    dh = (plan.dst.height, plan.dst.width, 3)
+    dh = (oh, ow, 3)
     n_in = int(np.prod(sh))
     d_in = pipe.take_ring(n_in, depth)
+    ws = pipe.take_workspace(_ss_bytes(plan, supersample, interpolation, d_in[0].data_ptr()))  # (used in s_run's order, frame after frame)
     s_up, s_run = Stream(), Stream()
     uploaded = [Event() for _ in range(depth)]
     computed = [Event() for _ in range(depth)]
@@ -175,7 +216,7 @@ def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, i
             uploaded[slot].record(s_up)
             s_run.wait(uploaded[slot])
             out = results[slot] = PINNED.ndarray(dh, np.uint8)
-            plan.launch(d_in[slot].data_ptr(), out.ctypes.data, 1, s_run.handle, interpolation)
+            plan.launch(d_in[slot].data_ptr(), out.ctypes.data, 1, s_run.handle, interpolation, **_ss_kw(supersample, ws))
             computed[slot].record(s_run)
             pending.append(slot)
             if direct and ahead is not None:
@@ -200,3 +241,4 @@ def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, i
         s_up.sync()
         s_run.sync()
         pipe.give_ring(n_in, d_in)
+        pipe.give_workspace(ws)

@@ -53,6 +53,11 @@ ABI_VERSION = 5
 PB_MAX_ROTATIONS = 8
 PLAN_DEFER, PLAN_TUNE, PLAN_MATH_SVML, PLAN_MATH_LIBM, PLAN_NO_BILINEAR, PLAN_BILINEAR = 1, 2, 4, 8, 16, 32
 MODE_AUTO, MODE_FAITHFUL, MODE_FAST, MODE_FAST_DIRECT = 0, 1, 2, 3
+INTERP_IDS = {"nearest": 0, "bilinear": 1}
+SS_GENERIC = 1  # pb_remap_ss_u8: force the generic path (tests, A/B measurement)
+SUPERSAMPLE_FACTORS = (1, 2, 4)
+# the largest map any pb_proj may describe (photonbend_hip.hip, pb_end_ok): h * w <= (2^31 - 1) / 4
+MAX_PROJ_PIXELS = 0x7FFFFFFF // 4
 KIND_CAMERA, KIND_DOUBLE, KIND_PANO = 0, 1, 2
 LENS_IDS = {
     "equidistant": 0,
@@ -113,6 +118,9 @@ SIGNATURES = {
     "pb_remap_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_u8v": (C.c_int, [_VP, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, _VP]),
     "pb_remap_bilinear_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
+    "pb_remap_ss_workspace": (C.c_int, [_VP, C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_size_t)]),
+    "pb_remap_ss_u8": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP, C.c_size_t, C.c_uint, _VP]),
+    "pb_box_reduce": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "pb_index_map_i32": (C.c_int, [_VP, _VP, _VP, _VP]),
     "pb_coordmap_f64": (C.c_int, [C.POINTER(pb_proj), _VP, _VP]),
     "pb_rotate_f64": (C.c_int, [C.POINTER(C.c_double), _VP, _VP, C.c_int, C.c_int, _VP]),
@@ -190,6 +198,13 @@ def load() -> C.CDLL:
             MATH_FLAVOUR = theirs
         _lib = lib
     return _lib
+
+
+def check_supersample(n) -> int:
+    """The supersample factor as an int: 1 (off), 2 or 4 (n x n subsamples per output pixel); anything else is a ValueError.  Needs no GPU."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) not in SUPERSAMPLE_FACTORS:
+        raise ValueError(f"supersample must be one of {SUPERSAMPLE_FACTORS} (n x n subsamples per output pixel), got {n!r}")
+    return int(n)
 
 
 def check(status: int) -> None:
@@ -481,12 +496,58 @@ class Plan:
 
     # -- launches (device arrays in, device arrays out: CUDA tensors or DeviceArrays; on the current stream unless told otherwise)
     def launch(self, src_ptr: int, dst_ptr: int, n_frames: int = 1, stream: int | None = None, interpolation: str = "nearest",
-               src_stride: int = 0, dst_stride: int = 0) -> None:
-        """The raw call: n_frames frames at src_ptr / dst_ptr (device addresses, strides in bytes, 0 = packed) on `stream`."""
+               src_stride: int = 0, dst_stride: int = 0, supersample: int = 1, generic: bool = False, workspace=None) -> None:
+        """The raw call: n_frames frames at src_ptr / dst_ptr (device addresses, strides in bytes, 0 = packed) on `stream`.
+        ``supersample`` n in (2, 4): this plan is the n x destination's and each output frame is (H / n, W / n, 3), the n x n block
+        means (pb_remap_ss_u8; ``generic`` forces its generic path).  ``workspace``: a device array of at least
+        ``supersample_workspace_bytes(...)`` bytes the caller owns (allocate it outside a graph capture and keep it per stream); without
+        one, a call that needs it takes a temporary buffer - from PyTorch's stream-ordered allocator where torch is installed, else a
+        DeviceArray that is freed after the call (on a stream other than the default one the call then synchronises that stream)."""
+        n = check_supersample(supersample)
         if interpolation != "nearest":
             self.ensure_bilinear()
-        fn = load().pb_remap_u8 if interpolation == "nearest" else load().pb_remap_bilinear_u8
-        self._gated(fn, self._h, src_ptr, dst_ptr, int(n_frames), int(src_stride), int(dst_stride), current_stream() if stream is None else stream)
+        st = current_stream() if stream is None else stream
+        if n == 1:
+            fn = load().pb_remap_u8 if interpolation == "nearest" else load().pb_remap_bilinear_u8
+            self._gated(fn, self._h, src_ptr, dst_ptr, int(n_frames), int(src_stride), int(dst_stride), st)
+            return
+        interp, flags = INTERP_IDS[interpolation], (SS_GENERIC if generic else 0)
+        nbytes = self.supersample_workspace_bytes(n, interpolation, generic, src_ptr, src_stride)
+        args = (self._h, n, interp, src_ptr, dst_ptr, int(n_frames), int(src_stride), int(dst_stride))
+        if nbytes == 0:
+            self._gated(load().pb_remap_ss_u8, *args, None, 0, flags, st)
+        elif workspace is not None:
+            have = int(workspace.nbytes) if not is_tensor(workspace) else int(workspace.numel() * workspace.element_size())
+            if have < nbytes:
+                raise PbError(f"the supersample workspace holds {have} bytes, this call needs {nbytes}")
+            self._gated(load().pb_remap_ss_u8, *args, workspace.data_ptr(), have, flags, st)
+        else:
+            with _temporary_workspace(nbytes, st) as ws:
+                self._gated(load().pb_remap_ss_u8, *args, ws.data_ptr(), nbytes, flags, st)
+
+    def supersample_workspace_bytes(self, supersample: int, interpolation: str = "nearest", generic: bool = False, src_ptr: int = 0,
+                                    src_stride: int = 0) -> int:
+        """Device bytes a supersampled launch of this plan needs as workspace (pb_remap_ss_workspace): 0 when the fused kernel takes it,
+        else one n x frame.  ``src_ptr`` / ``src_stride``: the frames the call will pass (the fused kernel needs 16-byte aligned frames; a
+        packed frame's size is its stride)."""
+        n = check_supersample(supersample)
+        if n == 1:
+            return 0
+        if interpolation not in INTERP_IDS:
+            raise ValueError("interpolation must be 'nearest' or 'bilinear'")
+        need = C.c_size_t(0)
+        check(load().pb_remap_ss_workspace(self._h, n, INTERP_IDS[interpolation], SS_GENERIC if generic else 0, C.byref(need)))
+        nbytes = int(need.value)
+        if nbytes == 0 and (int(src_ptr) | (int(src_stride) or 3 * self.src.height * self.src.width)) & 15:
+            nbytes = 3 * self.dst.height * self.dst.width
+        return nbytes
+
+    def out_shape(self, supersample: int = 1) -> tuple:
+        """(H, W) of an output frame: the plan's destination, divided by the supersample factor."""
+        n = check_supersample(supersample)
+        if self.dst.height % n or self.dst.width % n:
+            raise ValueError(f"the plan's destination {self.dst.height} x {self.dst.width} is not divisible by supersample={n}")
+        return self.dst.height // n, self.dst.width // n
 
     def _gated(self, fn, *args) -> None:
         """One library call that launches this plan's kernels: through the gate while the plan's tables may still be rebuilt."""
@@ -500,11 +561,14 @@ class Plan:
         finally:
             g.leave()
 
-    def remap(self, src, out=None, interpolation: str = "nearest"):
+    def remap(self, src, out=None, interpolation: str = "nearest", supersample: int = 1, generic: bool = False, workspace=None):
         """src: uint8 device array (h, w, 3) or (N, h, w, 3) -> (H, W, 3) / (N, H, W, 3), of src's kind.
-        interpolation: "nearest" (the reference's truncating sample) or the opt-in "bilinear"."""
+        interpolation: "nearest" (the reference's truncating sample) or the opt-in "bilinear".
+        supersample: n in (2, 4) on a plan of the n x destination -> (H / n, W / n, 3) frames of n x n block means (see ``launch``)."""
         if interpolation not in ("nearest", "bilinear"):
             raise ValueError("interpolation must be 'nearest' or 'bilinear'")
+        ss = check_supersample(supersample)
+        oh, ow = self.out_shape(ss)
         require_gpu()
         if not is_device_array(src):
             raise PbError(f"source frames must be uint8 device arrays (CUDA tensors or DeviceArrays), got {type(src).__name__}")
@@ -516,7 +580,7 @@ class Plan:
         if not u8 or shp[-3:] != (self.src.height, self.src.width, 3) or len(shp) not in (3, 4):
             raise PbError(f"source frames must be uint8 cuda (N, {self.src.height}, {self.src.width}, 3), got {shp} {src.dtype}")
         s = src.contiguous() if tens else src
-        oshape = (n, self.dst.height, self.dst.width, 3)
+        oshape = (n, oh, ow, 3)
         if out is None:
             o = empty(oshape, np.uint8, like=s)
         else:
@@ -528,7 +592,7 @@ class Plan:
             if tens and (not o.is_cuda or o.device != s.device):
                 raise PbError(f"out must live on the source's device ({s.device}), got {o.device}")
         with _on(s):
-            self.launch(s.data_ptr(), o.data_ptr(), n, None, interpolation)
+            self.launch(s.data_ptr(), o.data_ptr(), n, None, interpolation, supersample=ss, generic=generic, workspace=workspace)
         if out is not None:
             return out
         return o if batched else o[0]
@@ -572,6 +636,63 @@ class Plan:
         with _on(idx):
             self._gated(load().pb_index_map_i32, self._h, idx.data_ptr(), w.data_ptr() if w is not None else None, current_stream())
         return (idx, w) if weights else idx
+
+
+_WS_NULL: dict = {}  # device -> DeviceArray: the default stream's workspace when torch is absent (one per device, grown on demand)
+_WS_LOCK = threading.Lock()
+
+
+@contextlib.contextmanager
+def _temporary_workspace(nbytes: int, stream: int):
+    """A workspace for ONE launch on `stream` that the caller did not provide.  With torch: a block of its caching allocator, allocated on
+    that stream - freed when the launch is queued, handed out again only to work ordered after it on the same stream (graph captures
+    allocate from their own pool).  Without torch: the default stream shares one buffer per device (its work is ordered); any other stream
+    gets a buffer of its own, released after the stream has drained."""
+    if torch is not None and torch.cuda.is_available():
+        cur = torch.cuda.current_stream()
+        ts = cur if int(cur.cuda_stream) == int(stream or 0) else (torch.cuda.ExternalStream(int(stream)) if stream else torch.cuda.default_stream())
+        with torch.cuda.stream(ts):
+            buf = torch.empty((int(nbytes),), dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
+        yield buf
+        return
+    if not stream:
+        dev = current_device()
+        with _WS_LOCK:
+            buf = _WS_NULL.get(dev)
+            if buf is None or buf.nbytes < nbytes:
+                _WS_NULL.pop(dev, None)
+                buf = _WS_NULL[dev] = DeviceArray((int(nbytes),), np.uint8)
+        yield buf
+        return
+    buf = DeviceArray((int(nbytes),), np.uint8)
+    try:
+        yield buf
+    finally:
+        check(load().pb_stream_sync(stream))
+        del buf
+
+
+def box_reduce(x, n: int):
+    """(n H, n W, *trailing) uint8 / uint16 device array -> (H, W, *trailing) of n x n block means, round half to even (pb_box_reduce)."""
+    require_gpu()
+    shp = tuple(int(v) for v in x.shape)
+    dt = np.dtype(torch_dtype_np(x.dtype)) if is_tensor(x) else np.dtype(x.dtype)
+    if dt not in (np.dtype(np.uint8), np.dtype(np.uint16)):
+        raise NotImplementedError(f"supersampling takes 8- or 16-bit unsigned samples, got {dt}")
+    if shp[0] % n or shp[1] % n:
+        raise ValueError(f"a ({shp[0]}, {shp[1]}) sample array is not divisible by supersample={n}")
+    H, W, tail = shp[0] // n, shp[1] // n, shp[2:]
+    channels = int(np.prod(tail, dtype=np.int64)) if tail else 1
+    if is_tensor(x):
+        x = x.contiguous()
+    out = empty((H, W) + tail, dt, like=x)
+    with _on(x):
+        check(load().pb_box_reduce(x.data_ptr(), out.data_ptr(), H, W, channels, dt.itemsize, int(n), 1, current_stream()))
+    return out
+
+
+def torch_dtype_np(tdt) -> np.dtype:
+    return torch.empty(0, dtype=tdt).numpy().dtype
 
 
 def make_proj(kind: int, height: int, width: int, lens: int = 0, fov: float = 0.0, magnitude: float = 0.0, f_distance: float = 0.0) -> pb_proj:

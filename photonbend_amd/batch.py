@@ -18,14 +18,17 @@ from . import _native as nat
 from .core.projection import _plan_for
 
 
-def plan_for(dst_image, rotations, src_image) -> nat.Plan:
-    """The plan of ``src_image.process_coordinate_map(rotations(dst_image.get_coordinate_map()))``.
-    ``rotations``: sequence of ``Rotation`` objects (or 3x3 matrices), applied in order."""
+def plan_for(dst_image, rotations, src_image, supersample: int = 1) -> nat.Plan:
+    """The plan of ``src_image.process_coordinate_map(rotations(dst_image.get_coordinate_map(supersample)))``.
+    ``rotations``: sequence of ``Rotation`` objects (or 3x3 matrices), applied in order.  ``supersample`` n: the plan of the n x
+    destination - pass the same n to ``remap_frames``."""
     mats = [getattr(r, "rotation_matrix", r) for r in rotations]
-    return _plan_for(dst_image._proj("dst"), mats, src_image._proj("src"))
+    return _plan_for(dst_image._proj_ss(nat.check_supersample(supersample)), mats, src_image._proj("src"))
 
 
-def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, interpolation: str = "nearest") -> Iterator[np.ndarray]:
+def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, interpolation: str = "nearest",
+                 supersample: int = 1) -> Iterator[np.ndarray]:
     """Remaps an iterable of uint8 (h, w, 3) ndarrays with ``plan``; yields uint8 (H, W, 3) ndarrays in order
-    (``_hostpipe.remap_frames``: upload stream + launch stream, page-locked results the kernel writes directly, no PyTorch)."""
-    return _hostpipe.remap_frames(plan, frames, depth, interpolation)
+    (``_hostpipe.remap_frames``: upload stream + launch stream, page-locked results the kernel writes directly, no PyTorch).
+    ``supersample`` n: ``plan`` came from ``plan_for(..., supersample=n)``; the frames are (H, W, 3) block means of its n x output."""
+    return _hostpipe.remap_frames(plan, frames, depth, interpolation, supersample)

@@ -11,6 +11,12 @@ The object still satisfies code that treats the map as an ndarray: ``shape``,
 GPU (pb_coordmap_f64 / pb_rotate_f64) and from then on the ndarray is the truth -
 an edited map is sampled through the materialised-map kernel
 (pb_sample_map_u8), never through a stale recipe.
+
+``get_coordinate_map(supersample=n)`` (n = 2, 4) gives the recipe of the n x
+destination (image n H x n W, camera magnitude n x); ``supersample`` tells
+``process_coordinate_map`` to return the n x n block means.  A lazy recipe keeps
+it through rotations and ``copy()``; a materialised map that leaves as a plain
+array does not - pass ``supersample=`` to ``process_coordinate_map`` with it.
 """
 
 from __future__ import annotations
@@ -23,17 +29,18 @@ from .. import _native as nat
 class CoordinateMap:
     __array_priority__ = 100
 
-    def __init__(self, dst_proj: nat.pb_proj, rotations=(), device=None):
+    def __init__(self, dst_proj: nat.pb_proj, rotations=(), device=None, supersample: int = 1):
         self._dst = dst_proj
+        self.supersample = nat.check_supersample(supersample)  # n x n samples per output pixel (dst_proj is the n x destination)
         self._rotations = [np.array(r, dtype=np.float64).reshape(3, 3) for r in rotations]
         self._device = device
         self._array = None
         self._zero_invalid = False  # a later stage zeroed invalid lat/lon "in place"
 
     @classmethod
-    def from_array(cls, dst_proj: nat.pb_proj, array: np.ndarray) -> "CoordinateMap":
+    def from_array(cls, dst_proj: nat.pb_proj, array: np.ndarray, supersample: int = 1) -> "CoordinateMap":
         """A map that is an ndarray from the start (a destination whose lens the host evaluated)."""
-        m = cls(dst_proj)
+        m = cls(dst_proj, supersample=supersample)
         m._array = np.ascontiguousarray(array, dtype=np.float64)
         return m
 
@@ -51,7 +58,7 @@ class CoordinateMap:
         return list(self._rotations)
 
     def rotated(self, matrix) -> "CoordinateMap":
-        return CoordinateMap(self._dst, self._rotations + [matrix], self._device)
+        return CoordinateMap(self._dst, self._rotations + [matrix], self._device, self.supersample)
 
     def note_invalid_zeroed(self) -> None:
         """Rotation.rotate_coordinate_map and PanoramaImage.process_coordinate_map
@@ -106,10 +113,11 @@ class CoordinateMap:
     def copy(self):
         if self._array is not None:
             return self._array.copy()
-        c = CoordinateMap(self._dst, self._rotations, self._device)
+        c = CoordinateMap(self._dst, self._rotations, self._device, self.supersample)
         c._zero_invalid = self._zero_invalid
         return c
 
     def __repr__(self):
         state = "lazy" if self.is_lazy else "materialised"
-        return f"<CoordinateMap {self.shape} {state}, {len(self._rotations)} rotation(s)>"
+        ss = f", supersample {self.supersample}" if self.supersample != 1 else ""
+        return f"<CoordinateMap {self.shape} {state}, {len(self._rotations)} rotation(s){ss}>"

@@ -294,14 +294,36 @@ class _GpuProjection:
     def _proj(self, role: str = "src") -> nat.pb_proj:  # pragma: no cover - overridden
         raise NotImplementedError
 
-    def get_coordinate_map(self) -> CoordinateMap:
+    def get_coordinate_map(self, supersample: int = 1) -> CoordinateMap:
         """This image's coordinate map, as a lazy recipe (see ``CoordinateMap``).  A destination whose lens is made
         of user callables gets a materialised map: ``reverse_function`` runs on the host over the exact radius mesh
-        (lens.py:48-64, projection.py:186-189), everything around it on the GPU."""
-        proj = self._proj("dst")
+        (lens.py:48-64, projection.py:186-189), everything around it on the GPU.
+
+        ``supersample`` n in (2, 4): the map of the n x destination (``_proj_ss``), marked so that ``process_coordinate_map``
+        returns the n x n block means at this image's size.  1 (the default) is the plain map."""
+        n = nat.check_supersample(supersample)
+        proj = self._proj_ss(n)
         if proj.kind != nat.KIND_PANO and proj.lens == nat.LENS_CUSTOM:
-            return CoordinateMap.from_array(proj, self._custom_coordinate_map(proj))
-        return CoordinateMap(proj)
+            return CoordinateMap.from_array(proj, self._custom_coordinate_map(proj), supersample=n)
+        return CoordinateMap(proj, supersample=n)
+
+    def _forward_half_fov(self) -> float:  # pragma: no cover - overridden by the camera classes
+        raise NotImplementedError
+
+    def _proj_ss(self, n: int) -> nat.pb_proj:
+        """The destination projection of the n x object: image (n H, n W) - a double fisheye's map width 2 (W // 2) scaled the same way -
+        and, for a camera, magnitude n x with f_distance recomputed as magnitude / forward(fov / 2) (n a power of two: exactly n x
+        f_distance).  Geometric scaling, not the CLI's size rules for an n x image (its "inscribed" magnitude would be n H / 2 - 0.5)."""
+        p = self._proj("dst")
+        if n == 1:
+            return p
+        if (n * p.height) * (n * p.width) > nat.MAX_PROJ_PIXELS:
+            raise ValueError(f"supersample={n} of a {p.height} x {p.width} destination is a {n * p.height} x {n * p.width} map: beyond the "
+                             f"projection limit of {nat.MAX_PROJ_PIXELS} pixels")
+        if p.kind == nat.KIND_PANO:
+            return nat.make_proj(p.kind, n * p.height, n * p.width)
+        mag = p.magnitude * n
+        return nat.make_proj(p.kind, n * p.height, n * p.width, p.lens, p.fov, mag, mag / self._forward_half_fov())
 
     # -- the sampling half, for everything the fused uint8 RGB kernel does not take ------------------------------
     def _source_distances(self, lat: np.ndarray):  # pragma: no cover - overridden by the camera classes
@@ -338,9 +360,14 @@ class _GpuProjection:
             return out.reshape(H, W, tail[0])
         return _typed(nat.gather_px(idx, img_bytes), tail, dt, H, W)
 
-    def process_coordinate_map(self, coordinate_map, interpolation: str = "nearest"):
+    def process_coordinate_map(self, coordinate_map, interpolation: str = "nearest", supersample=None):
         """Maps this image's pixels through ``coordinate_map`` and returns the new image
         (projection.py:197-245, :408-462, :515-547).
+
+        ``supersample``: None takes the map's own (``get_coordinate_map(supersample=n)``; 1 for a plain array or tensor); an explicit
+        n in (2, 4) declares that the map holds n x n samples per output pixel.  The result is then (map_H / n, map_W / n) + trailing:
+        per channel the round-half-to-even mean of each n x n block of what this call returns for the map at n = 1 (same side effects).
+        1 is exactly the plain call.
 
         uint8 (H, W, 3) images with built-in lenses take the fused kernel (one launch, no map in memory); any other
         image the reference accepts - grey (H, W), RGBA, 16-bit samples - and sources whose lens is made of user
@@ -350,6 +377,14 @@ class _GpuProjection:
         pixel).  A lazy map + a uint8 RGB image + built-in lenses take the tile kernels (one launch); a materialised or edited map, a
         grey / RGBA / 16-bit image or a Lens of user callables take the mode's definition per pixel from the map
         (pb_sample_map_bilinear_px) - same definition, float64 arithmetic."""
+        n = _map_supersample(coordinate_map, supersample)
+        if n == 1:
+            return self._process(coordinate_map, interpolation)
+        return self._process_ss(coordinate_map, interpolation, n)
+
+    def _process(self, coordinate_map, interpolation: str = "nearest", device_out: bool = False):
+        """process_coordinate_map at n = 1; ``device_out``: the result stays on the device whatever the image is (the generic supersampled
+        path reduces it there)."""
         src = self._proj("src")
         h, w, tail, dt = _image_info(self.image)
         rgb8 = tail == (3,) and dt == np.dtype(np.uint8)
@@ -365,7 +400,7 @@ class _GpuProjection:
                 # (the reference's blend cannot broadcast (H, W) samples against its (H, W, 1) factor maps either)
                 H_, W_ = tuple(coordinate_map.shape[:2])
                 raise ValueError(f"operands could not be broadcast together with shapes ({H_},{W_}) ({H_},{W_},1)")
-        on_device = nat.is_device_array(self.image)  # the pixels live on the device: so does the result
+        on_device = nat.is_device_array(self.image) or device_out  # the pixels live on the device: so does the result
         fused = rgb8 and not custom_src
         rotations = coordinate_map.rotations if lazy else ()
         if bilinear and lazy and len(rotations) > nat.PB_MAX_ROTATIONS:
@@ -435,6 +470,56 @@ class _GpuProjection:
                 host[...] = nat.to_host(dmap)  # the in-place zeroing of invalid pixels
             return out if on_device else _to_host(out)
 
+    def _process_ss(self, coordinate_map, interpolation: str, n: int):
+        """The supersampled result.  A lazy map + a uint8 RGB image + built-in lenses: ONE pb_remap_ss_u8 call on the
+        n x plan (the fused kernel where the plan takes it, else its generic path); anything else: the n = 1 call's result on the device,
+        then pb_box_reduce."""
+        src = self._proj("src")
+        h, w, tail, dt = _image_info(self.image)
+        if interpolation not in ("nearest", "bilinear"):
+            raise ValueError("interpolation must be 'nearest' or 'bilinear'")
+        if dt not in (np.dtype(np.uint8), np.dtype(np.uint16)):
+            raise NotImplementedError(f"supersampling takes 8- or 16-bit unsigned samples, got {dt}")
+        mh, mw = (int(v) for v in tuple(coordinate_map.shape)[:2])
+        if mh % n or mw % n:
+            raise ValueError(f"a ({mh}, {mw}) coordinate map is not divisible by supersample={n}")
+        lazy = isinstance(coordinate_map, CoordinateMap) and coordinate_map.is_lazy
+        rgb8 = tail == (3,) and dt == np.dtype(np.uint8)
+        custom_src = src.kind != nat.KIND_PANO and src.lens == nat.LENS_CUSTOM
+        on_device = nat.is_device_array(self.image)
+        rotations = coordinate_map.rotations if lazy else ()
+        if interpolation == "bilinear" and len(rotations) > nat.PB_MAX_ROTATIONS:
+            return self._process_ss_generic(coordinate_map, interpolation, n, on_device)  # (the folded chain: _process's own rule)
+        if not (lazy and rgb8 and not custom_src and len(rotations) <= nat.PB_MAX_ROTATIONS):
+            return self._process_ss_generic(coordinate_map, interpolation, n, on_device)
+        nat.require_gpu()
+        if not on_device:
+            a = _checked_rgb8(self.image, h, w)
+            plan = _plan_for(coordinate_map.dst_proj, rotations, src, eager=interpolation != "nearest")
+            out = _hostpipe.remap_ndarray(plan, a, interpolation, supersample=n)
+        else:
+            img = _device_image(self.image, h, w)
+            dev = img.device if nat.is_tensor(img) else None
+            plan = _plan_for(coordinate_map.dst_proj, rotations, src, device=dev, eager=interpolation != "nearest")
+            with nat.on_device(nat.device_index_of(img)):
+                out = plan.remap(img, interpolation=interpolation, supersample=n)
+        if src.kind == nat.KIND_PANO:
+            coordinate_map.note_invalid_zeroed()  # projection.py:534-536
+        return out
+
+    def _process_ss_generic(self, coordinate_map, interpolation: str, n: int, on_device: bool):
+        full = self._process(coordinate_map, interpolation, device_out=True)
+        with nat.on_device(nat.device_index_of(full)):
+            out = nat.box_reduce(full, n)
+        return out if on_device else _to_host(out)
+
+
+def _map_supersample(coordinate_map, supersample) -> int:
+    """The supersample factor of a process_coordinate_map call: the explicit one, else the map's own (1 for plain arrays / tensors)."""
+    if supersample is None:
+        return coordinate_map.supersample if isinstance(coordinate_map, CoordinateMap) else 1
+    return nat.check_supersample(supersample)
+
 
 def _role_lens_id(lens: Lens, role: str) -> int:
     """pb_lens id of the function the role uses: a destination inverts (reverse_function), a source projects
@@ -462,6 +547,9 @@ class CameraImage(_GpuProjection):
         """Pixels per focal length: magnitude / forward(fov / 2) (projection.py:123-144);
         raises what the lens raises (rectilinear beyond 178 degrees)."""
         return self.magnitude / self.forward_lens(self.fov / 2)
+
+    def _forward_half_fov(self) -> float:
+        return self.forward_lens(self.fov / 2)
 
     def _proj(self, role: str = "src") -> nat.pb_proj:
         h, w = _shape_hw(self.image)
@@ -503,6 +591,9 @@ class DoubleCameraImage(_GpuProjection):
 
     def _compute_f_distance(self) -> float:
         return self.magnitude / self.forward_lens(self.sensor_fov / 2)
+
+    def _forward_half_fov(self) -> float:
+        return self.forward_lens(self.sensor_fov / 2)
 
     def _proj(self, role: str = "src") -> nat.pb_proj:
         h, w = _shape_hw(self.image)

@@ -31,6 +31,7 @@
 #include "pb_kernels_sep.hpp"
 #include "pb_kernels_double.hpp"
 #include "pb_kernels_bilinear.hpp"
+#include "pb_kernels_supersample.hpp"
 
 #define PB_DOUBLE_FRAMES_PER_WAVE 1  // frames a double-source wave loops over (the rest of a batch is a grid dimension)
 #define PB_WAVES_PER_WG 4  // waves per workgroup of the hot kernel (LDS is released per workgroup)
@@ -2507,6 +2508,119 @@ int pb_host_register(void* host_ptr, size_t bytes) {
 int pb_host_unregister(void* host_ptr) {
     if (!host_ptr) return pb_fail(PB_ERR_INVALID, "null argument");
     PB_HIP(hipHostUnregister(host_ptr));
+    return PB_OK;
+}
+
+}  // extern "C"
+
+// ---- supersampled remapping ----------------------------------------------------------------------------------------
+// Can the fused kernel take a call of this plan (16-byte aligned frames assumed)?  Exactly the plans pb_launch_fast sends through
+// pb_hot_win_kernel: prepared single-source plans under AUTO / FAST with their launch-order table, nearest mode.
+static bool pb_ss_fused_ok(const pb_plan* pl, int interpolation, unsigned flags) {
+    const PbParams& P = pl->P;
+    return interpolation == PB_INTERP_NEAREST && !(flags & PB_SS_GENERIC) && P.src.kind != PB_KIND_DOUBLE && !pl->dbl_ready && pb_use_fast(pl) &&
+           pl->ltable && pl->P_dev && pl->launch_groups > 0 && pl->mode != PB_MODE_FAST_DIRECT && P.src.width < 32768 && P.src.height < 32768;
+}
+
+static int pb_ss_check(const pb_plan* plan, int n, int interpolation) {
+    if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
+    if (n != 2 && n != 4) return pb_fail(PB_ERR_INVALID, "supersample factor must be 2 or 4");
+    if (interpolation != PB_INTERP_NEAREST && interpolation != PB_INTERP_BILINEAR) return pb_fail(PB_ERR_INVALID, "interpolation must be PB_INTERP_NEAREST or PB_INTERP_BILINEAR");
+    if (plan->P.dst.height % n || plan->P.dst.width % n)
+        return pb_fail(PB_ERR_INVALID, "the plan's destination is not divisible by the supersample factor (pass the plan of the n x destination)");
+    return PB_OK;
+}
+
+static void pb_box_reduce_launch(const void* src, void* dst, unsigned H, unsigned W, int channels, int sample_bytes, int n, int n_frames, hipStream_t st) {
+    const unsigned long long n_px = (unsigned long long)H * W * (unsigned)n_frames;
+    const unsigned long long want = (n_px + 255) / 256;
+    const dim3 grid((unsigned)(want < (1ull << 20) ? want : (1ull << 20))), block(256);
+    const uint8_t* s = (const uint8_t*)src;
+    uint8_t* d = (uint8_t*)dst;
+    if (n == 2 && sample_bytes == 1) hipLaunchKernelGGL((pb_box_reduce_kernel<2, 1>), grid, block, 0, st, s, d, W, channels, n_px);
+    else if (n == 2) hipLaunchKernelGGL((pb_box_reduce_kernel<2, 2>), grid, block, 0, st, s, d, W, channels, n_px);
+    else if (sample_bytes == 1) hipLaunchKernelGGL((pb_box_reduce_kernel<4, 1>), grid, block, 0, st, s, d, W, channels, n_px);
+    else hipLaunchKernelGGL((pb_box_reduce_kernel<4, 2>), grid, block, 0, st, s, d, W, channels, n_px);
+}
+
+extern "C" {
+
+int pb_remap_ss_workspace(const pb_plan* plan, int n, int interpolation, unsigned flags, size_t* bytes) {
+    if (!bytes) return pb_fail(PB_ERR_INVALID, "null argument");
+    const int rc = pb_ss_check(plan, n, interpolation);
+    if (rc) return rc;
+    *bytes = pb_ss_fused_ok(plan, interpolation, flags) ? 0 : 3ull * plan->P.dst.height * plan->P.dst.width;
+    return PB_OK;
+}
+
+int pb_remap_ss_u8(const pb_plan* plan, int n, int interpolation, const uint8_t* src_dev, uint8_t* dst_dev, int n_frames, size_t src_frame_stride,
+                   size_t dst_frame_stride, void* workspace_dev, size_t workspace_bytes, unsigned flags, void* stream) {
+    const int rc = pb_ss_check(plan, n, interpolation);
+    if (rc) return rc;
+    if (!src_dev || !dst_dev) return pb_fail(PB_ERR_INVALID, "null argument");
+    if (n_frames < 0) return pb_fail(PB_ERR_INVALID, "negative frame count");
+    if (n_frames == 0) return PB_OK;
+    if (plan->device >= 0) {
+        int dev = -1;
+        PB_HIP(hipGetDevice(&dev));
+        if (dev != plan->device) return pb_fail(PB_ERR_INVALID, "plan was prepared on another device; create one plan per device");
+    }
+    const PbParams& P = plan->P;
+    const unsigned Ho = (unsigned)P.dst.height / n, Wo = (unsigned)P.dst.width / n;
+    const unsigned long long out_bytes = 3ull * Ho * Wo, src_bytes = 3ull * P.src.height * P.src.width;
+    if (!src_frame_stride) src_frame_stride = src_bytes;
+    if (!dst_frame_stride) dst_frame_stride = out_bytes;
+    if (dst_frame_stride < out_bytes) return pb_fail(PB_ERR_INVALID, "dst_frame_stride smaller than a frame");
+    if (n_frames > 1 && src_frame_stride < src_bytes) return pb_fail(PB_ERR_INVALID, "src_frame_stride smaller than a frame");
+    hipStream_t st = (hipStream_t)stream;
+    if (pb_ss_fused_ok(plan, interpolation, flags) && ((((uintptr_t)src_dev) | src_frame_stride) & 15u) == 0) {
+        const unsigned gpf = plan->launch_groups;
+        const size_t lds = pb_window_lds_bytes(P);
+        const int per_launch = (int)(0x7FFFFFFFu / gpf);
+        for (int f0 = 0; f0 < n_frames; f0 += per_launch) {
+            const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
+            const dim3 bgrid(gpf * (unsigned)nf), block(64 * PB_TILE_WAVES);
+            const uint8_t* sf = src_dev + (unsigned long long)f0 * src_frame_stride;
+            uint8_t* df = dst_dev + (unsigned long long)f0 * dst_frame_stride;
+#define PB_LAUNCH_SS(KIND, NS)                                                                                                     \
+    hipLaunchKernelGGL((pb_ss_win_kernel<KIND, NS>), bgrid, block, lds, st, (const PbParams*)plan->P_dev, pb_hot_of_host(P), plan->ltable, sf, df, \
+                       gpf, (unsigned long long)src_frame_stride, (unsigned long long)dst_frame_stride, plan->idx_tab, plan->fix_px, plan->fix_idx)
+            if (P.src.kind == PB_KIND_PANO && n == 2) PB_LAUNCH_SS(PB_KIND_PANO, 2);
+            else if (P.src.kind == PB_KIND_PANO) PB_LAUNCH_SS(PB_KIND_PANO, 4);
+            else if (n == 2) PB_LAUNCH_SS(PB_KIND_CAMERA, 2);
+            else PB_LAUNCH_SS(PB_KIND_CAMERA, 4);
+#undef PB_LAUNCH_SS
+        }
+        PB_HIP(hipGetLastError());
+        return PB_OK;
+    }
+    // generic path: frame by frame, the n x remap into the workspace, then the box reduction into the caller's frame
+    const unsigned long long ws_need = 3ull * P.dst.height * P.dst.width;
+    if (!workspace_dev || workspace_bytes < ws_need)
+        return pb_fail(PB_ERR_INVALID, "workspace smaller than one n x frame (pb_remap_ss_workspace; frames that are not 16-byte aligned need it too)");
+    uint8_t* ws = (uint8_t*)workspace_dev;
+    for (int f = 0; f < n_frames; ++f) {
+        const uint8_t* sf = src_dev + (unsigned long long)f * src_frame_stride;
+        const int r = interpolation == PB_INTERP_NEAREST ? pb_remap_u8(plan, sf, ws, 1, src_frame_stride, 0, stream)
+                                                         : pb_remap_bilinear_u8(plan, sf, ws, 1, src_frame_stride, 0, stream);
+        if (r) return r;
+        pb_box_reduce_launch(ws, dst_dev + (unsigned long long)f * dst_frame_stride, Ho, Wo, 3, 1, n, 1, st);
+        PB_HIP(hipGetLastError());
+    }
+    return PB_OK;
+}
+
+int pb_box_reduce(const void* src_dev, void* dst_dev, int height, int width, int channels, int sample_bytes, int n, int n_frames, void* stream) {
+    if (!src_dev || !dst_dev) return pb_fail(PB_ERR_INVALID, "null argument");
+    if (n != 2 && n != 4) return pb_fail(PB_ERR_INVALID, "supersample factor must be 2 or 4");
+    if (sample_bytes != 1 && sample_bytes != 2) return pb_fail(PB_ERR_INVALID, "sample_bytes must be 1 or 2");
+    if (channels < 1 || channels > 64) return pb_fail(PB_ERR_INVALID, "channels out of range (1..64)");
+    if (height < 1 || width < 1 || n_frames < 0) return pb_fail(PB_ERR_INVALID, "bad shape");
+    // the n x frame obeys the projection limit of every map in the library (h * w < 2^29)
+    if ((long long)height * width * n * n > 0x7FFFFFFFll / 4) return pb_fail(PB_ERR_INVALID, "n x frame beyond the projection limit (n^2 h w < 2^29)");
+    if (n_frames == 0) return PB_OK;
+    pb_box_reduce_launch(src_dev, dst_dev, (unsigned)height, (unsigned)width, channels, sample_bytes, n, n_frames, (hipStream_t)stream);
+    PB_HIP(hipGetLastError());
     return PB_OK;
 }
 

@@ -110,9 +110,16 @@ def camera_object(image_type: str, pixels: np.ndarray, fov: float, lens: str, ma
     return cls(pixels, fov, LENSES[lens](), magnitude=magnitude)
 
 
-def run_chain(source, destiny, rotations, out: Path) -> None:
-    """dst.get_coordinate_map() -> rotations in order -> src.process_coordinate_map() -> save."""
-    cmap = destiny.get_coordinate_map()
+def run_chain(source, destiny, rotations, out: Path, supersample: int = 1) -> None:
+    """dst.get_coordinate_map() -> rotations in order -> src.process_coordinate_map() -> save.  ``supersample`` n > 1: the map of the n x
+    destination, each output pixel the mean of its n x n samples (the output size stays what the size rules gave)."""
+    if supersample == 1:
+        cmap = destiny.get_coordinate_map()
+    else:
+        try:
+            cmap = destiny.get_coordinate_map(supersample=supersample)
+        except ValueError as exc:
+            raise click.BadParameter(str(exc), param_hint="--supersample")
     for rot in rotations:
         cmap = Rotation(*map(to_radians, rot)).rotate_coordinate_map(cmap)
     mapped = source.process_coordinate_map(cmap)
@@ -132,6 +139,8 @@ _type_choice = click.Choice(list(TYPES))
 def _common(fn):
     fn = click.option("-s", "--size", type=click.INT, default=None, help="The vertical size of the destiny image")(fn)
     fn = click.option("-r", "--rotation", type=click.FLOAT, nargs=3, multiple=True, default=[], help=ROTATION_HELP)(fn)
+    fn = click.option("--supersample", type=click.Choice(["1", "2", "4"]), default="1", show_default=True,
+                      help="Antialiasing: each output pixel is the mean of n x n samples (1 = off).")(fn)
     return fn
 
 
@@ -147,7 +156,7 @@ def main():
 @click.option("--fov", required=True, type=click.FLOAT, help="The lens field of view of the output photo in degrees. " + DOUBLE_FOV_NOTE)
 @_common
 @click.argument("output_image", type=click.Path(exists=False, path_type=Path))
-def make_photo(input_image, otype, lens, fov, output_image, rotation, size):
+def make_photo(input_image, otype, lens, fov, output_image, rotation, size, supersample):
     """Make a photo out of a panorama.
 
     \b
@@ -159,7 +168,7 @@ def make_photo(input_image, otype, lens, fov, output_image, rotation, size):
     _, _, _ = pano.shape  # make_photo.py:112 unpacks three dimensions: grey inputs are a ValueError in the reference CLI
     shape = camera_shape(otype, pano, size)
     destiny = camera_object(otype, np.zeros(shape, np.uint8), radians_fov(fov, otype), lens, magnitude_for(otype, shape))
-    run_chain(PanoramaImage(pano), destiny, rotation, out)
+    run_chain(PanoramaImage(pano), destiny, rotation, out, int(supersample))
 
 
 @main.command("alter-photo")
@@ -172,7 +181,7 @@ def make_photo(input_image, otype, lens, fov, output_image, rotation, size):
 @click.option("--ofov", required=True, type=click.FLOAT, help="The lens field of view of the output photo in degrees.")
 @click.argument("output_image", type=click.Path(exists=False, path_type=Path))
 @_common
-def alter_photo(input_image, itype, ilens, ifov, otype, olens, ofov, output_image, rotation, size):
+def alter_photo(input_image, itype, ilens, ifov, otype, olens, ofov, output_image, rotation, size, supersample):
     """Change the the lens and FoV of a photo.
 
     \b
@@ -185,7 +194,7 @@ def alter_photo(input_image, itype, ilens, ifov, otype, olens, ofov, output_imag
     shape = camera_shape(otype, photo, size)
     # the destination magnitude comes from the SOURCE shape (alter_photo.py:142): only visible when --size differs
     destiny = camera_object(otype, np.zeros(shape, np.uint8), radians_fov(ofov, otype), olens, magnitude_for(otype, photo.shape))
-    run_chain(source, destiny, rotation, out)
+    run_chain(source, destiny, rotation, out, int(supersample))
 
 
 @main.command("make-pano")
@@ -195,7 +204,7 @@ def alter_photo(input_image, itype, ilens, ifov, otype, olens, ofov, output_imag
 @click.option("--fov", required=True, type=click.FLOAT, help="The lens field of view of the input photo in degrees. " + DOUBLE_FOV_NOTE)
 @_common
 @click.argument("output_image", type=click.Path(exists=False, path_type=Path))
-def make_pano(input_image, itype, lens, fov, output_image, rotation, size):
+def make_pano(input_image, itype, lens, fov, output_image, rotation, size, supersample):
     """Make a panorama out of a photo.
 
     \b
@@ -207,7 +216,7 @@ def make_pano(input_image, itype, lens, fov, output_image, rotation, size):
     source = camera_object(itype, photo, radians_fov(fov, itype), lens, magnitude_for(itype, photo.shape))
     h = photo.shape[0] if size is None else size
     destiny = PanoramaImage(np.zeros((h, int(h * 2), 3), np.uint8))  # make_pano.py:142-149
-    run_chain(source, destiny, rotation, out)
+    run_chain(source, destiny, rotation, out, int(supersample))
 
 
 if __name__ == "__main__":
