@@ -19,6 +19,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -34,7 +35,6 @@
 #include "pb_kernels_supersample.hpp"
 
 #define PB_DOUBLE_FRAMES_PER_WAVE 1  // frames a double-source wave loops over (the rest of a batch is a grid dimension)
-#define PB_WAVES_PER_WG 4  // waves per workgroup of the hot kernel (LDS is released per workgroup)
 struct pb_plan {
     PbParams P;
     int mode = PB_MODE_AUTO;     // PB_MODE_AUTO / PB_MODE_FAITHFUL / PB_MODE_FAST
@@ -638,63 +638,240 @@ static int pb_plan_prepare_on_device(pb_plan* pl) {
 
 static bool pb_use_fast(const pb_plan* plan) { return plan->fast_ready && plan->mode != PB_MODE_FAITHFUL; }
 
-// hot kernel + fix kernel on `st`; OUT 0 = frames, OUT 1 = int32 index map
-template <int OUT>
-static void pb_launch_fast(const pb_plan* pl, const uint8_t* src, uint8_t* dst, int n_frames, unsigned long long ss,
-                           unsigned long long ds, int32_t* idx_out, hipStream_t st) {
+// ---- what a remap call launches ------------------------------------------------------------------------------------
+// The plan's tables live on the device it was prepared on (a deferred plan has none yet).
+static int pb_check_device(const pb_plan* plan) {
+    if (plan->device < 0) return PB_OK;
+    int dev = -1;
+    PB_HIP(hipGetDevice(&dev));
+    if (dev != plan->device) return pb_fail(PB_ERR_INVALID, "plan was prepared on another device; create one plan per device");
+    return PB_OK;
+}
+
+// The arguments of every frame-launching entry point, in this order: null plan / frames, the frame count (0: PB_OK and nothing to
+// launch - callers return), the plan's device, the frame strides (0: tightly packed; the defaults are filled in here and nowhere
+// else).  n: the supersample factor - an output frame is H/n x W/n of the plan's destination.  tables: src / dst are pb_remap_u8v's
+// pointer tables, which may be null when there are no frames.
+static int pb_check_frames(const pb_plan* plan, const void* src, const void* dst, int n_frames, int n, size_t& src_stride, size_t& dst_stride,
+                           bool tables = false) {
+    if (!plan || ((!src || !dst) && (n_frames > 0 || !tables))) return pb_fail(PB_ERR_INVALID, "null argument");
+    if (n_frames < 0) return pb_fail(PB_ERR_INVALID, "negative frame count");
+    if (n_frames == 0) return PB_OK;
+    const int rc = pb_check_device(plan);
+    if (rc != PB_OK) return rc;
+    const PbParams& P = plan->P;
+    const unsigned long long src_bytes = 3ull * P.src.height * P.src.width, dst_bytes = 3ull * ((unsigned)P.dst.height / n) * ((unsigned)P.dst.width / n);
+    if (!src_stride) src_stride = src_bytes;
+    if (!dst_stride) dst_stride = dst_bytes;
+    if (dst_stride < dst_bytes) return pb_fail(PB_ERR_INVALID, "dst_frame_stride smaller than a frame");
+    if (n_frames > 1 && src_stride < src_bytes) return pb_fail(PB_ERR_INVALID, "src_frame_stride smaller than a frame");
+    return PB_OK;
+}
+
+// The one routing decision: which kernels a remap call of `pl` launches (the table in DESIGN §3.7).  aligned: the source frames and
+// their stride are 16-byte aligned (the window kernels' LDS-DMA row segments); n: the supersample factor (1: a plain call).
+// What the plan builders guarantee, and the conditions below rely on: fast_ready is set for single sources only (pb_fast_possible),
+// dbl_ready and sep_ready for double-fisheye sources only, dbl_ready for sources below 32768 px a side only (pb_fast_possible_dims);
+// a non-null ltable / ltable_bil comes with launch_groups / launch_groups_bil >= 8 (pb_build_launch_table sets and clears both).
+struct PbRoute {
+    enum Kind {
+        DOUBLE,              // nearest: pb_hot_double_kernel
+        SEP,                 // nearest: pb_sep_double_kernel once its tables' check has passed (pb_sep_usable), else as FLOAT64
+        WIN,                 // nearest: pb_hot_win_kernel
+        DIRECT,              // nearest: pb_hot_kernel + pb_fix_kernel
+        FLOAT64,             // nearest: pb_remap_kernel
+        BIL_DOUBLE,          // bilinear: pb_bilinear_double_hot_kernel (+ pb_bilinear_double_fix_kernel without coordinate tables)
+        BIL_DOUBLE_FLOAT64,  // bilinear: pb_bilinear_double_kernel
+        BIL_TILES,           // bilinear: pb_bilinear_hot_kernel (+ pb_bilinear_fix_kernel over the listed tiles without coordinate tables)
+        BIL_FLOAT64,         // bilinear: pb_bilinear_fix_kernel over every pixel
+        SS_FUSED,            // supersampled: pb_ss_win_kernel
+        SS_GENERIC,          // supersampled: frame by frame the route of n = 1 into a workspace, then pb_box_reduce_kernel
+    } kind;
+    bool windows;  // BIL_DOUBLE / BIL_TILES: LEAN tiles gather from LDS windows
+};
+static bool pb_aligned16(const void* src, unsigned long long stride) { return ((((uintptr_t)src) | stride) & 15u) == 0; }
+static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned flags, bool aligned) {
     const PbParams& P = pl->P;
-    const dim3 grid(pb_hot_blocks(P)), block(64 * PB_TILE_WAVES);
-    const unsigned fix_blocks = 4u * pl->n_fail_tiles + (pl->n_fix_px + PB_BLOCK - 1) / PB_BLOCK;
-    // the windowed kernel needs 16-byte aligned frames (LDS-DMA row segments); PB_MODE_FAST_DIRECT and
-    // unaligned frames take the direct-gather hot kernel + the fix kernel
-    const bool windowed = OUT == 0 && pl->ltable && pl->P_dev && pl->mode != PB_MODE_FAST_DIRECT && P.src.width < 32768 && P.src.height < 32768 &&
-                          ((((uintptr_t)src) | ss) & 15u) == 0;
-    if (windowed) {
-        // one launch per frame: failed tiles and fix pixels are looked up in the plan's exact-index tables by the
-        // hot waves themselves (pb_kernels_tile.hpp)
-        // frames are a grid dimension, frame-major; a frame's share of the grid is a multiple of 8 workgroups so that a
-        // tile group keeps its XCD residue in every frame
-        const unsigned gpf = pl->launch_groups;
-        static const unsigned wpw = [] { const int v = pb_knob("PB_WPW", PB_WAVES_PER_WG); return (v == 1 || v == 2) ? (unsigned)v : 4u; }();
-        const dim3 wblock(64u * wpw);
-        const size_t lds = pb_window_lds_bytes(P) / PB_TILE_WAVES * wpw + (size_t)pb_knob("PB_LDS_PAD", 0);  // (the pad: occupancy experiments, -DPB_ABLATION only)
-        const unsigned wpf = gpf * (4u / wpw);
-        const int per_launch = (int)(0x7FFFFFFFu / wpf);  // grid limit: absurdly long batches go in several launches
-        for (int f0 = 0; f0 < n_frames; f0 += per_launch) {
-            const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
-            const dim3 bgrid(wpf * (unsigned)nf);
-            const uint8_t* sf = src + (unsigned long long)f0 * ss;
-            uint8_t* df = dst + (unsigned long long)f0 * ds;
-#define PB_LAUNCH_WIN(KIND)                                                                                                   \
-    hipLaunchKernelGGL((pb_hot_win_kernel<KIND>), bgrid, wblock, lds, st, (const PbParams*)pl->P_dev, pb_hot_of_host(P), pl->ltable, sf, df, gpf, ss, ds, pl->idx_tab, \
-                       pl->fix_px, pl->fix_idx, (unsigned)nf, PbNoFrameTab{0})
-            if (P.src.kind == PB_KIND_PANO) PB_LAUNCH_WIN(PB_KIND_PANO);
-            else PB_LAUNCH_WIN(PB_KIND_CAMERA);
-        }
-#undef PB_LAUNCH_WIN
-        return;
+    if (n > 1) {
+        const bool fused = interpolation == PB_INTERP_NEAREST && !(flags & PB_SS_GENERIC) && pb_route(pl, interpolation, 1, 0, aligned).kind == PbRoute::WIN;
+        return {fused ? PbRoute::SS_FUSED : PbRoute::SS_GENERIC, false};
     }
-    // the direct-gather hot kernel + the fix kernel (index maps, PB_MODE_FAST_DIRECT, frames LDS-DMA cannot address)
-    if (P.src.kind == PB_KIND_PANO)
-        hipLaunchKernelGGL((pb_hot_kernel<PB_KIND_PANO, OUT>), grid, block, 0, st, P, pl->table, src, dst, n_frames, ss, ds, idx_out);
-    else
-        hipLaunchKernelGGL((pb_hot_kernel<PB_KIND_CAMERA, OUT>), grid, block, 0, st, P, pl->table, src, dst, n_frames, ss, ds, idx_out);
+    const bool tiled = pl->mode != PB_MODE_FAITHFUL;
+    const bool windows = pl->mode != PB_MODE_FAST_DIRECT && P.src.width < 32768 && P.src.height < 32768 && aligned;
+    if (interpolation == PB_INTERP_BILINEAR) {
+        if (P.src.kind == PB_KIND_DOUBLE)
+            return (tiled && pl->dbl_ready && pl->ltable_bil && pl->bil_tiles && pl->bil_dbl_tables) ? PbRoute{PbRoute::BIL_DOUBLE, windows}
+                                                                                                     : PbRoute{PbRoute::BIL_DOUBLE_FLOAT64, false};
+        return (pb_use_fast(pl) && pl->ltable_bil && pl->bil_tiles) ? PbRoute{PbRoute::BIL_TILES, windows} : PbRoute{PbRoute::BIL_FLOAT64, false};
+    }
+    if (tiled && pl->dbl_ready && pl->ltable && windows) return {PbRoute::DOUBLE, true};
+    if (tiled && pl->sep_ready) return {PbRoute::SEP, false};
+    if (pb_use_fast(pl) && pl->ltable && pl->P_dev && windows) return {PbRoute::WIN, true};
+    if (pb_use_fast(pl)) return {PbRoute::DIRECT, false};
+    return {PbRoute::FLOAT64, false};
+}
+
+// Template arguments from run-time values: f(PbInt<A>()) if `first`, else f(PbInt<B>()) - the kernel's KIND, its waves per workgroup,
+// the supersample factor.
+template <int V>
+using PbInt = std::integral_constant<int, V>;
+template <int A, int B, class F>
+static void pb_pick(bool first, F&& f) {
+    if (first) f(PbInt<A>());
+    else f(PbInt<B>());
+}
+template <class F>
+static void pb_pick_kind(const PbParams& P, F&& f) {  // (single sources)
+    pb_pick<PB_KIND_PANO, PB_KIND_CAMERA>(P.src.kind == PB_KIND_PANO, f);
+}
+template <class F>
+static void pb_pick_any_kind(const PbParams& P, F&& f) {
+    if (P.src.kind == PB_KIND_DOUBLE) f(PbInt<PB_KIND_DOUBLE>());
+    else pb_pick_kind(P, f);
+}
+// the double-fisheye kernels' WMODE: 1 the separable path's exact row weights, 2 stored merge-band latitudes, 0 neither
+static const PbSepRow* pb_sep_rows(const pb_plan* pl) { return pl->sep_ready ? pl->sep_rows : nullptr; }
+template <class F>
+static void pb_pick_wmode(const pb_plan* pl, F&& f) {
+    if (pb_sep_rows(pl)) f(PbInt<1>());
+    else if (pl->n_lat_tiles) f(PbInt<2>());
+    else f(PbInt<0>());
+}
+// Frames are a grid dimension of the tile launches: a batch goes in launches of at most 0x7FFFFFFF / gpf frames (gpf: workgroups per
+// frame), launch(src, dst, frames) with the pointers of each piece's first frame.
+template <class F>
+static void pb_each_launch(const uint8_t* src, uint8_t* dst, int n_frames, unsigned long long ss, unsigned long long ds, unsigned gpf, F&& launch) {
+    const int per_launch = (int)(0x7FFFFFFFu / gpf);
+    for (int f0 = 0; f0 < n_frames; f0 += per_launch)
+        launch(src + (unsigned long long)f0 * ss, dst + (unsigned long long)f0 * ds, n_frames - f0 < per_launch ? n_frames - f0 : per_launch);
+}
+// real workgroups per frame of a bilinear tile launch
+static unsigned pb_bil_groups(const pb_plan* pl) { return pl->launch_groups_bil * (4u / (unsigned)pl->bil_waves); }
+
+// the direct-gather hot kernel + the fix kernel; OUT 0 = frames, OUT 1 = int32 index map
+template <int OUT>
+static void pb_launch_direct(const pb_plan* pl, const uint8_t* src, uint8_t* dst, int n_frames, unsigned long long ss, unsigned long long ds,
+                             int32_t* idx_out, hipStream_t st) {
+    const PbParams& P = pl->P;
+    pb_pick_kind(P, [&](auto K) {
+        hipLaunchKernelGGL((pb_hot_kernel<K.value, OUT>), dim3(pb_hot_blocks(P)), dim3(64 * PB_TILE_WAVES), 0, st, P, pl->table, src, dst, n_frames, ss, ds, idx_out);
+    });
+    const unsigned fix_blocks = 4u * pl->n_fail_tiles + (pl->n_fix_px + PB_BLOCK - 1) / PB_BLOCK;
     if (fix_blocks)
-        hipLaunchKernelGGL((pb_fix_kernel<OUT>), dim3(fix_blocks), dim3(PB_BLOCK), 0, st, P, pl->fail_tiles, (int)pl->n_fail_tiles,
-                           pl->fix_px, (int)pl->n_fix_px, pl->idx_tab, pl->fix_idx, src, dst, n_frames, ss, ds, idx_out);
+        hipLaunchKernelGGL((pb_fix_kernel<OUT>), dim3(fix_blocks), dim3(PB_BLOCK), 0, st, P, pl->fail_tiles, (int)pl->n_fail_tiles, pl->fix_px,
+                           (int)pl->n_fix_px, pl->idx_tab, pl->fix_idx, src, dst, n_frames, ss, ds, idx_out);
 }
 
-template <int KIND>
-static void pb_launch_faithful_remap(const PbParams& P, const uint8_t* src, uint8_t* dst, int n_frames, unsigned long long ss,
-                                     unsigned long long ds, hipStream_t st) {
+// Launches a nearest or bilinear route (n = 1) for n_frames frames at strides ss / ds (pb_check_frames has filled them in).
+static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* dst, int n_frames, unsigned long long ss, unsigned long long ds,
+                     hipStream_t st) {
+    const PbParams& P = pl->P;
     const unsigned long long npx = (unsigned long long)P.dst.height * P.dst.width;
-    const int aligned = (((uintptr_t)dst | ds) & 3u) == 0;
-    PB_LAUNCH_BY_ROT(P.n_rot, pb_remap_kernel, KIND, dim3(pb_blocks((npx + PB_PX - 1) / PB_PX)), dim3(PB_BLOCK), 0, st, P, src, dst,
-                       n_frames, ss, ds, aligned);
+    switch (r.kind) {
+        case PbRoute::DOUBLE: {
+            // failed tiles and fix pixels go through the plan's stored faithful taps
+            static const int fpw_env = pb_knob("PB_DOUBLE_FPW", 0);
+            const int fpw = fpw_env > 0 ? fpw_env : PB_DOUBLE_FRAMES_PER_WAVE;
+            const unsigned gpf = pl->launch_groups;  // workgroups per frame of the plan's launch-order table
+            const dim3 grid(gpf * (unsigned)((n_frames + fpw - 1) / fpw));  // (h*w < 2^29 and n_frames an int: far below the grid limit for any batch that fits memory)
+            pb_pick_wmode(pl, [&](auto W) {
+                pb_pick<1, 0>(n_frames == 1 || fpw == 1, [&](auto ONE) {
+                    hipLaunchKernelGGL((pb_hot_double_kernel<W.value, ONE.value != 0>), grid, dim3(64 * PB_TILE_WAVES), pb_window_lds_bytes(P, 8), st, P, pl->table,
+                                       pl->table_r, pl->ltable, pb_sep_rows(pl), pl->lat_tab, pl->fix_px, pl->dbl_px_fix, pl->dbl_tile_fix, src, dst, n_frames, ss,
+                                       ds, gpf, fpw, PbNoFrameTab{0});
+                });
+            });
+            break;
+        }
+        case PbRoute::SEP:
+            if (pb_sep_usable(pl, st)) {
+                hipLaunchKernelGGL(pb_sep_double_kernel, dim3(pb_hot_blocks(P)), dim3(64 * PB_TILE_WAVES), 0, st, P, pl->sep_rows, pl->sep_cols, src, dst,
+                                   n_frames, ss, ds);
+                break;
+            }
+            [[fallthrough]];
+        case PbRoute::FLOAT64: {
+            const int dst_aligned = (((uintptr_t)dst | ds) & 3u) == 0;
+            pb_pick_any_kind(P, [&](auto K) {
+                PB_LAUNCH_BY_ROT(P.n_rot, pb_remap_kernel, K.value, dim3(pb_blocks((npx + PB_PX - 1) / PB_PX)), dim3(PB_BLOCK), 0, st, P, src, dst, n_frames,
+                                 ss, ds, dst_aligned);
+            });
+            break;
+        }
+        case PbRoute::WIN: {
+            // failed tiles and fix pixels are looked up in the plan's exact-index tables by the hot waves themselves (pb_kernels_tile.hpp);
+            // a frame's share of the grid is a multiple of 8 workgroups so that a tile group keeps its XCD residue in every frame
+            const unsigned gpf = pl->launch_groups;
+            pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
+                pb_pick_kind(P, [&](auto K) {
+                    hipLaunchKernelGGL((pb_hot_win_kernel<K.value>), dim3(gpf * (unsigned)nf), dim3(64 * PB_TILE_WAVES), pb_window_lds_bytes(P), st,
+                                       (const PbParams*)pl->P_dev, pb_hot_of_host(P), pl->ltable, sf, df, gpf, ss, ds, pl->idx_tab, pl->fix_px, pl->fix_idx,
+                                       (unsigned)nf, PbNoFrameTab{0});
+                });
+            });
+            break;
+        }
+        case PbRoute::DIRECT:
+            pb_launch_direct<0>(pl, src, dst, n_frames, ss, ds, nullptr, st);
+            break;
+        case PbRoute::BIL_DOUBLE: {
+            // the per-eye tile models of the nearest mode's plan + the exact coordinate tables: one wave per tile
+            const unsigned gpf = pb_bil_groups(pl);
+            PbHot Hb = pb_hot_of_host(P);  // (the bilinear mode's window budget travels in it)
+            Hb.win_budget = pl->bil_budget;
+            pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
+                pb_pick_wmode(pl, [&](auto W) {
+                    pb_pick<2, 4>(pl->bil_waves == 2, [&](auto WAVES) {
+                        hipLaunchKernelGGL((pb_bilinear_double_hot_kernel<W.value, WAVES.value>), dim3(gpf * (unsigned)nf), dim3(64 * pl->bil_waves),
+                                           (size_t)pl->bil_pool_bytes, st, Hb, P.src_eye_w, pl->ltable_bil, pl->bil_dbl_tables, sf, df, gpf, ss, ds,
+                                           (int)r.windows, pl->bil_xy);
+                    });
+                });
+            });
+            if (!pl->bil_xy) {  // no coordinate tables (they would not fit): the failed / listed tiles and the fix pixels from the float64 chain
+                const unsigned n_tiles64 = pl->n_fail_tiles + pl->n_bil_tiles;
+                const unsigned fix_blocks = 4u * n_tiles64 + (pl->n_fix_px + PB_BLOCK - 1) / PB_BLOCK;
+                if (fix_blocks)
+                    hipLaunchKernelGGL(pb_bilinear_double_fix_kernel, dim3(fix_blocks), dim3(PB_BLOCK), 0, st, P, pl->fail_tiles, (int)pl->n_fail_tiles,
+                                       pl->bil_tiles, (int)n_tiles64, pl->fix_px, (int)pl->n_fix_px, src, dst, n_frames, ss, ds);
+            }
+            break;
+        }
+        case PbRoute::BIL_DOUBLE_FLOAT64:
+            hipLaunchKernelGGL(pb_bilinear_double_kernel, dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, src, dst, n_frames, ss, ds);
+            break;
+        case PbRoute::BIL_TILES: {
+            // launched like the nearest hot kernel: the mode's launch-order table, frames of a batch as a grid dimension
+            const unsigned gpf = pb_bil_groups(pl);
+            PbParams Pb = P;
+            Pb.win_budget = pl->bil_budget;
+            pb_pick_kind(P, [&](auto K) {
+                pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
+                    pb_pick<2, 4>(pl->bil_waves == 2, [&](auto WAVES) {
+                        hipLaunchKernelGGL((pb_bilinear_hot_kernel<K.value, WAVES.value>), dim3(gpf * (unsigned)nf), dim3(64 * pl->bil_waves),
+                                           (size_t)pl->bil_pool_bytes, st, pb_hot_of_host(Pb), pl->ltable_bil, sf, df, gpf, ss, ds, (int)r.windows, pl->bil_xy,
+                                           pl->fix_px, pl->bil_fix_xy);
+                    });
+                });
+                const unsigned n64 = pl->n_fail_tiles + pl->n_bil_tiles;  // failed + listed tiles
+                if (!pl->bil_xy && (n64 || pl->n_fix_px))  // no coordinate tables (they would not fit): the float64 chain
+                    hipLaunchKernelGGL(pb_bilinear_fix_kernel<K.value>, dim3(4u * n64 + (pl->n_fix_px + PB_BLOCK - 1) / PB_BLOCK), dim3(PB_BLOCK), 0, st, P,
+                                       pl->fail_tiles, 0, src, dst, n_frames, ss, ds, (int)n64, pl->fix_px, (int)pl->n_fix_px, pl->bil_tiles,
+                                       (int)pl->n_fail_tiles);
+            });
+            break;
+        }
+        case PbRoute::BIL_FLOAT64:
+            pb_pick_kind(P, [&](auto K) {
+                hipLaunchKernelGGL(pb_bilinear_fix_kernel<K.value>, dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, nullptr, 1, src, dst, n_frames, ss, ds);
+            });
+            break;
+        default:
+            return pb_fail(PB_ERR_INVALID, "not a route of one frame");  // (the supersampled routes: pb_remap_ss_u8)
+    }
+    PB_HIP(hipGetLastError());
+    return PB_OK;
 }
-
-static int pb_remap_launch(const pb_plan* plan, const uint8_t* src_dev, uint8_t* dst_dev, int n_frames, size_t src_frame_stride,
-                           size_t dst_frame_stride, hipStream_t st);
 
 // The LDS window budget of a plan (bytes per wave).  Smaller windows let more workgroups share a CU (the hot
 // kernels are latency x concurrency bound) but push tiles with larger windows onto the direct-gather path; which
@@ -1138,6 +1315,11 @@ static int pb_tune_window_budget(pb_plan* pl) {
         if (hipMalloc((void**)&src, n_scratch * sb16) != hipSuccess || hipMalloc((void**)&dst, n_scratch * db16) != hipSuccess) break;
         if (hipMemsetAsync(src, 0x55, n_scratch * sb16, 0) != hipSuccess) break;
         if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) break;
+        // one frame of scratch slot `slot`, launched as pb_remap_u8 launches it
+        const auto launch = [&](int slot) {
+            const uint8_t* s = src + slot * sb16;
+            return pb_launch(pl, pb_route(pl, PB_INTERP_NEAREST, 1, 0, pb_aligned16(s, sb)), s, dst + slot * db16, 1, sb, db, 0);
+        };
         const int cand[4] = {PB_WINLDS_MAX, 10224, 8176, 7168};  // 3, 4, 5 and 5 workgroups per CU (LDS-wise)
         float t_min[4] = {1e30f, 1e30f, 1e30f, 1e30f};
         bool failed = false;
@@ -1148,7 +1330,7 @@ static int pb_tune_window_budget(pb_plan* pl) {
                 for (int rep = 0; rep < 4; ++rep) {  // the first launch after a reclassification is not counted
                     (void)hipEventRecord(e0, 0);
                     const int slot = launch_no++ % n_scratch;
-                    if (pb_remap_launch(pl, src + slot * sb16, dst + slot * db16, 1, 0, 0, 0) != PB_OK) { failed = true; break; }
+                    if (launch(slot) != PB_OK) { failed = true; break; }
                     (void)hipEventRecord(e1, 0);
                     if (hipEventSynchronize(e1) != hipSuccess) { failed = true; break; }
                     float ms = 0.f;
@@ -1171,7 +1353,7 @@ static int pb_tune_window_budget(pb_plan* pl) {
                     for (int rep = 0; rep < 7; ++rep) {
                         (void)hipEventRecord(e0, 0);
                         const int slot = launch_no++ % n_scratch;
-                        if (pb_remap_launch(pl, src + slot * sb16, dst + slot * db16, 1, 0, 0, 0) != PB_OK) { failed = true; break; }
+                        if (launch(slot) != PB_OK) { failed = true; break; }
                         (void)hipEventRecord(e1, 0);
                         if (hipEventSynchronize(e1) != hipSuccess) { failed = true; break; }
                         float ms = 0.f;
@@ -1372,11 +1554,8 @@ int pb_plan_prepare(pb_plan* plan, unsigned flags, int win_budget) {
     if (flags & ~(unsigned)(PB_PLAN_TUNE | PB_PLAN_BILINEAR)) return pb_fail(PB_ERR_INVALID, "unknown plan flags");
     if (win_budget < 0) return pb_fail(PB_ERR_INVALID, "negative window budget");
     if (flags & PB_PLAN_BILINEAR) plan->bil_wanted = 1;  // (a deferred plan: its preparation now includes the mode's tables)
-    if (plan->device >= 0) {
-        int dev = -1;
-        PB_HIP(hipGetDevice(&dev));
-        if (dev != plan->device) return pb_fail(PB_ERR_INVALID, "plan was prepared on another device; create one plan per device");
-    }
+    const int rc = pb_check_device(plan);
+    if (rc != PB_OK) return rc;
     return pb_plan_prepare_full(plan, flags, win_budget);
 }
 
@@ -1465,7 +1644,7 @@ int pb_plan_bilinear_launch_shape(const pb_plan* plan, int* lds_bytes, int* work
     if (!plan || !lds_bytes || !workgroups_per_frame) return pb_fail(PB_ERR_INVALID, "null argument");
     const bool tiles = (plan->fast_ready || plan->dbl_ready) && plan->ltable_bil && plan->launch_groups_bil > 0;
     *lds_bytes = tiles ? (int)plan->bil_pool_bytes : 0;
-    *workgroups_per_frame = tiles ? (int)(plan->launch_groups_bil * (4u / (unsigned)plan->bil_waves)) : 0;
+    *workgroups_per_frame = tiles ? (int)pb_bil_groups(plan) : 0;
     return PB_OK;
 }
 int pb_plan_window_budget(const pb_plan* plan) {
@@ -1480,106 +1659,34 @@ int pb_plan_src_shape(const pb_plan* plan, int* height, int* width) {
 
 int pb_remap_u8(const pb_plan* plan, const uint8_t* src_dev, uint8_t* dst_dev, int n_frames, size_t src_frame_stride,
                 size_t dst_frame_stride, void* stream) {
-    if (!plan || !src_dev || !dst_dev) return pb_fail(PB_ERR_INVALID, "null argument");
-    if (n_frames < 0) return pb_fail(PB_ERR_INVALID, "negative frame count");
-    if (n_frames == 0) return PB_OK;
-    if (plan->device >= 0) {  // the plan's tables live on the device it was created on
-        int dev = -1;
-        PB_HIP(hipGetDevice(&dev));
-        if (dev != plan->device) return pb_fail(PB_ERR_INVALID, "plan was prepared on another device; create one plan per device");
-    }
-    const PbParams& P = plan->P;
-    const unsigned long long npx = (unsigned long long)P.dst.height * P.dst.width;
-    if (!src_frame_stride) src_frame_stride = 3ull * P.src.height * P.src.width;
-    if (!dst_frame_stride) dst_frame_stride = 3ull * npx;
-    if (dst_frame_stride < 3ull * npx) return pb_fail(PB_ERR_INVALID, "dst_frame_stride smaller than a frame");
-    if (n_frames > 1 && src_frame_stride < 3ull * P.src.height * P.src.width)
-        return pb_fail(PB_ERR_INVALID, "src_frame_stride smaller than a frame");
-    return pb_remap_launch(plan, src_dev, dst_dev, n_frames, src_frame_stride, dst_frame_stride, (hipStream_t)stream);
+    const int rc = pb_check_frames(plan, src_dev, dst_dev, n_frames, 1, src_frame_stride, dst_frame_stride);
+    if (rc != PB_OK || n_frames == 0) return rc;
+    return pb_launch(plan, pb_route(plan, PB_INTERP_NEAREST, 1, 0, pb_aligned16(src_dev, src_frame_stride)), src_dev, dst_dev, n_frames,
+                     src_frame_stride, dst_frame_stride, (hipStream_t)stream);
 }
-}  // extern "C"
-
-static int pb_remap_launch(const pb_plan* plan, const uint8_t* src_dev, uint8_t* dst_dev, int n_frames, size_t src_frame_stride,
-                           size_t dst_frame_stride, hipStream_t st) {
-    const PbParams& P = plan->P;
-    const unsigned long long npx = (unsigned long long)P.dst.height * P.dst.width;
-    if (!src_frame_stride) src_frame_stride = 3ull * P.src.height * P.src.width;
-    if (!dst_frame_stride) dst_frame_stride = 3ull * npx;
-    const bool windowable = ((((uintptr_t)src_dev) | src_frame_stride) & 15u) == 0;  // LDS-DMA row segments
-    if (plan->dbl_ready && plan->ltable && plan->mode != PB_MODE_FAITHFUL && plan->mode != PB_MODE_FAST_DIRECT && windowable) {
-        const dim3 block(64 * PB_TILE_WAVES);
-        // one launch per frame: failed tiles and fix pixels go through the plan's stored faithful taps
-        const PbSepRow* rows = plan->sep_ready ? plan->sep_rows : nullptr;
-        static const int fpw_env = pb_knob("PB_DOUBLE_FPW", 0);
-        const int fpw = fpw_env > 0 ? fpw_env : PB_DOUBLE_FRAMES_PER_WAVE;
-        const unsigned gpf = plan->launch_groups;  // workgroups per frame of the plan's launch-order table
-        const unsigned chunks = (unsigned)((n_frames + fpw - 1) / fpw);
-        const dim3 bgrid(gpf * chunks);  // (h*w < 2^29 and n_frames an int: far below the grid limit for any batch that fits memory)
-#define PB_LAUNCH_DOUBLE(WMODE, ONE)                                                                                              \
-    hipLaunchKernelGGL((pb_hot_double_kernel<WMODE, ONE>), bgrid, block, pb_window_lds_bytes(P, 8) + (size_t)pb_knob("PB_LDS_PAD", 0), st, P, plan->table, plan->table_r, plan->ltable, rows, plan->lat_tab, \
-                       plan->fix_px, plan->dbl_px_fix, plan->dbl_tile_fix, src_dev, dst_dev, n_frames, src_frame_stride,           \
-                       dst_frame_stride, gpf, fpw, PbNoFrameTab{0})
-        const bool one = n_frames == 1 || fpw == 1;
-        if (rows && one) PB_LAUNCH_DOUBLE(1, true);
-        else if (rows) PB_LAUNCH_DOUBLE(1, false);
-        else if (plan->n_lat_tiles && one) PB_LAUNCH_DOUBLE(2, true);
-        else if (plan->n_lat_tiles) PB_LAUNCH_DOUBLE(2, false);
-        else if (one) PB_LAUNCH_DOUBLE(0, true);
-        else PB_LAUNCH_DOUBLE(0, false);
-#undef PB_LAUNCH_DOUBLE
-    } else if (plan->sep_ready && plan->mode != PB_MODE_FAITHFUL && pb_sep_usable(plan, st)) {
-        hipLaunchKernelGGL(pb_sep_double_kernel, dim3(pb_hot_blocks(P)), dim3(64 * PB_TILE_WAVES), 0, st, P, plan->sep_rows, plan->sep_cols,
-                           src_dev, dst_dev, n_frames, src_frame_stride, dst_frame_stride);
-    } else if (pb_use_fast(plan)) {
-        pb_launch_fast<0>(plan, src_dev, dst_dev, n_frames, src_frame_stride, dst_frame_stride, nullptr, st);
-    } else if (P.src.kind == PB_KIND_PANO) {
-        pb_launch_faithful_remap<PB_KIND_PANO>(P, src_dev, dst_dev, n_frames, src_frame_stride, dst_frame_stride, st);
-    } else if (P.src.kind == PB_KIND_CAMERA) {
-        pb_launch_faithful_remap<PB_KIND_CAMERA>(P, src_dev, dst_dev, n_frames, src_frame_stride, dst_frame_stride, st);
-    } else {
-        pb_launch_faithful_remap<PB_KIND_DOUBLE>(P, src_dev, dst_dev, n_frames, src_frame_stride, dst_frame_stride, st);
-    }
-    PB_HIP(hipGetLastError());
-    return PB_OK;
-}
-
-// pb_remap_u8v: can the plan's hot kernel take a table of frame pointers?  (The windowed single-source kernel or the windowed
-// double-fisheye kernel, as pb_remap_launch would choose them for 16-byte aligned frames.)
-static bool pb_vec_launchable(const pb_plan* plan) {
-    const PbParams& P = plan->P;
-    if (plan->mode == PB_MODE_FAITHFUL || plan->mode == PB_MODE_FAST_DIRECT || !plan->ltable || plan->launch_groups == 0) return false;
-    if (plan->dbl_ready) return true;
-    return pb_use_fast(plan) && plan->P_dev && P.src.width < 32768 && P.src.height < 32768;
-}
-
-extern "C" {
 
 int pb_remap_u8v(const pb_plan* plan, const uint8_t* const* src_dev, uint8_t* const* dst_dev, int n_frames, void* stream) {
-    if (!plan || (n_frames > 0 && (!src_dev || !dst_dev))) return pb_fail(PB_ERR_INVALID, "null argument");
-    if (n_frames < 0) return pb_fail(PB_ERR_INVALID, "negative frame count");
-    if (n_frames == 0) return PB_OK;
-    if (plan->device >= 0) {
-        int dev = -1;
-        PB_HIP(hipGetDevice(&dev));
-        if (dev != plan->device) return pb_fail(PB_ERR_INVALID, "plan was prepared on another device; create one plan per device");
-    }
+    size_t ss = 0, ds = 0;
+    const int rc = pb_check_frames(plan, src_dev, dst_dev, n_frames, 1, ss, ds, true);
+    if (rc != PB_OK || n_frames == 0) return rc;
     bool aligned = true;
     for (int f = 0; f < n_frames; ++f) {
         if (!src_dev[f] || !dst_dev[f]) return pb_fail(PB_ERR_INVALID, "null frame pointer");
-        aligned = aligned && (((uintptr_t)src_dev[f]) & 15u) == 0;
+        aligned = aligned && pb_aligned16(src_dev[f], 0);
     }
     hipStream_t st = (hipStream_t)stream;
-    if (!aligned || !pb_vec_launchable(plan)) {
+    const PbRoute r = pb_route(plan, PB_INTERP_NEAREST, 1, 0, aligned);
+    if (r.kind != PbRoute::DOUBLE && r.kind != PbRoute::WIN) {
         // frames LDS-DMA cannot address, deferred plans, the float64 mode: the frames one by one (same bytes, n launches)
         for (int f = 0; f < n_frames; ++f) {
-            const int rc = pb_remap_launch(plan, src_dev[f], dst_dev[f], 1, 0, 0, st);
-            if (rc != PB_OK) return rc;
+            const int rf = pb_launch(plan, pb_route(plan, PB_INTERP_NEAREST, 1, 0, pb_aligned16(src_dev[f], ss)), src_dev[f], dst_dev[f], 1, ss, ds, st);
+            if (rf != PB_OK) return rf;
         }
         return PB_OK;
     }
+    // the VEC instantiations of the two windowed kernels: frame f's pointers from a by-value table, at most PB_MAX_VFRAMES per launch
     const PbParams& P = plan->P;
     const unsigned gpf = plan->launch_groups;
-    const dim3 block(64 * PB_TILE_WAVES);
     for (int f0 = 0; f0 < n_frames; f0 += PB_MAX_VFRAMES) {
         const int nf = n_frames - f0 < PB_MAX_VFRAMES ? n_frames - f0 : PB_MAX_VFRAMES;
         PbFrameTab tab;
@@ -1587,24 +1694,18 @@ int pb_remap_u8v(const pb_plan* plan, const uint8_t* const* src_dev, uint8_t* co
             tab.src[f] = src_dev[f0 + (f < nf ? f : 0)];
             tab.dst[f] = dst_dev[f0 + (f < nf ? f : 0)];
         }
-        const dim3 grid(gpf * (unsigned)nf);
-        if (plan->dbl_ready) {
-            const PbSepRow* rows = plan->sep_ready ? plan->sep_rows : nullptr;
-#define PB_LAUNCH_DOUBLE_V(WMODE)                                                                                                          \
-    hipLaunchKernelGGL((pb_hot_double_kernel<WMODE, true, true>), grid, block, pb_window_lds_bytes(P, 8), st, P, plan->table, plan->table_r, plan->ltable, \
-                       rows, plan->lat_tab, plan->fix_px, plan->dbl_px_fix, plan->dbl_tile_fix, tab.src[0], tab.dst[0], nf, 0ull, 0ull, gpf, 1, tab)
-            if (rows) PB_LAUNCH_DOUBLE_V(1);
-            else if (plan->n_lat_tiles) PB_LAUNCH_DOUBLE_V(2);
-            else PB_LAUNCH_DOUBLE_V(0);
-#undef PB_LAUNCH_DOUBLE_V
-        } else {
-#define PB_LAUNCH_WIN_V(KIND)                                                                                                              \
-    hipLaunchKernelGGL((pb_hot_win_kernel<KIND, true>), grid, block, pb_window_lds_bytes(P), st, (const PbParams*)plan->P_dev, pb_hot_of_host(P), plan->ltable, \
-                       tab.src[0], tab.dst[0], gpf, 0ull, 0ull, plan->idx_tab, plan->fix_px, plan->fix_idx, (unsigned)nf, tab)
-            if (P.src.kind == PB_KIND_PANO) PB_LAUNCH_WIN_V(PB_KIND_PANO);
-            else PB_LAUNCH_WIN_V(PB_KIND_CAMERA);
-#undef PB_LAUNCH_WIN_V
-        }
+        const dim3 grid(gpf * (unsigned)nf), block(64 * PB_TILE_WAVES);
+        if (r.kind == PbRoute::DOUBLE)
+            pb_pick_wmode(plan, [&](auto W) {
+                hipLaunchKernelGGL((pb_hot_double_kernel<W.value, true, true>), grid, block, pb_window_lds_bytes(P, 8), st, P, plan->table, plan->table_r,
+                                   plan->ltable, pb_sep_rows(plan), plan->lat_tab, plan->fix_px, plan->dbl_px_fix, plan->dbl_tile_fix, tab.src[0], tab.dst[0], nf,
+                                   0ull, 0ull, gpf, 1, tab);
+            });
+        else
+            pb_pick_kind(P, [&](auto K) {
+                hipLaunchKernelGGL((pb_hot_win_kernel<K.value, true>), grid, block, pb_window_lds_bytes(P), st, (const PbParams*)plan->P_dev, pb_hot_of_host(P),
+                                   plan->ltable, tab.src[0], tab.dst[0], gpf, 0ull, 0ull, plan->idx_tab, plan->fix_px, plan->fix_idx, (unsigned)nf, tab);
+            });
     }
     PB_HIP(hipGetLastError());
     return PB_OK;
@@ -1612,123 +1713,25 @@ int pb_remap_u8v(const pb_plan* plan, const uint8_t* const* src_dev, uint8_t* co
 
 int pb_remap_bilinear_u8(const pb_plan* plan, const uint8_t* src_dev, uint8_t* dst_dev, int n_frames, size_t src_frame_stride,
                          size_t dst_frame_stride, void* stream) {
-    if (!plan || !src_dev || !dst_dev) return pb_fail(PB_ERR_INVALID, "null argument");
-    if (n_frames < 0) return pb_fail(PB_ERR_INVALID, "negative frame count");
-    if (n_frames == 0) return PB_OK;
-    const PbParams& P = plan->P;
-    if (plan->device >= 0) {
-        int dev = -1;
-        PB_HIP(hipGetDevice(&dev));
-        if (dev != plan->device) return pb_fail(PB_ERR_INVALID, "plan was prepared on another device; create one plan per device");
-    }
-    const unsigned long long npx = (unsigned long long)P.dst.height * P.dst.width;
-    if (!src_frame_stride) src_frame_stride = 3ull * P.src.height * P.src.width;
-    if (!dst_frame_stride) dst_frame_stride = 3ull * npx;
-    if (dst_frame_stride < 3ull * npx) return pb_fail(PB_ERR_INVALID, "dst_frame_stride smaller than a frame");
-    if (n_frames > 1 && src_frame_stride < 3ull * P.src.height * P.src.width)
-        return pb_fail(PB_ERR_INVALID, "src_frame_stride smaller than a frame");
-    hipStream_t st = (hipStream_t)stream;
-    if (P.src.kind == PB_KIND_DOUBLE) {
-        if (plan->dbl_ready && plan->ltable_bil && plan->launch_groups_bil > 0 && plan->bil_tiles && plan->bil_dbl_tables && plan->mode != PB_MODE_FAITHFUL) {
-            // the per-eye tile models of the nearest mode's plan + the exact coordinate tables: one wave per tile, ONE launch
-            const unsigned gpf = plan->launch_groups_bil * (4u / (unsigned)plan->bil_waves);  // real workgroups per frame
-            PbHot Hb = pb_hot_of_host(P);  // (the bilinear mode's window budget travels in it)
-            Hb.win_budget = plan->bil_budget;
-            const int windows = plan->mode != PB_MODE_FAST_DIRECT && ((((uintptr_t)src_dev) | src_frame_stride) & 15u) == 0;
-            const PbSepRow* rows = plan->sep_ready ? plan->sep_rows : nullptr;
-            const int per_launch = (int)(0x7FFFFFFFu / gpf);
-            for (int f0 = 0; f0 < n_frames; f0 += per_launch) {
-                const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
-                const dim3 grid(gpf * (unsigned)nf), block(64 * plan->bil_waves);
-                const uint8_t* sf = src_dev + (unsigned long long)f0 * src_frame_stride;
-                uint8_t* df = dst_dev + (unsigned long long)f0 * dst_frame_stride;
-#define PB_LAUNCH_BILINEAR_DOUBLE(WMODE)                                                                                                       \
-    if (plan->bil_waves == 2)                                                                                                                  \
-        hipLaunchKernelGGL((pb_bilinear_double_hot_kernel<WMODE, 2>), grid, block, (size_t)plan->bil_pool_bytes, st, Hb, P.src_eye_w, plan->ltable_bil, plan->bil_dbl_tables, \
-                           sf, df, gpf, (unsigned long long)src_frame_stride, (unsigned long long)dst_frame_stride, windows, plan->bil_xy);    \
-    else                                                                                                                                       \
-    hipLaunchKernelGGL((pb_bilinear_double_hot_kernel<WMODE, 4>), grid, block, (size_t)plan->bil_pool_bytes, st, Hb, P.src_eye_w, plan->ltable_bil, plan->bil_dbl_tables, \
-                       sf, df, gpf, (unsigned long long)src_frame_stride, (unsigned long long)dst_frame_stride, windows, plan->bil_xy)
-                if (rows) PB_LAUNCH_BILINEAR_DOUBLE(1);
-                else if (plan->n_lat_tiles) PB_LAUNCH_BILINEAR_DOUBLE(2);
-                else PB_LAUNCH_BILINEAR_DOUBLE(0);
-#undef PB_LAUNCH_BILINEAR_DOUBLE
-            }
-            if (!plan->bil_xy) {  // no coordinate tables (they would not fit): the failed / listed tiles and the fix pixels from the float64 chain
-                const unsigned n_tiles64 = plan->n_fail_tiles + plan->n_bil_tiles;
-                const unsigned fix_blocks = 4u * n_tiles64 + (plan->n_fix_px + PB_BLOCK - 1) / PB_BLOCK;
-                if (fix_blocks)
-                    hipLaunchKernelGGL(pb_bilinear_double_fix_kernel, dim3(fix_blocks), dim3(PB_BLOCK), 0, st, P, plan->fail_tiles, (int)plan->n_fail_tiles, plan->bil_tiles,
-                                       (int)n_tiles64, plan->fix_px, (int)plan->n_fix_px, src_dev, dst_dev, n_frames, src_frame_stride, dst_frame_stride);
-            }
-        } else {
-            hipLaunchKernelGGL(pb_bilinear_double_kernel, dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, src_dev, dst_dev, n_frames, src_frame_stride,
-                               dst_frame_stride);
-        }
-        PB_HIP(hipGetLastError());
-        return PB_OK;
-    }
-    if (pb_use_fast(plan) && plan->ltable_bil && plan->launch_groups_bil > 0 && plan->bil_tiles) {
-        // launched like the nearest hot kernel: the mode's launch-order table, frames of a batch as a grid dimension, ONE launch;
-        // LEAN tiles take their taps from LDS windows, except for frames LDS-DMA cannot address (not 16-byte aligned)
-        const unsigned gpf = plan->launch_groups_bil * (4u / (unsigned)plan->bil_waves);  // real workgroups per frame
-        PbParams Pb = P;
-        Pb.win_budget = plan->bil_budget;
-        const dim3 block(64 * plan->bil_waves);
-        const int windows = plan->mode != PB_MODE_FAST_DIRECT && P.src.width < 32768 && P.src.height < 32768 &&
-                            ((((uintptr_t)src_dev) | src_frame_stride) & 15u) == 0;
-        const int per_launch = (int)(0x7FFFFFFFu / gpf);
-#define PB_LAUNCH_BILINEAR(KIND)                                                                                                     \
-    do {                                                                                                                             \
-        for (int f0 = 0; f0 < n_frames; f0 += per_launch) {                                                                          \
-            const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;                                                  \
-            if (plan->bil_waves == 2)                                                                                                \
-                hipLaunchKernelGGL((pb_bilinear_hot_kernel<KIND, 2>), dim3(gpf * (unsigned)nf), block, (size_t)plan->bil_pool_bytes, st, pb_hot_of_host(Pb), plan->ltable_bil, \
-                                   src_dev + (unsigned long long)f0 * src_frame_stride, dst_dev + (unsigned long long)f0 * dst_frame_stride, gpf, \
-                                   (unsigned long long)src_frame_stride, (unsigned long long)dst_frame_stride, windows, plan->bil_xy, plan->fix_px, \
-                                   plan->bil_fix_xy);                                                                                \
-            else                                                                                                                     \
-            hipLaunchKernelGGL((pb_bilinear_hot_kernel<KIND, 4>), dim3(gpf * (unsigned)nf), block, (size_t)plan->bil_pool_bytes, st, pb_hot_of_host(Pb), plan->ltable_bil, \
-                               src_dev + (unsigned long long)f0 * src_frame_stride, dst_dev + (unsigned long long)f0 * dst_frame_stride, gpf, \
-                               (unsigned long long)src_frame_stride, (unsigned long long)dst_frame_stride, windows, plan->bil_xy, plan->fix_px, \
-                               plan->bil_fix_xy);                                                                                    \
-        }                                                                                                                            \
-        const unsigned n64 = plan->n_fail_tiles + plan->n_bil_tiles; /* failed + listed tiles */                                    \
-        if (!plan->bil_xy && (n64 || plan->n_fix_px)) /* no coordinate tables (they would not fit): the float64 chain */             \
-            hipLaunchKernelGGL(pb_bilinear_fix_kernel<KIND>, dim3(4u * n64 + (plan->n_fix_px + PB_BLOCK - 1) / PB_BLOCK),            \
-                               dim3(PB_BLOCK), 0, st, P, plan->fail_tiles, 0, src_dev, dst_dev, n_frames, src_frame_stride,          \
-                               dst_frame_stride, (int)n64, plan->fix_px, (int)plan->n_fix_px, plan->bil_tiles,                       \
-                               (int)plan->n_fail_tiles);                                                                             \
-    } while (0)
-        if (P.src.kind == PB_KIND_PANO) PB_LAUNCH_BILINEAR(PB_KIND_PANO);
-        else PB_LAUNCH_BILINEAR(PB_KIND_CAMERA);
-#undef PB_LAUNCH_BILINEAR
-    } else {
-        if (P.src.kind == PB_KIND_PANO)
-            hipLaunchKernelGGL(pb_bilinear_fix_kernel<PB_KIND_PANO>, dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, nullptr, 1, src_dev,
-                               dst_dev, n_frames, src_frame_stride, dst_frame_stride);
-        else
-            hipLaunchKernelGGL(pb_bilinear_fix_kernel<PB_KIND_CAMERA>, dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, nullptr, 1, src_dev,
-                               dst_dev, n_frames, src_frame_stride, dst_frame_stride);
-    }
-    PB_HIP(hipGetLastError());
-    return PB_OK;
+    const int rc = pb_check_frames(plan, src_dev, dst_dev, n_frames, 1, src_frame_stride, dst_frame_stride);
+    if (rc != PB_OK || n_frames == 0) return rc;
+    return pb_launch(plan, pb_route(plan, PB_INTERP_BILINEAR, 1, 0, pb_aligned16(src_dev, src_frame_stride)), src_dev, dst_dev, n_frames,
+                     src_frame_stride, dst_frame_stride, (hipStream_t)stream);
 }
 
 int pb_index_map_i32(const pb_plan* plan, int32_t* idx_dev, double* weights_dev, void* stream) {
     if (!plan || !idx_dev) return pb_fail(PB_ERR_INVALID, "null argument");
+    const int rc = pb_check_device(plan);
+    if (rc != PB_OK) return rc;
     const PbParams& P = plan->P;
     hipStream_t st = (hipStream_t)stream;
     const unsigned blocks = pb_blocks((unsigned long long)P.dst.height * P.dst.width);
-    if (pb_use_fast(plan)) {
-        pb_launch_fast<1>(plan, nullptr, nullptr, 0, 0, 0, idx_dev, st);
-    } else if (P.src.kind == PB_KIND_PANO) {
-        PB_LAUNCH_BY_ROT(P.n_rot, pb_index_kernel, PB_KIND_PANO, dim3(blocks), dim3(PB_BLOCK), 0, st, P, idx_dev, weights_dev);
-    } else if (P.src.kind == PB_KIND_CAMERA) {
-        PB_LAUNCH_BY_ROT(P.n_rot, pb_index_kernel, PB_KIND_CAMERA, dim3(blocks), dim3(PB_BLOCK), 0, st, P, idx_dev, weights_dev);
-    } else {
-        PB_LAUNCH_BY_ROT(P.n_rot, pb_index_kernel, PB_KIND_DOUBLE, dim3(blocks), dim3(PB_BLOCK), 0, st, P, idx_dev, weights_dev);
-    }
+    if (pb_use_fast(plan))
+        pb_launch_direct<1>(plan, nullptr, nullptr, 0, 0, 0, idx_dev, st);
+    else
+        pb_pick_any_kind(P, [&](auto K) {
+            PB_LAUNCH_BY_ROT(P.n_rot, pb_index_kernel, K.value, dim3(blocks), dim3(PB_BLOCK), 0, st, P, idx_dev, weights_dev);
+        });
     PB_HIP(hipGetLastError());
     return PB_OK;
 }
@@ -1943,19 +1946,15 @@ int pb_sample_map_bilinear_px(const pb_proj* src, double* map_dev, int height, i
     pb_derive(P);
     const unsigned total = (unsigned)height * (unsigned)width;
     hipStream_t st = (hipStream_t)stream;
-#define PB_LAUNCH_MAP_BIL(KIND, SAMPLE)                                                                                                  \
-    hipLaunchKernelGGL((pb_sample_map_bilinear_kernel<KIND, SAMPLE>), dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, st, P, map_dev, total, dist_l_dev, \
-                       dist_r_dev, static_cast<const SAMPLE*>(img_dev), out_dev, channels)
-    if (sample_bytes == 1) {
-        if (P.src.kind == PB_KIND_PANO) PB_LAUNCH_MAP_BIL(PB_KIND_PANO, uint8_t);
-        else if (P.src.kind == PB_KIND_CAMERA) PB_LAUNCH_MAP_BIL(PB_KIND_CAMERA, uint8_t);
-        else PB_LAUNCH_MAP_BIL(PB_KIND_DOUBLE, uint8_t);
-    } else {
-        if (P.src.kind == PB_KIND_PANO) PB_LAUNCH_MAP_BIL(PB_KIND_PANO, uint16_t);
-        else if (P.src.kind == PB_KIND_CAMERA) PB_LAUNCH_MAP_BIL(PB_KIND_CAMERA, uint16_t);
-        else PB_LAUNCH_MAP_BIL(PB_KIND_DOUBLE, uint16_t);
-    }
-#undef PB_LAUNCH_MAP_BIL
+    const auto launch = [&](auto* sample) {  // (the sample type: uint8_t or uint16_t)
+        using SAMPLE = std::remove_pointer_t<decltype(sample)>;
+        pb_pick_any_kind(P, [&](auto K) {
+            hipLaunchKernelGGL((pb_sample_map_bilinear_kernel<K.value, SAMPLE>), dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, st, P, map_dev, total, dist_l_dev,
+                               dist_r_dev, static_cast<const SAMPLE*>(img_dev), out_dev, channels);
+        });
+    };
+    if (sample_bytes == 1) launch((uint8_t*)nullptr);
+    else launch((uint16_t*)nullptr);
     PB_HIP(hipGetLastError());
     return PB_OK;
 }
@@ -2396,9 +2395,6 @@ int pb_remap_batch_sharded(const pb_comm* comm, const pb_plan* plan, const uint8
     if (first_out) *first_out = first;
     if (count_out) *count_out = count;
     if (count == 0) return PB_OK;
-    const PbParams& P = plan->P;
-    if (!src_frame_stride) src_frame_stride = 3ull * P.src.height * P.src.width;
-    if (!dst_frame_stride) dst_frame_stride = 3ull * P.dst.height * P.dst.width;
     // this rank's contiguous share of the batch, addressed in the caller's (rank-local) buffers from frame 0 on
     return pb_remap_u8(plan, src_dev, dst_dev, count, src_frame_stride, dst_frame_stride, stream);
 }
@@ -2514,14 +2510,6 @@ int pb_host_unregister(void* host_ptr) {
 }  // extern "C"
 
 // ---- supersampled remapping ----------------------------------------------------------------------------------------
-// Can the fused kernel take a call of this plan (16-byte aligned frames assumed)?  Exactly the plans pb_launch_fast sends through
-// pb_hot_win_kernel: prepared single-source plans under AUTO / FAST with their launch-order table, nearest mode.
-static bool pb_ss_fused_ok(const pb_plan* pl, int interpolation, unsigned flags) {
-    const PbParams& P = pl->P;
-    return interpolation == PB_INTERP_NEAREST && !(flags & PB_SS_GENERIC) && P.src.kind != PB_KIND_DOUBLE && !pl->dbl_ready && pb_use_fast(pl) &&
-           pl->ltable && pl->P_dev && pl->launch_groups > 0 && pl->mode != PB_MODE_FAST_DIRECT && P.src.width < 32768 && P.src.height < 32768;
-}
-
 static int pb_ss_check(const pb_plan* plan, int n, int interpolation) {
     if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
     if (n != 2 && n != 4) return pb_fail(PB_ERR_INVALID, "supersample factor must be 2 or 4");
@@ -2549,48 +2537,30 @@ int pb_remap_ss_workspace(const pb_plan* plan, int n, int interpolation, unsigne
     if (!bytes) return pb_fail(PB_ERR_INVALID, "null argument");
     const int rc = pb_ss_check(plan, n, interpolation);
     if (rc) return rc;
-    *bytes = pb_ss_fused_ok(plan, interpolation, flags) ? 0 : 3ull * plan->P.dst.height * plan->P.dst.width;
+    // (16-byte aligned frames assumed: the caller's unaligned frames need the workspace too)
+    *bytes = pb_route(plan, interpolation, n, flags, true).kind == PbRoute::SS_FUSED ? 0 : 3ull * plan->P.dst.height * plan->P.dst.width;
     return PB_OK;
 }
 
 int pb_remap_ss_u8(const pb_plan* plan, int n, int interpolation, const uint8_t* src_dev, uint8_t* dst_dev, int n_frames, size_t src_frame_stride,
                    size_t dst_frame_stride, void* workspace_dev, size_t workspace_bytes, unsigned flags, void* stream) {
-    const int rc = pb_ss_check(plan, n, interpolation);
-    if (rc) return rc;
-    if (!src_dev || !dst_dev) return pb_fail(PB_ERR_INVALID, "null argument");
-    if (n_frames < 0) return pb_fail(PB_ERR_INVALID, "negative frame count");
-    if (n_frames == 0) return PB_OK;
-    if (plan->device >= 0) {
-        int dev = -1;
-        PB_HIP(hipGetDevice(&dev));
-        if (dev != plan->device) return pb_fail(PB_ERR_INVALID, "plan was prepared on another device; create one plan per device");
-    }
+    int rc = pb_ss_check(plan, n, interpolation);
+    if (rc == PB_OK) rc = pb_check_frames(plan, src_dev, dst_dev, n_frames, n, src_frame_stride, dst_frame_stride);
+    if (rc != PB_OK || n_frames == 0) return rc;
     const PbParams& P = plan->P;
-    const unsigned Ho = (unsigned)P.dst.height / n, Wo = (unsigned)P.dst.width / n;
-    const unsigned long long out_bytes = 3ull * Ho * Wo, src_bytes = 3ull * P.src.height * P.src.width;
-    if (!src_frame_stride) src_frame_stride = src_bytes;
-    if (!dst_frame_stride) dst_frame_stride = out_bytes;
-    if (dst_frame_stride < out_bytes) return pb_fail(PB_ERR_INVALID, "dst_frame_stride smaller than a frame");
-    if (n_frames > 1 && src_frame_stride < src_bytes) return pb_fail(PB_ERR_INVALID, "src_frame_stride smaller than a frame");
     hipStream_t st = (hipStream_t)stream;
-    if (pb_ss_fused_ok(plan, interpolation, flags) && ((((uintptr_t)src_dev) | src_frame_stride) & 15u) == 0) {
+    const bool aligned = pb_aligned16(src_dev, src_frame_stride);
+    if (pb_route(plan, interpolation, n, flags, aligned).kind == PbRoute::SS_FUSED) {
         const unsigned gpf = plan->launch_groups;
-        const size_t lds = pb_window_lds_bytes(P);
-        const int per_launch = (int)(0x7FFFFFFFu / gpf);
-        for (int f0 = 0; f0 < n_frames; f0 += per_launch) {
-            const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
-            const dim3 bgrid(gpf * (unsigned)nf), block(64 * PB_TILE_WAVES);
-            const uint8_t* sf = src_dev + (unsigned long long)f0 * src_frame_stride;
-            uint8_t* df = dst_dev + (unsigned long long)f0 * dst_frame_stride;
-#define PB_LAUNCH_SS(KIND, NS)                                                                                                     \
-    hipLaunchKernelGGL((pb_ss_win_kernel<KIND, NS>), bgrid, block, lds, st, (const PbParams*)plan->P_dev, pb_hot_of_host(P), plan->ltable, sf, df, \
-                       gpf, (unsigned long long)src_frame_stride, (unsigned long long)dst_frame_stride, plan->idx_tab, plan->fix_px, plan->fix_idx)
-            if (P.src.kind == PB_KIND_PANO && n == 2) PB_LAUNCH_SS(PB_KIND_PANO, 2);
-            else if (P.src.kind == PB_KIND_PANO) PB_LAUNCH_SS(PB_KIND_PANO, 4);
-            else if (n == 2) PB_LAUNCH_SS(PB_KIND_CAMERA, 2);
-            else PB_LAUNCH_SS(PB_KIND_CAMERA, 4);
-#undef PB_LAUNCH_SS
-        }
+        pb_each_launch(src_dev, dst_dev, n_frames, src_frame_stride, dst_frame_stride, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
+            pb_pick_kind(P, [&](auto K) {
+                pb_pick<2, 4>(n == 2, [&](auto NS) {
+                    hipLaunchKernelGGL((pb_ss_win_kernel<K.value, NS.value>), dim3(gpf * (unsigned)nf), dim3(64 * PB_TILE_WAVES), pb_window_lds_bytes(P), st,
+                                       (const PbParams*)plan->P_dev, pb_hot_of_host(P), plan->ltable, sf, df, gpf, (unsigned long long)src_frame_stride,
+                                       (unsigned long long)dst_frame_stride, plan->idx_tab, plan->fix_px, plan->fix_idx);
+                });
+            });
+        });
         PB_HIP(hipGetLastError());
         return PB_OK;
     }
@@ -2599,12 +2569,11 @@ int pb_remap_ss_u8(const pb_plan* plan, int n, int interpolation, const uint8_t*
     if (!workspace_dev || workspace_bytes < ws_need)
         return pb_fail(PB_ERR_INVALID, "workspace smaller than one n x frame (pb_remap_ss_workspace; frames that are not 16-byte aligned need it too)");
     uint8_t* ws = (uint8_t*)workspace_dev;
+    const PbRoute frame_route = pb_route(plan, interpolation, 1, 0, aligned);  // (every frame of the batch is aligned alike)
     for (int f = 0; f < n_frames; ++f) {
-        const uint8_t* sf = src_dev + (unsigned long long)f * src_frame_stride;
-        const int r = interpolation == PB_INTERP_NEAREST ? pb_remap_u8(plan, sf, ws, 1, src_frame_stride, 0, stream)
-                                                         : pb_remap_bilinear_u8(plan, sf, ws, 1, src_frame_stride, 0, stream);
-        if (r) return r;
-        pb_box_reduce_launch(ws, dst_dev + (unsigned long long)f * dst_frame_stride, Ho, Wo, 3, 1, n, 1, st);
+        rc = pb_launch(plan, frame_route, src_dev + (unsigned long long)f * src_frame_stride, ws, 1, src_frame_stride, ws_need, st);
+        if (rc != PB_OK) return rc;
+        pb_box_reduce_launch(ws, dst_dev + (unsigned long long)f * dst_frame_stride, (unsigned)P.dst.height / n, (unsigned)P.dst.width / n, 3, 1, n, 1, st);
         PB_HIP(hipGetLastError());
     }
     return PB_OK;

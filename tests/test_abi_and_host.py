@@ -61,6 +61,38 @@ def test_abi_argument_validation_without_gpu():
     lib.pb_plan_destroy(h)
 
 
+def test_remap_entry_points_share_their_argument_checks():
+    """Every frame-launching entry point refuses null frames and a negative frame count with the same messages.  A deferred plan has
+    no device, and only null pointers are passed: a check that wrongly let a call through could not start a launch."""
+    lib = nat.load()
+    h = ctypes.c_void_p()
+    good = nat.make_proj(nat.KIND_PANO, 4, 8)
+    assert lib.pb_plan_create_ex(ctypes.byref(good), None, 0, ctypes.byref(good), nat.PLAN_DEFER, 0, ctypes.byref(h)) == 0
+    calls = {
+        "pb_remap_u8": lambda n: lib.pb_remap_u8(h, None, None, n, 0, 0, None),
+        "pb_remap_bilinear_u8": lambda n: lib.pb_remap_bilinear_u8(h, None, None, n, 0, 0, None),
+        "pb_remap_ss_u8": lambda n: lib.pb_remap_ss_u8(h, 2, nat.INTERP_IDS["nearest"], None, None, n, 0, 0, None, 0, 0, None),
+        # (pointer tables, which may be null for an empty batch: a negative count is reported as such)
+        "pb_remap_u8v": lambda n: lib.pb_remap_u8v(h, None, None, n, None),
+    }
+    try:
+        for name, call in calls.items():
+            for n in (1, 3):
+                assert call(n) == -1 and lib.pb_last_error() == b"null argument", (name, n)
+            if name == "pb_remap_u8v":
+                assert call(-1) == -1 and lib.pb_last_error() == b"negative frame count", name
+                assert call(0) == 0, name
+            else:
+                assert call(-1) == -1 and lib.pb_last_error() == b"null argument", name
+                assert call(0) == -1 and lib.pb_last_error() == b"null argument", name
+        # the null plan, before anything else
+        assert lib.pb_remap_u8(None, None, None, -1, 0, 0, None) == -1 and lib.pb_last_error() == b"null argument"
+        assert lib.pb_remap_u8v(None, None, None, 0, None) == -1 and lib.pb_last_error() == b"null argument"
+        assert lib.pb_index_map_i32(h, None, None, None) == -1 and lib.pb_last_error() == b"null argument"
+    finally:
+        lib.pb_plan_destroy(h)
+
+
 @pytest.mark.parametrize("case", small_cases(), ids=lambda c: c.name)
 def test_host_scalars_match_reference_bits(case):
     n = case.name

@@ -349,6 +349,19 @@ def test_stride_validation_and_stream_copy():
     assert lib.pb_remap_u8(plan.handle, frames.data_ptr(), out.data_ptr(), 2, 16, 0, None) == -1
     assert b"src_frame_stride" in lib.pb_last_error()
     assert lib.pb_remap_u8(plan.handle, frames.data_ptr(), out.data_ptr(), 2, 0, 16, None) == -1
+    # the bilinear and supersampled entry points check their strides alike; a supersampled output frame is H/n x W/n
+    small_src, small_dst = b"src_frame_stride smaller than a frame", b"dst_frame_stride smaller than a frame"
+    assert lib.pb_remap_bilinear_u8(plan.handle, frames.data_ptr(), out.data_ptr(), 2, 16, 0, None) == -1
+    assert lib.pb_last_error() == small_src
+    assert lib.pb_remap_bilinear_u8(plan.handle, frames.data_ptr(), out.data_ptr(), 2, 0, 16, None) == -1
+    assert lib.pb_last_error() == small_dst
+    for n in (2, 4):
+        ss_frame = 3 * (d.height // n) * (d.width // n)
+        args = (plan.handle, n, nat.INTERP_IDS["nearest"], frames.data_ptr(), out.data_ptr(), 2)
+        assert lib.pb_remap_ss_u8(*args, 16, 0, None, 0, 0, None) == -1
+        assert lib.pb_last_error() == small_src
+        assert lib.pb_remap_ss_u8(*args, 0, ss_frame - 1, None, 0, 0, None) == -1
+        assert lib.pb_last_error() == small_dst
     a = torch.randint(0, 255, (1 << 20,), dtype=torch.uint8, device="cuda")
     b = torch.zeros_like(a)
     nat.check(lib.pb_stream_copy(b.data_ptr(), a.data_ptr(), a.numel(), None))
