@@ -232,6 +232,18 @@ int pb_remap_u8v(const pb_plan* plan, const uint8_t* const* src_dev, uint8_t* co
 int pb_remap_bilinear_u8(const pb_plan* plan, const uint8_t* src_dev, uint8_t* dst_dev, int n_frames,
                          size_t src_frame_stride, size_t dst_frame_stride, void* stream);
 
+/* OPT-IN Catmull-Rom sampling (ABI 5, additive), no reference counterpart: the bilinear definition above with a 4 x 4
+ * footprint.  s = f - 0.5, i0 = floor(s), t = s - i0; taps rows i0 - 1 .. i0 + 2 x columns j0 - 1 .. j0 + 2, clamped like bilinear's
+ * (panorama columns wrap, an eye's taps stay in its half); Keys' cubic weights with a = -0.5; row sums, then the column sum; round half to
+ * even, clipped to [0, 255] (the cubic overshoots).  Black exactly where the bilinear mode is black; a double-fisheye source blends the two
+ * eyes' rounded samples like the reference.  pb_remap_bilinear_u8's contract: pb_remap_u8's argument checks and messages, asynchronous,
+ * no allocation, no synchronisation (graph-capture safe).  Prepared single-source plans (AUTO / FAST, built with the bilinear mode's tables
+ * - PB_PLAN_BILINEAR) take one tile-kernel launch per batch, float32 arithmetic on coordinates certified to 1/1024 px: within 1 LSB of the
+ * definition.  Deferred plans, PB_MODE_FAITHFUL, plans without those tables and double-fisheye sources evaluate the definition per pixel in
+ * float64 (its bytes exactly).  The supersampled entry points do not take this mode. */
+int pb_remap_catmull_rom_u8(const pb_plan* plan, const uint8_t* src_dev, uint8_t* dst_dev, int n_frames,
+                            size_t src_frame_stride, size_t dst_frame_stride, void* stream);
+
 /* SUPERSAMPLED REMAPPING (ABI 5, additive).  Output pixel (i, j) is, per channel, the round-half-to-even mean of the n x n block
  * S[n i : n i + n, n j : n j + n] of S = the remap of the n x destination: the same kind and lens with image (n H, n W) and, for a camera,
  * magnitude n x (a double fisheye's magnitude = height / 2 scales by itself); n in {2, 4}, a power of two, so its f_distance is exactly
@@ -329,6 +341,10 @@ int pb_index_from_map_i32(const pb_proj* src, double* map_dev, int height, int w
 int pb_sample_map_bilinear_px(const pb_proj* src, double* map_dev, int height, int width, const double* dist_l_dev, const double* dist_r_dev,
                               const void* img_dev, void* out_dev, int channels, int sample_bytes, void* stream);
 int pb_sample_map_bilinear_u8(const pb_proj* src, double* map_dev, int height, int width, const uint8_t* src_dev, uint8_t* dst_dev, void* stream);
+/* The opt-in Catmull-Rom mode (pb_remap_catmull_rom_u8's definition) on a MATERIALISED map and on ANY image: pb_sample_map_bilinear_px's
+ * arguments, checks and side effects, evaluated per pixel in float64 in the definition's order - its bytes exactly. */
+int pb_sample_map_catmull_rom_px(const pb_proj* src, double* map_dev, int height, int width, const double* dist_l_dev, const double* dist_r_dev,
+                                 const void* img_dev, void* out_dev, int channels, int sample_bytes, void* stream);
 /* dst[p] = idx[p] < 0 ? 0 : src[idx[p]], bytes_per_px bytes each (1..64). */
 int pb_gather_px(const int32_t* idx_dev, const void* src_dev, void* dst_dev, size_t n_px, int bytes_per_px, void* stream);
 /* The double-fisheye blend for `channels` interleaved samples of 1 or 2 bytes (unsigned): per channel

@@ -159,7 +159,9 @@ def _ss_bytes(plan, supersample: int, interpolation: str, src_ptr: int) -> int:
 
 def remap_ndarray(plan: nat.Plan, image: np.ndarray, interpolation: str = "nearest", device: int | None = None, supersample: int = 1) -> np.ndarray:
     """One frame: uint8 (h, w, 3) ndarray -> fresh uint8 (H, W, 3) ndarray (upload, ONE kernel launch, download).  ``supersample`` n: `plan`
-    is the n x destination's and the result (H / n, W / n, 3) holds the n x n block means (``Plan.launch``)."""
+    is the n x destination's and the result (H / n, W / n, 3) holds the n x n block means (``Plan.launch``).  ``interpolation``: "nearest",
+    "bilinear" or "catmull-rom" (not supersampled)."""
+    nat.check_interpolation(interpolation, supersample)
     oh, ow = _out_shape(plan, supersample)
     nat.require_gpu()
     pipe = pipe_for(device)
@@ -181,6 +183,7 @@ def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, i
     output over PCIe straight into frame k's result ndarray (page-locked, device-visible), through `depth` rotating device input
     buffers.  Yields uint8 (H, W, 3) ndarrays in order (page-locked, recycled when dropped).  ``supersample`` n: `plan` is the n x
     destination's, the results are (H / n, W / n, 3) block means - the fused kernel stores only those over PCIe."""
+    nat.check_interpolation(interpolation, supersample)
     oh, ow = _out_shape(plan, supersample)
     nat.require_gpu()
     depth = max(2, int(depth))

@@ -54,6 +54,7 @@ PB_MAX_ROTATIONS = 8
 PLAN_DEFER, PLAN_TUNE, PLAN_MATH_SVML, PLAN_MATH_LIBM, PLAN_NO_BILINEAR, PLAN_BILINEAR = 1, 2, 4, 8, 16, 32
 MODE_AUTO, MODE_FAITHFUL, MODE_FAST, MODE_FAST_DIRECT = 0, 1, 2, 3
 INTERP_IDS = {"nearest": 0, "bilinear": 1}
+INTERPOLATIONS = ("nearest", "bilinear", "catmull-rom")  # every mode a plain remap takes (INTERP_IDS: the supersampled ABI's ids)
 SS_GENERIC = 1  # pb_remap_ss_u8: force the generic path (tests, A/B measurement)
 SUPERSAMPLE_FACTORS = (1, 2, 4)
 # the largest map any pb_proj may describe (photonbend_hip.hip, pb_end_ok): h * w <= (2^31 - 1) / 4
@@ -118,6 +119,7 @@ SIGNATURES = {
     "pb_remap_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_u8v": (C.c_int, [_VP, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, _VP]),
     "pb_remap_bilinear_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
+    "pb_remap_catmull_rom_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_ss_workspace": (C.c_int, [_VP, C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_size_t)]),
     "pb_remap_ss_u8": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP, C.c_size_t, C.c_uint, _VP]),
     "pb_box_reduce": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
@@ -128,6 +130,7 @@ SIGNATURES = {
     "pb_index_from_map_i32": (C.c_int, [C.POINTER(pb_proj), _VP, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP]),
     "pb_sample_map_bilinear_px": (C.c_int, [C.POINTER(pb_proj), _VP, C.c_int, C.c_int, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP]),
     "pb_sample_map_bilinear_u8": (C.c_int, [C.POINTER(pb_proj), _VP, C.c_int, C.c_int, _VP, _VP, _VP]),
+    "pb_sample_map_catmull_rom_px": (C.c_int, [C.POINTER(pb_proj), _VP, C.c_int, C.c_int, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP]),
     "pb_gather_px": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_int, _VP]),
     "pb_gather_blend_u8": (C.c_int, [_VP, _VP, _VP, _VP, C.c_size_t, C.c_int, C.c_int, _VP]),
     "pb_map_projection_u8": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, _VP]),
@@ -198,6 +201,12 @@ def load() -> C.CDLL:
             MATH_FLAVOUR = theirs
         _lib = lib
     return _lib
+
+
+def check_interpolation(interpolation: str, supersample: int = 1) -> None:
+    """The rule the entry points check before any library call: catmull-rom is not supersampled (ValueError)."""
+    if interpolation == "catmull-rom" and check_supersample(supersample) > 1:
+        raise ValueError("catmull-rom sampling is not supersampled: pass supersample=1")
 
 
 def check_supersample(n) -> int:
@@ -402,7 +411,8 @@ class Plan:
                 self._gate = None
 
     def ensure_bilinear(self) -> None:
-        """The opt-in bilinear mode's tables, built once when the mode is first used (synchronous).  Launches of this plan made through
+        """The opt-in bilinear mode's tables (which the Catmull-Rom mode reads too), built once when either mode is first used
+        (synchronous: it waits for the device).  Launches of this plan made through
         this object on other threads wait while the tables are built; launches through the raw ``handle`` follow the C ABI's rule
         (none in flight, as for ``set_window_budget``).  A deferred plan stays deferred - its launches run the float64 kernels of
         either mode - and remembers the wish for ``prepare()``."""
@@ -504,11 +514,13 @@ class Plan:
         one, a call that needs it takes a temporary buffer - from PyTorch's stream-ordered allocator where torch is installed, else a
         DeviceArray that is freed after the call (on a stream other than the default one the call then synchronises that stream)."""
         n = check_supersample(supersample)
+        cr = interpolation == "catmull-rom"
+        check_interpolation(interpolation, n)
         if interpolation != "nearest":
-            self.ensure_bilinear()
+            self.ensure_bilinear()  # (catmull-rom reads the bilinear mode's tables too)
         st = current_stream() if stream is None else stream
         if n == 1:
-            fn = load().pb_remap_u8 if interpolation == "nearest" else load().pb_remap_bilinear_u8
+            fn = load().pb_remap_u8 if interpolation == "nearest" else (load().pb_remap_catmull_rom_u8 if cr else load().pb_remap_bilinear_u8)
             self._gated(fn, self._h, src_ptr, dst_ptr, int(n_frames), int(src_stride), int(dst_stride), st)
             return
         interp, flags = INTERP_IDS[interpolation], (SS_GENERIC if generic else 0)
@@ -563,11 +575,13 @@ class Plan:
 
     def remap(self, src, out=None, interpolation: str = "nearest", supersample: int = 1, generic: bool = False, workspace=None):
         """src: uint8 device array (h, w, 3) or (N, h, w, 3) -> (H, W, 3) / (N, H, W, 3), of src's kind.
-        interpolation: "nearest" (the reference's truncating sample) or the opt-in "bilinear".
-        supersample: n in (2, 4) on a plan of the n x destination -> (H / n, W / n, 3) frames of n x n block means (see ``launch``)."""
-        if interpolation not in ("nearest", "bilinear"):
-            raise ValueError("interpolation must be 'nearest' or 'bilinear'")
+        interpolation: "nearest" (the reference's truncating sample), the opt-in "bilinear" or the opt-in "catmull-rom".
+        supersample: n in (2, 4) on a plan of the n x destination -> (H / n, W / n, 3) frames of n x n block means (see ``launch``;
+        nearest and bilinear only)."""
+        if interpolation not in INTERPOLATIONS:
+            raise ValueError("interpolation must be 'nearest', 'bilinear' or 'catmull-rom'")
         ss = check_supersample(supersample)
+        check_interpolation(interpolation, ss)
         oh, ow = self.out_shape(ss)
         require_gpu()
         if not is_device_array(src):
@@ -760,6 +774,20 @@ def sample_map_bilinear(src: pb_proj, cmap, img, channels: int, dt: np.dtype, di
         check(load().pb_sample_map_bilinear_px(C.byref(src), cmap.data_ptr(), H, W, dist_l.data_ptr() if dist_l is not None else None,
                                                dist_r.data_ptr() if dist_r is not None else None, img.data_ptr(), out.data_ptr(), int(channels),
                                                dt.itemsize, current_stream()))
+    return out
+
+
+def sample_map_catmull_rom(src: pb_proj, cmap, img, channels: int, dt: np.dtype, dist_l=None, dist_r=None):
+    """The opt-in Catmull-Rom mode from a materialised float64 map, like ``sample_map_bilinear`` (pb_sample_map_catmull_rom_px)."""
+    require_gpu()
+    H, W = int(cmap.shape[0]), int(cmap.shape[1])
+    dt = np.dtype(dt)
+    out_dt = np.dtype(np.uint8) if src.kind == KIND_DOUBLE else dt
+    out = empty((H, W, channels), out_dt, like=cmap)
+    with _on(cmap):
+        check(load().pb_sample_map_catmull_rom_px(C.byref(src), cmap.data_ptr(), H, W, dist_l.data_ptr() if dist_l is not None else None,
+                                                  dist_r.data_ptr() if dist_r is not None else None, img.data_ptr(), out.data_ptr(), int(channels),
+                                                  dt.itemsize, current_stream()))
     return out
 
 

@@ -30,5 +30,7 @@ def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, i
                  supersample: int = 1) -> Iterator[np.ndarray]:
     """Remaps an iterable of uint8 (h, w, 3) ndarrays with ``plan``; yields uint8 (H, W, 3) ndarrays in order
     (``_hostpipe.remap_frames``: upload stream + launch stream, page-locked results the kernel writes directly, no PyTorch).
-    ``supersample`` n: ``plan`` came from ``plan_for(..., supersample=n)``; the frames are (H, W, 3) block means of its n x output."""
+    ``supersample`` n: ``plan`` came from ``plan_for(..., supersample=n)``; the frames are (H, W, 3) block means of its n x output.
+    ``interpolation``: "nearest", "bilinear" or "catmull-rom" (not supersampled) - checked here, before the first frame."""
+    nat.check_interpolation(interpolation, supersample)
     return _hostpipe.remap_frames(plan, frames, depth, interpolation, supersample)

@@ -376,8 +376,13 @@ class _GpuProjection:
         ``interpolation="bilinear"`` is an opt-in extension with no reference counterpart (the reference truncates to the nearest
         pixel).  A lazy map + a uint8 RGB image + built-in lenses take the tile kernels (one launch); a materialised or edited map, a
         grey / RGBA / 16-bit image or a Lens of user callables take the mode's definition per pixel from the map
-        (pb_sample_map_bilinear_px) - same definition, float64 arithmetic."""
+        (pb_sample_map_bilinear_px) - same definition, float64 arithmetic.
+
+        ``interpolation="catmull-rom"`` (opt-in): the same with a 4 x 4 footprint and Keys' cubic weights (a = -0.5) - sharp
+        where the source is magnified.  Served like bilinear (pb_remap_catmull_rom_u8 / pb_sample_map_catmull_rom_px); not supersampled."""
         n = _map_supersample(coordinate_map, supersample)
+        if interpolation == "catmull-rom" and n > 1:
+            raise ValueError(f"catmull-rom sampling is not supersampled (supersample={n}): use nearest or bilinear, or a plain map")
         if n == 1:
             return self._process(coordinate_map, interpolation)
         return self._process_ss(coordinate_map, interpolation, n)
@@ -390,12 +395,13 @@ class _GpuProjection:
         rgb8 = tail == (3,) and dt == np.dtype(np.uint8)
         custom_src = src.kind != nat.KIND_PANO and src.lens == nat.LENS_CUSTOM
         lazy = isinstance(coordinate_map, CoordinateMap) and coordinate_map.is_lazy
-        bilinear = interpolation != "nearest"
+        bilinear = interpolation != "nearest"  # (an interpolating mode: bilinear or catmull-rom)
+        catmull_rom = interpolation == "catmull-rom"
         if bilinear:
-            if interpolation != "bilinear":
-                raise ValueError("interpolation must be 'nearest' or 'bilinear'")
+            if interpolation != "bilinear" and not catmull_rom:
+                raise ValueError("interpolation must be 'nearest', 'bilinear' or 'catmull-rom'")
             if dt not in (np.dtype(np.uint8), np.dtype(np.uint16)):
-                raise NotImplementedError(f"bilinear sampling takes 8- or 16-bit unsigned samples, got {dt}")
+                raise NotImplementedError(f"{interpolation} sampling takes 8- or 16-bit unsigned samples, got {dt}")
             if src.kind == nat.KIND_DOUBLE and len(tail) != 1:
                 # (the reference's blend cannot broadcast (H, W) samples against its (H, W, 1) factor maps either)
                 H_, W_ = tuple(coordinate_map.shape[:2])
@@ -457,7 +463,8 @@ class _GpuProjection:
                 # layout, a source Lens of user callables - everything the tile kernels do not take
                 dl, dr = self._distance_planes(src, dmap)
                 channels = int(np.prod(tail, dtype=np.int64))
-                out = nat.sample_map_bilinear(src, dmap, img, channels, dt, dl, dr)
+                sample = nat.sample_map_catmull_rom if catmull_rom else nat.sample_map_bilinear
+                out = sample(src, dmap, img, channels, dt, dl, dr)
                 out_dt = np.dtype(np.uint8) if src.kind == nat.KIND_DOUBLE else dt
                 H_, W_ = int(dmap.shape[0]), int(dmap.shape[1])
                 out = out.reshape((H_, W_) + tuple(tail)) if nat.is_tensor(out) else out.view(out_dt, (H_, W_) + tuple(tail))

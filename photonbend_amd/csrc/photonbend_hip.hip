@@ -33,6 +33,7 @@
 #include "pb_kernels_double.hpp"
 #include "pb_kernels_bilinear.hpp"
 #include "pb_kernels_supersample.hpp"
+#include "pb_kernels_catmull_rom.hpp"
 
 #define PB_DOUBLE_FRAMES_PER_WAVE 1  // frames a double-source wave loops over (the rest of a batch is a grid dimension)
 struct pb_plan {
@@ -686,10 +687,14 @@ struct PbRoute {
         BIL_FLOAT64,         // bilinear: pb_bilinear_fix_kernel over every pixel
         SS_FUSED,            // supersampled: pb_ss_win_kernel
         SS_GENERIC,          // supersampled: frame by frame the route of n = 1 into a workspace, then pb_box_reduce_kernel
+        CR_TILES,            // catmull-rom: pb_catmull_rom_hot_kernel (+ pb_catmull_rom_fix_kernel over the listed tiles without coordinate tables)
+        CR_FLOAT64,          // catmull-rom: pb_catmull_rom_fix_kernel over every pixel
+        CR_DOUBLE_FLOAT64,   // catmull-rom: pb_catmull_rom_double_kernel
     } kind;
     bool windows;  // BIL_DOUBLE / BIL_TILES: LEAN tiles gather from LDS windows
 };
 static bool pb_aligned16(const void* src, unsigned long long stride) { return ((((uintptr_t)src) | stride) & 15u) == 0; }
+#define PB_INTERP_CATMULL_ROM 2  // (a routing id of pb_remap_catmull_rom_u8 only: the supersampled entry points take 0 and 1)
 static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned flags, bool aligned) {
     const PbParams& P = pl->P;
     if (n > 1) {
@@ -698,6 +703,10 @@ static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned fl
     }
     const bool tiled = pl->mode != PB_MODE_FAITHFUL;
     const bool windows = pl->mode != PB_MODE_FAST_DIRECT && P.src.width < 32768 && P.src.height < 32768 && aligned;
+    if (interpolation == PB_INTERP_CATMULL_ROM) {  // (the bilinear mode's tables; no LDS windows)
+        if (P.src.kind == PB_KIND_DOUBLE) return {PbRoute::CR_DOUBLE_FLOAT64, false};
+        return (pb_use_fast(pl) && pl->ltable_bil && pl->bil_tiles) ? PbRoute{PbRoute::CR_TILES, false} : PbRoute{PbRoute::CR_FLOAT64, false};
+    }
     if (interpolation == PB_INTERP_BILINEAR) {
         if (P.src.kind == PB_KIND_DOUBLE)
             return (tiled && pl->dbl_ready && pl->ltable_bil && pl->bil_tiles && pl->bil_dbl_tables) ? PbRoute{PbRoute::BIL_DOUBLE, windows}
@@ -865,6 +874,30 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
             pb_pick_kind(P, [&](auto K) {
                 hipLaunchKernelGGL(pb_bilinear_fix_kernel<K.value>, dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, nullptr, 1, src, dst, n_frames, ss, ds);
             });
+            break;
+        case PbRoute::CR_TILES: {
+            // the bilinear mode's launch-order table read with four waves per workgroup: launch_groups_bil workgroups per frame
+            const unsigned gpf = pl->launch_groups_bil;
+            pb_pick_kind(P, [&](auto K) {
+                pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
+                    hipLaunchKernelGGL((pb_catmull_rom_hot_kernel<K.value>), dim3(gpf * (unsigned)nf), dim3(64 * PB_CR_WAVES), 0, st, pb_hot_of_host(P),
+                                       pl->ltable_bil, sf, df, gpf, ss, ds, pl->bil_xy, pl->fix_px, pl->bil_fix_xy);
+                });
+                const unsigned n64 = pl->n_fail_tiles + pl->n_bil_tiles;  // failed + listed tiles
+                if (!pl->bil_xy && (n64 || pl->n_fix_px))  // no coordinate tables (they would not fit): the float64 chain
+                    hipLaunchKernelGGL(pb_catmull_rom_fix_kernel<K.value>, dim3(4u * n64 + (pl->n_fix_px + PB_BLOCK - 1) / PB_BLOCK), dim3(PB_BLOCK), 0, st,
+                                       P, pl->fail_tiles, 0, src, dst, n_frames, ss, ds, (int)n64, pl->fix_px, (int)pl->n_fix_px, pl->bil_tiles,
+                                       (int)pl->n_fail_tiles);
+            });
+            break;
+        }
+        case PbRoute::CR_FLOAT64:
+            pb_pick_kind(P, [&](auto K) {
+                hipLaunchKernelGGL(pb_catmull_rom_fix_kernel<K.value>, dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, nullptr, 1, src, dst, n_frames, ss, ds);
+            });
+            break;
+        case PbRoute::CR_DOUBLE_FLOAT64:
+            hipLaunchKernelGGL(pb_catmull_rom_double_kernel, dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, src, dst, n_frames, ss, ds);
             break;
         default:
             return pb_fail(PB_ERR_INVALID, "not a route of one frame");  // (the supersampled routes: pb_remap_ss_u8)
@@ -1719,6 +1752,14 @@ int pb_remap_bilinear_u8(const pb_plan* plan, const uint8_t* src_dev, uint8_t* d
                      src_frame_stride, dst_frame_stride, (hipStream_t)stream);
 }
 
+int pb_remap_catmull_rom_u8(const pb_plan* plan, const uint8_t* src_dev, uint8_t* dst_dev, int n_frames, size_t src_frame_stride,
+                            size_t dst_frame_stride, void* stream) {
+    const int rc = pb_check_frames(plan, src_dev, dst_dev, n_frames, 1, src_frame_stride, dst_frame_stride);
+    if (rc != PB_OK || n_frames == 0) return rc;
+    return pb_launch(plan, pb_route(plan, PB_INTERP_CATMULL_ROM, 1, 0, pb_aligned16(src_dev, src_frame_stride)), src_dev, dst_dev, n_frames,
+                     src_frame_stride, dst_frame_stride, (hipStream_t)stream);
+}
+
 int pb_index_map_i32(const pb_plan* plan, int32_t* idx_dev, double* weights_dev, void* stream) {
     if (!plan || !idx_dev) return pb_fail(PB_ERR_INVALID, "null argument");
     const int rc = pb_check_device(plan);
@@ -1924,8 +1965,12 @@ int pb_index_from_map_i32(const pb_proj* src, double* map_dev, int height, int w
     return PB_OK;
 }
 
-int pb_sample_map_bilinear_px(const pb_proj* src, double* map_dev, int height, int width, const double* dist_l_dev, const double* dist_r_dev,
-                              const void* img_dev, void* out_dev, int channels, int sample_bytes, void* stream) {
+}  // extern "C"
+
+// pb_sample_map_bilinear_px (CR false) and pb_sample_map_catmull_rom_px (CR true): the same arguments, checks and launch
+template <bool CR>
+static int pb_sample_map_px(const pb_proj* src, double* map_dev, int height, int width, const double* dist_l_dev, const double* dist_r_dev,
+                            const void* img_dev, void* out_dev, int channels, int sample_bytes, void* stream) {
     std::string why;
     if (!map_dev || !img_dev || !out_dev) return pb_fail(PB_ERR_INVALID, "null argument");
     if (!pb_end_ok(src, why, PB_ROLE_SRC | PB_ROLE_CUSTOM_OK)) return pb_fail(PB_ERR_INVALID, why);
@@ -1949,14 +1994,30 @@ int pb_sample_map_bilinear_px(const pb_proj* src, double* map_dev, int height, i
     const auto launch = [&](auto* sample) {  // (the sample type: uint8_t or uint16_t)
         using SAMPLE = std::remove_pointer_t<decltype(sample)>;
         pb_pick_any_kind(P, [&](auto K) {
-            hipLaunchKernelGGL((pb_sample_map_bilinear_kernel<K.value, SAMPLE>), dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, st, P, map_dev, total, dist_l_dev,
-                               dist_r_dev, static_cast<const SAMPLE*>(img_dev), out_dev, channels);
+            if (CR)
+                hipLaunchKernelGGL((pb_sample_map_catmull_rom_kernel<K.value, SAMPLE>), dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, st, P, map_dev, total,
+                                   dist_l_dev, dist_r_dev, static_cast<const SAMPLE*>(img_dev), out_dev, channels);
+            else
+                hipLaunchKernelGGL((pb_sample_map_bilinear_kernel<K.value, SAMPLE>), dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, st, P, map_dev, total, dist_l_dev,
+                                   dist_r_dev, static_cast<const SAMPLE*>(img_dev), out_dev, channels);
         });
     };
     if (sample_bytes == 1) launch((uint8_t*)nullptr);
     else launch((uint16_t*)nullptr);
     PB_HIP(hipGetLastError());
     return PB_OK;
+}
+
+extern "C" {
+
+int pb_sample_map_bilinear_px(const pb_proj* src, double* map_dev, int height, int width, const double* dist_l_dev, const double* dist_r_dev,
+                              const void* img_dev, void* out_dev, int channels, int sample_bytes, void* stream) {
+    return pb_sample_map_px<false>(src, map_dev, height, width, dist_l_dev, dist_r_dev, img_dev, out_dev, channels, sample_bytes, stream);
+}
+
+int pb_sample_map_catmull_rom_px(const pb_proj* src, double* map_dev, int height, int width, const double* dist_l_dev, const double* dist_r_dev,
+                                 const void* img_dev, void* out_dev, int channels, int sample_bytes, void* stream) {
+    return pb_sample_map_px<true>(src, map_dev, height, width, dist_l_dev, dist_r_dev, img_dev, out_dev, channels, sample_bytes, stream);
 }
 
 int pb_sample_map_bilinear_u8(const pb_proj* src, double* map_dev, int height, int width, const uint8_t* src_dev, uint8_t* dst_dev, void* stream) {

@@ -32,6 +32,7 @@ LENSES = {
     "stereographic": stereographic,
 }
 TYPES = ("inscribed", "double", "cropped", "full")
+INTERPOLATIONS = ("nearest", "bilinear", "catmull-rom")
 
 TYPE_HELP = """
 
@@ -110,9 +111,12 @@ def camera_object(image_type: str, pixels: np.ndarray, fov: float, lens: str, ma
     return cls(pixels, fov, LENSES[lens](), magnitude=magnitude)
 
 
-def run_chain(source, destiny, rotations, out: Path, supersample: int = 1) -> None:
+def run_chain(source, destiny, rotations, out: Path, supersample: int = 1, interpolation: str = "nearest") -> None:
     """dst.get_coordinate_map() -> rotations in order -> src.process_coordinate_map() -> save.  ``supersample`` n > 1: the map of the n x
-    destination, each output pixel the mean of its n x n samples (the output size stays what the size rules gave)."""
+    destination, each output pixel the mean of its n x n samples (the output size stays what the size rules gave).  ``interpolation``:
+    the sampler - "nearest" (the reference's), or the opt-in "bilinear" / "catmull-rom" (the latter not supersampled)."""
+    if interpolation == "catmull-rom" and supersample > 1:
+        raise click.BadParameter("catmull-rom sampling is not supersampled: use --supersample 1", param_hint="--interpolation")
     if supersample == 1:
         cmap = destiny.get_coordinate_map()
     else:
@@ -122,13 +126,18 @@ def run_chain(source, destiny, rotations, out: Path, supersample: int = 1) -> No
             raise click.BadParameter(str(exc), param_hint="--supersample")
     for rot in rotations:
         cmap = Rotation(*map(to_radians, rot)).rotate_coordinate_map(cmap)
-    mapped = source.process_coordinate_map(cmap)
+    mapped = source.process_coordinate_map(cmap) if interpolation == "nearest" else source.process_coordinate_map(cmap, interpolation=interpolation)
     try:
         Image.fromarray(np.ascontiguousarray(mapped)).save(out)
     except IOError:
         print("Could not save to the specified location!")
         print("Exiting!")
         sys.exit(1)
+
+
+def _sampler(interpolation: str) -> dict:
+    """run_chain's keyword for --interpolation: none at the default, so that a plain call is exactly what it was."""
+    return {} if interpolation == "nearest" else {"interpolation": interpolation}
 
 
 # ---- commands -----------------------------------------------------------------------------------
@@ -141,6 +150,8 @@ def _common(fn):
     fn = click.option("-r", "--rotation", type=click.FLOAT, nargs=3, multiple=True, default=[], help=ROTATION_HELP)(fn)
     fn = click.option("--supersample", type=click.Choice(["1", "2", "4"]), default="1", show_default=True,
                       help="Antialiasing: each output pixel is the mean of n x n samples (1 = off).")(fn)
+    fn = click.option("--interpolation", type=click.Choice(list(INTERPOLATIONS)), default="nearest", show_default=True,
+                      help="The sampler: nearest (the reference's), bilinear or catmull-rom (sharp when magnifying; not with --supersample).")(fn)
     return fn
 
 
@@ -156,7 +167,7 @@ def main():
 @click.option("--fov", required=True, type=click.FLOAT, help="The lens field of view of the output photo in degrees. " + DOUBLE_FOV_NOTE)
 @_common
 @click.argument("output_image", type=click.Path(exists=False, path_type=Path))
-def make_photo(input_image, otype, lens, fov, output_image, rotation, size, supersample):
+def make_photo(input_image, otype, lens, fov, output_image, rotation, size, supersample, interpolation):
     """Make a photo out of a panorama.
 
     \b
@@ -168,7 +179,7 @@ def make_photo(input_image, otype, lens, fov, output_image, rotation, size, supe
     _, _, _ = pano.shape  # make_photo.py:112 unpacks three dimensions: grey inputs are a ValueError in the reference CLI
     shape = camera_shape(otype, pano, size)
     destiny = camera_object(otype, np.zeros(shape, np.uint8), radians_fov(fov, otype), lens, magnitude_for(otype, shape))
-    run_chain(PanoramaImage(pano), destiny, rotation, out, int(supersample))
+    run_chain(PanoramaImage(pano), destiny, rotation, out, int(supersample), **_sampler(interpolation))
 
 
 @main.command("alter-photo")
@@ -181,7 +192,7 @@ def make_photo(input_image, otype, lens, fov, output_image, rotation, size, supe
 @click.option("--ofov", required=True, type=click.FLOAT, help="The lens field of view of the output photo in degrees.")
 @click.argument("output_image", type=click.Path(exists=False, path_type=Path))
 @_common
-def alter_photo(input_image, itype, ilens, ifov, otype, olens, ofov, output_image, rotation, size, supersample):
+def alter_photo(input_image, itype, ilens, ifov, otype, olens, ofov, output_image, rotation, size, supersample, interpolation):
     """Change the the lens and FoV of a photo.
 
     \b
@@ -194,7 +205,7 @@ def alter_photo(input_image, itype, ilens, ifov, otype, olens, ofov, output_imag
     shape = camera_shape(otype, photo, size)
     # the destination magnitude comes from the SOURCE shape (alter_photo.py:142): only visible when --size differs
     destiny = camera_object(otype, np.zeros(shape, np.uint8), radians_fov(ofov, otype), olens, magnitude_for(otype, photo.shape))
-    run_chain(source, destiny, rotation, out, int(supersample))
+    run_chain(source, destiny, rotation, out, int(supersample), **_sampler(interpolation))
 
 
 @main.command("make-pano")
@@ -204,7 +215,7 @@ def alter_photo(input_image, itype, ilens, ifov, otype, olens, ofov, output_imag
 @click.option("--fov", required=True, type=click.FLOAT, help="The lens field of view of the input photo in degrees. " + DOUBLE_FOV_NOTE)
 @_common
 @click.argument("output_image", type=click.Path(exists=False, path_type=Path))
-def make_pano(input_image, itype, lens, fov, output_image, rotation, size, supersample):
+def make_pano(input_image, itype, lens, fov, output_image, rotation, size, supersample, interpolation):
     """Make a panorama out of a photo.
 
     \b
@@ -216,7 +227,7 @@ def make_pano(input_image, itype, lens, fov, output_image, rotation, size, super
     source = camera_object(itype, photo, radians_fov(fov, itype), lens, magnitude_for(itype, photo.shape))
     h = photo.shape[0] if size is None else size
     destiny = PanoramaImage(np.zeros((h, int(h * 2), 3), np.uint8))  # make_pano.py:142-149
-    run_chain(source, destiny, rotation, out, int(supersample))
+    run_chain(source, destiny, rotation, out, int(supersample), **_sampler(interpolation))
 
 
 if __name__ == "__main__":

@@ -1,0 +1,36 @@
+"""The Catmull-Rom tile kernel's budget, read from the compiler's listing of the product build (like test_isa_supersample.py): no scratch,
+no float64, and no tile entry dragged through VGPR lanes (DESIGN 3.4 "A finding worth its own line")."""
+
+import importlib.util
+import os
+import shutil
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def stats(tmp_path_factory):
+    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
+        pytest.skip("needs hipcc")
+    spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "experiments", "r6", "isa_stats.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    rows = mod.kernel_stats(out=str(tmp_path_factory.mktemp("isa") / "pb.s"))
+    return {r["name"]: r for r in rows}
+
+
+def test_tile_kernel_budget(stats):
+    got = {k: v for k, v in stats.items() if k.startswith("pb_catmull_rom_hot_kernel")}
+    assert len(got) == 2, sorted(got)  # {camera, panorama}
+    for name, r in got.items():
+        assert r["scratch"] == 0 and r["f64"] == 0, (name, r)
+        assert r["vgpr"] <= 168 and r["occupancy"] >= 3, (name, r)
+        assert r["lane_traffic"] <= 8, (name, r)
+
+
+def test_float64_kernels_are_there(stats):
+    for prefix, n in (("pb_catmull_rom_fix_kernel", 2), ("pb_catmull_rom_double_kernel", 1), ("pb_sample_map_catmull_rom_kernel", 6)):
+        got = [k for k in stats if k.startswith(prefix)]
+        assert len(got) == n, (prefix, sorted(got))
