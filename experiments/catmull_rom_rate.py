@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Catmull-Rom sampling: the tile kernel (pb_catmull_rom_hot_kernel) next to the bilinear tile kernel (pb_bilinear_hot_kernel) and
-next to the mode's float64 route (pb_catmull_rom_fix_kernel, the same geometry's plan in PB_MODE_FAITHFUL), measured in the SAME process,
+next to the mode's float64 route (pb_interp_fix_kernel<PbCatmullRom>, the same geometry's plan in PB_MODE_FAITHFUL), measured in the SAME process,
 alternating, per BASELINE config.
     python experiments/catmull_rom_rate.py [--reps 5] [--iters 20] [--configs c1,c2,c3] [--out file.json]
 Per round and way: `iters` launches between two HIP events, after a warm-up launch; the figure is the median over `reps` rounds."""

@@ -203,10 +203,15 @@ def load() -> C.CDLL:
     return _lib
 
 
-def check_interpolation(interpolation: str, supersample: int = 1) -> None:
-    """The rule the entry points check before any library call: catmull-rom is not supersampled (ValueError)."""
-    if interpolation == "catmull-rom" and check_supersample(supersample) > 1:
-        raise ValueError("catmull-rom sampling is not supersampled: pass supersample=1")
+def check_interpolation(interpolation: str, supersample: int = 1) -> int:
+    """The one check of an interpolation name, made by every entry point before any library call (ValueError): one of INTERPOLATIONS,
+    and catmull-rom is not supersampled (the supersampled ABI takes INTERP_IDS only).  Returns the supersample factor as an int."""
+    if interpolation not in INTERPOLATIONS:
+        raise ValueError(f"interpolation must be one of {', '.join(map(repr, INTERPOLATIONS))}, got {interpolation!r}")
+    n = check_supersample(supersample)
+    if n > 1 and interpolation not in INTERP_IDS:
+        raise ValueError(f"{interpolation} sampling is not supersampled: pass supersample=1")
+    return n
 
 
 def check_supersample(n) -> int:
@@ -513,14 +518,12 @@ class Plan:
         ``supersample_workspace_bytes(...)`` bytes the caller owns (allocate it outside a graph capture and keep it per stream); without
         one, a call that needs it takes a temporary buffer - from PyTorch's stream-ordered allocator where torch is installed, else a
         DeviceArray that is freed after the call (on a stream other than the default one the call then synchronises that stream)."""
-        n = check_supersample(supersample)
-        cr = interpolation == "catmull-rom"
-        check_interpolation(interpolation, n)
+        n = check_interpolation(interpolation, supersample)
         if interpolation != "nearest":
             self.ensure_bilinear()  # (catmull-rom reads the bilinear mode's tables too)
         st = current_stream() if stream is None else stream
         if n == 1:
-            fn = load().pb_remap_u8 if interpolation == "nearest" else (load().pb_remap_catmull_rom_u8 if cr else load().pb_remap_bilinear_u8)
+            fn = {"nearest": load().pb_remap_u8, "bilinear": load().pb_remap_bilinear_u8, "catmull-rom": load().pb_remap_catmull_rom_u8}[interpolation]
             self._gated(fn, self._h, src_ptr, dst_ptr, int(n_frames), int(src_stride), int(dst_stride), st)
             return
         interp, flags = INTERP_IDS[interpolation], (SS_GENERIC if generic else 0)
@@ -545,8 +548,7 @@ class Plan:
         n = check_supersample(supersample)
         if n == 1:
             return 0
-        if interpolation not in INTERP_IDS:
-            raise ValueError("interpolation must be 'nearest' or 'bilinear'")
+        check_interpolation(interpolation, n)
         need = C.c_size_t(0)
         check(load().pb_remap_ss_workspace(self._h, n, INTERP_IDS[interpolation], SS_GENERIC if generic else 0, C.byref(need)))
         nbytes = int(need.value)
@@ -578,10 +580,7 @@ class Plan:
         interpolation: "nearest" (the reference's truncating sample), the opt-in "bilinear" or the opt-in "catmull-rom".
         supersample: n in (2, 4) on a plan of the n x destination -> (H / n, W / n, 3) frames of n x n block means (see ``launch``;
         nearest and bilinear only)."""
-        if interpolation not in INTERPOLATIONS:
-            raise ValueError("interpolation must be 'nearest', 'bilinear' or 'catmull-rom'")
-        ss = check_supersample(supersample)
-        check_interpolation(interpolation, ss)
+        ss = check_interpolation(interpolation, supersample)
         oh, ow = self.out_shape(ss)
         require_gpu()
         if not is_device_array(src):
@@ -762,33 +761,28 @@ def index_from_map(src: pb_proj, cmap, dist_l=None, dist_r=None):
     return idx, w
 
 
-def sample_map_bilinear(src: pb_proj, cmap, img, channels: int, dt: np.dtype, dist_l=None, dist_r=None):
-    """The opt-in bilinear mode from a materialised float64 map (H, W, 3) on the device: img = the image's samples as a device array
-    (h, w, channels) of dtype dt (uint8 / uint16) -> (H, W, channels), uint8 for a double-fisheye source (pb_sample_map_bilinear_px)."""
+def sample_map_interp(interpolation: str, src: pb_proj, cmap, img, channels: int, dt: np.dtype, dist_l=None, dist_r=None):
+    """An interpolating mode ("bilinear", "catmull-rom") from a materialised float64 map (H, W, 3) on the device: img = the image's samples
+    as a device array (h, w, channels) of dtype dt (uint8 / uint16) -> (H, W, channels), uint8 for a double-fisheye source
+    (pb_sample_map_bilinear_px / pb_sample_map_catmull_rom_px)."""
     require_gpu()
+    fn = {"bilinear": load().pb_sample_map_bilinear_px, "catmull-rom": load().pb_sample_map_catmull_rom_px}[interpolation]
     H, W = int(cmap.shape[0]), int(cmap.shape[1])
     dt = np.dtype(dt)
     out_dt = np.dtype(np.uint8) if src.kind == KIND_DOUBLE else dt
     out = empty((H, W, channels), out_dt, like=cmap)
     with _on(cmap):
-        check(load().pb_sample_map_bilinear_px(C.byref(src), cmap.data_ptr(), H, W, dist_l.data_ptr() if dist_l is not None else None,
-                                               dist_r.data_ptr() if dist_r is not None else None, img.data_ptr(), out.data_ptr(), int(channels),
-                                               dt.itemsize, current_stream()))
+        check(fn(C.byref(src), cmap.data_ptr(), H, W, dist_l.data_ptr() if dist_l is not None else None,
+                 dist_r.data_ptr() if dist_r is not None else None, img.data_ptr(), out.data_ptr(), int(channels), dt.itemsize, current_stream()))
     return out
+
+
+def sample_map_bilinear(src: pb_proj, cmap, img, channels: int, dt: np.dtype, dist_l=None, dist_r=None):
+    return sample_map_interp("bilinear", src, cmap, img, channels, dt, dist_l, dist_r)
 
 
 def sample_map_catmull_rom(src: pb_proj, cmap, img, channels: int, dt: np.dtype, dist_l=None, dist_r=None):
-    """The opt-in Catmull-Rom mode from a materialised float64 map, like ``sample_map_bilinear`` (pb_sample_map_catmull_rom_px)."""
-    require_gpu()
-    H, W = int(cmap.shape[0]), int(cmap.shape[1])
-    dt = np.dtype(dt)
-    out_dt = np.dtype(np.uint8) if src.kind == KIND_DOUBLE else dt
-    out = empty((H, W, channels), out_dt, like=cmap)
-    with _on(cmap):
-        check(load().pb_sample_map_catmull_rom_px(C.byref(src), cmap.data_ptr(), H, W, dist_l.data_ptr() if dist_l is not None else None,
-                                                  dist_r.data_ptr() if dist_r is not None else None, img.data_ptr(), out.data_ptr(), int(channels),
-                                                  dt.itemsize, current_stream()))
-    return out
+    return sample_map_interp("catmull-rom", src, cmap, img, channels, dt, dist_l, dist_r)
 
 
 def gather_px(idx, img_bytes):

@@ -380,9 +380,7 @@ class _GpuProjection:
 
         ``interpolation="catmull-rom"`` (opt-in): the same with a 4 x 4 footprint and Keys' cubic weights (a = -0.5) - sharp
         where the source is magnified.  Served like bilinear (pb_remap_catmull_rom_u8 / pb_sample_map_catmull_rom_px); not supersampled."""
-        n = _map_supersample(coordinate_map, supersample)
-        if interpolation == "catmull-rom" and n > 1:
-            raise ValueError(f"catmull-rom sampling is not supersampled (supersample={n}): use nearest or bilinear, or a plain map")
+        n = nat.check_interpolation(interpolation, _map_supersample(coordinate_map, supersample))
         if n == 1:
             return self._process(coordinate_map, interpolation)
         return self._process_ss(coordinate_map, interpolation, n)
@@ -395,11 +393,9 @@ class _GpuProjection:
         rgb8 = tail == (3,) and dt == np.dtype(np.uint8)
         custom_src = src.kind != nat.KIND_PANO and src.lens == nat.LENS_CUSTOM
         lazy = isinstance(coordinate_map, CoordinateMap) and coordinate_map.is_lazy
-        bilinear = interpolation != "nearest"  # (an interpolating mode: bilinear or catmull-rom)
-        catmull_rom = interpolation == "catmull-rom"
-        if bilinear:
-            if interpolation != "bilinear" and not catmull_rom:
-                raise ValueError("interpolation must be 'nearest', 'bilinear' or 'catmull-rom'")
+        nat.check_interpolation(interpolation)
+        interpolating = interpolation != "nearest"  # (bilinear or catmull-rom)
+        if interpolating:
             if dt not in (np.dtype(np.uint8), np.dtype(np.uint16)):
                 raise NotImplementedError(f"{interpolation} sampling takes 8- or 16-bit unsigned samples, got {dt}")
             if src.kind == nat.KIND_DOUBLE and len(tail) != 1:
@@ -409,7 +405,7 @@ class _GpuProjection:
         on_device = nat.is_device_array(self.image) or device_out  # the pixels live on the device: so does the result
         fused = rgb8 and not custom_src
         rotations = coordinate_map.rotations if lazy else ()
-        if bilinear and lazy and len(rotations) > nat.PB_MAX_ROTATIONS:
+        if interpolating and lazy and len(rotations) > nat.PB_MAX_ROTATIONS:
             # The reference applies any number of -r rotations one after the other (scripts/commands/make_photo.py:128-131).  A chain
             # longer than one fused plan takes leaves the plan for the materialised-map kernels, which only truncate; in THIS mode
             # (our own definition, no reference bits to keep) the chain folds into one matrix product R_k ... R_1 instead.
@@ -430,7 +426,7 @@ class _GpuProjection:
             return out
         img = _device_image(self.image, h, w) if fused else _device_bytes(self.image)
         dev = img.device if nat.is_tensor(img) else None
-        if lazy and not too_many and not custom_src and (fused or not bilinear):
+        if lazy and not too_many and not custom_src and (fused or not interpolating):
             # bilinear taps come from the tile models: that mode needs the prepared plan from the first use on
             plan = _plan_for(coordinate_map.dst_proj, rotations, src, device=dev, eager=interpolation != "nearest")
             with nat.on_device(nat.device_index_of(img)):
@@ -458,13 +454,12 @@ class _GpuProjection:
                 if not (isinstance(host, np.ndarray) and host.dtype == np.float64 and host.ndim == 3 and host.shape[2] == 3):
                     raise TypeError("coordinate_map must be a float64 array of shape (H, W, 3)")
                 dmap = _upload(host, dev)
-            if bilinear:
+            if interpolating:
                 # the mode's definition per pixel from the map (pb_sample_map_bilinear_px): a materialised or edited map, any image
                 # layout, a source Lens of user callables - everything the tile kernels do not take
                 dl, dr = self._distance_planes(src, dmap)
                 channels = int(np.prod(tail, dtype=np.int64))
-                sample = nat.sample_map_catmull_rom if catmull_rom else nat.sample_map_bilinear
-                out = sample(src, dmap, img, channels, dt, dl, dr)
+                out = nat.sample_map_interp(interpolation, src, dmap, img, channels, dt, dl, dr)
                 out_dt = np.dtype(np.uint8) if src.kind == nat.KIND_DOUBLE else dt
                 H_, W_ = int(dmap.shape[0]), int(dmap.shape[1])
                 out = out.reshape((H_, W_) + tuple(tail)) if nat.is_tensor(out) else out.view(out_dt, (H_, W_) + tuple(tail))
@@ -483,8 +478,7 @@ class _GpuProjection:
         then pb_box_reduce."""
         src = self._proj("src")
         h, w, tail, dt = _image_info(self.image)
-        if interpolation not in ("nearest", "bilinear"):
-            raise ValueError("interpolation must be 'nearest' or 'bilinear'")
+        nat.check_interpolation(interpolation, n)
         if dt not in (np.dtype(np.uint8), np.dtype(np.uint16)):
             raise NotImplementedError(f"supersampling takes 8- or 16-bit unsigned samples, got {dt}")
         mh, mw = (int(v) for v in tuple(coordinate_map.shape)[:2])

@@ -27,9 +27,12 @@
 //   pb_bilinear_hot_kernel          pano / camera sources: one wave per tile over the plan's launch-order table
 //   pb_bilinear_double_hot_kernel   double-fisheye sources: one-eye (SOLO) tiles through the same tile code, two-eye tiles
 //                                   sample both eyes and blend with the tile's weight class
-//   pb_bilinear_fix_kernel, pb_bilinear_double_kernel, pb_bilinear_double_fix_kernel
+//   pb_interp_fix_kernel, pb_interp_double_kernel, pb_bilinear_double_fix_kernel
 //                                   the float64 chain per pixel: the mode's definition on the device (PB_MODE_FAITHFUL, plans
 //                                   without tile tables) and the fallback for plans whose coordinate table would not fit
+//   pb_sample_map_interp_kernel     the mode from a materialised map, any image
+// The three pb_*_interp_* kernels, pb_tap_addr and the liveness / picker / store helpers they use (pb_live, pb_pick_pixel, pb_store_px) are
+// SHARED with the Catmull-Rom mode (pb_kernels_catmull_rom.hpp): templates over a FILTER, PbBilinear here, that supplies the arithmetic.
 #pragma once
 #include "pb_kernels_tile.hpp"
 
@@ -85,38 +88,65 @@ template <typename SAMPLE>
 __device__ __forceinline__ double pb_bil64_tap(const SAMPLE* __restrict__ img, long long r, long long c, int w, int channels, int ch) {
     return (double)img[((unsigned long long)r * (unsigned)w + (unsigned long long)c) * (unsigned)channels + (unsigned)ch];
 }
-// one source's sample of channel ch at pre-truncation coordinate (fy, fx): taps clamped to rows [0, h) and columns [cmin, cmax) of a
-// frame `w` wide (`mirror`: the right eye's image is its half mirrored - projection.py:430-431 - eye column x = frame column
-// cmax - 1 - x); WRAP: a panorama's columns wrap first.  Rounded half to even and clamped to the sample type's range.
-template <typename SAMPLE, bool WRAP>
-__device__ __forceinline__ double pb_bil64_sample(const SAMPLE* __restrict__ img, double fy, double fx, int h, int w, int cmin, int cmax, bool mirror,
-                                                  int channels, int ch) {
-    const double sy = fy - 0.5, sx = fx - 0.5;
-    const double ry = floor(sy), rx = floor(sx);
-    const double ty = sy - ry, tx = sx - rx;
-    long long r0 = (long long)ry, c0 = (long long)rx;
-    long long r1 = r0 + 1, c1 = c0 + 1;
-    r0 = r0 < 0 ? 0 : (r0 > h - 1 ? h - 1 : r0);
-    r1 = r1 < 0 ? 0 : (r1 > h - 1 ? h - 1 : r1);
-    const long long we = cmax - cmin;
-    if (WRAP) {
-        c0 %= we; if (c0 < 0) c0 += we;
-        c1 %= we; if (c1 < 0) c1 += we;
+// The addresses of a filter's N x N taps from its first tap (i0, j0): rows r[k] clamped to [0, h); columns g[l] clamped to the columns
+// [cmin, cmax) of the frame that the source (or an eye) owns, as frame columns (`mirror`: the right eye's image is its half mirrored -
+// projection.py:430-431 - eye column x = frame column cmax - 1 - x); WRAP: a panorama's columns wrap first.
+template <int N, bool WRAP, typename I>
+__device__ __forceinline__ void pb_tap_addr(I i0, I j0, int h, int cmin, int cmax, bool mirror, I r[N], I g[N]) {
+    const I we = cmax - cmin;
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        const I y = i0 + n;
+        r[n] = y < 0 ? 0 : (y > h - 1 ? h - 1 : y);
+        I c = j0 + n;
+        if (WRAP) {
+            c %= we;
+            if (c < 0) c += we;
+        }
+        c = c < 0 ? 0 : (c > we - 1 ? we - 1 : c);
+        g[n] = mirror ? (cmax - 1 - c) : (cmin + c);
     }
-    c0 = c0 < 0 ? 0 : (c0 > we - 1 ? we - 1 : c0);
-    c1 = c1 < 0 ? 0 : (c1 > we - 1 ? we - 1 : c1);
-    const long long g0 = mirror ? (cmax - 1 - c0) : (cmin + c0), g1 = mirror ? (cmax - 1 - c1) : (cmin + c1);
-    const double a = pb_bil64_tap(img, r0, g0, w, channels, ch), b = pb_bil64_tap(img, r0, g1, w, channels, ch);
-    const double c = pb_bil64_tap(img, r1, g0, w, channels, ch), d = pb_bil64_tap(img, r1, g1, w, channels, ch);
-    const double top = a + tx * (b - a), bot = c + tx * (d - c);
-    const double v = rint(top + ty * (bot - top));
-    const double vmax = (double)(SAMPLE)~(SAMPLE)0;
-    return v < 0.0 ? 0.0 : (v > vmax ? vmax : v);
 }
-template <int SRC_KIND, typename SAMPLE>
-__global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_bilinear_kernel(const PbParams P, double* __restrict__ map, unsigned total,
-                                                                          const double* __restrict__ dist_l, const double* __restrict__ dist_r,
-                                                                          const SAMPLE* __restrict__ img, void* __restrict__ out, int channels) {
+// A FILTER is what the shared sampler code below is parametrised by (PbBilinear here, PbCatmullRom in pb_kernels_catmull_rom.hpp):
+//   sample64<SAMPLE, WRAP>   the float64 definition: one source's sample of channel ch at pre-truncation coordinate (fy, fx), taps addressed
+//                            by pb_tap_addr, rounded half to even and clamped to the sample type's range
+//   Px, prepare<SRC_KIND>, sample<SRC_KIND>, eye
+//                            the per-pixel routes of a plan (pb_interp_fix_kernel, pb_interp_double_kernel): prepare() is what a pixel
+//                            needs once (its coordinate from the chain's, liveness), sample() one frame's packed RGB pixel from it, eye()
+//                            one eye's of a double fisheye (0 where that eye is black)
+struct PbBilinear {
+    template <typename SAMPLE, bool WRAP>
+    static __device__ __forceinline__ double sample64(const SAMPLE* __restrict__ img, double fy, double fx, int h, int w, int cmin, int cmax, bool mirror,
+                                                      int channels, int ch) {
+        const double sy = fy - 0.5, sx = fx - 0.5;
+        const double ry = floor(sy), rx = floor(sx);
+        const double ty = sy - ry, tx = sx - rx;
+        long long r[2], g[2];
+        pb_tap_addr<2, WRAP>((long long)ry, (long long)rx, h, cmin, cmax, mirror, r, g);
+        const double a = pb_bil64_tap(img, r[0], g[0], w, channels, ch), b = pb_bil64_tap(img, r[0], g[1], w, channels, ch);
+        const double c = pb_bil64_tap(img, r[1], g[0], w, channels, ch), d = pb_bil64_tap(img, r[1], g[1], w, channels, ch);
+        const double top = a + tx * (b - a), bot = c + tx * (d - c);
+        const double v = rint(top + ty * (bot - top));
+        const double vmax = (double)(SAMPLE)~(SAMPLE)0;
+        return v < 0.0 ? 0.0 : (v > vmax ? vmax : v);
+    }
+    // (the per-pixel routes: below, after the float32 taps' users)
+    struct Px {
+        bool live;
+        int by, bx;    // integer bases keep the float32 tap arithmetic exact enough: s - base is in [-1, 1)
+        float ty, tx;
+    };
+    template <int SRC_KIND>
+    static __device__ __forceinline__ Px prepare(const PbParams& P, const PbCoord& c);
+    template <int SRC_KIND>
+    static __device__ __forceinline__ unsigned sample(const PbParams& P, const Px& q, const uint8_t* __restrict__ s);
+    static __device__ __forceinline__ unsigned eye(const PbParams& P, const uint8_t* __restrict__ s, double lat, double sl, double cl, int we, double cx,
+                                                   int cmin, bool mirror);
+};
+template <class FILTER, int SRC_KIND, typename SAMPLE>
+__global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_interp_kernel(const PbParams P, double* __restrict__ map, unsigned total, const double* __restrict__ dist_l,
+                                                                 const double* __restrict__ dist_r, const SAMPLE* __restrict__ img, void* __restrict__ out,
+                                                                 int channels) {
     const unsigned p = blockIdx.x * PB_BLOCK + threadIdx.x;
     if (p >= total) return;
     double* a = map + 3ull * p;
@@ -129,9 +159,10 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_bilinear_kernel(const 
     const int h = P.src.height, w = P.src.width;
     if (SRC_KIND == PB_KIND_PANO) {
         const double fy = lat / P.src_hseg, fx = lon / P.src_wseg + P.src_half_w;
-        const bool live = !inv && fabs(fy) < 1.0e300 && fabs(fx) < 1.0e300 && fy == fy && fx == fx;
+        const bool live = !inv && pb_live(fy, fx, 1.0e300);
         SAMPLE* o = static_cast<SAMPLE*>(out) + (unsigned long long)p * (unsigned)channels;
-        for (int ch = 0; ch < channels; ++ch) o[ch] = live ? (SAMPLE)pb_bil64_sample<SAMPLE, true>(img, fy, fx, h, w, 0, w, false, channels, ch) : (SAMPLE)0;
+        for (int ch = 0; ch < channels; ++ch)
+            o[ch] = live ? (SAMPLE)FILTER::template sample64<SAMPLE, true>(img, fy, fx, h, w, 0, w, false, channels, ch) : (SAMPLE)0;
         return;
     }
     double sl, cl;
@@ -139,9 +170,10 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_bilinear_kernel(const 
     if (SRC_KIND == PB_KIND_CAMERA) {
         const double dist = dist_l ? dist_l[p] : pb_lens_forward(P.src.lens, lat, P.rect_max) * P.src.f_distance;
         const double fy = ((sl * dist) * -1.0) + P.src_cy, fx = (cl * dist) + P.src_cx;
-        const bool live = !inv && fy == fy && fx == fx && fabs(fy) < 1.0e300 && fabs(fx) < 1.0e300 && fy >= 0.0 && fy < (double)h && fx >= 0.0 && fx < (double)w;
+        const bool live = !inv && pb_live_in(fy, fx, 1.0e300, h, w);
         SAMPLE* o = static_cast<SAMPLE*>(out) + (unsigned long long)p * (unsigned)channels;
-        for (int ch = 0; ch < channels; ++ch) o[ch] = live ? (SAMPLE)pb_bil64_sample<SAMPLE, false>(img, fy, fx, h, w, 0, w, false, channels, ch) : (SAMPLE)0;
+        for (int ch = 0; ch < channels; ++ch)
+            o[ch] = live ? (SAMPLE)FILTER::template sample64<SAMPLE, false>(img, fy, fx, h, w, 0, w, false, channels, ch) : (SAMPLE)0;
         return;
     }
     // two eyes (projection.py:408-462): each sampled like a camera source on its half (the right one mirrored), then the reference's blend
@@ -151,13 +183,12 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_bilinear_kernel(const 
     const int wl = P.src_eye_w, wr = P.src_eye_w_right;
     const double fyl = ((sl * dl) * -1.0) + P.src_cy, fxl = (cl * dl) + P.src_cx;
     const double fyr = ((sl * dr) * -1.0) + P.src_cy, fxr = (cl * dr) + P.src_cx_r;
-    const bool live_l = !inv && fyl == fyl && fxl == fxl && fabs(fyl) < 1.0e300 && fabs(fxl) < 1.0e300 && fyl >= 0.0 && fyl < (double)h && fxl >= 0.0 && fxl < (double)wl;
-    const bool live_r = !inv && fyr == fyr && fxr == fxr && fabs(fyr) < 1.0e300 && fabs(fxr) < 1.0e300 && fyr >= 0.0 && fyr < (double)h && fxr >= 0.0 && fxr < (double)wr;
+    const bool live_l = !inv && pb_live_in(fyl, fxl, 1.0e300, h, wl), live_r = !inv && pb_live_in(fyr, fxr, 1.0e300, h, wr);
     const double fl = pb_merge_factor(P, lat), fr = pb_merge_factor(P, lat_r);
     uint8_t* o = static_cast<uint8_t*>(out) + (unsigned long long)p * (unsigned)channels;  // (left * fl + right * fr).astype(np.uint8): uint8 whatever the samples
     for (int ch = 0; ch < channels; ++ch) {
-        const double l = live_l ? pb_bil64_sample<SAMPLE, false>(img, fyl, fxl, h, w, 0, wl, false, channels, ch) : 0.0;
-        const double r = live_r ? pb_bil64_sample<SAMPLE, false>(img, fyr, fxr, h, w, wl, wl + wr, true, channels, ch) : 0.0;
+        const double l = live_l ? FILTER::template sample64<SAMPLE, false>(img, fyl, fxl, h, w, 0, wl, false, channels, ch) : 0.0;
+        const double r = live_r ? FILTER::template sample64<SAMPLE, false>(img, fyr, fxr, h, w, wl, wl + wr, true, channels, ch) : 0.0;
         o[ch] = inv ? (uint8_t)0 : (uint8_t)pb_cvt_u8(l * fl + r * fr);
     }
 }
@@ -190,7 +221,7 @@ __device__ __forceinline__ PbBilCoord pb_bil_coord_of(const PbParams& P, const P
     bool live;
     if (SRC_KIND == PB_KIND_PANO) {
         pb_src_pretrunc<PB_KIND_PANO>(P, c, f0, f1);
-        live = f0 == f0 && f1 == f1 && fabs(f0) < 1.0e9 && fabs(f1) < 1.0e9;
+        live = pb_live(f0, f1, 1.0e9);
     } else {
         // one fisheye (or one eye, sampled like a camera source on its half: projection.py:429-434) in ITS pixel space
         const double lat = (SRC_KIND == PB_KIND_EYE_R) ? (c.lat * -1.0) + PB_PI : c.lat;  // projection.py:426-427
@@ -201,7 +232,7 @@ __device__ __forceinline__ PbBilCoord pb_bil_coord_of(const PbParams& P, const P
         pb_expi_np(c.lon, &sl, &cl);  // np.exp(lon * 1j)
         f0 = ((sl * dist) * -1.0) + P.src_cy;
         f1 = (cl * dist) + cx;
-        live = f0 == f0 && f1 == f1 && fabs(f0) < 1.0e9 && fabs(f1) < 1.0e9 && f0 >= 0.0 && f0 < (double)P.src.height && f1 >= 0.0 && f1 < (double)we;
+        live = pb_live_in(f0, f1, 1.0e9, P.src.height, we);
         if (SRC_KIND == PB_KIND_EYE_R) f1 = (double)P.src.width - f1;  // the mirrored half of the frame (projection.py:430-431)
     }
     if (!live) return q;
@@ -763,7 +794,7 @@ __device__ __forceinline__ unsigned pb_bil_slot_of(unsigned wg, unsigned wave) {
 // coordinate a hair from an integer, harmless here, but also the genuine discontinuities a polynomial cannot follow inside an
 // otherwise modelled tile (the edge of a lens inverse's domain, a validity or image boundary) - are redone from their exact
 // coordinates by the tile's wave after its stores, like the nearest mode's.  bil_xy == nullptr: the plan has no coordinate table
-// (it would not fit); tiles that need one, and the fix pixels, are then left to pb_bilinear_fix_kernel.
+// (it would not fit); tiles that need one, and the fix pixels, are then left to pb_interp_fix_kernel<PbBilinear>.
 template <int SRC_KIND, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, PB_BIL_WPE) void pb_bilinear_hot_kernel(const PbHot Hd, const PbTileEntry* __restrict__ table,
                                                                               const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
@@ -801,89 +832,64 @@ __global__ __launch_bounds__(64 * WAVES, PB_BIL_WPE) void pb_bilinear_hot_kernel
             const PbBilCoord q = fix_xy[e->fix_off + lane];
             const unsigned px = pb_bil_table_px<SRC_KIND == PB_KIND_PANO>(src, q.y, q.x, Hd.src_h, Hd.src_w, 0, Hd.src_w, 3u * (unsigned)Hd.src_w * (unsigned)Hd.src_h);
             uint8_t* o = dst + 3ull * p;
-            o[0] = (uint8_t)(px & 0xFF);
-            o[1] = (uint8_t)((px >> 8) & 0xFF);
-            o[2] = (uint8_t)((px >> 16) & 0xFF);
+            pb_store_px(o, px);
         }
     }
 }
 
-// float64 faithful coordinates; mode 0: the plan's failed tiles (4 blocks each), mode 1: every pixel (no plan state)
-// mode 0 also takes the plan's fix list (blocks beyond the failed tiles): a pixel is on it because the model's index
-// differs from the faithful one - mostly a coordinate a hair from an integer, harmless here, but also the genuine
-// discontinuities a polynomial cannot follow inside an otherwise modelled tile (the edge of a lens inverse's domain,
-// a validity or image boundary): those pixels take the float64 coordinates like the failed tiles.
+// ---- the per-pixel routes of a plan: float64 faithful coordinates from the chain, frames of a batch in a loop ------------------------------
+// A pixel is on the plan's fix list because the model's index differs from the faithful one - mostly a coordinate a hair from an integer,
+// harmless here, but also the genuine discontinuities a polynomial cannot follow inside an otherwise modelled tile (the edge of a lens
+// inverse's domain, a validity or image boundary): those pixels take the float64 coordinates like the failed tiles.
+// The filter is FILTER's; for bilinear this is NOT the float64 definition: the coordinate is taken once per pixel in float64 (liveness bound
+// 1.0e9), the taps are pb_bilinear_taps' float32.  all_pixels: every pixel of the image; else the listed tiles and the fix pixels
+// (pb_pick_pixel; n_tiles: fail_tiles' first n_fail_only and more_tiles' together).
+template <class FILTER, int SRC_KIND>
+__global__ __launch_bounds__(PB_BLOCK) void pb_interp_fix_kernel(const PbParams P, const int32_t* __restrict__ fail_tiles, int all_pixels,
+                                                                 const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,
+                                                                 unsigned long long src_stride, unsigned long long dst_stride, int n_tiles = 0,
+                                                                 const int32_t* __restrict__ fix_px = nullptr, int n_fix_px = 0,
+                                                                 const int32_t* __restrict__ more_tiles = nullptr, int n_fail_only = 0) {
+    PbPixelPick k;
+    if (!pb_pick_pixel(P, all_pixels != 0, fail_tiles, n_fail_only, more_tiles, n_tiles, fix_px, n_fix_px, k) || !k.inside) return;
+    const typename FILTER::Px q = FILTER::template prepare<SRC_KIND>(P, pb_rotate_all(P, pb_dst_coord(P, k.i, k.j)));
+    const size_t p = (size_t)k.i * P.dst.width + k.j;
+    for (int f = 0; f < n_frames; ++f)
+        pb_store_px(dst + (unsigned long long)f * dst_stride + 3 * p, FILTER::template sample<SRC_KIND>(P, q, src + (unsigned long long)f * src_stride));
+}
 template <int SRC_KIND>
-__global__ __launch_bounds__(PB_BLOCK) void pb_bilinear_fix_kernel(const PbParams P, const int32_t* __restrict__ fail_tiles,
-                                                                   int all_pixels, const uint8_t* __restrict__ src,
-                                                                   uint8_t* __restrict__ dst, int n_frames,
-                                                                   unsigned long long src_stride, unsigned long long dst_stride,
-                                                                   int n_fail_tiles = 0, const int32_t* __restrict__ fix_px = nullptr,
-                                                                   int n_fix_px = 0, const int32_t* __restrict__ more_tiles = nullptr,
-                                                                   int n_fail_only = 0) {
-    int i, j;
-    if (all_pixels) {
-        const unsigned p = blockIdx.x * PB_BLOCK + threadIdx.x;
-        if (p >= (unsigned)P.dst.height * (unsigned)P.dst.width) return;
-        i = p / (unsigned)P.dst.width;
-        j = p - (unsigned)i * (unsigned)P.dst.width;
-    } else if ((int)blockIdx.x >= 4 * n_fail_tiles && fix_px) {
-        const unsigned item = (blockIdx.x - 4u * (unsigned)n_fail_tiles) * PB_BLOCK + threadIdx.x;
-        if (item >= (unsigned)n_fix_px) return;
-        const unsigned p = (unsigned)fix_px[item];
-        i = p / (unsigned)P.dst.width;
-        j = p - (unsigned)i * (unsigned)P.dst.width;
-    } else {
-        // n_fail_tiles: the plan's failed tiles (the first n_fail_only, from fail_tiles) and its COARSE tiles (more_tiles) together
-        const int k = blockIdx.x >> 2;
-        const int t = (more_tiles && k >= n_fail_only) ? more_tiles[k - n_fail_only] : fail_tiles[k];
-        const int ty = t / pb_tiles_x(P), tx = t - ty * pb_tiles_x(P);
-        const int local = (blockIdx.x & 3) * 256 + threadIdx.x;
-        i = ty * PB_TILE + (local >> 5);
-        j = tx * PB_TILE + (local & 31);
-        if (i >= P.dst.height || j >= P.dst.width) return;
-    }
-    PbCoord c = pb_dst_coord(P, i, j);
-    c = pb_rotate_all(P, c);
+__device__ __forceinline__ PbBilinear::Px PbBilinear::prepare(const PbParams& P, const PbCoord& c) {
     double f0, f1;
     pb_src_pretrunc<SRC_KIND>(P, c, f0, f1);
-    bool live = !c.inv && f0 == f0 && f1 == f1 && fabs(f0) < 1.0e9 && fabs(f1) < 1.0e9;
-    if (SRC_KIND == PB_KIND_CAMERA) live = live && f0 >= 0.0 && f0 < (double)P.src.height && f1 >= 0.0 && f1 < (double)P.src.width;
-    const size_t p = (size_t)i * P.dst.width + j;
-    // integer bases keep the float32 tap arithmetic exact enough: s - base is in [-1, 1)
+    Px q;
+    q.live = !c.inv && (SRC_KIND == PB_KIND_CAMERA ? pb_live_in(f0, f1, 1.0e9, P.src.height, P.src.width) : pb_live(f0, f1, 1.0e9));
     const double sy = f0 - 0.5, sx = f1 - 0.5;
-    const int by = live ? (int)floor(sy) : 0, bx = live ? (int)floor(sx) : 0;
-    for (int f = 0; f < n_frames; ++f) {
-        unsigned v = 0;
-        if (live) v = pb_bilinear_taps<SRC_KIND>(P, src + (unsigned long long)f * src_stride, (float)(sy - by), (float)(sx - bx), by, bx);
-        uint8_t* o = dst + (unsigned long long)f * dst_stride + 3 * p;
-        o[0] = (uint8_t)(v & 0xFF);
-        o[1] = (uint8_t)((v >> 8) & 0xFF);
-        o[2] = (uint8_t)((v >> 16) & 0xFF);
-    }
+    q.by = q.live ? (int)floor(sy) : 0;
+    q.bx = q.live ? (int)floor(sx) : 0;
+    q.ty = (float)(sy - q.by);
+    q.tx = (float)(sx - q.bx);
+    return q;
+}
+template <int SRC_KIND>
+__device__ __forceinline__ unsigned PbBilinear::sample(const PbParams& P, const Px& q, const uint8_t* __restrict__ s) {
+    return q.live ? pb_bilinear_taps<SRC_KIND>(P, s, q.ty, q.tx, q.by, q.bx) : 0u;
 }
 
 // ---- double-fisheye source (faithful float64 coordinates per pixel; an opt-in mode off the hot path) ----------------
-// one eye's bilinear sample (0 where the nearest mode is black for that eye): eye image = columns [col0, col0 + we) of the
-// frame, mirrored when `mirror` (the right eye, projection.py:430-431)
-__device__ __forceinline__ unsigned pb_bilinear_eye(const PbParams& P, const uint8_t* __restrict__ s, double lat, double lon, int we, double cx,
-                                                    int col0, bool mirror) {
+// one eye's bilinear sample: eye image = columns [cmin, cmin + we) of the frame; (sl, cl) = np.exp(lon * 1j)
+__device__ __forceinline__ unsigned PbBilinear::eye(const PbParams& P, const uint8_t* __restrict__ s, double lat, double sl, double cl, int we, double cx,
+                                                    int cmin, bool mirror) {
     const int h = P.src.height, w = P.src.width;
     const double dist = pb_lens_forward(P.src.lens, lat, P.rect_max) * P.src.f_distance;
-    double sl, cl;
-    pb_expi_np(lon, &sl, &cl);  // np.exp(lon * 1j)
     const double f0 = ((sl * dist) * -1.0) + P.src_cy, f1 = (cl * dist) + cx;
-    const bool live = f0 == f0 && f1 == f1 && fabs(f0) < 1.0e9 && fabs(f1) < 1.0e9 && f0 >= 0.0 && f0 < (double)h && f1 >= 0.0 && f1 < (double)we;
-    if (!live) return 0u;
+    if (!pb_live_in(f0, f1, 1.0e9, h, we)) return 0u;
     const double sy = f0 - 0.5, sx = f1 - 0.5;
     const int by = (int)floor(sy), bx = (int)floor(sx);
     const float ty = (float)(sy - by), tx = (float)(sx - bx);
-    const int r0 = min(max(by, 0), h - 1), r1 = min(max(by + 1, 0), h - 1);
-    int c0 = min(max(bx, 0), we - 1), c1 = min(max(bx + 1, 0), we - 1);
-    c0 = col0 + (mirror ? we - 1 - c0 : c0);
-    c1 = col0 + (mirror ? we - 1 - c1 : c1);
-    const unsigned p00 = pb_load_px(s, r0 * w + c0), p01 = pb_load_px(s, r0 * w + c1);
-    const unsigned p10 = pb_load_px(s, r1 * w + c0), p11 = pb_load_px(s, r1 * w + c1);
+    int r[2], g[2];
+    pb_tap_addr<2, false>(by, bx, h, cmin, cmin + we, mirror, r, g);
+    const unsigned p00 = pb_load_px(s, r[0] * w + g[0]), p01 = pb_load_px(s, r[0] * w + g[1]);
+    const unsigned p10 = pb_load_px(s, r[1] * w + g[0]), p11 = pb_load_px(s, r[1] * w + g[1]);
     unsigned out = 0;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
@@ -896,31 +902,30 @@ __device__ __forceinline__ unsigned pb_bilinear_eye(const PbParams& P, const uin
     return out;
 }
 
-// one output pixel of the double-fisheye bilinear mode from the float64 chain (the mode's definition on the device)
-__device__ __forceinline__ unsigned pb_bilinear_double_px(const PbParams& P, int i, int j, const uint8_t* __restrict__ s) {
+// One output pixel from a double-fisheye source, from the float64 chain: the reference's blend (projection.py:439-460) of the two eyes'
+// rounded samples, each eye sampled like a camera source on its half of the frame (the right one mirrored).  (Whole inside the frame loop
+// of its callers: with the chain hoisted out of it by hand both filters' kernels need 256 VGPRs and more, one wave per SIMD.)
+template <class FILTER>
+__device__ __forceinline__ unsigned pb_interp_double_px(const PbParams& P, int i, int j, const uint8_t* __restrict__ s) {
     PbCoord c = pb_dst_coord(P, i, j);
     c = pb_rotate_all(P, c);
     if (c.inv) return 0u;
     const double lat_r = (c.lat * -1.0) + PB_PI;  // projection.py:426-427
     const double fl = pb_merge_factor(P, c.lat), fr = pb_merge_factor(P, lat_r);
-    const unsigned l = pb_bilinear_eye(P, s, c.lat, c.lon, P.src_eye_w, P.src_cx, 0, false);
-    const unsigned r = pb_bilinear_eye(P, s, lat_r, c.lon, P.src_eye_w_right, P.src_cx_r, P.src_eye_w, true);
+    double sl, cl;
+    pb_expi_np(c.lon, &sl, &cl);  // np.exp(lon * 1j)
+    const unsigned l = FILTER::eye(P, s, c.lat, sl, cl, P.src_eye_w, P.src_cx, 0, false);
+    const unsigned r = FILTER::eye(P, s, lat_r, sl, cl, P.src_eye_w_right, P.src_cx_r, P.src_eye_w, true);
     return pb_blend_u8(l & 0xFF, r & 0xFF, fl, fr) | (pb_blend_u8((l >> 8) & 0xFF, (r >> 8) & 0xFF, fl, fr) << 8) |
            (pb_blend_u8((l >> 16) & 0xFF, (r >> 16) & 0xFF, fl, fr) << 16);
 }
-
-__global__ __launch_bounds__(PB_BLOCK) void pb_bilinear_double_kernel(const PbParams P, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                                                      int n_frames, unsigned long long src_stride, unsigned long long dst_stride) {
-    const unsigned p = blockIdx.x * PB_BLOCK + threadIdx.x;
-    if (p >= (unsigned)P.dst.height * (unsigned)P.dst.width) return;
-    const int i = p / (unsigned)P.dst.width, j = p - (unsigned)i * (unsigned)P.dst.width;
-    for (int f = 0; f < n_frames; ++f) {
-        const unsigned v = pb_bilinear_double_px(P, i, j, src + (unsigned long long)f * src_stride);
-        uint8_t* o = dst + (unsigned long long)f * dst_stride + 3ull * p;
-        o[0] = (uint8_t)(v & 0xFF);
-        o[1] = (uint8_t)((v >> 8) & 0xFF);
-        o[2] = (uint8_t)((v >> 16) & 0xFF);
-    }
+template <class FILTER>
+__global__ __launch_bounds__(PB_BLOCK) void pb_interp_double_kernel(const PbParams P, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,
+                                                                    unsigned long long src_stride, unsigned long long dst_stride) {
+    PbPixelPick k;
+    if (!pb_pick_pixel(P, true, nullptr, 0, nullptr, 0, nullptr, 0, k)) return;
+    for (int f = 0; f < n_frames; ++f)
+        pb_store_px(dst + (unsigned long long)f * dst_stride + 3ull * k.p, pb_interp_double_px<FILTER>(P, k.i, k.j, src + (unsigned long long)f * src_stride));
 }
 
 // ---- double-fisheye source -------------------------------------------------------------------------------------------------
@@ -1084,9 +1089,7 @@ __global__ __launch_bounds__(64 * WAVES, PB_BIL_WPE_DBL) void pb_bilinear_double
                 const unsigned r = pb_bil_table_px<false>(src, qr.y, qr.x, Hd.src_h, Hd.src_w, eye_w, Hd.src_w, frame_bytes);
                 const unsigned px = pb_sep_blend(l, r, px_fix[item].fl, px_fix[item].fr);
                 uint8_t* o = dst + 3ull * p;
-                o[0] = (uint8_t)(px & 0xFF);
-                o[1] = (uint8_t)((px >> 8) & 0xFF);
-                o[2] = (uint8_t)((px >> 16) & 0xFF);
+                pb_store_px(o, px);
             }
         }
     }
@@ -1412,29 +1415,8 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_bilinear_double_fix_kernel(const 
                                                                           const int32_t* __restrict__ fix_px, int n_fix_px,
                                                                           const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,
                                                                           unsigned long long src_stride, unsigned long long dst_stride) {
-    int i, j;
-    // n_fail_tiles: both lists together; the first n_fail_only entries come from fail_tiles
-    if ((int)blockIdx.x < 4 * n_fail_tiles) {
-        const int k = blockIdx.x >> 2;
-        const int t = k < n_fail_only ? fail_tiles[k] : more_tiles[k - n_fail_only];
-        const int ty = t / pb_tiles_x(P), tx = t - ty * pb_tiles_x(P);
-        const int local = (blockIdx.x & 3) * 256 + threadIdx.x;
-        i = ty * PB_TILE + (local >> 5);
-        j = tx * PB_TILE + (local & 31);
-        if (i >= P.dst.height || j >= P.dst.width) return;
-    } else {
-        const unsigned item = (blockIdx.x - 4u * (unsigned)n_fail_tiles) * PB_BLOCK + threadIdx.x;
-        if (item >= (unsigned)n_fix_px) return;
-        const unsigned p = (unsigned)fix_px[item];
-        i = p / (unsigned)P.dst.width;
-        j = p - (unsigned)i * (unsigned)P.dst.width;
-    }
-    const size_t p = (size_t)i * P.dst.width + j;
-    for (int f = 0; f < n_frames; ++f) {
-        const unsigned v = pb_bilinear_double_px(P, i, j, src + (unsigned long long)f * src_stride);
-        uint8_t* o = dst + (unsigned long long)f * dst_stride + 3 * p;
-        o[0] = (uint8_t)(v & 0xFF);
-        o[1] = (uint8_t)((v >> 8) & 0xFF);
-        o[2] = (uint8_t)((v >> 16) & 0xFF);
-    }
+    PbPixelPick k;  // n_fail_tiles: both lists together; the first n_fail_only entries come from fail_tiles
+    if (!pb_pick_pixel(P, false, fail_tiles, n_fail_only, more_tiles, n_fail_tiles, fix_px, n_fix_px, k) || !k.inside) return;
+    for (int f = 0; f < n_frames; ++f)
+        pb_store_px(dst + (unsigned long long)f * dst_stride + 3ull * k.p, pb_interp_double_px<PbBilinear>(P, k.i, k.j, src + (unsigned long long)f * src_stride));
 }

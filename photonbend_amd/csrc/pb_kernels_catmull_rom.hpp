@@ -10,10 +10,11 @@
 // rounded half to even and clipped to the sample type's range (the cubic overshoots).  Black exactly where the bilinear mode is black.
 // A double-fisheye source blends the two eyes' rounded samples like the reference, (l fl + r fr).astype(uint8).
 //
-//   pb_sample_map_catmull_rom_kernel   the definition per pixel from a materialised map, any image (C channels of 8- or 16-bit samples)
-//   pb_catmull_rom_fix_kernel          the definition per pixel from the plan's float64 chain: every pixel (PB_MODE_FAITHFUL, deferred
-//                                      plans, plans without the bilinear mode's tables), or the tiles the tile kernel leaves to it
-//   pb_catmull_rom_double_kernel       the same for double-fisheye sources (every pixel)
+//   PbCatmullRom                       the FILTER of the shared sampler kernels of pb_kernels_bilinear.hpp: with it
+//                                      pb_sample_map_interp_kernel is the definition per pixel from a materialised map, any image (C channels
+//                                      of 8- or 16-bit samples); pb_interp_fix_kernel the definition per pixel from the plan's float64 chain -
+//                                      every pixel (PB_MODE_FAITHFUL, deferred plans, plans without the bilinear mode's tables) or the tiles
+//                                      and fix pixels the tile kernel leaves to it; pb_interp_double_kernel the same for double-fisheye sources
 //   pb_catmull_rom_hot_kernel          THE hot path, single sources: one wave per tile over the bilinear mode's launch-order table,
 //                                      coordinates from its certified tile models and exact coordinate tables, float32 arithmetic
 // The float64 kernels evaluate the definition's own expressions under the build's -ffp-contract=off: their bytes are the definition's.
@@ -27,202 +28,72 @@ __device__ __forceinline__ void pb_cr64_weights(double t, double w[4]) {
     w[2] = ((-1.5 * t + 2.0) * t + 0.5) * t;
     w[3] = (0.5 * t - 0.5) * t * t;
 }
-// one source's sample of channel ch at pre-truncation coordinate (fy, fx): taps clamped to rows [0, h) and to columns [cmin, cmax) of a frame
-// `w` wide (`mirror`: the right eye's image is its half mirrored, eye column x = frame column cmax - 1 - x); WRAP: a panorama's columns
-// wrap first.  Rounded half to even and clipped to the sample type's range.  (pb_bil64_sample's 4 x 4 sibling.)
-template <typename SAMPLE, bool WRAP>
-__device__ __forceinline__ double pb_cr64_sample(const SAMPLE* __restrict__ img, double fy, double fx, int h, int w, int cmin, int cmax, bool mirror,
-                                                 int channels, int ch) {
-    const double sy = fy - 0.5, sx = fx - 0.5;
-    const double ry = floor(sy), rx = floor(sx);
-    double wy[4], wx[4];
-    pb_cr64_weights(sy - ry, wy);
-    pb_cr64_weights(sx - rx, wx);
-    const long long i0 = (long long)ry, j0 = (long long)rx, we = cmax - cmin;
-    long long g[4];
+// The FILTER (pb_kernels_bilinear.hpp) of this mode: PbBilinear's 4 x 4 sibling.  Its per-pixel routes ARE the definition: the coordinate as
+// the map kernel computes it from the chain's (lat, lon), liveness bound 1.0e300, sample64 per channel.
+struct PbCatmullRom {
+    template <typename SAMPLE, bool WRAP>
+    static __device__ __forceinline__ double sample64(const SAMPLE* __restrict__ img, double fy, double fx, int h, int w, int cmin, int cmax, bool mirror,
+                                                      int channels, int ch) {
+        const double sy = fy - 0.5, sx = fx - 0.5;
+        const double ry = floor(sy), rx = floor(sx);
+        double wy[4], wx[4];
+        pb_cr64_weights(sy - ry, wy);
+        pb_cr64_weights(sx - rx, wx);
+        long long r[4], g[4];
+        pb_tap_addr<4, WRAP>((long long)ry - 1, (long long)rx - 1, h, cmin, cmax, mirror, r, g);
+        double v = 0.0;
 #pragma unroll
-    for (int l = 0; l < 4; ++l) {
-        long long c = j0 - 1 + l;
-        if (WRAP) {
-            c %= we;
-            if (c < 0) c += we;
+        for (int k = 0; k < 4; ++k) {
+            double s = wx[0] * pb_bil64_tap(img, r[k], g[0], w, channels, ch);
+            s = s + wx[1] * pb_bil64_tap(img, r[k], g[1], w, channels, ch);
+            s = s + wx[2] * pb_bil64_tap(img, r[k], g[2], w, channels, ch);
+            s = s + wx[3] * pb_bil64_tap(img, r[k], g[3], w, channels, ch);
+            v = (k == 0) ? wy[0] * s : v + wy[k] * s;
         }
-        c = c < 0 ? 0 : (c > we - 1 ? we - 1 : c);
-        g[l] = mirror ? (cmax - 1 - c) : (cmin + c);
+        v = rint(v);
+        const double vmax = (double)(SAMPLE)~(SAMPLE)0;
+        return v < 0.0 ? 0.0 : (v > vmax ? vmax : v);
     }
-    double v = 0.0;
+    // one source's (or eye's) uint8 RGB pixel
+    template <bool WRAP>
+    static __device__ __forceinline__ unsigned rgb(const uint8_t* __restrict__ s, double fy, double fx, int h, int w, int cmin, int cmax, bool mirror) {
+        unsigned out = 0;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        long long r = i0 - 1 + k;
-        r = r < 0 ? 0 : (r > h - 1 ? h - 1 : r);
-        double s = wx[0] * pb_bil64_tap(img, r, g[0], w, channels, ch);
-        s = s + wx[1] * pb_bil64_tap(img, r, g[1], w, channels, ch);
-        s = s + wx[2] * pb_bil64_tap(img, r, g[2], w, channels, ch);
-        s = s + wx[3] * pb_bil64_tap(img, r, g[3], w, channels, ch);
-        v = (k == 0) ? wy[0] * s : v + wy[k] * s;
+        for (int ch = 0; ch < 3; ++ch) out |= (unsigned)sample64<uint8_t, WRAP>(s, fy, fx, h, w, cmin, cmax, mirror, 3, ch) << (8 * ch);
+        return out;
     }
-    v = rint(v);
-    const double vmax = (double)(SAMPLE)~(SAMPLE)0;
-    return v < 0.0 ? 0.0 : (v > vmax ? vmax : v);
-}
-
-// The mode on a MATERIALISED map, any image: pb_sample_map_bilinear_kernel with the 4 x 4 sample (same coordinates, same liveness).
-template <int SRC_KIND, typename SAMPLE>
-__global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_catmull_rom_kernel(const PbParams P, double* __restrict__ map, unsigned total,
-                                                                             const double* __restrict__ dist_l, const double* __restrict__ dist_r,
-                                                                             const SAMPLE* __restrict__ img, void* __restrict__ out, int channels) {
-    const unsigned p = blockIdx.x * PB_BLOCK + threadIdx.x;
-    if (p >= total) return;
-    double* a = map + 3ull * p;
-    const bool inv = a[2] != 0.0;
-    if (SRC_KIND == PB_KIND_PANO && inv) {
-        a[0] = 0.0;  // polar_map[invalid_map] = 0 writes through the view, projection.py:534-536
-        a[1] = 0.0;
-    }
-    const double lat = a[0], lon = a[1];
-    const int h = P.src.height, w = P.src.width;
-    if (SRC_KIND == PB_KIND_PANO) {
-        const double fy = lat / P.src_hseg, fx = lon / P.src_wseg + P.src_half_w;
-        const bool live = !inv && fabs(fy) < 1.0e300 && fabs(fx) < 1.0e300 && fy == fy && fx == fx;
-        SAMPLE* o = static_cast<SAMPLE*>(out) + (unsigned long long)p * (unsigned)channels;
-        for (int ch = 0; ch < channels; ++ch) o[ch] = live ? (SAMPLE)pb_cr64_sample<SAMPLE, true>(img, fy, fx, h, w, 0, w, false, channels, ch) : (SAMPLE)0;
-        return;
-    }
-    double sl, cl;
-    pb_expi_np(lon, &sl, &cl);  // np.exp(lon * 1j), projection.py:252
-    if (SRC_KIND == PB_KIND_CAMERA) {
-        const double dist = dist_l ? dist_l[p] : pb_lens_forward(P.src.lens, lat, P.rect_max) * P.src.f_distance;
-        const double fy = ((sl * dist) * -1.0) + P.src_cy, fx = (cl * dist) + P.src_cx;
-        const bool live = !inv && fy == fy && fx == fx && fabs(fy) < 1.0e300 && fabs(fx) < 1.0e300 && fy >= 0.0 && fy < (double)h && fx >= 0.0 && fx < (double)w;
-        SAMPLE* o = static_cast<SAMPLE*>(out) + (unsigned long long)p * (unsigned)channels;
-        for (int ch = 0; ch < channels; ++ch) o[ch] = live ? (SAMPLE)pb_cr64_sample<SAMPLE, false>(img, fy, fx, h, w, 0, w, false, channels, ch) : (SAMPLE)0;
-        return;
-    }
-    const double lat_r = (lat * -1.0) + PB_PI;
-    const double dl = dist_l ? dist_l[p] : pb_lens_forward(P.src.lens, lat, P.rect_max) * P.src.f_distance;
-    const double dr = dist_r ? dist_r[p] : pb_lens_forward(P.src.lens, lat_r, P.rect_max) * P.src.f_distance;
-    const int wl = P.src_eye_w, wr = P.src_eye_w_right;
-    const double fyl = ((sl * dl) * -1.0) + P.src_cy, fxl = (cl * dl) + P.src_cx;
-    const double fyr = ((sl * dr) * -1.0) + P.src_cy, fxr = (cl * dr) + P.src_cx_r;
-    const bool live_l = !inv && fyl == fyl && fxl == fxl && fabs(fyl) < 1.0e300 && fabs(fxl) < 1.0e300 && fyl >= 0.0 && fyl < (double)h && fxl >= 0.0 && fxl < (double)wl;
-    const bool live_r = !inv && fyr == fyr && fxr == fxr && fabs(fyr) < 1.0e300 && fabs(fxr) < 1.0e300 && fyr >= 0.0 && fyr < (double)h && fxr >= 0.0 && fxr < (double)wr;
-    const double fl = pb_merge_factor(P, lat), fr = pb_merge_factor(P, lat_r);
-    uint8_t* o = static_cast<uint8_t*>(out) + (unsigned long long)p * (unsigned)channels;  // (left * fl + right * fr).astype(np.uint8)
-    for (int ch = 0; ch < channels; ++ch) {
-        const double l = live_l ? pb_cr64_sample<SAMPLE, false>(img, fyl, fxl, h, w, 0, wl, false, channels, ch) : 0.0;
-        const double r = live_r ? pb_cr64_sample<SAMPLE, false>(img, fyr, fxr, h, w, wl, wl + wr, true, channels, ch) : 0.0;
-        o[ch] = inv ? (uint8_t)0 : (uint8_t)pb_cvt_u8(l * fl + r * fr);
-    }
-}
-
-// ---- float64 routes of a plan (the definition on the device chain's coordinates) -----------------------------------------------------
-// One single source's uint8 RGB pixel (0: black), the coordinate computed as the map kernel computes it from the chain's (lat, lon).
-template <int SRC_KIND>
-__device__ __forceinline__ unsigned pb_cr64_px(const PbParams& P, const PbCoord& c, const uint8_t* __restrict__ s) {
-    if (c.inv) return 0u;
-    const int h = P.src.height, w = P.src.width;
-    double fy, fx;
-    bool live;
-    if (SRC_KIND == PB_KIND_PANO) {
-        fy = c.lat / P.src_hseg;
-        fx = c.lon / P.src_wseg + P.src_half_w;
-        live = fabs(fy) < 1.0e300 && fabs(fx) < 1.0e300 && fy == fy && fx == fx;
-    } else {
-        double sl, cl;
-        pb_expi_np(c.lon, &sl, &cl);
-        const double dist = pb_lens_forward(P.src.lens, c.lat, P.rect_max) * P.src.f_distance;
-        fy = ((sl * dist) * -1.0) + P.src_cy;
-        fx = (cl * dist) + P.src_cx;
-        live = fy == fy && fx == fx && fabs(fy) < 1.0e300 && fabs(fx) < 1.0e300 && fy >= 0.0 && fy < (double)h && fx >= 0.0 && fx < (double)w;
-    }
-    if (!live) return 0u;
-    unsigned out = 0;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch)
-        out |= (unsigned)pb_cr64_sample<uint8_t, SRC_KIND == PB_KIND_PANO>(s, fy, fx, h, w, 0, w, false, 3, ch) << (8 * ch);
-    return out;
-}
-
-// Pixels as pb_bilinear_fix_kernel picks them: all_pixels = every pixel; else the listed tiles (the first n_fail_only from fail_tiles, the
-// rest from more_tiles; 4 blocks each), then the fix pixels (blocks beyond the tiles).
-template <int SRC_KIND>
-__global__ __launch_bounds__(PB_BLOCK) void pb_catmull_rom_fix_kernel(const PbParams P, const int32_t* __restrict__ fail_tiles, int all_pixels,
-                                                                      const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,
-                                                                      unsigned long long src_stride, unsigned long long dst_stride, int n_tiles = 0,
-                                                                      const int32_t* __restrict__ fix_px = nullptr, int n_fix_px = 0,
-                                                                      const int32_t* __restrict__ more_tiles = nullptr, int n_fail_only = 0) {
-    int i, j;
-    if (all_pixels) {
-        const unsigned p = blockIdx.x * PB_BLOCK + threadIdx.x;
-        if (p >= (unsigned)P.dst.height * (unsigned)P.dst.width) return;
-        i = p / (unsigned)P.dst.width;
-        j = p - (unsigned)i * (unsigned)P.dst.width;
-    } else if ((int)blockIdx.x >= 4 * n_tiles) {
-        const unsigned item = (blockIdx.x - 4u * (unsigned)n_tiles) * PB_BLOCK + threadIdx.x;
-        if (!fix_px || item >= (unsigned)n_fix_px) return;
-        const unsigned p = (unsigned)fix_px[item];
-        i = p / (unsigned)P.dst.width;
-        j = p - (unsigned)i * (unsigned)P.dst.width;
-    } else {
-        const int k = blockIdx.x >> 2;
-        const int t = (more_tiles && k >= n_fail_only) ? more_tiles[k - n_fail_only] : fail_tiles[k];
-        const int ty = t / pb_tiles_x(P), tx = t - ty * pb_tiles_x(P);
-        const int local = (blockIdx.x & 3) * 256 + threadIdx.x;
-        i = ty * PB_TILE + (local >> 5);
-        j = tx * PB_TILE + (local & 31);
-        if (i >= P.dst.height || j >= P.dst.width) return;
-    }
-    const PbCoord c = pb_rotate_all(P, pb_dst_coord(P, i, j));
-    const size_t p = (size_t)i * P.dst.width + j;
-    for (int f = 0; f < n_frames; ++f) {
-        const unsigned v = pb_cr64_px<SRC_KIND>(P, c, src + (unsigned long long)f * src_stride);
-        uint8_t* o = dst + (unsigned long long)f * dst_stride + 3 * p;
-        o[0] = (uint8_t)(v & 0xFF);
-        o[1] = (uint8_t)((v >> 8) & 0xFF);
-        o[2] = (uint8_t)((v >> 16) & 0xFF);
-    }
-}
-
-// one eye's sample (0 where the eye is black), as the map kernel takes it
-__device__ __forceinline__ unsigned pb_cr64_eye(const PbParams& P, const uint8_t* __restrict__ s, double lat, double sl, double cl, int we, double cx,
-                                                int cmin, bool mirror) {
-    const int h = P.src.height;
-    const double dist = pb_lens_forward(P.src.lens, lat, P.rect_max) * P.src.f_distance;
-    const double fy = ((sl * dist) * -1.0) + P.src_cy, fx = (cl * dist) + cx;
-    const bool live = fy == fy && fx == fx && fabs(fy) < 1.0e300 && fabs(fx) < 1.0e300 && fy >= 0.0 && fy < (double)h && fx >= 0.0 && fx < (double)we;
-    if (!live) return 0u;
-    unsigned out = 0;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch)
-        out |= (unsigned)pb_cr64_sample<uint8_t, false>(s, fy, fx, h, P.src.width, cmin, cmin + we, mirror, 3, ch) << (8 * ch);
-    return out;
-}
-
-__global__ __launch_bounds__(PB_BLOCK) void pb_catmull_rom_double_kernel(const PbParams P, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                                                         int n_frames, unsigned long long src_stride, unsigned long long dst_stride) {
-    const unsigned p = blockIdx.x * PB_BLOCK + threadIdx.x;
-    if (p >= (unsigned)P.dst.height * (unsigned)P.dst.width) return;
-    const int i = p / (unsigned)P.dst.width, j = p - (unsigned)i * (unsigned)P.dst.width;
-    const PbCoord c = pb_rotate_all(P, pb_dst_coord(P, i, j));
-    const double lat_r = (c.lat * -1.0) + PB_PI;  // projection.py:426-427
-    const double fl = pb_merge_factor(P, c.lat), fr = pb_merge_factor(P, lat_r);
-    double sl, cl;
-    pb_expi_np(c.lon, &sl, &cl);
-    for (int f = 0; f < n_frames; ++f) {
-        const uint8_t* s = src + (unsigned long long)f * src_stride;
-        unsigned v = 0;
-        if (!c.inv) {
-            const unsigned l = pb_cr64_eye(P, s, c.lat, sl, cl, P.src_eye_w, P.src_cx, 0, false);
-            const unsigned r = pb_cr64_eye(P, s, lat_r, sl, cl, P.src_eye_w_right, P.src_cx_r, P.src_eye_w, true);
-            v = pb_blend_u8(l & 0xFF, r & 0xFF, fl, fr) | (pb_blend_u8((l >> 8) & 0xFF, (r >> 8) & 0xFF, fl, fr) << 8) |
-                (pb_blend_u8((l >> 16) & 0xFF, (r >> 16) & 0xFF, fl, fr) << 16);
+    struct Px {
+        bool live;
+        double fy, fx;
+    };
+    template <int SRC_KIND>
+    static __device__ __forceinline__ Px prepare(const PbParams& P, const PbCoord& c) {
+        Px q;
+        if (SRC_KIND == PB_KIND_PANO) {
+            q.fy = c.lat / P.src_hseg;
+            q.fx = c.lon / P.src_wseg + P.src_half_w;
+            q.live = !c.inv && pb_live(q.fy, q.fx, 1.0e300);
+        } else {
+            double sl, cl;
+            pb_expi_np(c.lon, &sl, &cl);
+            const double dist = pb_lens_forward(P.src.lens, c.lat, P.rect_max) * P.src.f_distance;
+            q.fy = ((sl * dist) * -1.0) + P.src_cy;
+            q.fx = (cl * dist) + P.src_cx;
+            q.live = !c.inv && pb_live_in(q.fy, q.fx, 1.0e300, P.src.height, P.src.width);
         }
-        uint8_t* o = dst + (unsigned long long)f * dst_stride + 3ull * p;
-        o[0] = (uint8_t)(v & 0xFF);
-        o[1] = (uint8_t)((v >> 8) & 0xFF);
-        o[2] = (uint8_t)((v >> 16) & 0xFF);
+        return q;
     }
-}
+    template <int SRC_KIND>
+    static __device__ __forceinline__ unsigned sample(const PbParams& P, const Px& q, const uint8_t* __restrict__ s) {
+        return q.live ? rgb<SRC_KIND == PB_KIND_PANO>(s, q.fy, q.fx, P.src.height, P.src.width, 0, P.src.width, false) : 0u;
+    }
+    static __device__ __forceinline__ unsigned eye(const PbParams& P, const uint8_t* __restrict__ s, double lat, double sl, double cl, int we, double cx,
+                                                   int cmin, bool mirror) {
+        const double dist = pb_lens_forward(P.src.lens, lat, P.rect_max) * P.src.f_distance;
+        const double fy = ((sl * dist) * -1.0) + P.src_cy, fx = (cl * dist) + cx;
+        return pb_live_in(fy, fx, 1.0e300, P.src.height, we) ? rgb<false>(s, fy, fx, P.src.height, P.src.width, cmin, cmin + we, mirror) : 0u;
+    }
+};
 
 // ---- the tile kernel: float32 arithmetic -------------------------------------------------------------------------------------------
 // Precision budget.  The tile models are certified to PB_COARSE_PX = 1/1024 px per axis against the faithful coordinate; the
@@ -427,7 +298,7 @@ __device__ __forceinline__ void pb_cr_vals(const PbHot& Hd, const PbTileEntry* _
 
 // One wave per tile over the bilinear mode's launch-order table, four waves per workgroup (pb_bil_slot_of<4>), frames of a batch a grid
 // dimension.  The tile's fix pixels are redone from their exact coordinates after the tile's stores, like pb_bilinear_hot_kernel's.
-// bil_xy == nullptr: the plan has no coordinate table; its table tiles and fix pixels are left to pb_catmull_rom_fix_kernel.
+// bil_xy == nullptr: the plan has no coordinate table; its table tiles and fix pixels are left to pb_interp_fix_kernel<PbCatmullRom>.
 #define PB_CR_WAVES 4
 #define PB_CR_WPE 3  // waves per SIMD the tile kernel is compiled for (its register budget: 168 VGPRs; at 128 it spills)
 template <int SRC_KIND>
@@ -473,9 +344,7 @@ __global__ __launch_bounds__(64 * PB_CR_WAVES, PB_CR_WPE) void pb_catmull_rom_ho
             pb_cr_mix2(r, r, (pb_f2){ftx, ftx}, (pb_f2){fty, fty}, o);
             const unsigned px = dead ? 0u : o[0];
             uint8_t* d = dst + 3ull * p;
-            d[0] = (uint8_t)(px & 0xFF);
-            d[1] = (uint8_t)((px >> 8) & 0xFF);
-            d[2] = (uint8_t)((px >> 16) & 0xFF);
+            pb_store_px(d, px);
         }
     }
 }

@@ -471,9 +471,7 @@ __global__ __launch_bounds__(64 * PB_TILE_WAVES) void pb_hot_double_kernel(const
                 for (int f = 0; f < frames; ++f) {
                     const unsigned v = pb_double_fix_px(t, src + (unsigned long long)f * src_stride);
                     uint8_t* o = dst + (unsigned long long)f * dst_stride + 3ull * p;
-                    o[0] = (uint8_t)(v & 0xFF);
-                    o[1] = (uint8_t)((v >> 8) & 0xFF);
-                    o[2] = (uint8_t)((v >> 16) & 0xFF);
+                    pb_store_px(o, v);
                 }
             }
         }
@@ -490,24 +488,11 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_double_tables_kernel(const PbPara
                                                                     const int32_t* __restrict__ fail_tiles, int n_fail_tiles,
                                                                     const int32_t* __restrict__ fix_px, int n_fix_px,
                                                                     PbDoubleFix* __restrict__ tile_fix, PbDoubleFix* __restrict__ px_fix) {
-    int i, j;
-    PbDoubleFix* out;
-    if ((int)blockIdx.x < 4 * n_fail_tiles) {
-        const int s = blockIdx.x >> 2, t = fail_tiles[s];
-        const int ty = t / pb_tiles_x(P), tx = t - ty * pb_tiles_x(P);
-        const int local = (blockIdx.x & 3) * 256 + threadIdx.x;
-        i = min(ty * PB_TILE + (local >> 5), P.dst.height - 1);  // pixels beyond the image are never stored
-        j = min(tx * PB_TILE + (local & 31), P.dst.width - 1);
-        out = tile_fix + (size_t)s * (PB_TILE * PB_TILE) + local;
-        if (local == 0) table_r[t].aux_off = s;
-    } else {
-        const unsigned item = (blockIdx.x - 4u * n_fail_tiles) * PB_BLOCK + threadIdx.x;
-        if (item >= (unsigned)n_fix_px) return;
-        const unsigned p = (unsigned)fix_px[item];
-        i = (int)(p / (unsigned)P.dst.width);
-        j = (int)(p - (unsigned)i * (unsigned)P.dst.width);
-        out = px_fix + item;
-    }
+    PbPixelPick k;
+    if (!pb_pick_pixel(P, false, fail_tiles, n_fail_tiles, nullptr, n_fail_tiles, fix_px, n_fix_px, k)) return;
+    const int i = min(k.i, P.dst.height - 1), j = min(k.j, P.dst.width - 1);  // (a tile's pixels beyond the image are never stored)
+    PbDoubleFix* out = k.local >= 0 ? tile_fix + (size_t)k.slot * (PB_TILE * PB_TILE) + k.local : px_fix + k.slot;
+    if (k.local == 0) table_r[k.tile].aux_off = k.slot;
     PbCoord c = pb_dst_coord(P, i, j);
     c = pb_rotate_all(P, c);
     const PbDoubleTap t = pb_src_double_taps(P, c);

@@ -24,6 +24,18 @@ __device__ __forceinline__ unsigned pb_load_px(const uint8_t* __restrict__ src, 
     const uint8_t* p = src + 3ull * (unsigned)idx;
     return (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
 }
+// a packed RGB pixel (pb_load_px's layout) as three bytes
+__device__ __forceinline__ void pb_store_px(uint8_t* __restrict__ o, unsigned v) {
+    o[0] = (uint8_t)(v & 0xFF);
+    o[1] = (uint8_t)((v >> 8) & 0xFF);
+    o[2] = (uint8_t)((v >> 16) & 0xFF);
+}
+// Liveness of a pre-truncation source coordinate: a number below `bound` in magnitude (the float64 definitions take 1.0e300, whatever
+// feeds the 1/4096-px fixed point or float32 taps 1.0e9) and, for a source with an edge (pb_live_in), inside [0, h) x [0, w).
+__device__ __forceinline__ bool pb_live(double fy, double fx, double bound) { return fy == fy && fx == fx && fabs(fy) < bound && fabs(fx) < bound; }
+__device__ __forceinline__ bool pb_live_in(double fy, double fx, double bound, int h, int w) {
+    return pb_live(fy, fx, bound) && fy >= 0.0 && fy < (double)h && fx >= 0.0 && fx < (double)w;
+}
 
 // Packs 4 RGB pixels (24-bit each, in the low bits of a[0..3]) into 3 dwords and
 // stores them; `full` = all four pixels exist and the address is 4-byte aligned.
@@ -217,9 +229,7 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_kernel(const PbParams 
                 (pb_blend_u8((l >> 16) & 0xFF, (r >> 16) & 0xFF, t.fl, t.fr) << 16);
     }
     uint8_t* o = dst + 3ull * p;
-    o[0] = (uint8_t)(v & 0xFF);
-    o[1] = (uint8_t)((v >> 8) & 0xFF);
-    o[2] = (uint8_t)((v >> 16) & 0xFF);
+    pb_store_px(o, v);
 }
 
 // ---- generic images and user lenses (drop-in completeness; off the hot path) ------------------------------------

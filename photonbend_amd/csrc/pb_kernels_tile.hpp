@@ -33,6 +33,50 @@ __device__ __forceinline__ unsigned pb_load_px32(const uint8_t* __restrict__ src
 __device__ __forceinline__ int pb_tiles_x(const PbParams& P) { return (P.dst.width + PB_TILE - 1) / PB_TILE; }
 __device__ __forceinline__ int pb_tiles_y(const PbParams& P) { return (P.dst.height + PB_TILE - 1) / PB_TILE; }
 
+// Which pixel a work-item of a per-pixel launch (PB_BLOCK work-items a block) owns.  all_pixels: pixel blockIdx.x * PB_BLOCK + threadIdx.x
+// of the image.  Otherwise a fix launch: blocks [0, 4 * n_tiles) take the listed tiles, four blocks of 256 pixels each - tile k of the list
+// is fail_tiles[k] for k < n_fail_only and more_tiles[k - n_fail_only] beyond (more_tiles == nullptr: fail_tiles holds them all) -, the
+// blocks after them the items of fix_px.  false: the work-item owns nothing (beyond the image's or the list's end).
+struct PbPixelPick {
+    int i, j;     // the pixel; a listed tile's may lie beyond the image's edge: `inside` says
+    bool inside;
+    unsigned p;   // i * width + j (inside)
+    int tile;     // the listed tile (else unset)
+    int slot;     // the tile's position in the list / the pixel's in fix_px (all_pixels: unset)
+    int local;    // the pixel's index inside its listed tile, [0, PB_TILE * PB_TILE); -1: not a listed tile's pixel
+};
+__device__ __forceinline__ bool pb_pick_pixel(const PbParams& P, bool all_pixels, const int32_t* __restrict__ fail_tiles, int n_fail_only,
+                                              const int32_t* __restrict__ more_tiles, int n_tiles, const int32_t* __restrict__ fix_px, int n_fix_px,
+                                              PbPixelPick& k) {
+    if (all_pixels || (int)blockIdx.x >= 4 * n_tiles) {
+        unsigned p;
+        if (all_pixels) {
+            p = blockIdx.x * PB_BLOCK + threadIdx.x;
+            if (p >= (unsigned)P.dst.height * (unsigned)P.dst.width) return false;
+        } else {
+            const unsigned item = (blockIdx.x - 4u * (unsigned)n_tiles) * PB_BLOCK + threadIdx.x;
+            if (item >= (unsigned)n_fix_px) return false;  // (no list: n_fix_px == 0)
+            k.slot = (int)item;
+            p = (unsigned)fix_px[item];
+        }
+        k.p = p;
+        k.local = -1;
+        k.i = (int)(p / (unsigned)P.dst.width);
+        k.j = (int)(p - (unsigned)k.i * (unsigned)P.dst.width);
+        k.inside = true;
+        return true;
+    }
+    k.slot = blockIdx.x >> 2;
+    k.tile = (more_tiles && k.slot >= n_fail_only) ? more_tiles[k.slot - n_fail_only] : fail_tiles[k.slot];
+    const int ty = k.tile / pb_tiles_x(P), tx = k.tile - ty * pb_tiles_x(P);
+    k.local = (blockIdx.x & 3) * 256 + threadIdx.x;
+    k.i = ty * PB_TILE + (k.local >> 5);
+    k.j = tx * PB_TILE + (k.local & 31);
+    k.inside = k.i < P.dst.height && k.j < P.dst.width;
+    k.p = (unsigned)k.i * (unsigned)P.dst.width + (unsigned)k.j;
+    return true;
+}
+
 // block -> 2x2 group of tiles; wave -> tile.  Returns false for waves beyond the image.
 __device__ __forceinline__ bool pb_tile_of_wave(const PbParams& P, int wave, int& tx, int& ty, unsigned block = blockIdx.x) {
     const int gx = (pb_tiles_x(P) + 1) / 2, gy = (pb_tiles_y(P) + 1) / 2;
@@ -751,9 +795,7 @@ __global__ __launch_bounds__(64 * PB_TILE_WAVES) void pb_hot_win_kernel(const Pb
             const int id = fix_idx[e->fix_off + lane];
             const unsigned v = pb_load_px(src, id);
             uint8_t* o = dst + 3ull * p;
-            o[0] = (uint8_t)(v & 0xFF);
-            o[1] = (uint8_t)((v >> 8) & 0xFF);
-            o[2] = (uint8_t)((v >> 16) & 0xFF);
+            pb_store_px(o, v);
         }
     }
 #ifdef PB_TRACE
@@ -1002,20 +1044,14 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_fix_tables_kernel(const PbParams 
                                                                  const int32_t* __restrict__ fail_tiles, int n_fail_tiles,
                                                                  const int32_t* __restrict__ fix_px, int n_fix_px,
                                                                  int32_t* __restrict__ idx_tab, int32_t* __restrict__ fix_idx) {
-    if ((int)blockIdx.x < 4 * n_fail_tiles) {
-        const int s = blockIdx.x >> 2, t = fail_tiles[s];
-        const int ty = t / pb_tiles_x(P), tx = t - ty * pb_tiles_x(P);
-        const int local = (blockIdx.x & 3) * 256 + threadIdx.x;
-        const int i = ty * PB_TILE + (local >> 5), j = tx * PB_TILE + (local & 31);
-        idx_tab[(size_t)s * (PB_TILE * PB_TILE) + local] = (i < P.dst.height && j < P.dst.width) ? pb_exact_index<SRC_KIND>(P, i, j) : -1;
-        if (local == 0) table[t].aux_off = s;
+    PbPixelPick k;
+    if (!pb_pick_pixel(P, false, fail_tiles, n_fail_tiles, nullptr, n_fail_tiles, fix_px, n_fix_px, k)) return;
+    if (k.local >= 0) {
+        idx_tab[(size_t)k.slot * (PB_TILE * PB_TILE) + k.local] = k.inside ? pb_exact_index<SRC_KIND>(P, k.i, k.j) : -1;
+        if (k.local == 0) table[k.tile].aux_off = k.slot;
         return;
     }
-    const unsigned item = (blockIdx.x - 4u * n_fail_tiles) * PB_BLOCK + threadIdx.x;
-    if (item >= (unsigned)n_fix_px) return;
-    const unsigned p = (unsigned)fix_px[item];
-    const int i = (int)(p / (unsigned)P.dst.width), j = (int)(p - (unsigned)i * (unsigned)P.dst.width);
-    fix_idx[item] = pb_exact_index<SRC_KIND>(P, i, j);
+    fix_idx[k.slot] = pb_exact_index<SRC_KIND>(P, k.i, k.j);
 }
 
 // The plan's fix list behind pb_hot_kernel (frames LDS-DMA cannot address, and the int32 index-map output): blocks
@@ -1029,22 +1065,10 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_fix_kernel(const PbParams P, cons
                                                           uint8_t* __restrict__ dst, int n_frames,
                                                           unsigned long long src_stride, unsigned long long dst_stride,
                                                           int32_t* __restrict__ idx_out) {
-    int id;
-    size_t p;
-    if ((int)blockIdx.x < 4 * n_fail_tiles) {
-        const int s = blockIdx.x >> 2, t = fail_tiles[s];
-        const int ty = t / pb_tiles_x(P), tx = t - ty * pb_tiles_x(P);
-        const int local = (blockIdx.x & 3) * 256 + threadIdx.x;
-        const int i = ty * PB_TILE + (local >> 5), j = tx * PB_TILE + (local & 31);
-        if (i >= P.dst.height || j >= P.dst.width) return;
-        id = idx_tab[(size_t)s * (PB_TILE * PB_TILE) + local];
-        p = (size_t)i * P.dst.width + j;
-    } else {
-        const unsigned item = (blockIdx.x - 4u * n_fail_tiles) * PB_BLOCK + threadIdx.x;
-        if (item >= (unsigned)n_fix_px) return;
-        id = fix_idx[item];
-        p = (size_t)(unsigned)fix_px[item];
-    }
+    PbPixelPick k;
+    if (!pb_pick_pixel(P, false, fail_tiles, n_fail_tiles, nullptr, n_fail_tiles, fix_px, n_fix_px, k) || !k.inside) return;
+    const int id = k.local >= 0 ? idx_tab[(size_t)k.slot * (PB_TILE * PB_TILE) + k.local] : fix_idx[k.slot];
+    const size_t p = k.p;
     if (OUT == 1) {
         idx_out[p] = id;
         return;
@@ -1052,9 +1076,7 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_fix_kernel(const PbParams P, cons
     for (int f = 0; f < n_frames; ++f) {
         const unsigned v = pb_load_px(src + (unsigned long long)f * src_stride, id);
         uint8_t* o = dst + (unsigned long long)f * dst_stride + 3 * p;
-        o[0] = (uint8_t)(v & 0xFF);
-        o[1] = (uint8_t)((v >> 8) & 0xFF);
-        o[2] = (uint8_t)((v >> 16) & 0xFF);
+        pb_store_px(o, v);
     }
 }
 

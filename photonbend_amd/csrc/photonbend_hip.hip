@@ -389,6 +389,30 @@ static bool pb_bilinear_tiles_allowed(const PbParams& P) {
     // (below 180 degrees the band turns inside out; it exists down to 179.5 degrees, with factors from 1 up to 0.5 deg / (180 deg - fov))
     return !(P.src.kind == PB_KIND_DOUBLE && P.mrg_range != 0.0 && fabs(P.mrg_range) < 0.999 * (PB_PI / 180.0));  // (181 / 179 degrees themselves: tiles)
 }
+#define PB_INTERP_CATMULL_ROM 2  // (a routing id of this file only: the supersampled entry points take PB_INTERP_NEAREST and PB_INTERP_BILINEAR)
+// Template arguments from run-time values: f(PbInt<A>()) if `first`, else f(PbInt<B>()) - the kernel's KIND, its waves per workgroup,
+// the supersample factor.
+template <int V>
+using PbInt = std::integral_constant<int, V>;
+template <int A, int B, class F>
+static void pb_pick(bool first, F&& f) {
+    if (first) f(PbInt<A>());
+    else f(PbInt<B>());
+}
+template <class F>
+static void pb_pick_kind(const PbParams& P, F&& f) {  // (single sources)
+    pb_pick<PB_KIND_PANO, PB_KIND_CAMERA>(P.src.kind == PB_KIND_PANO, f);
+}
+template <class F>
+static void pb_pick_any_kind(const PbParams& P, F&& f) {
+    if (P.src.kind == PB_KIND_DOUBLE) f(PbInt<PB_KIND_DOUBLE>());
+    else pb_pick_kind(P, f);
+}
+template <class F>
+static void pb_pick_filter(int filter, F&& f) {  // (the FILTER of the shared sampler kernels, pb_kernels_bilinear.hpp)
+    if (filter == PB_INTERP_CATMULL_ROM) f(PbCatmullRom());
+    else f(PbBilinear());
+}
 static int pb_build_bilinear_list(pb_plan* pl) {
     const PbParams& P = pl->P;
     unsigned* cnt = nullptr;
@@ -429,12 +453,11 @@ static int pb_build_bilinear_list(pb_plan* pl) {
                     hipLaunchKernelGGL(pb_bilinear_fix_coord_kernel<PB_KIND_EYE_L>, fgrid, block, 0, 0, P, pl->fix_px, (int)np, pl->bil_fix_xy, 2, 0);
                     hipLaunchKernelGGL(pb_bilinear_fix_coord_kernel<PB_KIND_EYE_R>, fgrid, block, 0, 0, P, pl->fix_px, (int)np, pl->bil_fix_xy, 2, 1);
                 }
-            } else if (P.src.kind == PB_KIND_PANO) {
-                hipLaunchKernelGGL(pb_bilinear_coord_kernel<PB_KIND_PANO>, grid, block, 0, 0, P, pl->table, pl->bil_xy);
-                if (np) hipLaunchKernelGGL(pb_bilinear_fix_coord_kernel<PB_KIND_PANO>, fgrid, block, 0, 0, P, pl->fix_px, (int)np, pl->bil_fix_xy, 1, 0);
             } else {
-                hipLaunchKernelGGL(pb_bilinear_coord_kernel<PB_KIND_CAMERA>, grid, block, 0, 0, P, pl->table, pl->bil_xy);
-                if (np) hipLaunchKernelGGL(pb_bilinear_fix_coord_kernel<PB_KIND_CAMERA>, fgrid, block, 0, 0, P, pl->fix_px, (int)np, pl->bil_fix_xy, 1, 0);
+                pb_pick_kind(P, [&](auto K) {
+                    hipLaunchKernelGGL(pb_bilinear_coord_kernel<K.value>, grid, block, 0, 0, P, pl->table, pl->bil_xy);
+                    if (np) hipLaunchKernelGGL(pb_bilinear_fix_coord_kernel<K.value>, fgrid, block, 0, 0, P, pl->fix_px, (int)np, pl->bil_fix_xy, 1, 0);
+                });
             }
             // which way each slot is walked (lanes along the direction the source position moves least), slots walked by rows transposed
             // ... and whether its taps need the guards at all (PB_TILE_TAB_PLAIN); an eye's taps stay in its half of the frame
@@ -601,12 +624,10 @@ static int pb_plan_prepare_on_device(pb_plan* pl) {
                 pb_tmp_alloc((void**)&pl->fix_idx, (size_t)(np ? np : 1) * sizeof(int32_t)) != hipSuccess) { rc = PB_ERR_HIP; break; }
             const unsigned blocks = 4u * nf + (np + PB_BLOCK - 1) / PB_BLOCK;
             if (blocks) {
-                if (P.src.kind == PB_KIND_PANO)
-                    hipLaunchKernelGGL(pb_fix_tables_kernel<PB_KIND_PANO>, dim3(blocks), dim3(PB_BLOCK), 0, 0, P, pl->table, pl->fail_tiles, (int)nf,
-                                       pl->fix_px, (int)np, pl->idx_tab, pl->fix_idx);
-                else
-                    hipLaunchKernelGGL(pb_fix_tables_kernel<PB_KIND_CAMERA>, dim3(blocks), dim3(PB_BLOCK), 0, 0, P, pl->table, pl->fail_tiles, (int)nf,
-                                       pl->fix_px, (int)np, pl->idx_tab, pl->fix_idx);
+                pb_pick_kind(P, [&](auto K) {
+                    hipLaunchKernelGGL(pb_fix_tables_kernel<K.value>, dim3(blocks), dim3(PB_BLOCK), 0, 0, P, pl->table, pl->fail_tiles, (int)nf, pl->fix_px,
+                                       (int)np, pl->idx_tab, pl->fix_idx);
+                });
                 // (not waited for: the budget pass and the launch-order pass queue up behind it, and their readback reports a failure)
                 if (hipGetLastError() != hipSuccess) { rc = PB_ERR_HIP; break; }
             }
@@ -682,19 +703,17 @@ struct PbRoute {
         DIRECT,              // nearest: pb_hot_kernel + pb_fix_kernel
         FLOAT64,             // nearest: pb_remap_kernel
         BIL_DOUBLE,          // bilinear: pb_bilinear_double_hot_kernel (+ pb_bilinear_double_fix_kernel without coordinate tables)
-        BIL_DOUBLE_FLOAT64,  // bilinear: pb_bilinear_double_kernel
-        BIL_TILES,           // bilinear: pb_bilinear_hot_kernel (+ pb_bilinear_fix_kernel over the listed tiles without coordinate tables)
-        BIL_FLOAT64,         // bilinear: pb_bilinear_fix_kernel over every pixel
+        INTERP_TILES,           // bilinear / catmull-rom: pb_bilinear_hot_kernel / pb_catmull_rom_hot_kernel (+ pb_interp_fix_kernel<filter> over the
+                                // listed tiles and the fix pixels without coordinate tables)
+        INTERP_FLOAT64,         // bilinear / catmull-rom: pb_interp_fix_kernel<filter> over every pixel
+        INTERP_DOUBLE_FLOAT64,  // bilinear / catmull-rom: pb_interp_double_kernel<filter>
         SS_FUSED,            // supersampled: pb_ss_win_kernel
         SS_GENERIC,          // supersampled: frame by frame the route of n = 1 into a workspace, then pb_box_reduce_kernel
-        CR_TILES,            // catmull-rom: pb_catmull_rom_hot_kernel (+ pb_catmull_rom_fix_kernel over the listed tiles without coordinate tables)
-        CR_FLOAT64,          // catmull-rom: pb_catmull_rom_fix_kernel over every pixel
-        CR_DOUBLE_FLOAT64,   // catmull-rom: pb_catmull_rom_double_kernel
     } kind;
-    bool windows;  // BIL_DOUBLE / BIL_TILES: LEAN tiles gather from LDS windows
+    bool windows;                    // BIL_DOUBLE / bilinear INTERP_TILES: LEAN tiles gather from LDS windows
+    int filter = PB_INTERP_NEAREST;  // the INTERP_* routes: PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM
 };
 static bool pb_aligned16(const void* src, unsigned long long stride) { return ((((uintptr_t)src) | stride) & 15u) == 0; }
-#define PB_INTERP_CATMULL_ROM 2  // (a routing id of pb_remap_catmull_rom_u8 only: the supersampled entry points take 0 and 1)
 static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned flags, bool aligned) {
     const PbParams& P = pl->P;
     if (n > 1) {
@@ -703,15 +722,15 @@ static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned fl
     }
     const bool tiled = pl->mode != PB_MODE_FAITHFUL;
     const bool windows = pl->mode != PB_MODE_FAST_DIRECT && P.src.width < 32768 && P.src.height < 32768 && aligned;
-    if (interpolation == PB_INTERP_CATMULL_ROM) {  // (the bilinear mode's tables; no LDS windows)
-        if (P.src.kind == PB_KIND_DOUBLE) return {PbRoute::CR_DOUBLE_FLOAT64, false};
-        return (pb_use_fast(pl) && pl->ltable_bil && pl->bil_tiles) ? PbRoute{PbRoute::CR_TILES, false} : PbRoute{PbRoute::CR_FLOAT64, false};
-    }
-    if (interpolation == PB_INTERP_BILINEAR) {
+    if (interpolation == PB_INTERP_BILINEAR || interpolation == PB_INTERP_CATMULL_ROM) {
+        // (catmull-rom runs on the bilinear mode's tables: no LDS windows, no tile kernel for two eyes)
+        const bool bil = interpolation == PB_INTERP_BILINEAR;
         if (P.src.kind == PB_KIND_DOUBLE)
-            return (tiled && pl->dbl_ready && pl->ltable_bil && pl->bil_tiles && pl->bil_dbl_tables) ? PbRoute{PbRoute::BIL_DOUBLE, windows}
-                                                                                                     : PbRoute{PbRoute::BIL_DOUBLE_FLOAT64, false};
-        return (pb_use_fast(pl) && pl->ltable_bil && pl->bil_tiles) ? PbRoute{PbRoute::BIL_TILES, windows} : PbRoute{PbRoute::BIL_FLOAT64, false};
+            return (bil && tiled && pl->dbl_ready && pl->ltable_bil && pl->bil_tiles && pl->bil_dbl_tables)
+                       ? PbRoute{PbRoute::BIL_DOUBLE, windows, interpolation}
+                       : PbRoute{PbRoute::INTERP_DOUBLE_FLOAT64, false, interpolation};
+        return (pb_use_fast(pl) && pl->ltable_bil && pl->bil_tiles) ? PbRoute{PbRoute::INTERP_TILES, bil && windows, interpolation}
+                                                                    : PbRoute{PbRoute::INTERP_FLOAT64, false, interpolation};
     }
     if (tiled && pl->dbl_ready && pl->ltable && windows) return {PbRoute::DOUBLE, true};
     if (tiled && pl->sep_ready) return {PbRoute::SEP, false};
@@ -720,24 +739,6 @@ static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned fl
     return {PbRoute::FLOAT64, false};
 }
 
-// Template arguments from run-time values: f(PbInt<A>()) if `first`, else f(PbInt<B>()) - the kernel's KIND, its waves per workgroup,
-// the supersample factor.
-template <int V>
-using PbInt = std::integral_constant<int, V>;
-template <int A, int B, class F>
-static void pb_pick(bool first, F&& f) {
-    if (first) f(PbInt<A>());
-    else f(PbInt<B>());
-}
-template <class F>
-static void pb_pick_kind(const PbParams& P, F&& f) {  // (single sources)
-    pb_pick<PB_KIND_PANO, PB_KIND_CAMERA>(P.src.kind == PB_KIND_PANO, f);
-}
-template <class F>
-static void pb_pick_any_kind(const PbParams& P, F&& f) {
-    if (P.src.kind == PB_KIND_DOUBLE) f(PbInt<PB_KIND_DOUBLE>());
-    else pb_pick_kind(P, f);
-}
 // the double-fisheye kernels' WMODE: 1 the separable path's exact row weights, 2 stored merge-band latitudes, 0 neither
 static const PbSepRow* pb_sep_rows(const pb_plan* pl) { return pl->sep_ready ? pl->sep_rows : nullptr; }
 template <class F>
@@ -846,58 +847,48 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
             }
             break;
         }
-        case PbRoute::BIL_DOUBLE_FLOAT64:
-            hipLaunchKernelGGL(pb_bilinear_double_kernel, dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, src, dst, n_frames, ss, ds);
+        case PbRoute::INTERP_DOUBLE_FLOAT64:
+            pb_pick_filter(r.filter, [&](auto F) {
+                hipLaunchKernelGGL(pb_interp_double_kernel<decltype(F)>, dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, src, dst, n_frames, ss, ds);
+            });
             break;
-        case PbRoute::BIL_TILES: {
-            // launched like the nearest hot kernel: the mode's launch-order table, frames of a batch as a grid dimension
-            const unsigned gpf = pb_bil_groups(pl);
-            PbParams Pb = P;
-            Pb.win_budget = pl->bil_budget;
+        case PbRoute::INTERP_TILES:
+            // launched like the nearest hot kernel: the bilinear mode's launch-order table, frames of a batch as a grid dimension
             pb_pick_kind(P, [&](auto K) {
-                pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
-                    pb_pick<2, 4>(pl->bil_waves == 2, [&](auto WAVES) {
-                        hipLaunchKernelGGL((pb_bilinear_hot_kernel<K.value, WAVES.value>), dim3(gpf * (unsigned)nf), dim3(64 * pl->bil_waves),
-                                           (size_t)pl->bil_pool_bytes, st, pb_hot_of_host(Pb), pl->ltable_bil, sf, df, gpf, ss, ds, (int)r.windows, pl->bil_xy,
-                                           pl->fix_px, pl->bil_fix_xy);
+                if (r.filter == PB_INTERP_CATMULL_ROM) {  // the table read with four waves per workgroup: launch_groups_bil workgroups per frame
+                    const unsigned gpf = pl->launch_groups_bil;
+                    pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
+                        hipLaunchKernelGGL((pb_catmull_rom_hot_kernel<K.value>), dim3(gpf * (unsigned)nf), dim3(64 * PB_CR_WAVES), 0, st, pb_hot_of_host(P),
+                                           pl->ltable_bil, sf, df, gpf, ss, ds, pl->bil_xy, pl->fix_px, pl->bil_fix_xy);
                     });
-                });
+                } else {
+                    const unsigned gpf = pb_bil_groups(pl);
+                    PbParams Pb = P;
+                    Pb.win_budget = pl->bil_budget;
+                    pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
+                        pb_pick<2, 4>(pl->bil_waves == 2, [&](auto WAVES) {
+                            hipLaunchKernelGGL((pb_bilinear_hot_kernel<K.value, WAVES.value>), dim3(gpf * (unsigned)nf), dim3(64 * pl->bil_waves),
+                                               (size_t)pl->bil_pool_bytes, st, pb_hot_of_host(Pb), pl->ltable_bil, sf, df, gpf, ss, ds, (int)r.windows,
+                                               pl->bil_xy, pl->fix_px, pl->bil_fix_xy);
+                        });
+                    });
+                }
                 const unsigned n64 = pl->n_fail_tiles + pl->n_bil_tiles;  // failed + listed tiles
                 if (!pl->bil_xy && (n64 || pl->n_fix_px))  // no coordinate tables (they would not fit): the float64 chain
-                    hipLaunchKernelGGL(pb_bilinear_fix_kernel<K.value>, dim3(4u * n64 + (pl->n_fix_px + PB_BLOCK - 1) / PB_BLOCK), dim3(PB_BLOCK), 0, st, P,
-                                       pl->fail_tiles, 0, src, dst, n_frames, ss, ds, (int)n64, pl->fix_px, (int)pl->n_fix_px, pl->bil_tiles,
-                                       (int)pl->n_fail_tiles);
+                    pb_pick_filter(r.filter, [&](auto F) {
+                        hipLaunchKernelGGL((pb_interp_fix_kernel<decltype(F), K.value>), dim3(4u * n64 + (pl->n_fix_px + PB_BLOCK - 1) / PB_BLOCK),
+                                           dim3(PB_BLOCK), 0, st, P, pl->fail_tiles, 0, src, dst, n_frames, ss, ds, (int)n64, pl->fix_px, (int)pl->n_fix_px,
+                                           pl->bil_tiles, (int)pl->n_fail_tiles);
+                    });
             });
             break;
-        }
-        case PbRoute::BIL_FLOAT64:
+        case PbRoute::INTERP_FLOAT64:
             pb_pick_kind(P, [&](auto K) {
-                hipLaunchKernelGGL(pb_bilinear_fix_kernel<K.value>, dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, nullptr, 1, src, dst, n_frames, ss, ds);
-            });
-            break;
-        case PbRoute::CR_TILES: {
-            // the bilinear mode's launch-order table read with four waves per workgroup: launch_groups_bil workgroups per frame
-            const unsigned gpf = pl->launch_groups_bil;
-            pb_pick_kind(P, [&](auto K) {
-                pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
-                    hipLaunchKernelGGL((pb_catmull_rom_hot_kernel<K.value>), dim3(gpf * (unsigned)nf), dim3(64 * PB_CR_WAVES), 0, st, pb_hot_of_host(P),
-                                       pl->ltable_bil, sf, df, gpf, ss, ds, pl->bil_xy, pl->fix_px, pl->bil_fix_xy);
+                pb_pick_filter(r.filter, [&](auto F) {
+                    hipLaunchKernelGGL((pb_interp_fix_kernel<decltype(F), K.value>), dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, nullptr, 1, src, dst,
+                                       n_frames, ss, ds);
                 });
-                const unsigned n64 = pl->n_fail_tiles + pl->n_bil_tiles;  // failed + listed tiles
-                if (!pl->bil_xy && (n64 || pl->n_fix_px))  // no coordinate tables (they would not fit): the float64 chain
-                    hipLaunchKernelGGL(pb_catmull_rom_fix_kernel<K.value>, dim3(4u * n64 + (pl->n_fix_px + PB_BLOCK - 1) / PB_BLOCK), dim3(PB_BLOCK), 0, st,
-                                       P, pl->fail_tiles, 0, src, dst, n_frames, ss, ds, (int)n64, pl->fix_px, (int)pl->n_fix_px, pl->bil_tiles,
-                                       (int)pl->n_fail_tiles);
             });
-            break;
-        }
-        case PbRoute::CR_FLOAT64:
-            pb_pick_kind(P, [&](auto K) {
-                hipLaunchKernelGGL(pb_catmull_rom_fix_kernel<K.value>, dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, nullptr, 1, src, dst, n_frames, ss, ds);
-            });
-            break;
-        case PbRoute::CR_DOUBLE_FLOAT64:
-            hipLaunchKernelGGL(pb_catmull_rom_double_kernel, dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, src, dst, n_frames, ss, ds);
             break;
         default:
             return pb_fail(PB_ERR_INVALID, "not a route of one frame");  // (the supersampled routes: pb_remap_ss_u8)
@@ -1895,111 +1886,48 @@ int pb_rotate_f64(const double* rot3x3, double* map_in_dev, double* map_out_dev,
     return PB_OK;
 }
 
-int pb_sample_map_u8(const pb_proj* src, double* map_dev, int height, int width, const uint8_t* src_dev,
-                     uint8_t* dst_dev, void* stream) {
-    std::string why;
-    if (!map_dev || !src_dev || !dst_dev) return pb_fail(PB_ERR_INVALID, "null argument");
-    if (!pb_end_ok(src, why, PB_ROLE_SRC)) return pb_fail(PB_ERR_INVALID, why);
-    if (height < 1 || width < 1 || (long long)height * width > 0x7FFFFFFFll / 4)
-        return pb_fail(PB_ERR_INVALID, "map size out of range");
-    PbParams P;
-    memset(&P, 0, sizeof(P));
-    P.src = pb_to_end(src);
-    P.dst = P.src;
-    P.dst.height = height;
-    P.dst.width = width;
-    pb_derive(P);
-    const unsigned total = (unsigned)height * (unsigned)width;
-    hipStream_t st = (hipStream_t)stream;
-    switch (P.src.kind) {
-        case PB_KIND_PANO:
-            hipLaunchKernelGGL(pb_sample_map_kernel<PB_KIND_PANO>, dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, st, P,
-                               map_dev, total, src_dev, dst_dev);
-            break;
-        case PB_KIND_CAMERA:
-            hipLaunchKernelGGL(pb_sample_map_kernel<PB_KIND_CAMERA>, dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, st, P,
-                               map_dev, total, src_dev, dst_dev);
-            break;
-        default:
-            hipLaunchKernelGGL(pb_sample_map_kernel<PB_KIND_DOUBLE>, dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, st, P,
-                               map_dev, total, src_dev, dst_dev);
-    }
-    PB_HIP(hipGetLastError());
-    return PB_OK;
-}
-
-int pb_index_from_map_i32(const pb_proj* src, double* map_dev, int height, int width, const double* dist_l_dev, const double* dist_r_dev,
-                          int32_t* idx_dev, double* weights_dev, void* stream) {
-    std::string why;
-    if (!map_dev || !idx_dev) return pb_fail(PB_ERR_INVALID, "null argument");
-    if (!pb_end_ok(src, why, PB_ROLE_SRC | PB_ROLE_CUSTOM_OK)) return pb_fail(PB_ERR_INVALID, why);
-    if (height < 1 || width < 1 || (long long)height * width > 0x7FFFFFFFll / 4) return pb_fail(PB_ERR_INVALID, "map size out of range");
-    if (src->kind != PB_KIND_PANO && src->lens == PB_LENS_CUSTOM && !dist_l_dev)
-        return pb_fail(PB_ERR_INVALID, "a PB_LENS_CUSTOM source needs the host-evaluated distance plane(s)");
-    if (src->kind == PB_KIND_DOUBLE && dist_l_dev && !dist_r_dev) return pb_fail(PB_ERR_INVALID, "a double source needs both distance planes");
-    if (src->kind == PB_KIND_PANO && (dist_l_dev || dist_r_dev)) return pb_fail(PB_ERR_INVALID, "a panorama source has no lens");
-    PbParams P;
-    memset(&P, 0, sizeof(P));
-    P.src = pb_to_end(src);
-    P.dst = P.src;
-    P.dst.kind = PB_KIND_PANO;  // only the source half of the parameters is used
-    P.dst.height = height;
-    P.dst.width = width;
-    pb_derive(P);
-    const unsigned total = (unsigned)height * (unsigned)width;
-    hipStream_t st = (hipStream_t)stream;
-    switch (P.src.kind) {
-        case PB_KIND_PANO:
-            hipLaunchKernelGGL(pb_index_from_map_kernel<PB_KIND_PANO>, dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, st, P, map_dev, total, dist_l_dev,
-                               dist_r_dev, idx_dev, weights_dev);
-            break;
-        case PB_KIND_CAMERA:
-            hipLaunchKernelGGL(pb_index_from_map_kernel<PB_KIND_CAMERA>, dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, st, P, map_dev, total, dist_l_dev,
-                               dist_r_dev, idx_dev, weights_dev);
-            break;
-        default:
-            hipLaunchKernelGGL(pb_index_from_map_kernel<PB_KIND_DOUBLE>, dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, st, P, map_dev, total, dist_l_dev,
-                               dist_r_dev, idx_dev, weights_dev);
-    }
-    PB_HIP(hipGetLastError());
-    return PB_OK;
-}
-
 }  // extern "C"
 
-// pb_sample_map_bilinear_px (CR false) and pb_sample_map_catmull_rom_px (CR true): the same arguments, checks and launch
-template <bool CR>
-static int pb_sample_map_px(const pb_proj* src, double* map_dev, int height, int width, const double* dist_l_dev, const double* dist_r_dev,
-                            const void* img_dev, void* out_dev, int channels, int sample_bytes, void* stream) {
+// The map-stage calls (a materialised (height, width, 3) map sampled from `src`): their shared argument checks, in the order every one of
+// them makes them, and their parameters - only the source half is used.  pb_map_planes_ok: the host-evaluated distance planes.
+static int pb_map_stage(bool null_argument, const pb_proj* src, unsigned roles, int height, int width, PbParams& P) {
     std::string why;
-    if (!map_dev || !img_dev || !out_dev) return pb_fail(PB_ERR_INVALID, "null argument");
-    if (!pb_end_ok(src, why, PB_ROLE_SRC | PB_ROLE_CUSTOM_OK)) return pb_fail(PB_ERR_INVALID, why);
+    if (null_argument) return pb_fail(PB_ERR_INVALID, "null argument");
+    if (!pb_end_ok(src, why, roles)) return pb_fail(PB_ERR_INVALID, why);
     if (height < 1 || width < 1 || (long long)height * width > 0x7FFFFFFFll / 4) return pb_fail(PB_ERR_INVALID, "map size out of range");
-    if (channels < 1 || channels > 16) return pb_fail(PB_ERR_INVALID, "channels outside [1, 16]");
-    if (sample_bytes != 1 && sample_bytes != 2) return pb_fail(PB_ERR_INVALID, "sample_bytes must be 1 or 2");
+    memset(&P, 0, sizeof(P));
+    P.src = pb_to_end(src);
+    P.dst = P.src;
+    P.dst.kind = PB_KIND_PANO;
+    P.dst.height = height;
+    P.dst.width = width;
+    pb_derive(P);
+    return PB_OK;
+}
+static int pb_map_planes_ok(const pb_proj* src, const double* dist_l_dev, const double* dist_r_dev) {
     if (src->kind != PB_KIND_PANO && src->lens == PB_LENS_CUSTOM && !dist_l_dev)
         return pb_fail(PB_ERR_INVALID, "a PB_LENS_CUSTOM source needs the host-evaluated distance plane(s)");
     if (src->kind == PB_KIND_DOUBLE && dist_l_dev && !dist_r_dev) return pb_fail(PB_ERR_INVALID, "a double source needs both distance planes");
     if (src->kind == PB_KIND_PANO && (dist_l_dev || dist_r_dev)) return pb_fail(PB_ERR_INVALID, "a panorama source has no lens");
+    return PB_OK;
+}
+
+// pb_sample_map_bilinear_px and pb_sample_map_catmull_rom_px: the same arguments, checks and launch
+static int pb_sample_map_px(int filter, const pb_proj* src, double* map_dev, int height, int width, const double* dist_l_dev, const double* dist_r_dev,
+                            const void* img_dev, void* out_dev, int channels, int sample_bytes, void* stream) {
     PbParams P;
-    memset(&P, 0, sizeof(P));
-    P.src = pb_to_end(src);
-    P.dst = P.src;
-    P.dst.kind = PB_KIND_PANO;  // only the source half of the parameters is used
-    P.dst.height = height;
-    P.dst.width = width;
-    pb_derive(P);
+    if (int rc = pb_map_stage(!map_dev || !img_dev || !out_dev, src, PB_ROLE_SRC | PB_ROLE_CUSTOM_OK, height, width, P)) return rc;
+    if (channels < 1 || channels > 16) return pb_fail(PB_ERR_INVALID, "channels outside [1, 16]");
+    if (sample_bytes != 1 && sample_bytes != 2) return pb_fail(PB_ERR_INVALID, "sample_bytes must be 1 or 2");
+    if (int rc = pb_map_planes_ok(src, dist_l_dev, dist_r_dev)) return rc;
     const unsigned total = (unsigned)height * (unsigned)width;
-    hipStream_t st = (hipStream_t)stream;
     const auto launch = [&](auto* sample) {  // (the sample type: uint8_t or uint16_t)
         using SAMPLE = std::remove_pointer_t<decltype(sample)>;
         pb_pick_any_kind(P, [&](auto K) {
-            if (CR)
-                hipLaunchKernelGGL((pb_sample_map_catmull_rom_kernel<K.value, SAMPLE>), dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, st, P, map_dev, total,
-                                   dist_l_dev, dist_r_dev, static_cast<const SAMPLE*>(img_dev), out_dev, channels);
-            else
-                hipLaunchKernelGGL((pb_sample_map_bilinear_kernel<K.value, SAMPLE>), dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, st, P, map_dev, total, dist_l_dev,
-                                   dist_r_dev, static_cast<const SAMPLE*>(img_dev), out_dev, channels);
+            pb_pick_filter(filter, [&](auto F) {
+                hipLaunchKernelGGL((pb_sample_map_interp_kernel<decltype(F), K.value, SAMPLE>), dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, (hipStream_t)stream,
+                                   P, map_dev, total, dist_l_dev, dist_r_dev, static_cast<const SAMPLE*>(img_dev), out_dev, channels);
+            });
         });
     };
     if (sample_bytes == 1) launch((uint8_t*)nullptr);
@@ -2010,14 +1938,40 @@ static int pb_sample_map_px(const pb_proj* src, double* map_dev, int height, int
 
 extern "C" {
 
+int pb_sample_map_u8(const pb_proj* src, double* map_dev, int height, int width, const uint8_t* src_dev,
+                     uint8_t* dst_dev, void* stream) {
+    PbParams P;
+    if (int rc = pb_map_stage(!map_dev || !src_dev || !dst_dev, src, PB_ROLE_SRC, height, width, P)) return rc;
+    const unsigned total = (unsigned)height * (unsigned)width;
+    pb_pick_any_kind(P, [&](auto K) {
+        hipLaunchKernelGGL(pb_sample_map_kernel<K.value>, dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, (hipStream_t)stream, P, map_dev, total, src_dev, dst_dev);
+    });
+    PB_HIP(hipGetLastError());
+    return PB_OK;
+}
+
+int pb_index_from_map_i32(const pb_proj* src, double* map_dev, int height, int width, const double* dist_l_dev, const double* dist_r_dev,
+                          int32_t* idx_dev, double* weights_dev, void* stream) {
+    PbParams P;
+    if (int rc = pb_map_stage(!map_dev || !idx_dev, src, PB_ROLE_SRC | PB_ROLE_CUSTOM_OK, height, width, P)) return rc;
+    if (int rc = pb_map_planes_ok(src, dist_l_dev, dist_r_dev)) return rc;
+    const unsigned total = (unsigned)height * (unsigned)width;
+    pb_pick_any_kind(P, [&](auto K) {
+        hipLaunchKernelGGL(pb_index_from_map_kernel<K.value>, dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, (hipStream_t)stream, P, map_dev, total, dist_l_dev,
+                           dist_r_dev, idx_dev, weights_dev);
+    });
+    PB_HIP(hipGetLastError());
+    return PB_OK;
+}
+
 int pb_sample_map_bilinear_px(const pb_proj* src, double* map_dev, int height, int width, const double* dist_l_dev, const double* dist_r_dev,
                               const void* img_dev, void* out_dev, int channels, int sample_bytes, void* stream) {
-    return pb_sample_map_px<false>(src, map_dev, height, width, dist_l_dev, dist_r_dev, img_dev, out_dev, channels, sample_bytes, stream);
+    return pb_sample_map_px(PB_INTERP_BILINEAR, src, map_dev, height, width, dist_l_dev, dist_r_dev, img_dev, out_dev, channels, sample_bytes, stream);
 }
 
 int pb_sample_map_catmull_rom_px(const pb_proj* src, double* map_dev, int height, int width, const double* dist_l_dev, const double* dist_r_dev,
                                  const void* img_dev, void* out_dev, int channels, int sample_bytes, void* stream) {
-    return pb_sample_map_px<true>(src, map_dev, height, width, dist_l_dev, dist_r_dev, img_dev, out_dev, channels, sample_bytes, stream);
+    return pb_sample_map_px(PB_INTERP_CATMULL_ROM, src, map_dev, height, width, dist_l_dev, dist_r_dev, img_dev, out_dev, channels, sample_bytes, stream);
 }
 
 int pb_sample_map_bilinear_u8(const pb_proj* src, double* map_dev, int height, int width, const uint8_t* src_dev, uint8_t* dst_dev, void* stream) {

@@ -19,6 +19,7 @@ import numpy as np
 from PIL import Image
 
 from .. import core
+from .. import _native as nat
 from ..core.lens import equidistant, equisolid, orthographic, rectilinear, stereographic
 from ..core.projection import CameraImage, DoubleCameraImage, PanoramaImage
 from ..core.rotation import Rotation
@@ -32,7 +33,7 @@ LENSES = {
     "stereographic": stereographic,
 }
 TYPES = ("inscribed", "double", "cropped", "full")
-INTERPOLATIONS = ("nearest", "bilinear", "catmull-rom")
+INTERPOLATIONS = nat.INTERPOLATIONS
 
 TYPE_HELP = """
 
@@ -115,8 +116,10 @@ def run_chain(source, destiny, rotations, out: Path, supersample: int = 1, inter
     """dst.get_coordinate_map() -> rotations in order -> src.process_coordinate_map() -> save.  ``supersample`` n > 1: the map of the n x
     destination, each output pixel the mean of its n x n samples (the output size stays what the size rules gave).  ``interpolation``:
     the sampler - "nearest" (the reference's), or the opt-in "bilinear" / "catmull-rom" (the latter not supersampled)."""
-    if interpolation == "catmull-rom" and supersample > 1:
-        raise click.BadParameter("catmull-rom sampling is not supersampled: use --supersample 1", param_hint="--interpolation")
+    try:
+        nat.check_interpolation(interpolation, supersample)
+    except ValueError as exc:
+        raise click.BadParameter(str(exc), param_hint="--interpolation")
     if supersample == 1:
         cmap = destiny.get_coordinate_map()
     else:

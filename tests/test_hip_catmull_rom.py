@@ -96,7 +96,7 @@ def test_map_kernel_small_cases(case):
 
 @pytest.mark.parametrize("case", SMALL, ids=lambda c: c.name)
 def test_float64_route_small_cases(case):
-    """PB_MODE_FAITHFUL: the plan's float64 route (pb_catmull_rom_fix_kernel / pb_catmull_rom_double_kernel) from the device chain."""
+    """PB_MODE_FAITHFUL: the plan's float64 route (pb_interp_fix_kernel / pb_interp_double_kernel with the PbCatmullRom filter) from the device chain."""
     frame = synth_frame(case.src[1], case.src[2], frame=0, seed=0, circle_mask=case.mask)
     plan = H.pb_plan_private(case)
     plan.set_mode(nat.MODE_FAITHFUL)

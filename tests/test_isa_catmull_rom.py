@@ -31,6 +31,8 @@ def test_tile_kernel_budget(stats):
 
 
 def test_float64_kernels_are_there(stats):
-    for prefix, n in (("pb_catmull_rom_fix_kernel", 2), ("pb_catmull_rom_double_kernel", 1), ("pb_sample_map_catmull_rom_kernel", 6)):
-        got = [k for k in stats if k.startswith(prefix)]
-        assert len(got) == n, (prefix, sorted(got))
+    # the shared sampler templates (pb_kernels_bilinear.hpp), pinned from both filters' side
+    for flt in ("PbCatmullRom", "PbBilinear"):
+        for prefix, n in ((f"pb_interp_fix_kernel<{flt},", 2), (f"pb_interp_double_kernel<{flt}>", 1), (f"pb_sample_map_interp_kernel<{flt},", 6)):
+            got = [k for k in stats if k.startswith(prefix)]
+            assert len(got) == n, (prefix, sorted(got))
