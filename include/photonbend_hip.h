@@ -79,6 +79,25 @@ typedef struct pb_proj {
     double f_distance; /* focal distance in pixels */
 } pb_proj;
 
+/* POLYNOMIAL (KANNALA-BRANDT) LENSES (ABI 5, additive): the odd polynomial a fisheye calibration yields, the k1..k4 of
+ * OpenCV's fisheye module,
+ *     r(theta) = theta + k1 theta^3 + k2 theta^5 + k3 theta^7 + k4 theta^9        (r in focal-length units)
+ * on [0, max_theta] (radians, 0 < max_theta <= pi), +inf beyond; its inverse is ten Newton steps from t = r, +inf beyond r(max_theta).
+ * Evaluated by the float64 chain with + - * / only, each rounded on its own: bit-reproducible by any IEEE host, the same in both math
+ * flavours.  pb_proj does not grow: a lens is REGISTERED once and the id it gets (PB_LENS_POLYNOMIAL_BASE upwards) is a pb_proj.lens every
+ * entry point accepts, in either role, wherever it accepts a built-in lens.
+ *   pb_lens_polynomial       validates (finite coefficients; max_theta in range; r increasing on [0, max_theta]; the Newton steps invert it
+ *                            there - PB_ERR_INVALID otherwise) and registers.  Entries are immutable; the same coefficients and max_theta
+ *                            give the same id; thread-safe; at most 4096 distinct lenses per process, then PB_ERR_UNSUPPORTED.
+ *   pb_lens_polynomial_info  the coefficients and max_theta of a registered id (either pointer may be NULL).
+ * An id means something in THIS process only.  Nothing that outlives the process holds one: plans, their blobs (pb_plan_serialize),
+ * pb_plan_matches and pb_bcast_params carry and compare the coefficients.  The caller computes pb_proj.f_distance as for every lens:
+ * magnitude / r(fov / 2), with fov / 2 <= max_theta.  (The parameter block inside a plan blob grew with this addition: blobs written by
+ * earlier builds are refused by the size check, like blobs of any other build.) */
+#define PB_LENS_POLYNOMIAL_BASE 16
+int pb_lens_polynomial(const double k[4], double max_theta, int* lens_out);
+int pb_lens_polynomial_info(int lens, double k[4], double* max_theta);
+
 typedef struct pb_plan pb_plan; /* opaque, immutable after creation */
 
 /* ---- library / device ------------------------------------------------- */
@@ -286,7 +305,8 @@ int pb_index_map_i32(const pb_plan* plan, int32_t* idx_dev, double* weights_dev,
  *   pb_comm_unique_id   rank 0 makes the 128-byte rendezvous id (ncclGetUniqueId); the launcher hands it to the other ranks
  *   pb_comm_init        collective: every rank, on ITS current device (ncclCommInitRank)
  *   pb_bcast_params     collective: root's dst / rot3x3[9 * n_rot] / n_rot / src overwrite everyone else's (rot3x3 must hold
- *                       9 * PB_MAX_ROTATIONS doubles); synchronises `stream`.  PRECONDITION: non-null pointers and a root inside
+ *                       9 * PB_MAX_ROTATIONS doubles); synchronises `stream`.  A polynomial lens travels as its coefficients: every rank
+ *                       registers them and finds its OWN id in the pb_proj it gets back.  PRECONDITION: non-null pointers and a root inside
  *                       [0, n_ranks) on EVERY rank - those are checked before anyone enters the collective and must not differ
  *                       between ranks; everything only the root can know (its n_rot, its upload) travels WITH the broadcast: an
  *                       invalid root request makes every rank return PB_ERR_INVALID together, none is left waiting

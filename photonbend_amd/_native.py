@@ -69,6 +69,7 @@ LENS_IDS = {
     "thoby": 5,
 }
 LENS_CUSTOM = 6  # a Lens of user callables: the host evaluates it (pb_index_from_map_i32's distance planes)
+LENS_POLYNOMIAL_BASE = 16  # ids of registered polynomial lenses (pb_lens_polynomial) start here; they are process-local
 
 
 class PbError(RuntimeError):
@@ -87,7 +88,12 @@ class pb_proj(C.Structure):
     ]
 
     def key(self):
-        return (self.kind, self.lens, self.height, self.width, self.fov, self.magnitude, self.f_distance)
+        """What identifies this projection in a cache - also one that outlives the process: a registered polynomial lens is named
+        by its coefficients, never by its process-local id."""
+        lens = self.lens
+        if self.kind != KIND_PANO and lens >= LENS_POLYNOMIAL_BASE:
+            lens = ("polynomial",) + lens_polynomial_info(lens)
+        return (self.kind, lens, self.height, self.width, self.fov, self.magnitude, self.f_distance)
 
 
 # name -> (restype, argtypes); every symbol of include/photonbend_hip.h
@@ -99,6 +105,8 @@ SIGNATURES = {
     "pb_init": (C.c_int, [C.c_int]),
     "pb_shutdown": (C.c_int, []),
     "pb_device_name": (C.c_int, [C.c_char_p, C.c_size_t]),
+    "pb_lens_polynomial": (C.c_int, [C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int)]),
+    "pb_lens_polynomial_info": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "pb_plan_create": (C.c_int, [C.POINTER(pb_proj), C.POINTER(C.c_double), C.c_int, C.POINTER(pb_proj), C.POINTER(_VP)]),
     "pb_plan_create_ex": (C.c_int, [C.POINTER(pb_proj), C.POINTER(C.c_double), C.c_int, C.POINTER(pb_proj), C.c_uint, C.c_int, C.POINTER(_VP)]),
     "pb_plan_prepare": (C.c_int, [_VP, C.c_uint, C.c_int]),
@@ -710,6 +718,23 @@ def torch_dtype_np(tdt) -> np.dtype:
 
 def make_proj(kind: int, height: int, width: int, lens: int = 0, fov: float = 0.0, magnitude: float = 0.0, f_distance: float = 0.0) -> pb_proj:
     return pb_proj(int(kind), int(lens), int(height), int(width), float(fov), float(magnitude), float(f_distance))
+
+
+def lens_polynomial(k, max_theta: float) -> int:
+    """Registers a polynomial (Kannala-Brandt) lens with the library and returns its pb_lens id (the same coefficients and max_theta give
+    the same id; process-local).  The library validates like core.lens.polynomial: PbError on a set it refuses.  Needs no GPU."""
+    kk = (C.c_double * 4)(*[float(v) for v in k])
+    out = C.c_int()
+    check(load().pb_lens_polynomial(kk, float(max_theta), C.byref(out)))
+    return out.value
+
+
+def lens_polynomial_info(lens: int) -> tuple:
+    """(k1, k2, k3, k4, max_theta) of a registered polynomial lens id."""
+    kk = (C.c_double * 4)()
+    mt = C.c_double()
+    check(load().pb_lens_polynomial_info(int(lens), kk, C.byref(mt)))
+    return (kk[0], kk[1], kk[2], kk[3], mt.value)
 
 
 def coordmap(dst: pb_proj, device=None):

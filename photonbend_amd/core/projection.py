@@ -524,9 +524,19 @@ def _map_supersample(coordinate_map, supersample) -> int:
 
 def _role_lens_id(lens: Lens, role: str) -> int:
     """pb_lens id of the function the role uses: a destination inverts (reverse_function), a source projects
-    (forward_function).  A user callable gets PB_LENS_CUSTOM: the host evaluates it (lens.py:48-64)."""
-    lid = lens_id(lens.reverse_function if role == "dst" else lens.forward_function)
+    (forward_function).  A user callable gets PB_LENS_CUSTOM: the host evaluates it (lens.py:48-64).  A callable of core.lens.polynomial
+    gets the id the library's registry gives its coefficients (process-local; the same coefficients give the same id)."""
+    lid = lens_id(lens.reverse_function if role == "dst" else lens.forward_function)  # (a polynomial lens: registered here, lens.py)
     return nat.LENS_CUSTOM if lid is None else lid
+
+
+def _check_half_fov(lens: Lens, fov: float, what: str) -> None:
+    """A lens whose domain ends at max_theta (core.lens.polynomial) cannot image a half field of view beyond it: forward(fov / 2) would be
+    inf and f_distance = magnitude / inf = 0."""
+    for fn in (lens.forward_function, lens.reverse_function):
+        poly = getattr(fn, "pb_lens_polynomial", None)
+        if poly is not None and fov / 2 > poly[4]:
+            raise ValueError(f"{what}: half the field of view ({fov / 2!r} rad) exceeds the polynomial lens's max_theta ({poly[4]!r} rad)")
 
 
 class CameraImage(_GpuProjection):
@@ -554,6 +564,7 @@ class CameraImage(_GpuProjection):
 
     def _proj(self, role: str = "src") -> nat.pb_proj:
         h, w = _shape_hw(self.image)
+        _check_half_fov(self._lens, self.fov, "CameraImage")
         return nat.make_proj(nat.KIND_CAMERA, h, w, _role_lens_id(self._lens, role), self.fov, self.magnitude, self.f_distance)
 
     def _custom_coordinate_map(self, proj: nat.pb_proj) -> np.ndarray:
@@ -600,6 +611,7 @@ class DoubleCameraImage(_GpuProjection):
         h, w = _shape_hw(self.image)
         if role == "dst":
             w = 2 * (w // 2)  # the reference's map of an odd-width double frame has 2 * (W // 2) columns (projection.py:389-397)
+        _check_half_fov(self.lens, self.sensor_fov, "DoubleCameraImage")
         return nat.make_proj(nat.KIND_DOUBLE, h, w, _role_lens_id(self.lens, role), self.sensor_fov, self.magnitude, self.f_distance)
 
     def _custom_coordinate_map(self, proj: nat.pb_proj) -> np.ndarray:

@@ -168,7 +168,7 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_interp_kernel(const Pb
     double sl, cl;
     pb_expi_np(lon, &sl, &cl);  // np.exp(lon * 1j), projection.py:252
     if (SRC_KIND == PB_KIND_CAMERA) {
-        const double dist = dist_l ? dist_l[p] : pb_lens_forward(P.src.lens, lat, P.rect_max) * P.src.f_distance;
+        const double dist = dist_l ? dist_l[p] : pb_lens_forward(P, lat) * P.src.f_distance;
         const double fy = ((sl * dist) * -1.0) + P.src_cy, fx = (cl * dist) + P.src_cx;
         const bool live = !inv && pb_live_in(fy, fx, 1.0e300, h, w);
         SAMPLE* o = static_cast<SAMPLE*>(out) + (unsigned long long)p * (unsigned)channels;
@@ -178,8 +178,8 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_interp_kernel(const Pb
     }
     // two eyes (projection.py:408-462): each sampled like a camera source on its half (the right one mirrored), then the reference's blend
     const double lat_r = (lat * -1.0) + PB_PI;
-    const double dl = dist_l ? dist_l[p] : pb_lens_forward(P.src.lens, lat, P.rect_max) * P.src.f_distance;
-    const double dr = dist_r ? dist_r[p] : pb_lens_forward(P.src.lens, lat_r, P.rect_max) * P.src.f_distance;
+    const double dl = dist_l ? dist_l[p] : pb_lens_forward(P, lat) * P.src.f_distance;
+    const double dr = dist_r ? dist_r[p] : pb_lens_forward(P, lat_r) * P.src.f_distance;
     const int wl = P.src_eye_w, wr = P.src_eye_w_right;
     const double fyl = ((sl * dl) * -1.0) + P.src_cy, fxl = (cl * dl) + P.src_cx;
     const double fyr = ((sl * dr) * -1.0) + P.src_cy, fxr = (cl * dr) + P.src_cx_r;
@@ -227,7 +227,7 @@ __device__ __forceinline__ PbBilCoord pb_bil_coord_of(const PbParams& P, const P
         const double lat = (SRC_KIND == PB_KIND_EYE_R) ? (c.lat * -1.0) + PB_PI : c.lat;  // projection.py:426-427
         const int we = (SRC_KIND == PB_KIND_EYE_L) ? P.src_eye_w : (SRC_KIND == PB_KIND_EYE_R) ? P.src_eye_w_right : P.src.width;
         const double cx = (SRC_KIND == PB_KIND_EYE_R) ? P.src_cx_r : P.src_cx;
-        const double dist = pb_lens_forward(P.src.lens, lat, P.rect_max) * P.src.f_distance;
+        const double dist = pb_lens_forward(P, lat) * P.src.f_distance;
         double sl, cl;
         pb_expi_np(c.lon, &sl, &cl);  // np.exp(lon * 1j)
         f0 = ((sl * dist) * -1.0) + P.src_cy;
@@ -880,7 +880,7 @@ __device__ __forceinline__ unsigned PbBilinear::sample(const PbParams& P, const 
 __device__ __forceinline__ unsigned PbBilinear::eye(const PbParams& P, const uint8_t* __restrict__ s, double lat, double sl, double cl, int we, double cx,
                                                     int cmin, bool mirror) {
     const int h = P.src.height, w = P.src.width;
-    const double dist = pb_lens_forward(P.src.lens, lat, P.rect_max) * P.src.f_distance;
+    const double dist = pb_lens_forward(P, lat) * P.src.f_distance;
     const double f0 = ((sl * dist) * -1.0) + P.src_cy, f1 = (cl * dist) + cx;
     if (!pb_live_in(f0, f1, 1.0e9, h, we)) return 0u;
     const double sy = f0 - 0.5, sx = f1 - 0.5;

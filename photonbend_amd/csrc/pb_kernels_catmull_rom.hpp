@@ -76,7 +76,7 @@ struct PbCatmullRom {
         } else {
             double sl, cl;
             pb_expi_np(c.lon, &sl, &cl);
-            const double dist = pb_lens_forward(P.src.lens, c.lat, P.rect_max) * P.src.f_distance;
+            const double dist = pb_lens_forward(P, c.lat) * P.src.f_distance;
             q.fy = ((sl * dist) * -1.0) + P.src_cy;
             q.fx = (cl * dist) + P.src_cx;
             q.live = !c.inv && pb_live_in(q.fy, q.fx, 1.0e300, P.src.height, P.src.width);
@@ -89,7 +89,7 @@ struct PbCatmullRom {
     }
     static __device__ __forceinline__ unsigned eye(const PbParams& P, const uint8_t* __restrict__ s, double lat, double sl, double cl, int we, double cx,
                                                    int cmin, bool mirror) {
-        const double dist = pb_lens_forward(P.src.lens, lat, P.rect_max) * P.src.f_distance;
+        const double dist = pb_lens_forward(P, lat) * P.src.f_distance;
         const double fy = ((sl * dist) * -1.0) + P.src_cy, fx = (cl * dist) + cx;
         return pb_live_in(fy, fx, 1.0e300, P.src.height, we) ? rgb<false>(s, fy, fx, P.src.height, P.src.width, cmin, cmin + we, mirror) : 0u;
     }

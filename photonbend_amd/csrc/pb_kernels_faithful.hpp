@@ -63,8 +63,13 @@ __device__ __forceinline__ void pb_store_px4(uint8_t* __restrict__ out, unsigned
 // waves per SIMD the float64 remap kernel is compiled for (its register budget).  Measured on MI355X (experiments/r4/build_f64.sh):
 // four waves (128 VGPRs, a few spilled) against the compiler's own choice of three - c2 187 -> 163 us, c3 530 -> 499; the two-eye chain
 // is better left alone (434 against 454)
+// The three single-source instantiations that fit eight waves (at most 64 VGPRs and 96 scalar registers: a panorama source without and
+// with a run-time rotation count, an unrotated camera source) are held to eight: the polynomial lens's case in the lens switch (a rolled
+// loop: more live exec masks and kernel arguments) took them to 104 scalar registers and seven waves; under the bound the compiler moves
+// a few scalars through vector lanes instead.  Measured against the parent with a built-in lens (experiments/float64_kernel_ab.py): with the
+// bound the run-time-rotation instantiation is 5 % faster and the unrotated camera one level; without it they are level and 3 % slower.
 #ifndef PB_FAITHFUL_WPE
-#define PB_FAITHFUL_WPE(kind) ((kind) == PB_KIND_DOUBLE ? 1 : 4)
+#define PB_FAITHFUL_WPE(kind, rot) ((kind) == PB_KIND_DOUBLE ? 1 : (((kind) == PB_KIND_PANO && (rot) != 1) || ((kind) == PB_KIND_CAMERA && (rot) == 0)) ? 8 : 4)
 #endif
 #ifndef PB_FAITHFUL_UNROLL  // pixels of a work-item whose float64 chains the compiler may interleave
 #define PB_FAITHFUL_UNROLL 4
@@ -72,7 +77,7 @@ __device__ __forceinline__ void pb_store_px4(uint8_t* __restrict__ out, unsigned
 #define PB_PRAGMA(x) _Pragma(#x)
 #define PB_UNROLL(n) PB_PRAGMA(unroll n)
 template <int SRC_KIND, int ROT>
-__global__ __launch_bounds__(PB_BLOCK, PB_FAITHFUL_WPE(SRC_KIND)) void pb_remap_kernel(const PbParams P, const uint8_t* __restrict__ src,
+__global__ __launch_bounds__(PB_BLOCK, PB_FAITHFUL_WPE(SRC_KIND, ROT)) void pb_remap_kernel(const PbParams P, const uint8_t* __restrict__ src,
                                                             uint8_t* __restrict__ dst, int n_frames,
                                                             unsigned long long src_stride,
                                                             unsigned long long dst_stride, int aligned) {

@@ -26,8 +26,8 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_sep_tables_kernel(const PbParams 
         const PbCoord c = pb_dst_coord(P, t, 0);
         const double lat_r = (c.lat * -1.0) + PB_PI;  // projection.py:426-427
         PbSepRow r;
-        r.dist_l = pb_lens_forward(P.src.lens, c.lat, P.rect_max) * P.src.f_distance;  // projection.py:251
-        r.dist_r = pb_lens_forward(P.src.lens, lat_r, P.rect_max) * P.src.f_distance;
+        r.dist_l = pb_lens_forward(P, c.lat) * P.src.f_distance;  // projection.py:251
+        r.dist_r = pb_lens_forward(P, lat_r) * P.src.f_distance;
         r.f_l = pb_merge_factor(P, c.lat);
         r.f_r = pb_merge_factor(P, lat_r);
         rows[t] = r;

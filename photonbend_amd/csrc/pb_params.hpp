@@ -19,6 +19,32 @@ struct PbEnd {
     double fov, f_distance;
 };
 
+// A polynomial (Kannala-Brandt) lens, PB_LENS_POLYNOMIAL in PbEnd::lens:
+//   p(t) = t * (1 + t2*(k[0] + t2*(k[1] + t2*(k[2] + t2*k[3])))),  dp(t) = 1 + t2*(d[0] + ...),  t2 = t*t,  d = (3 k0, 5 k1, 7 k2, 9 k3)
+// max_theta ends the lens's domain, r_max = p(max_theta).  All zero for every other lens (pb_same_request compares the bytes).
+struct PbPoly {
+    double k[4], d[4];
+    double max_theta, r_max;
+};
+// PbEnd::lens of a registered polynomial lens (never a pb_proj.lens: the ABI's ids of such lenses start at PB_LENS_POLYNOMIAL_BASE)
+#define PB_LENS_POLYNOMIAL 7
+
+// the definition's two polynomials, every operation rounded on its own in exactly this nesting (host and device: -ffp-contract=off)
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define PB_HD __host__ __device__
+#else
+#define PB_HD
+#endif
+PB_HD static inline double pb_poly_p(const PbPoly& L, double t) {
+    const double t2 = t * t;
+    return t * (1.0 + t2 * (L.k[0] + t2 * (L.k[1] + t2 * (L.k[2] + t2 * L.k[3]))));
+}
+PB_HD static inline double pb_poly_dp(const PbPoly& L, double t) {
+    const double t2 = t * t;
+    return 1.0 + t2 * (L.d[0] + t2 * (L.d[1] + t2 * (L.d[2] + t2 * L.d[3])));
+}
+#define PB_POLY_NEWTON_STEPS 10  // a constant of the definition: host and device, scalar and array agree to the bit
+
 struct PbParams {
     PbEnd dst, src;
     int32_t n_rot;
@@ -52,6 +78,8 @@ struct PbParams {
     int32_t thresholds_ready;               // 0: kernels must evaluate the predicate per pixel
     int32_t fast_tiles;                     // 1: per-tile polynomial models allowed (certified plan)
     double mrg_min, mrg_max, mrg_range, mrg_max_safe;  // projection.py:414-418
+    // ---- polynomial lenses (appended: no earlier offset moves) -------------
+    PbPoly poly_dst, poly_src;  // the destination's / the source's coefficients when its PbEnd::lens == PB_LENS_POLYNOMIAL, else zero
 };
 
 static inline int64_t pb_floor_mod_i64(int64_t a, int64_t n) {

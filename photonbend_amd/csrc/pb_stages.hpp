@@ -52,8 +52,30 @@ __device__ __forceinline__ int pb_floor_mod(long long a, int n) {
 
 // ---- a-1 lens functions (array semantics of core/lens.py) --------------------
 // np.tan / np.arcsin / np.arctan are NumPy's own SIMD kernels, restated bit for bit in pb_math_np.hpp; np.sin is glibc's (pb_math.hpp).
-__device__ __forceinline__ double pb_lens_forward(int lens, double theta, double rect_max) {
-    switch (lens) {
+// A polynomial lens (PbPoly, pb_params.hpp) has no transcendental: + - * / in float64, the bits of the NumPy definition
+// in core/lens.py.  The Newton loop stays rolled (ten copies of two Horner chains in every float64 kernel buy nothing).
+// SMOOTH (model building only - pb_dst_coord_real, pb_chain_real - never an output value): past the end of its domain the lens continues
+// smoothly instead of jumping to +inf - the forward polynomial itself, the inverse along its tangent at max_theta.  Those pixels are black
+// whatever the model says (the validity thresholds and certification against the exact chain see to that); a finite model lets their tiles
+// be classified BLACK / MASKED like a built-in lens's instead of failing for want of a model.
+template <bool SMOOTH = false>
+__device__ __forceinline__ double pb_poly_forward(const PbPoly& L, double theta) {
+    return (SMOOTH || theta <= L.max_theta) ? pb_poly_p(L, theta) : __builtin_inf();
+}
+template <bool SMOOTH = false>
+__device__ __forceinline__ double pb_poly_inverse(const PbPoly& L, double r) {
+    if (!(r <= L.r_max)) return SMOOTH ? L.max_theta + (r - L.r_max) / pb_poly_dp(L, L.max_theta) : __builtin_inf();  // (NaN included: the comparison is false)
+    double t = r;
+#pragma clang loop unroll(disable)
+    for (int s = 0; s < PB_POLY_NEWTON_STEPS; ++s) t = t - (pb_poly_p(L, t) - r) / pb_poly_dp(L, t);
+    return t;
+}
+// forward: the SOURCE's lens (P.src.lens, P.poly_src); inverse: the DESTINATION's (P.dst.lens, P.poly_dst)
+template <bool SMOOTH = false>
+__device__ __forceinline__ double pb_lens_forward(const PbParams& P, double theta) {
+    const double rect_max = P.rect_max;
+    switch (P.src.lens) {
+        case PB_LENS_POLYNOMIAL: return pb_poly_forward<SMOOTH>(P.poly_src, theta);
         case PB_LENS_EQUIDISTANT: return theta;                          // lens.py:187
         case PB_LENS_EQUISOLID: return 2.0 * pb_sin_np(theta / 2.0);     // lens.py:240-243
         case PB_LENS_STEREOGRAPHIC: return 2.0 * pb_tan_np(theta / 2.0); // lens.py:142-145
@@ -65,8 +87,10 @@ __device__ __forceinline__ double pb_lens_forward(int lens, double theta, double
         }
     }
 }
-__device__ __forceinline__ double pb_lens_inverse(int lens, double r) {
-    switch (lens) {
+template <bool SMOOTH = false>
+__device__ __forceinline__ double pb_lens_inverse(const PbParams& P, double r) {
+    switch (P.dst.lens) {
+        case PB_LENS_POLYNOMIAL: return pb_poly_inverse<SMOOTH>(P.poly_dst, r);
         case PB_LENS_EQUIDISTANT: return r;                              // lens.py:165
         case PB_LENS_EQUISOLID: {                                        // lens.py:206-220
             double t = 2.0 * pb_asin_np(r / 2.0);
@@ -106,7 +130,7 @@ __device__ __forceinline__ PbCoord pb_dst_coord(const PbParams& P, int i, int j)
         x = (double)j + P.dst_x0;
     }
     const double dist = sqrt(x * x + y * y) / d.f_distance;  // projection.py:186, :375
-    double lat = pb_lens_inverse(d.lens, dist);
+    double lat = pb_lens_inverse(P, dist);
     if (d.kind == PB_KIND_DOUBLE && right) {
         lat = (lat * -1.0) + PB_PI;           // projection.py:381-382
         c.inv = lat < P.dst_right_min;        // projection.py:358-360
@@ -144,7 +168,7 @@ __device__ __forceinline__ PbCoord pb_dst_coord_real(const PbParams& P, double f
         x = fj + P.dst_x0;
     }
     const double dist = sqrt(x * x + y * y) / d.f_distance;
-    double lat = pb_lens_inverse(d.lens, dist);
+    double lat = pb_lens_inverse<true>(P, dist);
     if (right) lat = (lat * -1.0) + PB_PI;
     c.lat = lat;
     c.lon = atan2(y, x);
@@ -165,7 +189,7 @@ __device__ __forceinline__ void pb_src_col_range(const PbParams& P, int& cmin, i
 }
 
 // pre-truncation source coordinates (row-like, column-like) of a pano / camera source (or one eye)
-template <int SRC_KIND>
+template <int SRC_KIND, bool SMOOTH = false>
 __device__ __forceinline__ void pb_src_pretrunc(const PbParams& P, const PbCoord& c, double& f0, double& f1) {
     if (SRC_KIND == PB_KIND_PANO) {
         f0 = c.lat / P.src_hseg;
@@ -175,13 +199,13 @@ __device__ __forceinline__ void pb_src_pretrunc(const PbParams& P, const PbCoord
         // eye_w + (eye_w_right - 1 - x) with x = trunc(re + cx_r), i.e. floor(w - (re + cx_r)) wherever that
         // is not an exact integer (those pixels end on the plan's fix list like every other model miss)
         const double lat_r = (c.lat * -1.0) + PB_PI;
-        const double dist = pb_lens_forward(P.src.lens, lat_r, P.rect_max) * P.src.f_distance;
+        const double dist = pb_lens_forward<SMOOTH>(P, lat_r) * P.src.f_distance;
         double sl, cl;
         sincos(c.lon, &sl, &cl);
         f0 = ((sl * dist) * -1.0) + P.src_cy;
         f1 = (double)P.src.width - ((cl * dist) + P.src_cx_r);
     } else {
-        const double dist = pb_lens_forward(P.src.lens, c.lat, P.rect_max) * P.src.f_distance;
+        const double dist = pb_lens_forward<SMOOTH>(P, c.lat) * P.src.f_distance;
         double sl, cl;
         sincos(c.lon, &sl, &cl);
         f0 = ((sl * dist) * -1.0) + P.src_cy;
@@ -203,7 +227,7 @@ __device__ __forceinline__ bool pb_dst_inv_pred(const PbParams& P, long long n4,
         } break;
         case PB_LENS_ORTHOGRAPHIC: lat = pb_asin_np(dist); nan_region = (lat != lat); break;
         case PB_LENS_THOBY: lat = pb_asin_np(dist / 1.47) / 0.713; nan_region = (lat != lat); break;
-        default: lat = pb_lens_inverse(P.dst.lens, dist);
+        default: lat = pb_lens_inverse(P, dist);
     }
     if (outside_domain) *outside_domain = nan_region;
     if (right) {
@@ -280,7 +304,7 @@ __device__ __forceinline__ bool pb_src_camera_pos_sc(double dist, double sl, dou
 }
 __device__ __forceinline__ bool pb_src_camera_pos(const PbParams& P, double lat, double lon, int h, int w, double cy,
                                                   double cx, int& py, int& px) {
-    const double dist = pb_lens_forward(P.src.lens, lat, P.rect_max) * P.src.f_distance;
+    const double dist = pb_lens_forward(P, lat) * P.src.f_distance;
     double sl, cl;
     pb_expi_np(lon, &sl, &cl);  // np.exp(lon * 1j)   projection.py:252
     return pb_src_camera_pos_sc(dist, sl, cl, h, w, cy, cx, py, px);
@@ -300,12 +324,12 @@ __device__ __forceinline__ int pb_src_index_sc(const PbParams& P, const PbCoord&
     int py, px;
     if (SRC_KIND == PB_KIND_EYE_R) {
         const double lat_r = (c.lat * -1.0) + PB_PI;  // projection.py:426-427
-        const double dist = pb_lens_forward(P.src.lens, lat_r, P.rect_max) * P.src.f_distance;
+        const double dist = pb_lens_forward(P, lat_r) * P.src.f_distance;
         const bool ok = pb_src_camera_pos_sc(dist, sl, cl, P.src.height, P.src_eye_w_right, P.src_cy, P.src_cx_r, py, px);
         // the right eye is mirrored before it is sampled (projection.py:430-431)
         return (ok && !c.inv) ? py * P.src.width + (P.src_eye_w + (P.src_eye_w_right - 1 - px)) : -1;
     }
-    const double dist = pb_lens_forward(P.src.lens, c.lat, P.rect_max) * P.src.f_distance;
+    const double dist = pb_lens_forward(P, c.lat) * P.src.f_distance;
     const int we = (SRC_KIND == PB_KIND_EYE_L) ? P.src_eye_w : P.src.width;
     const bool ok = pb_src_camera_pos_sc(dist, sl, cl, P.src.height, we, P.src_cy, P.src_cx, py, px);
     return (ok && !c.inv) ? py * P.src.width + px : -1;
@@ -315,11 +339,11 @@ template <int SRC_KIND>
 __device__ __forceinline__ void pb_src_pretrunc_sc(const PbParams& P, const PbCoord& c, double sl, double cl, double& f0, double& f1) {
     if (SRC_KIND == PB_KIND_EYE_R) {
         const double lat_r = (c.lat * -1.0) + PB_PI;
-        const double dist = pb_lens_forward(P.src.lens, lat_r, P.rect_max) * P.src.f_distance;
+        const double dist = pb_lens_forward(P, lat_r) * P.src.f_distance;
         f0 = ((sl * dist) * -1.0) + P.src_cy;
         f1 = (double)P.src.width - ((cl * dist) + P.src_cx_r);
     } else {
-        const double dist = pb_lens_forward(P.src.lens, c.lat, P.rect_max) * P.src.f_distance;
+        const double dist = pb_lens_forward(P, c.lat) * P.src.f_distance;
         f0 = ((sl * dist) * -1.0) + P.src_cy;
         f1 = (cl * dist) + P.src_cx;
     }

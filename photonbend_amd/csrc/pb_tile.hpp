@@ -125,7 +125,7 @@ template <int SRC_KIND>
 __device__ __forceinline__ void pb_chain_real(const PbParams& P, double fi, double fj, double& f0, double& f1) {
     PbCoord c = pb_dst_coord_real(P, fi, fj);
     c = pb_rotate_all(P, c);
-    pb_src_pretrunc<SRC_KIND>(P, c, f0, f1);
+    pb_src_pretrunc<SRC_KIND, true>(P, c, f0, f1);
 }
 
 // faithful chain at an integer pixel -> source index (-1 = black); THE reference path

@@ -12,6 +12,7 @@
 // separately; fused multiply-adds appear only where written as fma()/fmaf()).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <ctime>
@@ -311,6 +312,123 @@ static bool pb_sep_usable(const pb_plan* plan, hipStream_t st) {
 // ----------------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------------
+// ---- polynomial (Kannala-Brandt) lenses: the process-wide registry behind pb_lens_polynomial --------------------------
+// Immutable entries; the same coefficients and max_theta (bit for bit) give the same id; ids are PB_LENS_POLYNOMIAL_BASE + slot and
+// mean something in THIS process only - a plan's PbParams, its blob and the broadcast block carry the coefficients, never an id.
+enum { PB_POLY_MAX_ENTRIES = 4096 };
+static struct {
+    std::mutex lock;
+    std::vector<PbPoly> entries;
+} g_poly;
+
+static bool pb_poly_lookup(int lens, PbPoly* out) {
+    if (lens < PB_LENS_POLYNOMIAL_BASE) return false;
+    std::lock_guard<std::mutex> g(g_poly.lock);
+    const size_t slot = (size_t)(lens - PB_LENS_POLYNOMIAL_BASE);
+    if (slot >= g_poly.entries.size()) return false;
+    if (out) *out = g_poly.entries[slot];
+    return true;
+}
+
+// real roots in [lo, hi] of the polynomial c[0] + c[1] x + ... + c[n] x^n (n <= 4): between consecutive roots of the derivative the
+// polynomial is monotonic, so every sign change brackets exactly one root, found by bisection
+static void pb_poly_roots(const double* c, int n, double lo, double hi, std::vector<double>& roots) {
+    while (n > 0 && c[n] == 0.0) --n;
+    if (n == 0) return;
+    if (n == 1) {
+        const double r = -c[0] / c[1];
+        if (r >= lo && r <= hi) roots.push_back(r);
+        return;
+    }
+    double dc[4];
+    for (int i = 1; i <= n; ++i) dc[i - 1] = (double)i * c[i];
+    std::vector<double> pts;
+    pts.push_back(lo);
+    pb_poly_roots(dc, n - 1, lo, hi, pts);
+    pts.push_back(hi);
+    std::sort(pts.begin(), pts.end());
+    const auto f = [&](double x) {
+        double v = c[n];
+        for (int i = n - 1; i >= 0; --i) v = v * x + c[i];
+        return v;
+    };
+    for (size_t i = 0; i + 1 < pts.size(); ++i) {
+        double a = pts[i], b = pts[i + 1];
+        const double fa = f(a), fb = f(b);
+        if (fa == 0.0) roots.push_back(a);
+        if (!((fa < 0.0 && fb > 0.0) || (fa > 0.0 && fb < 0.0))) continue;
+        for (int it = 0; it < 200; ++it) {
+            const double m = 0.5 * (a + b);
+            if (!(m > a && m < b)) break;
+            if ((f(m) < 0.0) == (fa < 0.0)) a = m;
+            else b = m;
+        }
+        roots.push_back(0.5 * (a + b));
+    }
+    if (f(hi) == 0.0) roots.push_back(hi);
+}
+
+// the checks of core/lens.py's polynomial(): finite coefficients, 0 < max_theta <= pi, dp > 0 on [0, max_theta] (its minimum is at an end
+// or at a real root of the derivative of the quartic in t^2), and ten Newton steps invert p on a grid of 4097 angles to 2^-40
+static bool pb_poly_make(const double k[4], double max_theta, PbPoly& L, std::string& why) {
+    memset(&L, 0, sizeof(L));
+    for (int i = 0; i < 4; ++i) {
+        if (!std::isfinite(k[i])) {
+            why = "polynomial lens: the coefficients must be finite";
+            return false;
+        }
+        L.k[i] = k[i];
+        L.d[i] = (double)(2 * i + 3) * k[i];
+    }
+    if (!(max_theta > 0.0 && max_theta <= PB_PI)) {
+        why = "polynomial lens: max_theta must lie in (0, pi]";
+        return false;
+    }
+    L.max_theta = max_theta;
+    L.r_max = pb_poly_p(L, max_theta);
+    const double U = max_theta * max_theta;
+    const double q[5] = {1.0, L.d[0], L.d[1], L.d[2], L.d[3]}, dq[4] = {q[1], 2.0 * q[2], 3.0 * q[3], 4.0 * q[4]};
+    std::vector<double> at;
+    at.push_back(0.0);
+    pb_poly_roots(dq, 3, 0.0, U, at);
+    at.push_back(U);
+    for (double u : at) {
+        const double v = q[0] + u * (q[1] + u * (q[2] + u * (q[3] + u * q[4])));
+        if (!(v > 0.0)) {
+            why = "polynomial lens: r(theta) is not increasing on [0, max_theta] (a non-monotonic model folds the image); a calibration holds on the lens's own field only - pass a smaller max_theta";
+            return false;
+        }
+    }
+    if (!(L.r_max > 0.0) || !std::isfinite(L.r_max)) {
+        why = "polynomial lens: r(max_theta) is not a positive finite number";
+        return false;
+    }
+    for (int i = 0; i <= 4096; ++i) {
+        const double theta = (i == 4096) ? max_theta : (double)i * (max_theta / 4096.0);
+        const double r = pb_poly_p(L, theta);
+        double t = r;
+        for (int s = 0; s < PB_POLY_NEWTON_STEPS; ++s) t = t - (pb_poly_p(L, t) - r) / pb_poly_dp(L, t);
+        if (!(fabs(t - theta) <= 9.094947017729282e-13)) {  // 2^-40
+            why = "polynomial lens: ten Newton steps from t = r do not invert r(theta) on [0, max_theta]";
+            return false;
+        }
+    }
+    return true;
+}
+
+static int pb_poly_register(const PbPoly& L, int* lens_out) {
+    std::lock_guard<std::mutex> g(g_poly.lock);
+    for (size_t i = 0; i < g_poly.entries.size(); ++i)
+        if (memcmp(&g_poly.entries[i], &L, sizeof(PbPoly)) == 0) {
+            *lens_out = PB_LENS_POLYNOMIAL_BASE + (int)i;
+            return PB_OK;
+        }
+    if (g_poly.entries.size() >= PB_POLY_MAX_ENTRIES) return PB_ERR_UNSUPPORTED;
+    g_poly.entries.push_back(L);
+    *lens_out = PB_LENS_POLYNOMIAL_BASE + (int)g_poly.entries.size() - 1;
+    return PB_OK;
+}
+
 enum { PB_ROLE_DST = 1, PB_ROLE_SRC = 2, PB_ROLE_CUSTOM_OK = 4 };
 static bool pb_end_ok(const pb_proj* p, std::string& why, int role = PB_ROLE_DST | PB_ROLE_SRC) {
     if (!p) {
@@ -321,9 +439,10 @@ static bool pb_end_ok(const pb_proj* p, std::string& why, int role = PB_ROLE_DST
         why = "pb_proj.kind out of range";
         return false;
     }
-    if (p->kind != PB_KIND_PANO && (p->lens < PB_LENS_EQUIDISTANT || p->lens > PB_LENS_THOBY) &&
+    if (p->kind != PB_KIND_PANO && (p->lens < PB_LENS_EQUIDISTANT || p->lens > PB_LENS_THOBY) && !pb_poly_lookup(p->lens, nullptr) &&
         !((role & PB_ROLE_CUSTOM_OK) && p->lens == PB_LENS_CUSTOM)) {
         why = p->lens == PB_LENS_CUSTOM ? "PB_LENS_CUSTOM is valid only where the host supplies the lens values (pb_index_from_map_i32 with distance planes)"
+                                        : p->lens >= PB_LENS_POLYNOMIAL_BASE ? "pb_proj.lens is not a registered polynomial lens of this process (pb_lens_polynomial)"
                                         : "pb_proj.lens out of range";
         return false;
     }
@@ -344,15 +463,24 @@ static bool pb_end_ok(const pb_proj* p, std::string& why, int role = PB_ROLE_DST
     return true;
 }
 
-static PbEnd pb_to_end(const pb_proj* p) {
+// one end of a request as the parameter block holds it: a registered polynomial id resolves into PB_LENS_POLYNOMIAL + its coefficients
+// (pb_end_ok and this function are the only places that know the registry)
+struct PbEndX {
     PbEnd e;
+    PbPoly poly;  // zero unless e.lens == PB_LENS_POLYNOMIAL
+};
+static PbEndX pb_to_end(const pb_proj* p) {
+    PbEndX x;
+    memset(&x, 0, sizeof(x));
+    PbEnd& e = x.e;
     e.kind = p->kind;
     e.lens = (p->kind == PB_KIND_PANO) ? PB_LENS_EQUIDISTANT : p->lens;
+    if (p->kind != PB_KIND_PANO && pb_poly_lookup(p->lens, &x.poly)) e.lens = PB_LENS_POLYNOMIAL;
     e.height = p->height;
     e.width = p->width;
     e.fov = p->fov;
     e.f_distance = p->f_distance;
-    return e;
+    return x;
 }
 
 static inline unsigned pb_blocks(unsigned long long items) { return (unsigned)((items + PB_BLOCK - 1) / PB_BLOCK); }
@@ -1406,10 +1534,12 @@ static int pb_tune_window_budget(pb_plan* pl) {
 }
 
 // the parameter block of a request, as pb_plan_create_ex fills it before any device work
-static void pb_params_of_request(PbParams& P, const PbEnd& dst, const double* rot3x3, int n_rot, const PbEnd& src) {
+static void pb_params_of_request(PbParams& P, const PbEndX& dst, const double* rot3x3, int n_rot, const PbEndX& src) {
     memset(&P, 0, sizeof(PbParams));
-    P.dst = dst;
-    P.src = src;
+    P.dst = dst.e;
+    P.src = src.e;
+    P.poly_dst = dst.poly;
+    P.poly_src = src.poly;
     P.n_rot = n_rot;
     for (int k = 0; k < n_rot; ++k)
         for (int e = 0; e < 9; ++e) P.R[k][e] = rot3x3[9 * k + e];
@@ -1567,6 +1697,25 @@ int pb_plan_matches(const pb_plan* plan, const pb_proj* dst, const double* rot3x
     PbParams Q;
     pb_params_of_request(Q, pb_to_end(dst), rot3x3, n_rot, pb_to_end(src));
     return pb_same_request(Q, plan->P) ? 1 : 0;
+}
+
+int pb_lens_polynomial(const double k[4], double max_theta, int* lens_out) {
+    if (!k || !lens_out) return pb_fail(PB_ERR_INVALID, "null argument");
+    PbPoly L;
+    std::string why;
+    if (!pb_poly_make(k, max_theta, L, why)) return pb_fail(PB_ERR_INVALID, why);
+    const int rc = pb_poly_register(L, lens_out);
+    if (rc != PB_OK) return pb_fail(rc, "the polynomial lens registry is full (4096 distinct lenses per process)");
+    return PB_OK;
+}
+
+int pb_lens_polynomial_info(int lens, double k[4], double* max_theta) {
+    PbPoly L;
+    if (!pb_poly_lookup(lens, &L)) return pb_fail(PB_ERR_INVALID, "not a registered polynomial lens of this process");
+    if (k)
+        for (int i = 0; i < 4; ++i) k[i] = L.k[i];
+    if (max_theta) *max_theta = L.max_theta;
+    return PB_OK;
 }
 
 int pb_plan_create(const pb_proj* dst, const double* rot3x3, int n_rot, const pb_proj* src, pb_plan** out) {
@@ -1863,8 +2012,9 @@ int pb_coordmap_f64(const pb_proj* dst, double* map_dev, void* stream) {
     if (!pb_end_ok(dst, why, PB_ROLE_DST)) return pb_fail(PB_ERR_INVALID, why);
     PbParams P;
     memset(&P, 0, sizeof(P));
-    P.dst = pb_to_end(dst);
-    P.src = P.dst;
+    const PbEndX d = pb_to_end(dst);
+    P.dst = P.src = d.e;
+    P.poly_dst = P.poly_src = d.poly;
     pb_derive(P);
     const unsigned blocks = pb_blocks((unsigned long long)P.dst.height * P.dst.width);
     hipLaunchKernelGGL(pb_coordmap_kernel, dim3(blocks), dim3(PB_BLOCK), 0, (hipStream_t)stream, P, map_dev);
@@ -1896,7 +2046,9 @@ static int pb_map_stage(bool null_argument, const pb_proj* src, unsigned roles, 
     if (!pb_end_ok(src, why, roles)) return pb_fail(PB_ERR_INVALID, why);
     if (height < 1 || width < 1 || (long long)height * width > 0x7FFFFFFFll / 4) return pb_fail(PB_ERR_INVALID, "map size out of range");
     memset(&P, 0, sizeof(P));
-    P.src = pb_to_end(src);
+    const PbEndX x = pb_to_end(src);
+    P.src = x.e;
+    P.poly_src = x.poly;
     P.dst = P.src;
     P.dst.kind = PB_KIND_PANO;
     P.dst.height = height;
@@ -2159,8 +2311,16 @@ int pb_plan_deserialize(const void* buf, size_t size, pb_plan** out) {
     bool ok = pl->P.n_rot >= 0 && pl->P.n_rot <= PB_MAX_ROTATIONS;
     if (ok) {
         PbParams Q;
-        pb_params_of_request(Q, pl->P.dst, &pl->P.R[0][0], pl->P.n_rot, pl->P.src);
-        ok = pb_same_request(Q, pl->P);
+        PbEndX ends[2];  // (a polynomial lens: its derived constants too are re-derived, from the blob's coefficients, and these re-validated)
+        memset(ends, 0, sizeof(ends));
+        ends[0].e = pl->P.dst;
+        ends[1].e = pl->P.src;
+        const PbPoly* polys[2] = {&pl->P.poly_dst, &pl->P.poly_src};
+        std::string why;
+        for (int e = 0; e < 2 && ok; ++e)
+            if (ends[e].e.lens == PB_LENS_POLYNOMIAL) ok = pb_poly_make(polys[e]->k, polys[e]->max_theta, ends[e].poly, why);
+        pb_params_of_request(Q, ends[0], &pl->P.R[0][0], pl->P.n_rot, ends[1]);
+        ok = ok && pb_same_request(Q, pl->P);
     }
     ok = ok && (!tiles || pl->n_tiles == pb_num_tiles(pl->P)) && pl->n_fail_tiles <= 2u * pl->n_tiles + 1u &&
               pl->P.win_budget >= PB_DIRECT_LDS_BYTES && pl->P.win_budget <= PB_WINLDS_MAX && (pl->P.win_budget & 15) == 0 &&
@@ -2291,7 +2451,8 @@ PbRccl* pb_rccl() {
 int pb_nccl_fail(const PbRccl* r, const char* what, int code) {
     return pb_fail(PB_ERR_HIP, std::string(what) + ": " + ((r && r->err) ? r->err(code) : "RCCL error"));
 }
-const int PB_BLOCK_DOUBLES = 2 + 2 * 7 + 9 * PB_MAX_ROTATIONS;  // the parameter block: photonbend_amd/parallel.py's layout
+const int PB_BLOCK_POLY = 2 + 2 * 7 + 9 * PB_MAX_ROTATIONS;  // then k1..k4 and max_theta of a polynomial destination lens, then of a polynomial source lens (zeros otherwise)
+const int PB_BLOCK_DOUBLES = PB_BLOCK_POLY + 2 * 5;  // the parameter block: photonbend_amd/parallel.py's layout
 }  // namespace
 
 struct pb_comm {
@@ -2373,6 +2534,19 @@ int pb_bcast_params(pb_comm* comm, pb_proj* dst, double* rot3x3, int* n_rot, pb_
             put(block + 2, *dst);
             put(block + 9, *src);
             for (int k = 0; k < 9 * *n_rot; ++k) block[16 + k] = rot3x3[k];
+            // a polynomial lens travels as its coefficients (ids are process-local): the lens field says PB_LENS_POLYNOMIAL_BASE
+            const pb_proj* ends[2] = {dst, src};
+            for (int e = 0; e < 2; ++e) {
+                PbPoly L;
+                if (ends[e]->kind == PB_KIND_PANO || ends[e]->lens < PB_LENS_POLYNOMIAL_BASE) continue;
+                if (!pb_poly_lookup(ends[e]->lens, &L)) {  // an id the root never registered must not travel: another rank's registry
+                    block[0] = -1.0;                       // may hold a different lens under it - every rank returns PB_ERR_INVALID
+                    break;
+                }
+                block[2 + 7 * e + 1] = PB_LENS_POLYNOMIAL_BASE;
+                for (int i = 0; i < 4; ++i) block[PB_BLOCK_POLY + 5 * e + i] = L.k[i];
+                block[PB_BLOCK_POLY + 5 * e + 4] = L.max_theta;
+            }
         }
         if (hipMemcpyAsync(comm->block_dev, block, sizeof(block), hipMemcpyHostToDevice, st) != hipSuccess) {
             (void)hipGetLastError();
@@ -2384,11 +2558,20 @@ int pb_bcast_params(pb_comm* comm, pb_proj* dst, double* rot3x3, int* n_rot, pb_
     PB_HIP(hipMemcpyAsync(block, comm->block_dev, sizeof(block), hipMemcpyDeviceToHost, st));
     PB_HIP(hipStreamSynchronize(st));
     if (block[0] != 1346522692.0 || !(block[1] >= 0 && block[1] <= PB_MAX_ROTATIONS))
-        return pb_fail(PB_ERR_INVALID, "the root's parameter block is invalid (n_rot outside [0, PB_MAX_ROTATIONS], a failed upload, or corrupt)");
+        return pb_fail(PB_ERR_INVALID, "the root's parameter block is invalid (n_rot outside [0, PB_MAX_ROTATIONS], a polynomial lens id the root never registered, a failed upload, or corrupt)");
     *n_rot = (int)block[1];
     get(block + 2, *dst);
     get(block + 9, *src);
     for (int k = 0; k < 9 * *n_rot; ++k) rot3x3[k] = block[16 + k];
+    // ... and the receiver (the root included) registers them and writes ITS id into the projection it returns
+    pb_proj* ends[2] = {dst, src};
+    for (int e = 0; e < 2; ++e) {
+        if (ends[e]->kind == PB_KIND_PANO || ends[e]->lens != PB_LENS_POLYNOMIAL_BASE) continue;
+        int id = 0;
+        const int rc = pb_lens_polynomial(block + PB_BLOCK_POLY + 5 * e, block[PB_BLOCK_POLY + 5 * e + 4], &id);
+        if (rc != PB_OK) return rc;
+        ends[e]->lens = id;
+    }
     return PB_OK;
 }
 

@@ -37,15 +37,29 @@ except ImportError:
 _MAGIC = 0x50424E44  # "PBND"
 _HEADER = 2
 _PROJ_FIELDS = 7
-BLOCK_LEN = _HEADER + 2 * _PROJ_FIELDS + 9 * nat.PB_MAX_ROTATIONS  # fixed size: receivers need no length exchange
+_POLY_FIELDS = 5  # k1..k4, max_theta of a polynomial lens (zeros for every other lens), destination then source, behind the rotations
+_POLY_BASE = _HEADER + 2 * _PROJ_FIELDS + 9 * nat.PB_MAX_ROTATIONS
+BLOCK_LEN = _POLY_BASE + 2 * _POLY_FIELDS  # fixed size: receivers need no length exchange
 
 
 def _proj_to_list(p: nat.pb_proj) -> List[float]:
-    return [float(p.kind), float(p.lens), float(p.height), float(p.width), p.fov, p.magnitude, p.f_distance]
+    """(a registered polynomial lens travels as LENS_POLYNOMIAL_BASE + its coefficients: ids are process-local)"""
+    lens = nat.LENS_POLYNOMIAL_BASE if _is_polynomial(p) else p.lens
+    return [float(p.kind), float(lens), float(p.height), float(p.width), p.fov, p.magnitude, p.f_distance]
 
 
-def _proj_from_list(v: Sequence[float]) -> nat.pb_proj:
-    return nat.make_proj(int(v[0]), int(v[2]), int(v[3]), int(v[1]), float(v[4]), float(v[5]), float(v[6]))
+def _is_polynomial(p: nat.pb_proj) -> bool:
+    return p.kind != nat.KIND_PANO and p.lens >= nat.LENS_POLYNOMIAL_BASE
+
+
+def _proj_from_list(v: Sequence[float], poly: Sequence[float] = ()) -> nat.pb_proj:
+    """(the receiving rank registers a polynomial lens's coefficients and uses ITS id)"""
+    lens = int(v[1])
+    if int(v[0]) != nat.KIND_PANO and lens >= nat.LENS_POLYNOMIAL_BASE:
+        if len(poly) != _POLY_FIELDS or not float(poly[4]) > 0.0:  # (a packed lens has max_theta > 0; zeros: the sender packed none)
+            raise nat.PbError("corrupt parameter block (polynomial lens without coefficients)")
+        lens = nat.lens_polynomial([float(x) for x in poly[:4]], float(poly[4]))
+    return nat.make_proj(int(v[0]), int(v[2]), int(v[3]), lens, float(v[4]), float(v[5]), float(v[6]))
 
 
 def pack_params(dst: nat.pb_proj, rotations, src: nat.pb_proj) -> np.ndarray:
@@ -60,6 +74,9 @@ def pack_params(dst: nat.pb_proj, rotations, src: nat.pb_proj) -> np.ndarray:
     block[_HEADER : _HEADER + _PROJ_FIELDS] = _proj_to_list(dst)
     block[_HEADER + _PROJ_FIELDS : _HEADER + 2 * _PROJ_FIELDS] = _proj_to_list(src)
     block[_HEADER + 2 * _PROJ_FIELDS : _HEADER + 2 * _PROJ_FIELDS + rots.size] = rots.ravel()
+    for e, p in enumerate((dst, src)):
+        if _is_polynomial(p):
+            block[_POLY_BASE + _POLY_FIELDS * e : _POLY_BASE + _POLY_FIELDS * (e + 1)] = nat.lens_polynomial_info(p.lens)
     return block
 
 
@@ -70,8 +87,8 @@ def unpack_params(block: np.ndarray) -> Tuple[nat.pb_proj, List[np.ndarray], nat
     n = int(block[1])
     if not 0 <= n <= nat.PB_MAX_ROTATIONS:
         raise nat.PbError("corrupt parameter block (rotation count)")
-    dst = _proj_from_list(block[_HEADER : _HEADER + _PROJ_FIELDS])
-    src = _proj_from_list(block[_HEADER + _PROJ_FIELDS : _HEADER + 2 * _PROJ_FIELDS])
+    dst = _proj_from_list(block[_HEADER : _HEADER + _PROJ_FIELDS], block[_POLY_BASE : _POLY_BASE + _POLY_FIELDS])
+    src = _proj_from_list(block[_HEADER + _PROJ_FIELDS : _HEADER + 2 * _PROJ_FIELDS], block[_POLY_BASE + _POLY_FIELDS : _POLY_BASE + 2 * _POLY_FIELDS])
     base = _HEADER + 2 * _PROJ_FIELDS
     rots = [block[base + 9 * k : base + 9 * (k + 1)].reshape(3, 3).copy() for k in range(n)]
     return dst, rots, src

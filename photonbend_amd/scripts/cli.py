@@ -20,7 +20,7 @@ from PIL import Image
 
 from .. import core
 from .. import _native as nat
-from ..core.lens import equidistant, equisolid, orthographic, rectilinear, stereographic
+from ..core.lens import equidistant, equisolid, orthographic, polynomial, rectilinear, stereographic
 from ..core.projection import CameraImage, DoubleCameraImage, PanoramaImage
 from ..core.rotation import Rotation
 from ..utils import to_radians
@@ -32,6 +32,7 @@ LENSES = {
     "rectilinear": rectilinear,
     "stereographic": stereographic,
 }
+POLYNOMIAL = "polynomial"  # a --lens choice with parameters (lens_object)
 TYPES = ("inscribed", "double", "cropped", "full")
 INTERPOLATIONS = nat.INTERPOLATIONS
 
@@ -106,10 +107,27 @@ def camera_shape(image_type: str, source: np.ndarray, height: Optional[int]) -> 
     return (h, 2 * h, 3) if image_type == "double" else (h, h, 3)
 
 
-def camera_object(image_type: str, pixels: np.ndarray, fov: float, lens: str, magnitude: float):
-    """CameraImage or DoubleCameraImage for the type (commands/__init__.py:84-88)."""
+def lens_object(lens: str, coefficients=None, max_theta=None, prefix: str = "--lens"):
+    """The Lens of a --lens choice.  ``polynomial`` (no reference counterpart: a calibrated Kannala-Brandt lens, core.lens.polynomial)
+    takes its K1 K2 K3 K4 from ``<prefix>-coefficients`` and the end of its domain, in degrees, from ``<prefix>-max-theta``; either
+    option without ``polynomial``, and ``polynomial`` without coefficients, are usage errors."""
+    coefficients = tuple(coefficients) if coefficients else None
+    if lens != POLYNOMIAL:
+        if coefficients is not None or max_theta is not None:
+            raise click.UsageError(f"{prefix}-coefficients / {prefix}-max-theta belong to `{prefix} {POLYNOMIAL}`, not to `{prefix} {lens}`")
+        return LENSES[lens]()
+    if coefficients is None:
+        raise click.UsageError(f"`{prefix} {POLYNOMIAL}` needs {prefix}-coefficients K1 K2 K3 K4")
+    try:
+        return polynomial(*coefficients, max_theta=None if max_theta is None else to_radians(max_theta))
+    except ValueError as exc:
+        raise click.BadParameter(str(exc), param_hint=f"{prefix}-coefficients")
+
+
+def camera_object(image_type: str, pixels: np.ndarray, fov: float, lens, magnitude: float):
+    """CameraImage or DoubleCameraImage for the type (commands/__init__.py:84-88); ``lens``: a built-in's name or a Lens."""
     cls = DoubleCameraImage if image_type == "double" else CameraImage
-    return cls(pixels, fov, LENSES[lens](), magnitude=magnitude)
+    return cls(pixels, fov, LENSES[lens]() if isinstance(lens, str) else lens, magnitude=magnitude)
 
 
 def run_chain(source, destiny, rotations, out: Path, supersample: int = 1, interpolation: str = "nearest") -> None:
@@ -144,7 +162,23 @@ def _sampler(interpolation: str) -> dict:
 
 
 # ---- commands -----------------------------------------------------------------------------------
-_lens_choice = click.Choice(list(LENSES))
+_lens_choice = click.Choice(list(LENSES) + [POLYNOMIAL])
+
+
+def _lens_parameters(prefix: str, dest: str):
+    """``<prefix>-coefficients K1 K2 K3 K4`` and ``<prefix>-max-theta DEGREES`` of a polynomial lens choice."""
+
+    def deco(fn):
+        fn = click.option(f"{prefix}-coefficients", f"{dest}_coefficients", type=click.FLOAT, nargs=4, default=None, metavar="K1 K2 K3 K4",
+                          help=f"With `{prefix} polynomial`: r(theta) = theta + K1 theta^3 + K2 theta^5 + K3 theta^7 + K4 theta^9 "
+                               "(a fisheye calibration's k1..k4, r in focal lengths).")(fn)
+        fn = click.option(f"{prefix}-max-theta", f"{dest}_max_theta", type=click.FLOAT, default=None, metavar="DEGREES",
+                          help=f"With `{prefix} polynomial`: the largest incidence angle the lens images, in degrees (default 180).")(fn)
+        return fn
+
+    return deco
+
+
 _type_choice = click.Choice(list(TYPES))
 
 
@@ -167,16 +201,18 @@ def main():
 @click.argument("input_image", type=click.Path(exists=True, path_type=Path))
 @click.option("--type", "otype", required=True, type=_type_choice, help="The type of the output image. " + TYPE_HELP)
 @click.option("--lens", required=True, type=_lens_choice, help="The lens type to be used on the output photo.")
+@_lens_parameters("--lens", "lens")
 @click.option("--fov", required=True, type=click.FLOAT, help="The lens field of view of the output photo in degrees. " + DOUBLE_FOV_NOTE)
 @_common
 @click.argument("output_image", type=click.Path(exists=False, path_type=Path))
-def make_photo(input_image, otype, lens, fov, output_image, rotation, size, supersample, interpolation):
+def make_photo(input_image, otype, lens, fov, output_image, rotation, size, supersample, interpolation, lens_coefficients, lens_max_theta):
     """Make a photo out of a panorama.
 
     \b
     INPUT is the path to the source panorama.
     OUTPUT is the desired path of the destiny photo.
     """
+    lens = lens_object(lens, lens_coefficients, lens_max_theta)
     out = checked_output(output_image)
     pano = open_image(input_image)
     _, _, _ = pano.shape  # make_photo.py:112 unpacks three dimensions: grey inputs are a ValueError in the reference CLI
@@ -189,19 +225,24 @@ def make_photo(input_image, otype, lens, fov, output_image, rotation, size, supe
 @click.argument("input_image", type=click.Path(exists=True, path_type=Path))
 @click.option("--itype", required=True, type=_type_choice, help="The type of the input image. " + TYPE_HELP)
 @click.option("--ilens", required=True, type=_lens_choice, help="The lens type that was used on the input photo.")
+@_lens_parameters("--ilens", "ilens")
 @click.option("--ifov", required=True, type=click.FLOAT, help="The lens field of view of the input photo in degrees. " + DOUBLE_FOV_NOTE)
 @click.option("--otype", required=True, type=_type_choice, help="The type of the output image." + TYPE_HELP)
 @click.option("--olens", required=True, type=_lens_choice, help="The lens type of the output photo. " + DOUBLE_FOV_NOTE)
+@_lens_parameters("--olens", "olens")
 @click.option("--ofov", required=True, type=click.FLOAT, help="The lens field of view of the output photo in degrees.")
 @click.argument("output_image", type=click.Path(exists=False, path_type=Path))
 @_common
-def alter_photo(input_image, itype, ilens, ifov, otype, olens, ofov, output_image, rotation, size, supersample, interpolation):
+def alter_photo(input_image, itype, ilens, ifov, otype, olens, ofov, output_image, rotation, size, supersample, interpolation,
+                ilens_coefficients, ilens_max_theta, olens_coefficients, olens_max_theta):
     """Change the the lens and FoV of a photo.
 
     \b
     INPUT is the path to the source photo.
     OUTPUT is the desired path of the destiny photo.
     """
+    ilens = lens_object(ilens, ilens_coefficients, ilens_max_theta, "--ilens")
+    olens = lens_object(olens, olens_coefficients, olens_max_theta, "--olens")
     out = checked_output(output_image)
     photo = open_image(input_image)
     source = camera_object(itype, photo, radians_fov(ifov, itype), ilens, magnitude_for(itype, photo.shape))
@@ -215,16 +256,18 @@ def alter_photo(input_image, itype, ilens, ifov, otype, olens, ofov, output_imag
 @click.argument("input_image", type=click.Path(exists=True, path_type=Path))
 @click.option("--type", "itype", required=True, type=_type_choice, help="The type of the input image. " + TYPE_HELP)
 @click.option("--lens", required=True, type=_lens_choice, help="The lens type that was used on the input photo.")
+@_lens_parameters("--lens", "lens")
 @click.option("--fov", required=True, type=click.FLOAT, help="The lens field of view of the input photo in degrees. " + DOUBLE_FOV_NOTE)
 @_common
 @click.argument("output_image", type=click.Path(exists=False, path_type=Path))
-def make_pano(input_image, itype, lens, fov, output_image, rotation, size, supersample, interpolation):
+def make_pano(input_image, itype, lens, fov, output_image, rotation, size, supersample, interpolation, lens_coefficients, lens_max_theta):
     """Make a panorama out of a photo.
 
     \b
     INPUT is the path to the source photo.
     OUTPUT is the desired path of the destiny panorama.
     """
+    lens = lens_object(lens, lens_coefficients, lens_max_theta)
     out = checked_output(output_image)
     photo = open_image(input_image)
     source = camera_object(itype, photo, radians_fov(fov, itype), lens, magnitude_for(itype, photo.shape))
