@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <ctime>
 #include <algorithm>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -37,66 +38,6 @@
 #include "pb_kernels_catmull_rom.hpp"
 
 #define PB_DOUBLE_FRAMES_PER_WAVE 1  // frames a double-source wave loops over (the rest of a batch is a grid dimension)
-struct pb_plan {
-    PbParams P;
-    int mode = PB_MODE_AUTO;     // PB_MODE_AUTO / PB_MODE_FAITHFUL / PB_MODE_FAST
-    int device = -1;             // device that owns the tables below
-    int fast_ready = 0;          // models + fix list built and certified on `device`
-    PbTileEntry* table = nullptr;
-    int32_t* fail_tiles = nullptr;
-    int32_t* fix_px = nullptr;
-    int32_t* idx_tab = nullptr;  // exact source indices of the pixels of failed tiles (4 KiB per tile) ...
-    int32_t* fix_idx = nullptr;  // ... and of the fix list's pixels: looked up per frame instead of recomputed
-    unsigned n_tiles = 0, n_fail_tiles = 0, n_fix_px = 0, n_lean_tiles = 0, n_black_tiles = 0, n_direct_tiles = 0;
-    long long diff_pixels = -1;  // pixels (outside failed tiles) where model and faithful index differed
-    // separable path (double source, unrotated pano destination): row / column tables.  sep_ready: the tables exist (their row weights
-    // are exact by construction and serve the tile kernels); sep_checked: the exhaustive check of their TAPS against the faithful ones -
-    // 0 not started, 2 in flight, 1 passed, -1 failed.  The check (one float64 chain per pixel: 0.27 ms of c5's 1.3 ms preparation) is only
-    // needed by pb_sep_double_kernel, the fallback for frames the windowed two-eye kernel cannot take; the first launch that wants the
-    // fallback ENQUEUES it (pb_sep_usable: no allocation, no synchronisation - the launch functions' contract) and takes the float64 kernel,
-    // later launches take the fallback once the check has been seen to pass.
-    int sep_ready = 0;
-    mutable int sep_checked = 0;
-    int sep_slot = -1;               // this plan's word of the process's pinned result page (pb_sep_setup)
-    hipEvent_t sep_event = nullptr;  // recorded behind the check
-    PbSepRow* sep_rows = nullptr;
-    PbSepCol* sep_cols = nullptr;
-    // double-fisheye source: one certified tile table per eye (pb_kernels_double.hpp); `table` is the left eye's
-    int dbl_ready = 0;
-    PbTileEntry* table_r = nullptr;
-    PbDoubleFix* dbl_tile_fix = nullptr;  // faithful taps + factors of failed tiles' pixels / of the fix list's pixels
-    PbDoubleFix* dbl_px_fix = nullptr;
-    double* lat_tab = nullptr;   // faithful latitudes of the pixels of merge-band tiles (PB_TILE_W_LAT), 8 KiB per tile
-    unsigned n_row_weight_tiles = 0, n_lat_tiles = 0;
-    // the tile flags as classified and certified with the largest window budget: pb_apply_budget derives the flags
-    // in use from them, so the budget can be changed at any time without touching a pixel
-    int32_t* saved_l = nullptr;
-    int32_t* saved_r = nullptr;
-    // the hot kernel's launch-order copy of `table` (rebuilt with every budget change; derived, never serialized)
-    PbTileEntry* ltable = nullptr;
-    int32_t* bil_tiles = nullptr;  // tiles the bilinear tile kernels leave to the float64 pass: PB_TILE_COARSE models; double-fisheye plans also tiles an eye sees but that are not plain for it
-    unsigned n_bil_tiles = 0;
-    // the bilinear mode's exact coordinate tables (pb_kernels_bilinear.hpp): 8 KiB per slot (PbTileEntry::bil_off), and the fix list's
-    // coordinates (two per pixel for a double-fisheye source); nullptr = the tables would not fit, those tiles take the float64 pass
-    PbBilCoord* bil_xy = nullptr;
-    PbBilCoord* bil_fix_xy = nullptr;
-    unsigned n_bil_slots = 0;
-    // ... and its own launch-order table, classified under ITS window budget (PB_BIL_WIN_BUDGET: a direct-gather tile costs the
-    // bilinear mode two 8-byte loads per pixel, the nearest mode one dword - its best budget is larger) and ordered by its own costs;
-    // built once per plan (pb_build_bilinear_launch), untouched by pb_plan_set_window_budget
-    PbTileEntry* ltable_bil = nullptr;
-    unsigned launch_groups_bil = 0;
-    int bil_budget = 0;
-    PbDblTables* bil_dbl_tables = nullptr;  // double-fisheye plans: what only some waves of the bilinear launch need, behind one pointer (pb_kernels_bilinear.hpp)
-    int bil_wanted = 1;           // 0: created with PB_PLAN_NO_BILINEAR - the opt-in mode's tables are built when pb_plan_prepare(PB_PLAN_BILINEAR) asks for them
-    int bil_waves = 4;            // waves per REAL workgroup of a bilinear launch (4 or 2: chosen with the pool, pb_build_bilinear_launch)
-    unsigned bil_pool_bytes = 0;  // dynamic LDS of a bilinear launch's workgroup: the slots' regions are packed into it (pb_bilinear_pool_kernel)
-    PbParams* P_dev = nullptr;   // device copy of P as the hot launches see it (refreshed with every budget change)
-    unsigned launch_groups = 0;  // virtual workgroups (of four waves) per frame, a multiple of 8
-    int walk = 0;                // launch-order rule: 0 = by policy (pb_build_launch_table), 1 = plain, 2 = rows from the heaviest outwards,
-                                 // 3 = super-tiles heaviest first; PB_PLAN_TUNE may pick 1-3 by timing, a serialized plan remembers it
-    double prepare_ms = 0.0, tune_ms = 0.0;  // host wall time of the device preparation / of the optional budget tuning
-};
 
 // Experiment knobs (environment variables) exist in the -DPB_ABLATION diagnostic build only (experiments/); the product
 // library reads no environment.
@@ -160,15 +101,17 @@ static int pb_fail(int code, const std::string& msg) {
             return pb_fail(PB_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));   \
     } while (0)
 
-// Small device buffers that live for a few launches of plan preparation (counters, per-unit costs, a column table): a hipFree costs ~35 us
-// on this stack (it synchronises the device) and a plan used to make nine - a third of a millisecond of a 1.3 ms preparation
-// (experiments/r4/plan_api.sh).  They come from a per-device cache instead: a freed block is kept (up to 96 MiB in blocks of up to 16 MiB: the tables of a 33-Mpx plan)
-// and handed to the next request it fits.  Safe because every user works on the NULL stream, which orders a block's next kernel behind its
-// last one device-wide, and because each site releases its block only after a synchronising copy or hipDeviceSynchronize.
-// Round 6: a plan's OWN tables (tile tables, fix lists, launch tables, parameter block) come from the same cache - a warm c2 plan made
-// eight hipMallocs (~40 us of its 0.45 ms) and its destruction up to ten hipFrees (~350 us).  Launches read those tables on the caller's
-// streams, which the NULL stream does not order: pb_plan_destroy and the budget change wait for the device ONCE before they hand blocks
-// back (what every one of their hipFrees did before).
+// THE BLOCK CACHE AND WHO OWNS ITS BLOCKS.  Every device buffer of plan preparation - the temporaries of a few launches (counters, per-unit
+// costs, a column table) and a plan's own tables (tile tables, fix lists, launch tables, parameter block) - comes from a per-device cache:
+// a hipFree costs ~35 us on this stack (it synchronises the device) and a hipMalloc ~5; a released block is kept (up to 96 MiB in blocks
+// of up to 16 MiB: the tables of a 33-Mpx plan) and handed to the next request it fits.  A block has ONE owner, a PbBlock: a local of the
+// function that needs a temporary, a member of one of pb_plan's groups for a table; nothing else calls pb_tmp_alloc / pb_tmp_free.  When
+// a block may go back depends on who may still be reading it - two rules:
+//   temporaries  every user works on the NULL stream, which orders a block's next kernel behind its last one device-wide: a local PbBlock
+//                goes out of scope after a synchronising copy or a hipDeviceSynchronize (error paths wait explicitly before they return),
+//                or behind kernels whose results only later NULL-stream work reads.
+//   plan tables  launches read them on the CALLER's streams, which the NULL stream does not order: ONE wait for the plan's device, then
+//                the blocks go back - pb_drain_and_drop for a group or a launch table that is replaced, pb_plan_destroy for all of them.
 namespace {
 struct PbTmpCache {
     struct Block { int device; size_t bytes; void* ptr; };
@@ -223,6 +166,39 @@ static void pb_tmp_free(void* ptr) {
     }
     (void)hipFree(ptr);
 }
+// The owner of one block of the cache: move-only, gives the block back when it dies or is reset().  Move assignment swaps - the block
+// held before leaves with the source (`x = PbBlock<T>()` releases at once).  PbBlockAny is the untyped part (the blob code walks a
+// plan's tables as bytes); PbBlock<T> converts to the T* the kernels take.
+class PbBlockAny {
+public:
+    PbBlockAny() = default;
+    PbBlockAny(const PbBlockAny&) = delete;
+    PbBlockAny& operator=(const PbBlockAny&) = delete;
+    PbBlockAny(PbBlockAny&& o) noexcept { swap(o); }
+    PbBlockAny& operator=(PbBlockAny&& o) noexcept { swap(o); return *this; }
+    ~PbBlockAny() { pb_tmp_free(p_); }
+    void reset() { PbBlockAny().swap(*this); }
+    void swap(PbBlockAny& o) noexcept { std::swap(p_, o.p_); }
+    bool holds() const { return p_ != nullptr; }
+    void* bytes() const { return p_; }
+    hipError_t alloc_bytes(size_t n) {
+        if (p_) return hipErrorInvalidValue;  // (a bug of the caller: reported, and the block it holds is not leaked)
+        const hipError_t e = pb_tmp_alloc(&p_, n);
+        if (e != hipSuccess) p_ = nullptr;
+        return e;
+    }
+
+protected:
+    void* p_ = nullptr;
+};
+template <class T>
+class PbBlock : public PbBlockAny {
+public:
+    hipError_t alloc(size_t count) { return alloc_bytes(count * sizeof(T)); }
+    T* get() const { return static_cast<T*>(p_); }
+    operator T*() const { return get(); }
+};
+
 // Waits for `device` (< 0: the current one): a plan's launches may still be reading its tables on the caller's streams when a block goes
 // back to the cache - what the hipFree of rounds 1-5 did by itself, once per table.
 static void pb_wait_device(int device) {
@@ -235,14 +211,7 @@ static void pb_wait_device(int device) {
     (void)hipDeviceSynchronize();
     (void)hipSetDevice(cur);
 }
-// one table of a plan back to the cache (nullptr: nothing, and no wait)
-static void pb_table_release(int device, void* ptr) {
-    if (!ptr) return;
-    pb_wait_device(device);
-    pb_tmp_free(ptr);
-}
 
-static inline unsigned pb_blocks(unsigned long long items);
 // The separable tables' taps against the faithful chain, every pixel, once per plan: enqueued by the first launch that wants
 // pb_sep_double_kernel, its verdict read - without waiting - by the launches after it.  The verdict lands in a word of a page of pinned,
 // device-mapped host memory the process allocates once (the check kernel counts mismatches straight into it).
@@ -254,9 +223,119 @@ struct PbSepPage {
     std::vector<int> idle;
 } g_sep;
 }  // namespace
+// a plan's word of that page and the event recorded behind its check (pb_sep_setup hands them out; an empty one touches neither HIP
+// nor the page); move-only, moves by swapping like PbBlock
+struct PbSepSlot {
+    int slot = -1;
+    hipEvent_t event = nullptr;
+    mutable int checked = 0;  // 0 not started, 2 in flight, 1 passed, -1 failed
+    PbSepSlot() = default;
+    PbSepSlot(PbSepSlot&& o) noexcept { swap(o); }
+    PbSepSlot& operator=(PbSepSlot&& o) noexcept { swap(o); return *this; }
+    void swap(PbSepSlot& o) noexcept { std::swap(slot, o.slot); std::swap(event, o.event); std::swap(checked, o.checked); }
+    ~PbSepSlot() {
+        if (slot < 0 && !event) return;
+        std::lock_guard<std::mutex> g(g_sep.lock);
+        if (event) {
+            (void)hipEventSynchronize(event);  // (a check still in flight writes its word: the slot must not be handed on before)
+            (void)hipEventDestroy(event);
+        }
+        if (slot >= 0) g_sep.idle.push_back(slot);
+    }
+};
+
+// ---- a plan's device state, grouped by what builds it: each group owns its blocks and the counters that describe them, so
+// "drop this state" is one assignment of a fresh group (pb_drain_and_drop where launches may be reading it) ---------------------------
+// a launch-order copy of the tile tables and its size: set together, dropped together (a non-null table comes with groups >= 8)
+struct PbLaunchTable {
+    PbBlock<PbTileEntry> entries;
+    unsigned groups = 0;  // virtual workgroups (of four waves) per frame, a multiple of 8
+    bool holds() const { return entries.holds(); }
+};
+// CERTIFIED TABLES: built by pb_plan_prepare_on_device, completed by the first pb_classify_under_budget (saved_l / saved_r), written to
+// blobs (pb_plan_sections) and restored from them
+struct PbCertified {
+    int fast_ready = 0;  // models + fix list built and certified on the plan's device
+    PbBlock<PbTileEntry> table;
+    PbBlock<int32_t> fail_tiles, fix_px;
+    PbBlock<int32_t> idx_tab;  // exact source indices of the pixels of failed tiles (4 KiB per tile) ...
+    PbBlock<int32_t> fix_idx;  // ... and of the fix list's pixels: looked up per frame instead of recomputed
+    unsigned n_tiles = 0, n_fail_tiles = 0, n_fix_px = 0, n_lean_tiles = 0, n_black_tiles = 0, n_direct_tiles = 0;
+    long long diff_pixels = -1;  // pixels (outside failed tiles) where model and faithful index differed
+    // separable path (double source, unrotated pano destination): row / column tables.  sep_ready: the tables exist (their row weights
+    // are exact by construction and serve the tile kernels); sep.checked: the exhaustive check of their TAPS against the faithful ones.
+    // The check (one float64 chain per pixel: 0.27 ms of c5's 1.3 ms preparation) is only needed by pb_sep_double_kernel, the fallback
+    // for frames the windowed two-eye kernel cannot take; the first launch that wants the fallback ENQUEUES it (pb_sep_usable: no
+    // allocation, no synchronisation - the launch functions' contract) and takes the float64 kernel, later launches take the fallback
+    // once the check has been seen to pass.
+    int sep_ready = 0;
+    PbSepSlot sep;
+    PbBlock<PbSepRow> sep_rows;
+    PbBlock<PbSepCol> sep_cols;
+    // double-fisheye source: one certified tile table per eye (pb_kernels_double.hpp); `table` is the left eye's
+    int dbl_ready = 0;
+    PbBlock<PbTileEntry> table_r;
+    PbBlock<PbDoubleFix> dbl_tile_fix, dbl_px_fix;  // faithful taps + factors of failed tiles' pixels / of the fix list's pixels
+    PbBlock<double> lat_tab;  // faithful latitudes of the pixels of merge-band tiles (PB_TILE_W_LAT), 8 KiB per tile
+    unsigned n_row_weight_tiles = 0, n_lat_tiles = 0;
+    // the tile flags as classified and certified with the largest window budget: pb_apply_budget derives the flags
+    // in use from them, so the budget can be changed at any time without touching a pixel
+    PbBlock<int32_t> saved_l, saved_r;
+    bool holds() const {
+        return table.holds() || fail_tiles.holds() || fix_px.holds() || idx_tab.holds() || fix_idx.holds() || sep_rows.holds() || sep_cols.holds() ||
+               table_r.holds() || dbl_tile_fix.holds() || dbl_px_fix.holds() || lat_tab.holds() || saved_l.holds() || saved_r.holds();
+    }
+};
+// NEAREST LAUNCH STATE: rebuilt by pb_apply_budget with every budget change; derived, never serialized
+struct PbNearestLaunch {
+    PbLaunchTable lt;         // the hot kernel's launch-order copy of `table`
+    PbBlock<PbParams> P_dev;  // device copy of P as the hot launches see it
+    bool holds() const { return lt.holds() || P_dev.holds(); }
+};
+// BILINEAR-MODE STATE (pb_kernels_bilinear.hpp): built by pb_build_bilinear_list + pb_build_bilinear_launch from the certified tables;
+// derived, never serialized, untouched by pb_plan_set_window_budget
+struct PbBilinearState {
+    PbBlock<int32_t> tiles;  // tiles the bilinear tile kernels leave to the float64 pass: PB_TILE_COARSE models; double-fisheye plans also tiles an eye sees but that are not plain for it
+    unsigned n_tiles = 0;
+    // the mode's exact coordinate tables: 8 KiB per slot (PbTileEntry::bil_off), and the fix list's coordinates (two per pixel for a
+    // double-fisheye source); empty = the tables would not fit, those tiles take the float64 pass
+    PbBlock<PbBilCoord> xy, fix_xy;
+    unsigned n_slots = 0;
+    // ... and its own launch-order table, classified under ITS window budget (PB_BIL_WIN_BUDGET: a direct-gather tile costs the
+    // bilinear mode two 8-byte loads per pixel, the nearest mode one dword - its best budget is larger) and ordered by its own costs
+    PbLaunchTable lt;
+    int budget = 0;
+    PbBlock<PbDblTables> dbl_tables;  // double-fisheye plans: what only some waves of the bilinear launch need, behind one pointer
+    int waves = 4;                    // waves per REAL workgroup of a bilinear launch (4 or 2: chosen with the pool, pb_build_bilinear_launch)
+    unsigned pool_bytes = 0;          // dynamic LDS of a bilinear launch's workgroup: the slots' regions are packed into it (pb_bilinear_pool_kernel)
+    bool holds() const { return tiles.holds() || xy.holds() || fix_xy.holds() || lt.holds() || dbl_tables.holds(); }
+};
+
+struct pb_plan {
+    PbParams P;
+    int mode = PB_MODE_AUTO;  // PB_MODE_AUTO / PB_MODE_FAITHFUL / PB_MODE_FAST
+    int device = -1;          // device that owns the blocks below
+    PbCertified cert;
+    PbNearestLaunch nearest;
+    PbBilinearState bil;
+    int bil_wanted = 1;  // 0: created with PB_PLAN_NO_BILINEAR - the opt-in mode's tables are built when pb_plan_prepare(PB_PLAN_BILINEAR) asks for them
+    int walk = 0;        // launch-order rule: 0 = by policy (pb_build_launch_table), 1 = plain, 2 = rows from the heaviest outwards,
+                         // 3 = super-tiles heaviest first; PB_PLAN_TUNE may pick 1-3 by timing, a serialized plan remembers it
+    double prepare_ms = 0.0, tune_ms = 0.0;  // host wall time of the device preparation / of the optional budget tuning
+    bool holds() const { return cert.holds() || nearest.holds() || bil.holds(); }
+};
+// The plan-table rule in one place: `state` (a group, a launch table, a single block) may be read by launches on the caller's streams, so
+// the plan's device is waited for ONCE - only if there is a block to give back - and then the state is a fresh one, counters included.
+template <class State>
+static void pb_drain_and_drop(const pb_plan* pl, State& state) {
+    if (state.holds()) pb_wait_device(pl->device);
+    state = State();
+}
+
+static inline unsigned pb_blocks(unsigned long long items);
 // plan preparation / deserialisation: a result word and an event for the plan (failure = the fallback stays unverified, i.e. unused)
-static void pb_sep_setup(pb_plan* pl) {
-    if (!pl->sep_ready || pl->sep_slot >= 0) return;
+static void pb_sep_setup(PbCertified& c) {
+    if (!c.sep_ready || c.sep.slot >= 0) return;
     std::lock_guard<std::mutex> g(g_sep.lock);
     if (!g_sep.host) {
         void* h = nullptr;
@@ -273,39 +352,29 @@ static void pb_sep_setup(pb_plan* pl) {
     if (g_sep.idle.empty()) return;
     hipEvent_t ev = nullptr;
     if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return;
-    pl->sep_slot = g_sep.idle.back();
+    c.sep.slot = g_sep.idle.back();
     g_sep.idle.pop_back();
-    pl->sep_event = ev;
-    pl->sep_checked = 0;
-}
-static void pb_sep_release(pb_plan* pl) {
-    std::lock_guard<std::mutex> g(g_sep.lock);
-    if (pl->sep_event) {
-        (void)hipEventSynchronize(pl->sep_event);  // (a check still in flight writes its word: the slot must not be handed on before)
-        (void)hipEventDestroy(pl->sep_event);
-    }
-    if (pl->sep_slot >= 0) g_sep.idle.push_back(pl->sep_slot);
-    pl->sep_event = nullptr;
-    pl->sep_slot = -1;
+    c.sep.event = ev;
+    c.sep.checked = 0;
 }
 // launch path: may pb_sep_double_kernel run?  Never waits, never allocates.
 static bool pb_sep_usable(const pb_plan* plan, hipStream_t st) {
-    if (!plan->sep_ready || plan->sep_slot < 0 || !plan->sep_event || !plan->sep_rows || !plan->sep_cols) return false;
+    if (!plan->cert.sep_ready || plan->cert.sep.slot < 0 || !plan->cert.sep.event || !plan->cert.sep_rows || !plan->cert.sep_cols) return false;
     std::lock_guard<std::mutex> g(g_sep.lock);
-    if (plan->sep_checked == 1) return true;
-    if (plan->sep_checked == -1) return false;
-    if (plan->sep_checked == 2) {
-        if (hipEventQuery(plan->sep_event) != hipSuccess) return false;  // still running (or the query failed): not yet
-        plan->sep_checked = g_sep.host[plan->sep_slot] == 0u ? 1 : -1;
-        return plan->sep_checked == 1;
+    if (plan->cert.sep.checked == 1) return true;
+    if (plan->cert.sep.checked == -1) return false;
+    if (plan->cert.sep.checked == 2) {
+        if (hipEventQuery(plan->cert.sep.event) != hipSuccess) return false;  // still running (or the query failed): not yet
+        plan->cert.sep.checked = g_sep.host[plan->cert.sep.slot] == 0u ? 1 : -1;
+        return plan->cert.sep.checked == 1;
     }
     hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;  // (an event recorded inside a capture could not be queried afterwards)
     if (st && hipStreamIsCapturing(st, &capturing) == hipSuccess && capturing != hipStreamCaptureStatusNone) return false;
     const PbParams& P = plan->P;
-    g_sep.host[plan->sep_slot] = 0u;
-    hipLaunchKernelGGL(pb_sep_check_kernel, dim3(pb_blocks((unsigned long long)P.dst.height * P.dst.width)), dim3(PB_BLOCK), 0, st, P, plan->sep_rows,
-                       plan->sep_cols, g_sep.dev + plan->sep_slot);
-    if (hipEventRecord(plan->sep_event, st) == hipSuccess) plan->sep_checked = 2;
+    g_sep.host[plan->cert.sep.slot] = 0u;
+    hipLaunchKernelGGL(pb_sep_check_kernel, dim3(pb_blocks((unsigned long long)P.dst.height * P.dst.width)), dim3(PB_BLOCK), 0, st, P, plan->cert.sep_rows,
+                       plan->cert.sep_cols, g_sep.dev + plan->cert.sep.slot);
+    if (hipEventRecord(plan->cert.sep.event, st) == hipSuccess) plan->cert.sep.checked = 2;
     return false;
 }
 
@@ -543,70 +612,63 @@ static void pb_pick_filter(int filter, F&& f) {  // (the FILTER of the shared sa
 }
 static int pb_build_bilinear_list(pb_plan* pl) {
     const PbParams& P = pl->P;
-    unsigned* cnt = nullptr;
-    pb_table_release(pl->device, pl->bil_tiles);
-    pb_table_release(pl->device, pl->bil_xy);
-    pb_table_release(pl->device, pl->bil_fix_xy);
-    pl->bil_tiles = nullptr;
-    pl->bil_xy = pl->bil_fix_xy = nullptr;
-    pl->n_bil_tiles = pl->n_bil_slots = 0;
+    pb_drain_and_drop(pl, pl->bil);  // (the whole mode's state: pb_build_bilinear_launch follows and builds the rest)
     if (!pb_bilinear_tiles_allowed(P)) return PB_OK;  // (no tables: pb_remap_bilinear_u8 takes the float64 kernels)
-    PB_HIP(pb_tmp_alloc((void**)&cnt, 2 * sizeof(unsigned)));
-    hipError_t e = hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned), 0);
-    if (e == hipSuccess) e = pb_tmp_alloc((void**)&pl->bil_tiles, (size_t)(pl->n_tiles ? pl->n_tiles : 1) * sizeof(int32_t));
     unsigned res[2] = {0u, 0u};
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(pb_bilinear_tile_list_kernel, dim3((pl->n_tiles + 255) / 256), dim3(256), 0, 0, pl->table, pl->table_r, pl->n_tiles, P.src_eye_w,
-                           P.src.width, pl->bil_tiles, cnt);
-        e = hipMemcpy(res, cnt, sizeof(res), hipMemcpyDeviceToHost);
-    } else {
-        (void)hipDeviceSynchronize();
+    hipError_t e;
+    {
+        PbBlock<unsigned> cnt;  // (its scope: back in the cache before the coordinate tables ask for their blocks)
+        PB_HIP(cnt.alloc(2));
+        e = hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned), 0);
+        if (e == hipSuccess) e = pl->bil.tiles.alloc(pl->cert.n_tiles ? pl->cert.n_tiles : 1);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(pb_bilinear_tile_list_kernel, dim3((pl->cert.n_tiles + 255) / 256), dim3(256), 0, 0, pl->cert.table, pl->cert.table_r, pl->cert.n_tiles,
+                               P.src_eye_w, P.src.width, pl->bil.tiles, cnt);
+            e = hipMemcpy(res, cnt, sizeof(res), hipMemcpyDeviceToHost);
+        } else {
+            (void)hipDeviceSynchronize();
+        }
     }
-    pb_tmp_free(cnt);
-    const bool dbl = pl->table_r != nullptr;
+    const bool dbl = pl->cert.table_r.holds();
     // the tables: sources the 1/4096-px fixed point holds, and at most 1 GiB of coordinates (a geometry the models mostly cannot
     // follow keeps the float64 pass)
     const bool tables = e == hipSuccess && P.src.width < PB_BIL_MAX_DIM && P.src.height < PB_BIL_MAX_DIM && (size_t)P.src.width * P.src.height >= 3 &&
                         (size_t)res[1] * PB_TILE * PB_TILE * sizeof(PbBilCoord) <= ((size_t)1 << 30);
     if (tables) {
-        const unsigned np = pl->n_fix_px, stride = dbl ? 2u : 1u;
-        e = pb_tmp_alloc((void**)&pl->bil_xy, (size_t)(res[1] ? res[1] : 1u) * PB_TILE * PB_TILE * sizeof(PbBilCoord));
-        if (e == hipSuccess) e = pb_tmp_alloc((void**)&pl->bil_fix_xy, (size_t)(np ? np : 1u) * stride * sizeof(PbBilCoord));
+        const unsigned np = pl->cert.n_fix_px, stride = dbl ? 2u : 1u;
+        e = pl->bil.xy.alloc((size_t)(res[1] ? res[1] : 1u) * PB_TILE * PB_TILE);
+        if (e == hipSuccess) e = pl->bil.fix_xy.alloc((size_t)(np ? np : 1u) * stride);
         if (e == hipSuccess) {
-            const dim3 grid(4u * pl->n_tiles), block(PB_BLOCK), fgrid((np + PB_BLOCK - 1) / PB_BLOCK);
+            const dim3 grid(4u * pl->cert.n_tiles), block(PB_BLOCK), fgrid((np + PB_BLOCK - 1) / PB_BLOCK);
             if (dbl) {
-                hipLaunchKernelGGL(pb_bilinear_coord_kernel<PB_KIND_EYE_L>, grid, block, 0, 0, P, pl->table, pl->bil_xy);
-                hipLaunchKernelGGL(pb_bilinear_coord_kernel<PB_KIND_EYE_R>, grid, block, 0, 0, P, pl->table_r, pl->bil_xy);
+                hipLaunchKernelGGL(pb_bilinear_coord_kernel<PB_KIND_EYE_L>, grid, block, 0, 0, P, pl->cert.table, pl->bil.xy);
+                hipLaunchKernelGGL(pb_bilinear_coord_kernel<PB_KIND_EYE_R>, grid, block, 0, 0, P, pl->cert.table_r, pl->bil.xy);
                 if (np) {
-                    hipLaunchKernelGGL(pb_bilinear_fix_coord_kernel<PB_KIND_EYE_L>, fgrid, block, 0, 0, P, pl->fix_px, (int)np, pl->bil_fix_xy, 2, 0);
-                    hipLaunchKernelGGL(pb_bilinear_fix_coord_kernel<PB_KIND_EYE_R>, fgrid, block, 0, 0, P, pl->fix_px, (int)np, pl->bil_fix_xy, 2, 1);
+                    hipLaunchKernelGGL(pb_bilinear_fix_coord_kernel<PB_KIND_EYE_L>, fgrid, block, 0, 0, P, pl->cert.fix_px, (int)np, pl->bil.fix_xy, 2, 0);
+                    hipLaunchKernelGGL(pb_bilinear_fix_coord_kernel<PB_KIND_EYE_R>, fgrid, block, 0, 0, P, pl->cert.fix_px, (int)np, pl->bil.fix_xy, 2, 1);
                 }
             } else {
                 pb_pick_kind(P, [&](auto K) {
-                    hipLaunchKernelGGL(pb_bilinear_coord_kernel<K.value>, grid, block, 0, 0, P, pl->table, pl->bil_xy);
-                    if (np) hipLaunchKernelGGL(pb_bilinear_fix_coord_kernel<K.value>, fgrid, block, 0, 0, P, pl->fix_px, (int)np, pl->bil_fix_xy, 1, 0);
+                    hipLaunchKernelGGL(pb_bilinear_coord_kernel<K.value>, grid, block, 0, 0, P, pl->cert.table, pl->bil.xy);
+                    if (np) hipLaunchKernelGGL(pb_bilinear_fix_coord_kernel<K.value>, fgrid, block, 0, 0, P, pl->cert.fix_px, (int)np, pl->bil.fix_xy, 1, 0);
                 });
             }
             // which way each slot is walked (lanes along the direction the source position moves least), slots walked by rows transposed
             // ... and whether its taps need the guards at all (PB_TILE_TAB_PLAIN); an eye's taps stay in its half of the frame
-            hipLaunchKernelGGL(pb_bilinear_orient_kernel, dim3(pl->n_tiles), dim3(256), 0, 0, pl->table, pl->bil_xy, P.src.height, P.src.width, 0,
-                               dbl ? P.src_eye_w : P.src.width, pb_knob("PB_BIL_OFF", 0), pl->saved_l);
+            hipLaunchKernelGGL(pb_bilinear_orient_kernel, dim3(pl->cert.n_tiles), dim3(256), 0, 0, pl->cert.table, pl->bil.xy, P.src.height, P.src.width, 0,
+                               dbl ? P.src_eye_w : P.src.width, pb_knob("PB_BIL_OFF", 0), pl->cert.saved_l);
             if (dbl)
-                hipLaunchKernelGGL(pb_bilinear_orient_kernel, dim3(pl->n_tiles), dim3(256), 0, 0, pl->table_r, pl->bil_xy, P.src.height, P.src.width, P.src_eye_w,
-                                   P.src.width, pb_knob("PB_BIL_OFF", 0), pl->saved_r);
+                hipLaunchKernelGGL(pb_bilinear_orient_kernel, dim3(pl->cert.n_tiles), dim3(256), 0, 0, pl->cert.table_r, pl->bil.xy, P.src.height, P.src.width, P.src_eye_w,
+                                   P.src.width, pb_knob("PB_BIL_OFF", 0), pl->cert.saved_r);
             e = hipGetLastError();  // (not waited for: the launch builder's read-backs follow on the same stream and report a failure)
         }
     }
     if (e != hipSuccess) {
-        pb_table_release(pl->device, pl->bil_tiles);
-        pb_table_release(pl->device, pl->bil_xy);
-        pb_table_release(pl->device, pl->bil_fix_xy);
-        pl->bil_tiles = nullptr;
-        pl->bil_xy = pl->bil_fix_xy = nullptr;
+        pb_drain_and_drop(pl, pl->bil);  // (the kernels above may be running)
         return pb_fail(PB_ERR_HIP, std::string("bilinear tables: ") + hipGetErrorString(e));
     }
-    pl->n_bil_tiles = res[0];
-    pl->n_bil_slots = res[1];
+    pl->bil.n_tiles = res[0];
+    pl->bil.n_slots = res[1];
     return PB_OK;
 }
 
@@ -617,9 +679,10 @@ static int pb_build_bilinear_list(pb_plan* pl) {
 //     pixels / tiles become the plan's fix list (pb_certify_kernel).
 static int pb_plan_prepare_on_device(pb_plan* pl) {
     PbParams& P = pl->P;
-    long long* scratch = nullptr;
+    PbCertified& c = pl->cert;
+    PbBlock<long long> scratch;
     PB_HIP(hipGetDevice(&pl->device));
-    PB_HIP(pb_tmp_alloc((void**)&scratch, 16 * sizeof(long long)));
+    PB_HIP(scratch.alloc(16));
     int rc = PB_OK;
     do {
         if (P.dst.kind != PB_KIND_PANO) {
@@ -627,9 +690,9 @@ static int pb_plan_prepare_on_device(pb_plan* pl) {
             // (a chain of ~10 dependent square roots and arcsines, and the kernel's launch: a single source's tile tables are allocated meanwhile)
             if (P.src.kind != PB_KIND_DOUBLE && pb_fast_possible(P)) {
                 const unsigned nt0 = pb_num_tiles(P);
-                if (pb_tmp_alloc((void**)&pl->table, (size_t)nt0 * sizeof(PbTileEntry)) != hipSuccess ||
-                    pb_tmp_alloc((void**)&pl->fail_tiles, (size_t)nt0 * sizeof(int32_t)) != hipSuccess ||
-                    pb_tmp_alloc((void**)&pl->fix_px, (size_t)nt0 * PB_TILE_FAIL_LIMIT * sizeof(int32_t)) != hipSuccess) { rc = PB_ERR_HIP; break; }
+                if (c.table.alloc(nt0) != hipSuccess ||
+                    c.fail_tiles.alloc(nt0) != hipSuccess ||
+                    c.fix_px.alloc((size_t)nt0 * PB_TILE_FAIL_LIMIT) != hipSuccess) { rc = PB_ERR_HIP; break; }
             }
             long long thr[4];
             if (hipMemcpy(thr, scratch, sizeof(thr), hipMemcpyDeviceToHost) != hipSuccess) { rc = PB_ERR_HIP; break; }
@@ -639,122 +702,119 @@ static int pb_plan_prepare_on_device(pb_plan* pl) {
         P.thresholds_ready = 1;
         if (P.src.kind == PB_KIND_DOUBLE && P.dst.kind == PB_KIND_PANO && P.n_rot == 0) {
             // separable path: the row / column tables (their taps are checked against the faithful ones when first needed: pb_sep_verified)
-            if (pb_tmp_alloc((void**)&pl->sep_rows, (size_t)P.dst.height * sizeof(PbSepRow)) != hipSuccess ||
-                pb_tmp_alloc((void**)&pl->sep_cols, (size_t)P.dst.width * sizeof(PbSepCol)) != hipSuccess) { rc = PB_ERR_HIP; break; }
+            if (c.sep_rows.alloc(P.dst.height) != hipSuccess ||
+                c.sep_cols.alloc(P.dst.width) != hipSuccess) { rc = PB_ERR_HIP; break; }
             hipLaunchKernelGGL(pb_sep_tables_kernel, dim3(pb_blocks((unsigned long long)P.dst.height + P.dst.width)), dim3(PB_BLOCK), 0, 0,
-                               P, pl->sep_rows, pl->sep_cols);
-            pl->sep_ready = 1;
-            pl->sep_checked = 0;
-            pb_sep_setup(pl);
+                               P, c.sep_rows, c.sep_cols);
+            c.sep_ready = 1;
+            c.sep.checked = 0;
+            pb_sep_setup(pl->cert);
         }
         if (P.src.kind == PB_KIND_DOUBLE) {
             // two certified tile tables (one per eye) + the weight class of every tile
             if (!pb_fast_possible_dims(P)) break;
             const unsigned ntiles = pb_num_tiles(P);
             const unsigned cap = 2u * ntiles * PB_TILE_FAIL_LIMIT;
-            if (pb_tmp_alloc((void**)&pl->table, (size_t)ntiles * sizeof(PbTileEntry)) != hipSuccess ||
-                pb_tmp_alloc((void**)&pl->table_r, (size_t)ntiles * sizeof(PbTileEntry)) != hipSuccess ||
-                pb_tmp_alloc((void**)&pl->fail_tiles, (size_t)2 * ntiles * sizeof(int32_t)) != hipSuccess ||
-                pb_tmp_alloc((void**)&pl->fix_px, (size_t)cap * sizeof(int32_t)) != hipSuccess) { rc = PB_ERR_HIP; break; }
+            if (c.table.alloc(ntiles) != hipSuccess ||
+                c.table_r.alloc(ntiles) != hipSuccess ||
+                c.fail_tiles.alloc((size_t)2 * ntiles) != hipSuccess ||
+                c.fix_px.alloc(cap) != hipSuccess) { rc = PB_ERR_HIP; break; }
             unsigned* counters = reinterpret_cast<unsigned*>(scratch + 4);
             if (hipMemsetAsync(counters, 0, 12 * sizeof(unsigned), 0) != hipSuccess) { rc = PB_ERR_HIP; break; }
             const dim3 grid(pb_hot_blocks(P)), block(64 * PB_TILE_WAVES);
             // (unrotated panorama destination: the separable path's column table holds the sine / cosine of every column's longitude)
-            const double* col_sc = (P.dst.kind == PB_KIND_PANO && P.n_rot == 0 && pl->sep_cols) ? reinterpret_cast<const double*>(pl->sep_cols) : nullptr;
-            hipLaunchKernelGGL(pb_model_kernel<PB_KIND_EYE_L>, grid, block, 0, 0, P, pl->table);
-            hipLaunchKernelGGL(pb_window_kernel<PB_KIND_EYE_L>, grid, block, 0, 0, P, pl->table);
-            PB_LAUNCH_BY_ROT(P.n_rot, pb_certify_kernel, PB_KIND_EYE_L, grid, block, 0, 0, P, pl->table, pl->fail_tiles, pl->fix_px, cap, counters, col_sc);
-            hipLaunchKernelGGL(pb_model_kernel<PB_KIND_EYE_R>, grid, block, 0, 0, P, pl->table_r);
-            hipLaunchKernelGGL(pb_window_kernel<PB_KIND_EYE_R>, grid, block, 0, 0, P, pl->table_r);
-            PB_LAUNCH_BY_ROT(P.n_rot, pb_certify_kernel, PB_KIND_EYE_R, grid, block, 0, 0, P, pl->table_r, pl->fail_tiles, pl->fix_px, cap, counters, col_sc);
-            hipLaunchKernelGGL(pb_count_flags_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, 0, pl->table, ntiles, counters);
-            hipLaunchKernelGGL(pb_count_flags_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, 0, pl->table_r, ntiles, counters);
+            const double* col_sc = (P.dst.kind == PB_KIND_PANO && P.n_rot == 0 && c.sep_cols) ? reinterpret_cast<const double*>(c.sep_cols.get()) : nullptr;
+            hipLaunchKernelGGL(pb_model_kernel<PB_KIND_EYE_L>, grid, block, 0, 0, P, c.table);
+            hipLaunchKernelGGL(pb_window_kernel<PB_KIND_EYE_L>, grid, block, 0, 0, P, c.table);
+            PB_LAUNCH_BY_ROT(P.n_rot, pb_certify_kernel, PB_KIND_EYE_L, grid, block, 0, 0, P, c.table, c.fail_tiles, c.fix_px, cap, counters, col_sc);
+            hipLaunchKernelGGL(pb_model_kernel<PB_KIND_EYE_R>, grid, block, 0, 0, P, c.table_r);
+            hipLaunchKernelGGL(pb_window_kernel<PB_KIND_EYE_R>, grid, block, 0, 0, P, c.table_r);
+            PB_LAUNCH_BY_ROT(P.n_rot, pb_certify_kernel, PB_KIND_EYE_R, grid, block, 0, 0, P, c.table_r, c.fail_tiles, c.fix_px, cap, counters, col_sc);
+            hipLaunchKernelGGL(pb_count_flags_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, 0, c.table, ntiles, counters);
+            hipLaunchKernelGGL(pb_count_flags_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, 0, c.table_r, ntiles, counters);
             const unsigned lat_capacity = ntiles < 65536u ? ntiles : 65536u;  // <= 512 MiB of latitudes
-            hipLaunchKernelGGL(pb_double_pair_kernel, grid, block, 0, 0, P, pl->table, pl->table_r, pl->sep_ready ? pl->sep_rows : nullptr,
-                               pl->fail_tiles, counters, lat_capacity);
+            hipLaunchKernelGGL(pb_double_pair_kernel, grid, block, 0, 0, P, c.table, c.table_r, c.sep_ready ? c.sep_rows : nullptr,
+                               c.fail_tiles, counters, lat_capacity);
             unsigned res[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
             if (hipMemcpy(res, counters, sizeof(res), hipMemcpyDeviceToHost) != hipSuccess) { rc = PB_ERR_HIP; break; }
-            pl->n_lat_tiles = res[8] < lat_capacity ? res[8] : lat_capacity;
-            if (pl->n_lat_tiles) {
-                if (pb_tmp_alloc((void**)&pl->lat_tab, (size_t)pl->n_lat_tiles * PB_LAT_TILE_DOUBLES * sizeof(double)) != hipSuccess) { rc = PB_ERR_HIP; break; }
-                hipLaunchKernelGGL(pb_double_lat_kernel, grid, block, 0, 0, P, pl->table, pl->lat_tab);
+            c.n_lat_tiles = res[8] < lat_capacity ? res[8] : lat_capacity;
+            if (c.n_lat_tiles) {
+                if (c.lat_tab.alloc((size_t)c.n_lat_tiles * PB_LAT_TILE_DOUBLES) != hipSuccess) { rc = PB_ERR_HIP; break; }
+                hipLaunchKernelGGL(pb_double_lat_kernel, grid, block, 0, 0, P, c.table, c.lat_tab);
                 if (hipGetLastError() != hipSuccess) { rc = PB_ERR_HIP; break; }  // (not waited for: see the fix tables below)
             }
             {   // faithful taps of failed tiles and fix pixels, looked up per frame
                 const unsigned nf = res[1], np = res[0] > cap ? cap : res[0];
                 // a geometry the models mostly cannot follow is not worth gigabytes of stored taps: faithful kernel
                 if ((size_t)nf * PB_TILE * PB_TILE * sizeof(PbDoubleFix) > ((size_t)1 << 30)) break;
-                if (pb_tmp_alloc((void**)&pl->dbl_tile_fix, (size_t)(nf ? nf : 1) * PB_TILE * PB_TILE * sizeof(PbDoubleFix)) != hipSuccess ||
-                    pb_tmp_alloc((void**)&pl->dbl_px_fix, (size_t)(np ? np : 1) * sizeof(PbDoubleFix)) != hipSuccess) { rc = PB_ERR_HIP; break; }
+                if (c.dbl_tile_fix.alloc((size_t)(nf ? nf : 1) * PB_TILE * PB_TILE) != hipSuccess ||
+                    c.dbl_px_fix.alloc((size_t)(np ? np : 1)) != hipSuccess) { rc = PB_ERR_HIP; break; }
                 const unsigned blocks = 4u * nf + (np + PB_BLOCK - 1) / PB_BLOCK;
                 if (blocks) {
-                    hipLaunchKernelGGL(pb_double_tables_kernel, dim3(blocks), dim3(PB_BLOCK), 0, 0, P, pl->table_r, pl->fail_tiles, (int)nf, pl->fix_px,
-                                       (int)np, pl->dbl_tile_fix, pl->dbl_px_fix);
+                    hipLaunchKernelGGL(pb_double_tables_kernel, dim3(blocks), dim3(PB_BLOCK), 0, 0, P, c.table_r, c.fail_tiles, (int)nf, c.fix_px,
+                                       (int)np, c.dbl_tile_fix, c.dbl_px_fix);
                     // (not waited for: the budget pass and the launch-order pass queue up behind it, and their readback reports a failure)
                     if (hipGetLastError() != hipSuccess) { rc = PB_ERR_HIP; break; }
                 }
             }
-            pl->n_tiles = ntiles;
-            pl->n_lean_tiles = res[4];
-            pl->n_black_tiles = res[5];
-            pl->n_direct_tiles = res[6];
-            pl->n_row_weight_tiles = res[7];
-            pl->n_fix_px = res[0] > cap ? cap : res[0];
-            pl->n_fail_tiles = res[1];
-            pl->diff_pixels = res[2];
+            c.n_tiles = ntiles;
+            c.n_lean_tiles = res[4];
+            c.n_black_tiles = res[5];
+            c.n_direct_tiles = res[6];
+            c.n_row_weight_tiles = res[7];
+            c.n_fix_px = res[0] > cap ? cap : res[0];
+            c.n_fail_tiles = res[1];
+            c.diff_pixels = res[2];
             if (pl->bil_wanted && pb_build_bilinear_list(pl) != PB_OK) { rc = PB_ERR_HIP; break; }
-            pl->dbl_ready = 1;
+            c.dbl_ready = 1;
             break;
         }
         PB_STAGE("thresholds");
         if (!pb_fast_possible(P)) break;
         const unsigned ntiles = pb_num_tiles(P);
         const unsigned cap = ntiles * PB_TILE_FAIL_LIMIT;
-        if (!pl->table &&  // (not allocated beside the threshold kernel above)
-            (pb_tmp_alloc((void**)&pl->table, (size_t)ntiles * sizeof(PbTileEntry)) != hipSuccess ||
-             pb_tmp_alloc((void**)&pl->fail_tiles, (size_t)ntiles * sizeof(int32_t)) != hipSuccess ||
-             pb_tmp_alloc((void**)&pl->fix_px, (size_t)cap * sizeof(int32_t)) != hipSuccess)) { rc = PB_ERR_HIP; break; }
+        if (!c.table &&  // (not allocated beside the threshold kernel above)
+            (c.table.alloc(ntiles) != hipSuccess ||
+             c.fail_tiles.alloc(ntiles) != hipSuccess ||
+             c.fix_px.alloc(cap) != hipSuccess)) { rc = PB_ERR_HIP; break; }
         PB_STAGE("malloc3");
         unsigned* counters = reinterpret_cast<unsigned*>(scratch + 4);
         if (hipMemsetAsync(counters, 0, 8 * sizeof(unsigned), 0) != hipSuccess) { rc = PB_ERR_HIP; break; }
         const dim3 grid(pb_hot_blocks(P)), block(64 * PB_TILE_WAVES);
         if (P.src.kind == PB_KIND_PANO) {
-            hipLaunchKernelGGL(pb_model_kernel<PB_KIND_PANO>, grid, block, 0, 0, P, pl->table);
-            hipLaunchKernelGGL(pb_window_kernel<PB_KIND_PANO>, grid, block, 0, 0, P, pl->table);
-            PB_LAUNCH_BY_ROT(P.n_rot, pb_certify_kernel, PB_KIND_PANO, grid, block, 0, 0, P, pl->table, pl->fail_tiles, pl->fix_px, cap, counters);
+            hipLaunchKernelGGL(pb_model_kernel<PB_KIND_PANO>, grid, block, 0, 0, P, c.table);
+            hipLaunchKernelGGL(pb_window_kernel<PB_KIND_PANO>, grid, block, 0, 0, P, c.table);
+            PB_LAUNCH_BY_ROT(P.n_rot, pb_certify_kernel, PB_KIND_PANO, grid, block, 0, 0, P, c.table, c.fail_tiles, c.fix_px, cap, counters);
         } else {
-            double* col_sc = nullptr;  // (unrotated panorama destination: one sine / cosine per column instead of one per pixel)
-            if (P.dst.kind == PB_KIND_PANO && P.n_rot == 0 && pb_tmp_alloc((void**)&col_sc, (size_t)P.dst.width * 2 * sizeof(double)) == hipSuccess)
+            PbBlock<double> col_sc;  // (unrotated panorama destination: one sine / cosine per column instead of one per pixel)
+            if (P.dst.kind == PB_KIND_PANO && P.n_rot == 0 && col_sc.alloc((size_t)P.dst.width * 2) == hipSuccess)
                 hipLaunchKernelGGL(pb_col_sincos_kernel, dim3((P.dst.width + 255) / 256), dim3(256), 0, 0, P, col_sc);
-            hipLaunchKernelGGL(pb_model_kernel<PB_KIND_CAMERA>, grid, block, 0, 0, P, pl->table);
-            hipLaunchKernelGGL(pb_window_kernel<PB_KIND_CAMERA>, grid, block, 0, 0, P, pl->table);
-            PB_LAUNCH_BY_ROT(P.n_rot, pb_certify_kernel, PB_KIND_CAMERA, grid, block, 0, 0, P, pl->table, pl->fail_tiles, pl->fix_px, cap, counters, (const double*)col_sc);
-            if (col_sc) {
-                (void)hipDeviceSynchronize();
-                pb_tmp_free(col_sc);
-            }
+            hipLaunchKernelGGL(pb_model_kernel<PB_KIND_CAMERA>, grid, block, 0, 0, P, c.table);
+            hipLaunchKernelGGL(pb_window_kernel<PB_KIND_CAMERA>, grid, block, 0, 0, P, c.table);
+            PB_LAUNCH_BY_ROT(P.n_rot, pb_certify_kernel, PB_KIND_CAMERA, grid, block, 0, 0, P, c.table, c.fail_tiles, c.fix_px, cap, counters, (const double*)col_sc);
+            if (col_sc) (void)hipDeviceSynchronize();  // (the block goes back at the end of this scope)
         }
         PB_STAGE("enqueue+colsync");
-        hipLaunchKernelGGL(pb_count_flags_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, 0, pl->table, ntiles, counters);
+        hipLaunchKernelGGL(pb_count_flags_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, 0, c.table, ntiles, counters);
         unsigned res[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (hipMemcpy(res, counters, sizeof(res), hipMemcpyDeviceToHost) != hipSuccess) { rc = PB_ERR_HIP; break; }
         PB_STAGE("certify-readback");
-        pl->n_lean_tiles = res[4];
-        pl->n_black_tiles = res[5];
-        pl->n_direct_tiles = res[6];
-        pl->n_fix_px = res[0] > cap ? cap : res[0];
-        pl->n_fail_tiles = res[1];
-        pl->diff_pixels = res[2];
-        pl->n_tiles = ntiles;
+        c.n_lean_tiles = res[4];
+        c.n_black_tiles = res[5];
+        c.n_direct_tiles = res[6];
+        c.n_fix_px = res[0] > cap ? cap : res[0];
+        c.n_fail_tiles = res[1];
+        c.diff_pixels = res[2];
+        c.n_tiles = ntiles;
         {   // exact-index tables for the windowed hot kernel
-            const unsigned nf = pl->n_fail_tiles, np = pl->n_fix_px;
-            if (pb_tmp_alloc((void**)&pl->idx_tab, (size_t)(nf ? nf : 1) * PB_TILE * PB_TILE * sizeof(int32_t)) != hipSuccess ||
-                pb_tmp_alloc((void**)&pl->fix_idx, (size_t)(np ? np : 1) * sizeof(int32_t)) != hipSuccess) { rc = PB_ERR_HIP; break; }
+            const unsigned nf = c.n_fail_tiles, np = c.n_fix_px;
+            if (c.idx_tab.alloc((size_t)(nf ? nf : 1) * PB_TILE * PB_TILE) != hipSuccess ||
+                c.fix_idx.alloc((size_t)(np ? np : 1)) != hipSuccess) { rc = PB_ERR_HIP; break; }
             const unsigned blocks = 4u * nf + (np + PB_BLOCK - 1) / PB_BLOCK;
             if (blocks) {
                 pb_pick_kind(P, [&](auto K) {
-                    hipLaunchKernelGGL(pb_fix_tables_kernel<K.value>, dim3(blocks), dim3(PB_BLOCK), 0, 0, P, pl->table, pl->fail_tiles, (int)nf, pl->fix_px,
-                                       (int)np, pl->idx_tab, pl->fix_idx);
+                    hipLaunchKernelGGL(pb_fix_tables_kernel<K.value>, dim3(blocks), dim3(PB_BLOCK), 0, 0, P, c.table, c.fail_tiles, (int)nf, c.fix_px,
+                                       (int)np, c.idx_tab, c.fix_idx);
                 });
                 // (not waited for: the budget pass and the launch-order pass queue up behind it, and their readback reports a failure)
                 if (hipGetLastError() != hipSuccess) { rc = PB_ERR_HIP; break; }
@@ -762,31 +822,24 @@ static int pb_plan_prepare_on_device(pb_plan* pl) {
         }
         PB_STAGE("fix-tables");
         if (pl->bil_wanted && pb_build_bilinear_list(pl) != PB_OK) { rc = PB_ERR_HIP; break; }
-        pl->fast_ready = 1;
+        c.fast_ready = 1;
     } while (0);
     if (rc != PB_OK) {
         g_err = std::string("plan preparation on device failed: ") + hipGetErrorString(hipGetLastError());
         (void)hipDeviceSynchronize();
-        pb_tmp_free(pl->table); pb_tmp_free(pl->fail_tiles); pb_tmp_free(pl->fix_px); pb_tmp_free(pl->idx_tab); pb_tmp_free(pl->fix_idx);
-        pl->idx_tab = nullptr; pl->fix_idx = nullptr;
-        pb_tmp_free(pl->sep_rows); pb_tmp_free(pl->sep_cols); pb_tmp_free(pl->table_r); pb_tmp_free(pl->lat_tab);
-        pb_tmp_free(pl->dbl_tile_fix); pb_tmp_free(pl->dbl_px_fix); pb_table_release(pl->device, pl->bil_tiles); pb_table_release(pl->device, pl->bil_xy); pb_table_release(pl->device, pl->bil_fix_xy);
-        pl->dbl_tile_fix = nullptr; pl->dbl_px_fix = nullptr; pl->bil_tiles = nullptr; pl->n_bil_tiles = 0;
-        pl->bil_xy = pl->bil_fix_xy = nullptr; pl->n_bil_slots = 0;
-        pb_sep_release(pl);
-        pl->table_r = nullptr; pl->lat_tab = nullptr; pl->sep_ready = 0; pl->dbl_ready = 0;
-        pl->table = nullptr; pl->fail_tiles = nullptr; pl->fix_px = nullptr; pl->sep_rows = nullptr; pl->sep_cols = nullptr;
+        // the failed attempt's state goes as a whole, counters and readiness included: the plan reads as never prepared
+        pl->cert = PbCertified();
+        pl->bil = PbBilinearState();
     }
     PB_STAGE("bil-list");
     // (the scratch block's next user is ordered behind these kernels by the NULL stream; pb_plan_prepare_full's budget pass ends the
     //  preparation with the wait - a failed one waits here, its tables have just been freed)
-    if (rc != PB_OK || !(pl->fast_ready || pl->dbl_ready)) (void)hipDeviceSynchronize();
-    pb_tmp_free(scratch);
+    if (rc != PB_OK || !(c.fast_ready || c.dbl_ready)) (void)hipDeviceSynchronize();
     PB_STAGE("final-sync");
     return rc;
 }
 
-static bool pb_use_fast(const pb_plan* plan) { return plan->fast_ready && plan->mode != PB_MODE_FAITHFUL; }
+static bool pb_use_fast(const pb_plan* plan) { return plan->cert.fast_ready && plan->mode != PB_MODE_FAITHFUL; }
 
 // ---- what a remap call launches ------------------------------------------------------------------------------------
 // The plan's tables live on the device it was prepared on (a deferred plan has none yet).
@@ -822,7 +875,7 @@ static int pb_check_frames(const pb_plan* plan, const void* src, const void* dst
 // their stride are 16-byte aligned (the window kernels' LDS-DMA row segments); n: the supersample factor (1: a plain call).
 // What the plan builders guarantee, and the conditions below rely on: fast_ready is set for single sources only (pb_fast_possible),
 // dbl_ready and sep_ready for double-fisheye sources only, dbl_ready for sources below 32768 px a side only (pb_fast_possible_dims);
-// a non-null ltable / ltable_bil comes with launch_groups / launch_groups_bil >= 8 (pb_build_launch_table sets and clears both).
+// a launch table (nearest.lt / bil.lt) that holds its entries comes with groups >= 8 (PbLaunchTable: pb_build_launch_table moves both in together).
 struct PbRoute {
     enum Kind {
         DOUBLE,              // nearest: pb_hot_double_kernel
@@ -854,25 +907,25 @@ static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned fl
         // (catmull-rom runs on the bilinear mode's tables: no LDS windows, no tile kernel for two eyes)
         const bool bil = interpolation == PB_INTERP_BILINEAR;
         if (P.src.kind == PB_KIND_DOUBLE)
-            return (bil && tiled && pl->dbl_ready && pl->ltable_bil && pl->bil_tiles && pl->bil_dbl_tables)
+            return (bil && tiled && pl->cert.dbl_ready && pl->bil.lt.entries && pl->bil.tiles && pl->bil.dbl_tables)
                        ? PbRoute{PbRoute::BIL_DOUBLE, windows, interpolation}
                        : PbRoute{PbRoute::INTERP_DOUBLE_FLOAT64, false, interpolation};
-        return (pb_use_fast(pl) && pl->ltable_bil && pl->bil_tiles) ? PbRoute{PbRoute::INTERP_TILES, bil && windows, interpolation}
+        return (pb_use_fast(pl) && pl->bil.lt.entries && pl->bil.tiles) ? PbRoute{PbRoute::INTERP_TILES, bil && windows, interpolation}
                                                                     : PbRoute{PbRoute::INTERP_FLOAT64, false, interpolation};
     }
-    if (tiled && pl->dbl_ready && pl->ltable && windows) return {PbRoute::DOUBLE, true};
-    if (tiled && pl->sep_ready) return {PbRoute::SEP, false};
-    if (pb_use_fast(pl) && pl->ltable && pl->P_dev && windows) return {PbRoute::WIN, true};
+    if (tiled && pl->cert.dbl_ready && pl->nearest.lt.entries && windows) return {PbRoute::DOUBLE, true};
+    if (tiled && pl->cert.sep_ready) return {PbRoute::SEP, false};
+    if (pb_use_fast(pl) && pl->nearest.lt.entries && pl->nearest.P_dev && windows) return {PbRoute::WIN, true};
     if (pb_use_fast(pl)) return {PbRoute::DIRECT, false};
     return {PbRoute::FLOAT64, false};
 }
 
 // the double-fisheye kernels' WMODE: 1 the separable path's exact row weights, 2 stored merge-band latitudes, 0 neither
-static const PbSepRow* pb_sep_rows(const pb_plan* pl) { return pl->sep_ready ? pl->sep_rows : nullptr; }
+static const PbSepRow* pb_sep_rows(const pb_plan* pl) { return pl->cert.sep_ready ? pl->cert.sep_rows : nullptr; }
 template <class F>
 static void pb_pick_wmode(const pb_plan* pl, F&& f) {
     if (pb_sep_rows(pl)) f(PbInt<1>());
-    else if (pl->n_lat_tiles) f(PbInt<2>());
+    else if (pl->cert.n_lat_tiles) f(PbInt<2>());
     else f(PbInt<0>());
 }
 // Frames are a grid dimension of the tile launches: a batch goes in launches of at most 0x7FFFFFFF / gpf frames (gpf: workgroups per
@@ -884,7 +937,7 @@ static void pb_each_launch(const uint8_t* src, uint8_t* dst, int n_frames, unsig
         launch(src + (unsigned long long)f0 * ss, dst + (unsigned long long)f0 * ds, n_frames - f0 < per_launch ? n_frames - f0 : per_launch);
 }
 // real workgroups per frame of a bilinear tile launch
-static unsigned pb_bil_groups(const pb_plan* pl) { return pl->launch_groups_bil * (4u / (unsigned)pl->bil_waves); }
+static unsigned pb_bil_groups(const pb_plan* pl) { return pl->bil.lt.groups * (4u / (unsigned)pl->bil.waves); }
 
 // the direct-gather hot kernel + the fix kernel; OUT 0 = frames, OUT 1 = int32 index map
 template <int OUT>
@@ -892,12 +945,12 @@ static void pb_launch_direct(const pb_plan* pl, const uint8_t* src, uint8_t* dst
                              int32_t* idx_out, hipStream_t st) {
     const PbParams& P = pl->P;
     pb_pick_kind(P, [&](auto K) {
-        hipLaunchKernelGGL((pb_hot_kernel<K.value, OUT>), dim3(pb_hot_blocks(P)), dim3(64 * PB_TILE_WAVES), 0, st, P, pl->table, src, dst, n_frames, ss, ds, idx_out);
+        hipLaunchKernelGGL((pb_hot_kernel<K.value, OUT>), dim3(pb_hot_blocks(P)), dim3(64 * PB_TILE_WAVES), 0, st, P, pl->cert.table, src, dst, n_frames, ss, ds, idx_out);
     });
-    const unsigned fix_blocks = 4u * pl->n_fail_tiles + (pl->n_fix_px + PB_BLOCK - 1) / PB_BLOCK;
+    const unsigned fix_blocks = 4u * pl->cert.n_fail_tiles + (pl->cert.n_fix_px + PB_BLOCK - 1) / PB_BLOCK;
     if (fix_blocks)
-        hipLaunchKernelGGL((pb_fix_kernel<OUT>), dim3(fix_blocks), dim3(PB_BLOCK), 0, st, P, pl->fail_tiles, (int)pl->n_fail_tiles, pl->fix_px,
-                           (int)pl->n_fix_px, pl->idx_tab, pl->fix_idx, src, dst, n_frames, ss, ds, idx_out);
+        hipLaunchKernelGGL((pb_fix_kernel<OUT>), dim3(fix_blocks), dim3(PB_BLOCK), 0, st, P, pl->cert.fail_tiles, (int)pl->cert.n_fail_tiles, pl->cert.fix_px,
+                           (int)pl->cert.n_fix_px, pl->cert.idx_tab, pl->cert.fix_idx, src, dst, n_frames, ss, ds, idx_out);
 }
 
 // Launches a nearest or bilinear route (n = 1) for n_frames frames at strides ss / ds (pb_check_frames has filled them in).
@@ -910,12 +963,12 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
             // failed tiles and fix pixels go through the plan's stored faithful taps
             static const int fpw_env = pb_knob("PB_DOUBLE_FPW", 0);
             const int fpw = fpw_env > 0 ? fpw_env : PB_DOUBLE_FRAMES_PER_WAVE;
-            const unsigned gpf = pl->launch_groups;  // workgroups per frame of the plan's launch-order table
+            const unsigned gpf = pl->nearest.lt.groups;  // workgroups per frame of the plan's launch-order table
             const dim3 grid(gpf * (unsigned)((n_frames + fpw - 1) / fpw));  // (h*w < 2^29 and n_frames an int: far below the grid limit for any batch that fits memory)
             pb_pick_wmode(pl, [&](auto W) {
                 pb_pick<1, 0>(n_frames == 1 || fpw == 1, [&](auto ONE) {
-                    hipLaunchKernelGGL((pb_hot_double_kernel<W.value, ONE.value != 0>), grid, dim3(64 * PB_TILE_WAVES), pb_window_lds_bytes(P, 8), st, P, pl->table,
-                                       pl->table_r, pl->ltable, pb_sep_rows(pl), pl->lat_tab, pl->fix_px, pl->dbl_px_fix, pl->dbl_tile_fix, src, dst, n_frames, ss,
+                    hipLaunchKernelGGL((pb_hot_double_kernel<W.value, ONE.value != 0>), grid, dim3(64 * PB_TILE_WAVES), pb_window_lds_bytes(P, 8), st, P, pl->cert.table,
+                                       pl->cert.table_r, pl->nearest.lt.entries, pb_sep_rows(pl), pl->cert.lat_tab, pl->cert.fix_px, pl->cert.dbl_px_fix, pl->cert.dbl_tile_fix, src, dst, n_frames, ss,
                                        ds, gpf, fpw, PbNoFrameTab{0});
                 });
             });
@@ -923,7 +976,7 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
         }
         case PbRoute::SEP:
             if (pb_sep_usable(pl, st)) {
-                hipLaunchKernelGGL(pb_sep_double_kernel, dim3(pb_hot_blocks(P)), dim3(64 * PB_TILE_WAVES), 0, st, P, pl->sep_rows, pl->sep_cols, src, dst,
+                hipLaunchKernelGGL(pb_sep_double_kernel, dim3(pb_hot_blocks(P)), dim3(64 * PB_TILE_WAVES), 0, st, P, pl->cert.sep_rows, pl->cert.sep_cols, src, dst,
                                    n_frames, ss, ds);
                 break;
             }
@@ -939,11 +992,11 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
         case PbRoute::WIN: {
             // failed tiles and fix pixels are looked up in the plan's exact-index tables by the hot waves themselves (pb_kernels_tile.hpp);
             // a frame's share of the grid is a multiple of 8 workgroups so that a tile group keeps its XCD residue in every frame
-            const unsigned gpf = pl->launch_groups;
+            const unsigned gpf = pl->nearest.lt.groups;
             pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
                 pb_pick_kind(P, [&](auto K) {
                     hipLaunchKernelGGL((pb_hot_win_kernel<K.value>), dim3(gpf * (unsigned)nf), dim3(64 * PB_TILE_WAVES), pb_window_lds_bytes(P), st,
-                                       (const PbParams*)pl->P_dev, pb_hot_of_host(P), pl->ltable, sf, df, gpf, ss, ds, pl->idx_tab, pl->fix_px, pl->fix_idx,
+                                       (const PbParams*)pl->nearest.P_dev, pb_hot_of_host(P), pl->nearest.lt.entries, sf, df, gpf, ss, ds, pl->cert.idx_tab, pl->cert.fix_px, pl->cert.fix_idx,
                                        (unsigned)nf, PbNoFrameTab{0});
                 });
             });
@@ -956,22 +1009,22 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
             // the per-eye tile models of the nearest mode's plan + the exact coordinate tables: one wave per tile
             const unsigned gpf = pb_bil_groups(pl);
             PbHot Hb = pb_hot_of_host(P);  // (the bilinear mode's window budget travels in it)
-            Hb.win_budget = pl->bil_budget;
+            Hb.win_budget = pl->bil.budget;
             pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
                 pb_pick_wmode(pl, [&](auto W) {
-                    pb_pick<2, 4>(pl->bil_waves == 2, [&](auto WAVES) {
-                        hipLaunchKernelGGL((pb_bilinear_double_hot_kernel<W.value, WAVES.value>), dim3(gpf * (unsigned)nf), dim3(64 * pl->bil_waves),
-                                           (size_t)pl->bil_pool_bytes, st, Hb, P.src_eye_w, pl->ltable_bil, pl->bil_dbl_tables, sf, df, gpf, ss, ds,
-                                           (int)r.windows, pl->bil_xy);
+                    pb_pick<2, 4>(pl->bil.waves == 2, [&](auto WAVES) {
+                        hipLaunchKernelGGL((pb_bilinear_double_hot_kernel<W.value, WAVES.value>), dim3(gpf * (unsigned)nf), dim3(64 * pl->bil.waves),
+                                           (size_t)pl->bil.pool_bytes, st, Hb, P.src_eye_w, pl->bil.lt.entries, pl->bil.dbl_tables, sf, df, gpf, ss, ds,
+                                           (int)r.windows, pl->bil.xy);
                     });
                 });
             });
-            if (!pl->bil_xy) {  // no coordinate tables (they would not fit): the failed / listed tiles and the fix pixels from the float64 chain
-                const unsigned n_tiles64 = pl->n_fail_tiles + pl->n_bil_tiles;
-                const unsigned fix_blocks = 4u * n_tiles64 + (pl->n_fix_px + PB_BLOCK - 1) / PB_BLOCK;
+            if (!pl->bil.xy) {  // no coordinate tables (they would not fit): the failed / listed tiles and the fix pixels from the float64 chain
+                const unsigned n_tiles64 = pl->cert.n_fail_tiles + pl->bil.n_tiles;
+                const unsigned fix_blocks = 4u * n_tiles64 + (pl->cert.n_fix_px + PB_BLOCK - 1) / PB_BLOCK;
                 if (fix_blocks)
-                    hipLaunchKernelGGL(pb_bilinear_double_fix_kernel, dim3(fix_blocks), dim3(PB_BLOCK), 0, st, P, pl->fail_tiles, (int)pl->n_fail_tiles,
-                                       pl->bil_tiles, (int)n_tiles64, pl->fix_px, (int)pl->n_fix_px, src, dst, n_frames, ss, ds);
+                    hipLaunchKernelGGL(pb_bilinear_double_fix_kernel, dim3(fix_blocks), dim3(PB_BLOCK), 0, st, P, pl->cert.fail_tiles, (int)pl->cert.n_fail_tiles,
+                                       pl->bil.tiles, (int)n_tiles64, pl->cert.fix_px, (int)pl->cert.n_fix_px, src, dst, n_frames, ss, ds);
             }
             break;
         }
@@ -983,30 +1036,30 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
         case PbRoute::INTERP_TILES:
             // launched like the nearest hot kernel: the bilinear mode's launch-order table, frames of a batch as a grid dimension
             pb_pick_kind(P, [&](auto K) {
-                if (r.filter == PB_INTERP_CATMULL_ROM) {  // the table read with four waves per workgroup: launch_groups_bil workgroups per frame
-                    const unsigned gpf = pl->launch_groups_bil;
+                if (r.filter == PB_INTERP_CATMULL_ROM) {  // the table read with four waves per workgroup: bil.lt.groups workgroups per frame
+                    const unsigned gpf = pl->bil.lt.groups;
                     pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
                         hipLaunchKernelGGL((pb_catmull_rom_hot_kernel<K.value>), dim3(gpf * (unsigned)nf), dim3(64 * PB_CR_WAVES), 0, st, pb_hot_of_host(P),
-                                           pl->ltable_bil, sf, df, gpf, ss, ds, pl->bil_xy, pl->fix_px, pl->bil_fix_xy);
+                                           pl->bil.lt.entries, sf, df, gpf, ss, ds, pl->bil.xy, pl->cert.fix_px, pl->bil.fix_xy);
                     });
                 } else {
                     const unsigned gpf = pb_bil_groups(pl);
                     PbParams Pb = P;
-                    Pb.win_budget = pl->bil_budget;
+                    Pb.win_budget = pl->bil.budget;
                     pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
-                        pb_pick<2, 4>(pl->bil_waves == 2, [&](auto WAVES) {
-                            hipLaunchKernelGGL((pb_bilinear_hot_kernel<K.value, WAVES.value>), dim3(gpf * (unsigned)nf), dim3(64 * pl->bil_waves),
-                                               (size_t)pl->bil_pool_bytes, st, pb_hot_of_host(Pb), pl->ltable_bil, sf, df, gpf, ss, ds, (int)r.windows,
-                                               pl->bil_xy, pl->fix_px, pl->bil_fix_xy);
+                        pb_pick<2, 4>(pl->bil.waves == 2, [&](auto WAVES) {
+                            hipLaunchKernelGGL((pb_bilinear_hot_kernel<K.value, WAVES.value>), dim3(gpf * (unsigned)nf), dim3(64 * pl->bil.waves),
+                                               (size_t)pl->bil.pool_bytes, st, pb_hot_of_host(Pb), pl->bil.lt.entries, sf, df, gpf, ss, ds, (int)r.windows,
+                                               pl->bil.xy, pl->cert.fix_px, pl->bil.fix_xy);
                         });
                     });
                 }
-                const unsigned n64 = pl->n_fail_tiles + pl->n_bil_tiles;  // failed + listed tiles
-                if (!pl->bil_xy && (n64 || pl->n_fix_px))  // no coordinate tables (they would not fit): the float64 chain
+                const unsigned n64 = pl->cert.n_fail_tiles + pl->bil.n_tiles;  // failed + listed tiles
+                if (!pl->bil.xy && (n64 || pl->cert.n_fix_px))  // no coordinate tables (they would not fit): the float64 chain
                     pb_pick_filter(r.filter, [&](auto F) {
-                        hipLaunchKernelGGL((pb_interp_fix_kernel<decltype(F), K.value>), dim3(4u * n64 + (pl->n_fix_px + PB_BLOCK - 1) / PB_BLOCK),
-                                           dim3(PB_BLOCK), 0, st, P, pl->fail_tiles, 0, src, dst, n_frames, ss, ds, (int)n64, pl->fix_px, (int)pl->n_fix_px,
-                                           pl->bil_tiles, (int)pl->n_fail_tiles);
+                        hipLaunchKernelGGL((pb_interp_fix_kernel<decltype(F), K.value>), dim3(4u * n64 + (pl->cert.n_fix_px + PB_BLOCK - 1) / PB_BLOCK),
+                                           dim3(PB_BLOCK), 0, st, P, pl->cert.fail_tiles, 0, src, dst, n_frames, ss, ds, (int)n64, pl->cert.fix_px, (int)pl->cert.n_fix_px,
+                                           pl->bil.tiles, (int)pl->cert.n_fail_tiles);
                     });
             });
             break;
@@ -1056,9 +1109,13 @@ static int pb_clamp_budget(int budget) {
 // words go - fetched with the cost pass's readback when there is one, by themselves otherwise.
 static int pb_build_launch_table(pb_plan* pl, const bool bil = false, const unsigned* class_dev = nullptr, unsigned* class_out = nullptr) {
     PbParams& P = pl->P;
-    PbTileEntry*& out_table = bil ? pl->ltable_bil : pl->ltable;
-    unsigned& out_groups = bil ? pl->launch_groups_bil : pl->launch_groups;
-    if (!pl->fast_ready && !pl->dbl_ready) return PB_OK;  // (a double-fisheye plan: the left eye's table + PB_TILE_SOLO entries)
+    PbLaunchTable& out = bil ? pl->bil.lt : pl->nearest.lt;
+    // every failure exit: the plan's old table goes (it may be classified under another budget), the error is reported
+    const auto fail = [&](const std::string& msg) {
+        pb_drain_and_drop(pl, out);
+        return pb_fail(PB_ERR_HIP, msg);
+    };
+    if (!pl->cert.fast_ready && !pl->cert.dbl_ready) return PB_OK;  // (a double-fisheye plan: the left eye's table + PB_TILE_SOLO entries)
     const unsigned tiles_x = (P.dst.width + PB_TILE - 1) / PB_TILE, tiles_y = (P.dst.height + PB_TILE - 1) / PB_TILE;
     const unsigned gx = (tiles_x + 1) / 2, gy = (tiles_y + 1) / 2;
     static const unsigned U = [] { const int v = pb_knob("PB_UNIT", 4); return (v == 2 || v == 8 || v == 16) ? (unsigned)v : 4u; }();  // workgroups per unit side
@@ -1089,16 +1146,11 @@ static int pb_build_launch_table(pb_plan* pl, const bool bil = false, const unsi
         const int walk = (order_mode >= 1 && order_mode <= 3) ? order_mode : pl->walk;  // (PB_ORDER=1 / 2 / 3, diagnostic build: force the plain walk / rows outwards / heaviest first)
         if (walk != 1 && sgy >= 4 && (ns >= 128u || walk != 0)) {  // (fewer than 16 super-tiles per XCD: too coarse to reorder - a 3072x2048 output measured 3-4 % slower)
             std::vector<unsigned> fixed(ns + 4u, 0u);
-            unsigned* cost_dev = nullptr;
-            if (pb_tmp_alloc((void**)&cost_dev, (ns + 4u) * sizeof(unsigned)) != hipSuccess) {
-                pb_table_release(pl->device, out_table);  // (the old table may be classified under another budget)
-                out_table = nullptr;
-                out_groups = 0;
-                return pb_fail(PB_ERR_HIP, "launch table: out of device memory");
-            }
+            PbBlock<unsigned> cost_dev;
+            if (cost_dev.alloc(ns + 4u) != hipSuccess) return fail("launch table: out of device memory");
             (void)hipMemsetAsync(cost_dev, 0, ns * sizeof(unsigned), 0);
-            hipLaunchKernelGGL(pb_unit_cost_kernel, dim3((pl->n_tiles + 255) / 256), dim3(256), 0, 0, pl->table, pl->n_tiles, tiles_x, 2u * U, sgx, cost_dev,
-                               pl->dbl_ready ? pl->table_r : nullptr, 2u * UY, bil ? 1 : 0, class_dev, ns);
+            hipLaunchKernelGGL(pb_unit_cost_kernel, dim3((pl->cert.n_tiles + 255) / 256), dim3(256), 0, 0, pl->cert.table, pl->cert.n_tiles, tiles_x, 2u * U, sgx, cost_dev,
+                               pl->cert.dbl_ready ? pl->cert.table_r : nullptr, 2u * UY, bil ? 1 : 0, class_dev, ns);
             PB_STAGE("lt-host0");
             const hipError_t ce = hipMemcpy(fixed.data(), cost_dev, (ns + (class_dev ? 4u : 0u)) * sizeof(unsigned), hipMemcpyDeviceToHost);
             if (class_dev && class_out && ce == hipSuccess) {
@@ -1107,13 +1159,9 @@ static int pb_build_launch_table(pb_plan* pl, const bool bil = false, const unsi
                 class_dev = nullptr;  // (delivered)
             }
             PB_STAGE("lt-cost-readback");
-            if (ce != hipSuccess) (void)hipDeviceSynchronize();
-            pb_tmp_free(cost_dev);
             if (ce != hipSuccess) {
-                pb_table_release(pl->device, out_table);
-                out_table = nullptr;
-                out_groups = 0;
-                return pb_fail(PB_ERR_HIP, std::string("launch table: ") + hipGetErrorString(ce));
+                (void)hipDeviceSynchronize();
+                return fail(std::string("launch table: ") + hipGetErrorString(ce));
             }
             std::vector<float> row_cost(sgy, 0.f);
             unit_cost.assign(ns, 0.f);
@@ -1125,7 +1173,7 @@ static int pb_build_launch_table(pb_plan* pl, const bool bil = false, const unsi
             const float umax = *std::max_element(unit_cost.begin(), unit_cost.end());
             float usum = 0.f;
             for (float c : unit_cost) usum += c;
-            if (walk == 0 && pl->dbl_ready) {
+            if (walk == 0 && pl->cert.dbl_ready) {
                 // double-fisheye sources keep the plain walk (two fronts measured 1.5 % slower on c5); their problem is another one, below
             } else if (walk == 2 || (walk == 0 && rmax > 1.45f * rmin)) {
                 const unsigned top = (unsigned)(std::max_element(row_cost.begin(), row_cost.end()) - row_cost.begin());
@@ -1152,7 +1200,7 @@ static int pb_build_launch_table(pb_plan* pl, const bool bil = false, const unsi
             for (unsigned S = 0; S < ns; ++S) tot[(S % sgx) & 7u] += unit_cost[S];
             imbalance = *std::max_element(tot, tot + 8) / std::max(1e-6f, *std::min_element(tot, tot + 8));
         }
-        if (walk == 0 && row_walk && sgx % 8 == 0 && !unit_cost.empty() && (pl->dbl_ready || imbalance > 1.15f)) {
+        if (walk == 0 && row_walk && sgx % 8 == 0 && !unit_cost.empty() && (pl->cert.dbl_ready || imbalance > 1.15f)) {
             // A stitch's expensive tiles - the seams where both eyes contribute, the eyes' rims - stand in COLUMNS of the
             // output, and "XCD = column mod 8" hands whole seams to the same XCDs row after row: the chip waits for them
             // (c5 76.5 us; super-tiles dealt at random 66.6).  Rows are still walked together and a column keeps its XCD from
@@ -1198,14 +1246,12 @@ static int pb_build_launch_table(pb_plan* pl, const bool bil = false, const unsi
             for (unsigned p = 0; p < ns; ++p) unit_of[(size_t)(p & 7u) * units_per_xcd + filled[p & 7u]++] = (int)seq[p];  // XCD = position in the walk, mod 8
         }
     }
-    // the new table is built aside and replaces the plan's only when it is complete: a failure leaves the plan WITHOUT a
-    // launch table (ltable == nullptr, launch_groups == 0 - its launches then take the direct-gather kernels), never with a
-    // half-written one or one classified under another budget
-    pb_table_release(pl->device, out_table);
-    out_table = nullptr;
-    out_groups = 0;
-    PbTileEntry* fresh = nullptr;
-    int* unit_dev = nullptr;
+    // the new table is built aside (`fresh`) and moved into the plan only when it is complete: a failure leaves the plan WITHOUT a
+    // launch table (no entries, groups == 0 - its launches then take the direct-gather kernels), never with a half-written one or
+    // one classified under another budget
+    pb_drain_and_drop(pl, out);
+    PbLaunchTable fresh;
+    PbBlock<int> unit_dev;
     hipError_t e = hipSuccess;
     if (class_dev && class_out) {  // (no cost pass has brought the budget pass's class counters along)
         unsigned r4[4] = {0, 0, 0, 0};
@@ -1214,7 +1260,7 @@ static int pb_build_launch_table(pb_plan* pl, const bool bil = false, const unsi
         class_out[1] = r4[1];
     }
     if (units && e == hipSuccess) {
-        e = pb_tmp_alloc((void**)&unit_dev, unit_of.size() * sizeof(int));
+        e = unit_dev.alloc(unit_of.size());
         PB_STAGE("lt-host-order");
         if (e == hipSuccess) {
             if (unit_of.size() <= 1024) {  // (up to four launches that nothing waits for)
@@ -1231,47 +1277,45 @@ static int pb_build_launch_table(pb_plan* pl, const bool bil = false, const unsi
         }
         PB_STAGE("lt-unit-upload");
     }
-    if (bil && pl->dbl_ready) {
+    if (bil && pl->cert.dbl_ready) {
         // the PAIR layout (pb_kernels_tile.hpp): a two-eye tile takes two slots of a pair workgroup, so the XCDs' lists grow by what
         // their tile groups need - counted, scanned per XCD and written in place of the plain layout's one workgroup per group
-        unsigned* scan = nullptr;  // n_wgs[n_groups], start[n_groups], totals[8]
+        PbBlock<unsigned> scan;  // n_wgs[n_groups], start[n_groups], totals[8]
         unsigned totals[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (e == hipSuccess) e = pb_tmp_alloc((void**)&scan, (2 * (size_t)n_groups + 8) * sizeof(unsigned));
+        if (e == hipSuccess) e = scan.alloc(2 * (size_t)n_groups + 8);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(pb_pair_count_kernel, dim3((n_groups + 255) / 256), dim3(256), 0, 0, P, pl->table, pl->table_r, unit_dev, units_per_xcd, n_groups, (int)U, (int)UY, scan);
+            hipLaunchKernelGGL(pb_pair_count_kernel, dim3((n_groups + 255) / 256), dim3(256), 0, 0, P, pl->cert.table, pl->cert.table_r, unit_dev, units_per_xcd, n_groups, (int)U, (int)UY, scan);
             hipLaunchKernelGGL(pb_pair_scan_kernel, dim3(1), dim3(512), 0, 0, scan, n_groups, scan + n_groups, scan + 2 * (size_t)n_groups);
             e = hipMemcpy(totals, scan + 2 * (size_t)n_groups, sizeof(totals), hipMemcpyDeviceToHost);
         }
         const unsigned per_xcd = *std::max_element(totals, totals + 8), pair_groups = 8u * per_xcd;
         if (e == hipSuccess && pair_groups == 0) e = hipErrorInvalidValue;  // (a plan without tiles does not get here)
-        if (e == hipSuccess) e = pb_tmp_alloc((void**)&fresh, (size_t)pair_groups * 4u * sizeof(PbTileEntry));
+        if (e == hipSuccess) e = fresh.entries.alloc((size_t)pair_groups * 4u);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(pb_skip_fill_kernel, dim3(pair_groups), dim3(256), 0, 0, fresh, 4u * pair_groups);
-            hipLaunchKernelGGL(pb_pair_table_kernel, dim3(n_groups), dim3(64), 0, 0, P, pl->table, pl->table_r, fresh, unit_dev, units_per_xcd, n_groups, (int)U, (int)UY,
+            hipLaunchKernelGGL(pb_skip_fill_kernel, dim3(pair_groups), dim3(256), 0, 0, fresh.entries, 4u * pair_groups);
+            hipLaunchKernelGGL(pb_pair_table_kernel, dim3(n_groups), dim3(64), 0, 0, P, pl->cert.table, pl->cert.table_r, fresh.entries, unit_dev, units_per_xcd, n_groups, (int)U, (int)UY,
                                scan + n_groups);
             e = hipDeviceSynchronize();
         }
-        pb_tmp_free(scan);
         n_groups = pair_groups;
     } else {
         const unsigned n_slots = 4u * n_groups;
-        if (e == hipSuccess) e = (!bil && pb_test_alloc_fails()) ? hipErrorOutOfMemory : pb_tmp_alloc((void**)&fresh, (size_t)n_slots * sizeof(PbTileEntry));  // (the test hook counts the nearest mode's tables)
+        if (e == hipSuccess) e = (!bil && pb_test_alloc_fails()) ? hipErrorOutOfMemory : fresh.entries.alloc(n_slots);  // (the test hook counts the nearest mode's tables)
         if (e == hipSuccess) {
             PB_STAGE("lt-malloc");
-            hipLaunchKernelGGL(pb_launch_table_kernel, dim3(n_groups), dim3(256), 0, 0, P, pl->table, fresh, unit_dev, units_per_xcd, n_slots, (int)U,
-                               pl->dbl_ready ? pl->table_r : nullptr, (int)UY);
+            hipLaunchKernelGGL(pb_launch_table_kernel, dim3(n_groups), dim3(256), 0, 0, P, pl->cert.table, fresh.entries, unit_dev, units_per_xcd, n_slots, (int)U,
+                               pl->cert.dbl_ready ? pl->cert.table_r : nullptr, (int)UY);
             e = hipDeviceSynchronize();
             PB_STAGE("lt-kernel-sync");
         }
     }
-    pb_tmp_free(unit_dev);
     if (e != hipSuccess) {
-        pb_table_release(pl->device, fresh);
+        pb_drain_and_drop(pl, fresh);  // (its kernels may be running)
         (void)hipGetLastError();
         return pb_fail(PB_ERR_HIP, std::string("launch table: ") + hipGetErrorString(e));
     }
-    out_table = fresh;
-    out_groups = n_groups;
+    fresh.groups = n_groups;
+    out = std::move(fresh);
     return PB_OK;
 }
 
@@ -1279,36 +1323,31 @@ static int pb_build_launch_table(pb_plan* pl, const bool bil = false, const unsi
 // wanted - then the call does not wait for the device).
 // keep_dev: the class counters stay on the device in that block (4 words, zeroed here) for the caller to fetch with something else.
 static int pb_classify_under_budget(pb_plan* pl, int budget, unsigned counts[2], unsigned* keep_dev = nullptr) {
-    const unsigned nt = pl->n_tiles;
+    const unsigned nt = pl->cert.n_tiles;
     const dim3 g((nt + 255) / 256), b(256);
-    if (!pl->saved_l) {
-        PB_HIP(pb_tmp_alloc((void**)&pl->saved_l, (size_t)nt * sizeof(int32_t)));
-        hipLaunchKernelGGL(pb_save_flags_kernel, g, b, 0, 0, pl->table, pl->saved_l, nt);
-        if (pl->dbl_ready) {
-            PB_HIP(pb_tmp_alloc((void**)&pl->saved_r, (size_t)nt * sizeof(int32_t)));
-            hipLaunchKernelGGL(pb_save_flags_kernel, g, b, 0, 0, pl->table_r, pl->saved_r, nt);
+    if (!pl->cert.saved_l) {
+        PB_HIP(pl->cert.saved_l.alloc(nt));
+        hipLaunchKernelGGL(pb_save_flags_kernel, g, b, 0, 0, pl->cert.table, pl->cert.saved_l, nt);
+        if (pl->cert.dbl_ready) {
+            PB_HIP(pl->cert.saved_r.alloc(nt));
+            hipLaunchKernelGGL(pb_save_flags_kernel, g, b, 0, 0, pl->cert.table_r, pl->cert.saved_r, nt);
         }
     }
-    unsigned* counters = keep_dev;
-    if (!counters) PB_HIP(pb_tmp_alloc((void**)&counters, 4 * sizeof(unsigned)));
+    PbBlock<unsigned> own;  // (the class counters, unless the caller keeps them)
+    if (!keep_dev) PB_HIP(own.alloc(4));
+    unsigned* const counters = keep_dev ? keep_dev : own.get();
     (void)hipMemsetAsync(counters, 0, 4 * sizeof(unsigned), 0);
-    if (pl->dbl_ready)
-        hipLaunchKernelGGL(pb_budget_double_kernel, g, b, 0, 0, pl->table, pl->table_r, pl->saved_l, pl->saved_r, nt, budget, counters);
+    if (pl->cert.dbl_ready)
+        hipLaunchKernelGGL(pb_budget_double_kernel, g, b, 0, 0, pl->cert.table, pl->cert.table_r, pl->cert.saved_l, pl->cert.saved_r, nt, budget, counters);
     else
-        hipLaunchKernelGGL(pb_budget_kernel, g, b, 0, 0, pl->table, pl->saved_l, nt, budget, counters);
-    if (keep_dev) {
-        PB_HIP(hipGetLastError());
-        return PB_OK;
-    }
-    if (!counts) {  // (nobody reads the class counts of this pass: no round trip - the block's next user is ordered behind the kernel by the stream)
-        pb_tmp_free(counters);
+        hipLaunchKernelGGL(pb_budget_kernel, g, b, 0, 0, pl->cert.table, pl->cert.saved_l, nt, budget, counters);
+    if (keep_dev || !counts) {  // (the caller fetches the counts, or nobody reads them: no round trip - a block's next user is ordered behind the kernel by the stream)
         PB_HIP(hipGetLastError());
         return PB_OK;
     }
     unsigned res[4] = {0, 0, 0, 0};
     const hipError_t e = hipMemcpy(res, counters, sizeof(res), hipMemcpyDeviceToHost);
     if (e != hipSuccess) (void)hipDeviceSynchronize();
-    pb_tmp_free(counters);
     PB_HIP(e);
     counts[0] = res[0];
     counts[1] = res[1];
@@ -1325,13 +1364,15 @@ static int pb_classify_under_budget(pb_plan* pl, int budget, unsigned counts[2],
 #endif
 //  // measured on MI355X (experiments/r4/budget_bil.sh): c1 28.7 us at 7 KiB, 25.2 at 12; c2 68.9 / 62.0; c5 109.8 / 103.4; c3 58.3 / 58.9
 static int pb_build_bilinear_launch(pb_plan* pl) {
-    if (!(pl->fast_ready || pl->dbl_ready)) return PB_OK;
-    pb_table_release(pl->device, pl->ltable_bil);
-    pl->ltable_bil = nullptr;
-    pl->launch_groups_bil = 0;
+    if (!(pl->cert.fast_ready || pl->cert.dbl_ready)) return PB_OK;
+    const auto fail = [&](const std::string& msg) {  // every failure exit behind the table's construction: no table, the error reported
+        pb_drain_and_drop(pl, pl->bil.lt);
+        return pb_fail(PB_ERR_HIP, msg);
+    };
+    pb_drain_and_drop(pl, pl->bil.lt);
     if (!pb_bilinear_tiles_allowed(pl->P)) return PB_OK;
-    pl->bil_budget = pb_clamp_budget(PB_BIL_WIN_BUDGET);
-    int rc = pb_classify_under_budget(pl, pl->bil_budget, nullptr);
+    pl->bil.budget = pb_clamp_budget(PB_BIL_WIN_BUDGET);
+    int rc = pb_classify_under_budget(pl, pl->bil.budget, nullptr);
     if (rc == PB_OK) rc = pb_build_launch_table(pl, true);
     if (rc != PB_OK) return rc;
     // Workgroup size and LDS pool, chosen together (a pool is accepted when at most 2 % of the tiles lose their window to it), best first:
@@ -1339,35 +1380,35 @@ static int pb_build_bilinear_launch(pb_plan* pl) {
     //   four waves, 39.5 KiB   sixteen waves in four workgroups: regions pooled over four slots fit where two slots do not (c1)
     //   two waves, 22.8 KiB    fourteen waves per CU
     //   two waves, 2 x budget  always fits: twelve waves per CU
-    unsigned* counters = nullptr;
-    const unsigned ng = pl->launch_groups_bil;
+    PbBlock<unsigned> counters;
+    const unsigned ng = pl->bil.lt.groups;
     unsigned res[2] = {0u, 0u};
-    hipError_t e = pb_tmp_alloc((void**)&counters, 8 * sizeof(unsigned));
+    hipError_t e = counters.alloc(8);
     if (e == hipSuccess) e = hipMemsetAsync(counters, 0, 8 * sizeof(unsigned), 0);
     if (e == hipSuccess && !pb_bil_off(1))  // direct-gather slots that can be served as two half windows
     {
-        hipLaunchKernelGGL(pb_bilinear_halves_kernel, dim3(ng), dim3(256), 0, 0, pl->ltable_bil, 4u * ng, pl->bil_budget, pl->P.src.height, pl->P.src.width,
+        hipLaunchKernelGGL(pb_bilinear_halves_kernel, dim3(ng), dim3(256), 0, 0, pl->bil.lt.entries, 4u * ng, pl->bil.budget, pl->P.src.height, pl->P.src.width,
                            pb_bil_off(8) ? 1 : 0, counters);
     }
-    const unsigned budget32 = (unsigned)pl->bil_budget + 32u;
+    const unsigned budget32 = (unsigned)pl->bil.budget + 32u;
     int waves = 2;
     unsigned pool = 2u * budget32;
     if (e == hipSuccess && !pb_bil_off(16)) {
         // (the one-eye slots of a virtual workgroup dealt to its two halves so that their LDS needs balance: largest with smallest)
-        hipLaunchKernelGGL(pb_bilinear_balance_kernel, dim3(ng), dim3(64), 0, 0, pl->ltable_bil, ng);
+        hipLaunchKernelGGL(pb_bilinear_balance_kernel, dim3(ng), dim3(64), 0, 0, pl->bil.lt.entries, ng);
         const struct { int waves; unsigned bytes; } tiers[3] = {{2, PB_BIL_POOL_SMALL / 2u}, {4, PB_BIL_POOL_SMALL}, {2, (163840u / 7u) & ~15u}};
         // the three dry passes back to back, ONE read-back (a round trip is ~25 us; a plan that takes the third tier made three)
         unsigned dry[6] = {0u, 0u, 0u, 0u, 0u, 0u};
         e = hipMemsetAsync(counters, 0, 6 * sizeof(unsigned), 0);
         for (int t = 0; t < 3 && e == hipSuccess; ++t) {
             if (tiers[t].bytes >= (unsigned)tiers[t].waves * budget32) continue;
-            hipLaunchKernelGGL(pb_bilinear_pool_kernel, dim3((ng * (4u / (unsigned)tiers[t].waves) + 127) / 128), dim3(128), 0, 0, pl->ltable_bil, ng, tiers[t].bytes, 1,
+            hipLaunchKernelGGL(pb_bilinear_pool_kernel, dim3((ng * (4u / (unsigned)tiers[t].waves) + 127) / 128), dim3(128), 0, 0, pl->bil.lt.entries, ng, tiers[t].bytes, 1,
                                counters + 2 * t, tiers[t].waves);
         }
         if (e == hipSuccess) e = hipMemcpy(dry, counters, sizeof(dry), hipMemcpyDeviceToHost);
         for (int t = 0; t < 3 && e == hipSuccess; ++t) {
             if (tiers[t].bytes >= (unsigned)tiers[t].waves * budget32) continue;
-            if (dry[2 * t + 1] == 0u && dry[2 * t] * PB_BIL_POOL_RULE <= pl->n_tiles) {
+            if (dry[2 * t + 1] == 0u && dry[2 * t] * PB_BIL_POOL_RULE <= pl->cert.n_tiles) {
                 waves = tiers[t].waves;
                 pool = tiers[t].bytes;
                 break;
@@ -1379,71 +1420,58 @@ static int pb_build_bilinear_launch(pb_plan* pl) {
     }
     if (e == hipSuccess) e = hipMemsetAsync(counters, 0, 2 * sizeof(unsigned), 0);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(pb_bilinear_pool_kernel, dim3((ng * (4u / (unsigned)waves) + 127) / 128), dim3(128), 0, 0, pl->ltable_bil, ng, pool, 0, counters, waves);
+        hipLaunchKernelGGL(pb_bilinear_pool_kernel, dim3((ng * (4u / (unsigned)waves) + 127) / 128), dim3(128), 0, 0, pl->bil.lt.entries, ng, pool, 0, counters, waves);
         e = hipMemcpy(res, counters, sizeof(res), hipMemcpyDeviceToHost);
     }
     if (e != hipSuccess) (void)hipDeviceSynchronize();
-    pb_tmp_free(counters);
-    if (e != hipSuccess || res[1] != 0u) {
-        pb_table_release(pl->device, pl->ltable_bil);
-        pl->ltable_bil = nullptr;
-        pl->launch_groups_bil = 0;
-        return pb_fail(PB_ERR_HIP, e != hipSuccess ? std::string("bilinear LDS pool: ") + hipGetErrorString(e) : std::string("bilinear LDS pool: a workgroup does not fit"));
+    counters.reset();  // (read back; a two-eye plan's table block below is of its size)
+    if (e != hipSuccess || res[1] != 0u) return fail(std::string("bilinear LDS pool: ") + (e != hipSuccess ? hipGetErrorString(e) : "a workgroup does not fit"));
+    if (pl->cert.dbl_ready) {
+        const PbDblTables T = {pl->P.mrg_min, pl->P.mrg_max_safe, pl->P.mrg_max, pl->P.mrg_range, pl->cert.sep_ready ? pl->cert.sep_rows : nullptr, pl->cert.lat_tab, pl->cert.fix_px,
+                               pl->bil.fix_xy, pl->cert.dbl_tile_fix, pl->cert.dbl_px_fix};
+        if ((!pl->bil.dbl_tables && pl->bil.dbl_tables.alloc(1) != hipSuccess) ||
+            hipMemcpy(pl->bil.dbl_tables, &T, sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
+            return fail("bilinear launch: out of device memory");
     }
-    if (pl->dbl_ready) {
-        const PbDblTables T = {pl->P.mrg_min, pl->P.mrg_max_safe, pl->P.mrg_max, pl->P.mrg_range, pl->sep_ready ? pl->sep_rows : nullptr, pl->lat_tab, pl->fix_px,
-                               pl->bil_fix_xy, pl->dbl_tile_fix, pl->dbl_px_fix};
-        if ((!pl->bil_dbl_tables && pb_tmp_alloc((void**)&pl->bil_dbl_tables, sizeof(PbDblTables)) != hipSuccess) ||
-            hipMemcpy(pl->bil_dbl_tables, &T, sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
-            pb_table_release(pl->device, pl->ltable_bil);
-            pl->ltable_bil = nullptr;
-            pl->launch_groups_bil = 0;
-            return pb_fail(PB_ERR_HIP, "bilinear launch: out of device memory");
-        }
-    }
-    pl->bil_pool_bytes = pool;
-    pl->bil_waves = waves;
+    pl->bil.pool_bytes = pool;
+    pl->bil.waves = waves;
     return PB_OK;
 }
 
 // applies `budget` to the certified flags and rebuilds the nearest mode's launch-order table; synchronous on the default stream
 static int pb_apply_budget(pb_plan* pl, int budget) {
     PbParams& P = pl->P;
-    if (!(pl->fast_ready || pl->dbl_ready)) return PB_OK;
+    if (!(pl->cert.fast_ready || pl->cert.dbl_ready)) return PB_OK;
     budget = pb_clamp_budget(budget);
     // the parameter block as the launches will see it goes up BEFORE anything of the plan changes (a failure used to
     // leave the old launch table, classified under the old budget, next to the new budget)
     PbParams Q = P;
     Q.win_budget = budget;
-    if (!pl->P_dev) PB_HIP(pb_tmp_alloc((void**)&pl->P_dev, sizeof(PbParams)));
+    if (!pl->nearest.P_dev) PB_HIP(pl->nearest.P_dev.alloc(1));
     // Nothing here waits for the device by itself (a round trip is 12-25 us of a 0.5 ms plan): the class counters of the budget pass stay
     // on the device and come back with the launch-order pass's costs, the parameter block is stored by a kernel from its own arguments.
-    unsigned counts[2] = {pl->n_lean_tiles, pl->n_direct_tiles};
-    unsigned* class_dev = nullptr;
-    PB_HIP(pb_tmp_alloc((void**)&class_dev, 4 * sizeof(unsigned)));
+    unsigned counts[2] = {pl->cert.n_lean_tiles, pl->cert.n_direct_tiles};
+    PbBlock<unsigned> class_dev;
+    PB_HIP(class_dev.alloc(4));
     PB_STAGE("ab-pdev-malloc");
     int rc = pb_classify_under_budget(pl, budget, nullptr, class_dev);
     PB_STAGE("ab-classify");
     if (rc == PB_OK) {
-        hipLaunchKernelGGL(pb_store_params_kernel, dim3(1), dim3(64), 0, 0, Q, pl->P_dev);
+        hipLaunchKernelGGL(pb_store_params_kernel, dim3(1), dim3(64), 0, 0, Q, pl->nearest.P_dev);
         if (hipGetLastError() != hipSuccess) rc = pb_fail(PB_ERR_HIP, "parameter block upload failed");
     }
     PB_STAGE("ab-pdev-upload");
     if (rc != PB_OK) {
         // the table may be half reclassified: no launch table at all (launches take the direct-gather kernels, which read no budget)
         (void)hipDeviceSynchronize();  // (the counter block goes back idle)
-        pb_tmp_free(pl->ltable);
-        pb_tmp_free(class_dev);
-        pl->ltable = nullptr;
-        pl->launch_groups = 0;
+        pl->nearest.lt = PbLaunchTable();  // (waited for just above)
         return rc;
     }
     P.win_budget = budget;
     rc = pb_build_launch_table(pl, false, class_dev, counts);
-    if (rc != PB_OK) (void)hipDeviceSynchronize();
-    pb_tmp_free(class_dev);  // (pb_build_launch_table has waited for the device)
-    pl->n_lean_tiles = counts[0];
-    pl->n_direct_tiles = counts[1];
+    if (rc != PB_OK) (void)hipDeviceSynchronize();  // (a success: pb_build_launch_table has waited for the device - class_dev may go back)
+    pl->cert.n_lean_tiles = counts[0];
+    pl->cert.n_direct_tiles = counts[1];
     return rc;
 }
 
@@ -1452,11 +1480,20 @@ static int pb_apply_budget(pb_plan* pl, int budget) {
 static int pb_tune_window_budget(pb_plan* pl) {
     PbParams& P = pl->P;
     int best = P.win_budget;
-    if (!(pl->fast_ready || pl->dbl_ready)) return best;
+    if (!(pl->cert.fast_ready || pl->cert.dbl_ready)) return best;
     const size_t sb = 3ull * P.src.height * P.src.width, db = 3ull * P.dst.height * P.dst.width;
     if (sb + db > (1ull << 30)) return best;
-    uint8_t *src = nullptr, *dst = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    struct Scratch {  // frame-sized and once per tuned plan: plain hipMalloc, not the cache's business; released behind the wait below
+        uint8_t *src = nullptr, *dst = nullptr;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Scratch() {
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+            (void)hipFree(src), (void)hipFree(dst);
+        }
+    } scratch;
+    uint8_t *&src = scratch.src, *&dst = scratch.dst;
+    hipEvent_t &e0 = scratch.e0, &e1 = scratch.e1;
     do {
         // scratch frames in rotation, more than the 256 MiB Infinity Cache in total: the launches being timed
         // must stream from HBM like real frames do, not hit a cache-resident copy
@@ -1527,9 +1564,6 @@ static int pb_tune_window_budget(pb_plan* pl) {
     } while (0);
     (void)hipDeviceSynchronize();
     (void)hipGetLastError();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(src); (void)hipFree(dst);
     return best;
 }
 
@@ -1567,10 +1601,10 @@ static double pb_now_ms() {
 // device preparation of a plan on the current device + its window budget (0 = default; PB_WIN_BUDGET overrides
 // the default for experiments); PB_PLAN_TUNE times candidates instead
 static int pb_plan_prepare_full(pb_plan* pl, unsigned flags, int win_budget) {
-    if (pl->fast_ready || pl->dbl_ready || pl->sep_ready || pl->device >= 0) {
+    if (pl->cert.fast_ready || pl->cert.dbl_ready || pl->cert.sep_ready || pl->device >= 0) {
         // already prepared: the budget may change, and the opt-in bilinear mode's tables may be asked for (PB_PLAN_BILINEAR) by a plan
         // that was created without them
-        if ((flags & PB_PLAN_BILINEAR) && (pl->fast_ready || pl->dbl_ready) && !pl->bil_tiles) {
+        if ((flags & PB_PLAN_BILINEAR) && (pl->cert.fast_ready || pl->cert.dbl_ready) && !pl->bil.tiles) {
             pl->bil_wanted = 1;
             int rc = pb_build_bilinear_list(pl);
             if (rc == PB_OK) rc = pb_build_bilinear_launch(pl);
@@ -1592,8 +1626,7 @@ static int pb_plan_prepare_full(pb_plan* pl, unsigned flags, int win_budget) {
     const double t0 = pb_now_ms();
     int rc = pb_plan_prepare_on_device(pl);
     if (rc != PB_OK) {
-        pl->fast_ready = 0;  // (pb_plan_prepare_on_device has released the tables): the plan is unprepared again and may be retried
-        pl->device = -1;
+        pl->device = -1;  // (pb_plan_prepare_on_device has dropped its state): the plan is unprepared again and may be retried
         return rc;
     }
     int budget = win_budget > 0 ? win_budget : PB_DEFAULT_WIN_BUDGET;
@@ -1615,6 +1648,12 @@ static int pb_plan_prepare_full(pb_plan* pl, unsigned flags, int win_budget) {
     }
     return rc;
 }
+
+// a plan under construction (pb_plan_create_ex, pb_plan_deserialize): destroyed like any other unless it is released into *out
+struct PbPlanDestroy {
+    void operator()(pb_plan* pl) const { pb_plan_destroy(pl); }
+};
+using PbPlanOwner = std::unique_ptr<pb_plan, PbPlanDestroy>;
 
 extern "C" {
 
@@ -1667,7 +1706,7 @@ int pb_plan_create_ex(const pb_proj* dst, const double* rot3x3, int n_rot, const
                                                            : "this is libphotonbend_hip.so (the float64 chain runs NumPy's AVX-512 arcsin / arccos / arctan / tan): load libphotonbend_hip_libm.so for the libm flavour");
     flags &= ~(unsigned)(PB_PLAN_MATH_SVML | PB_PLAN_MATH_LIBM);
     if (win_budget < 0) return pb_fail(PB_ERR_INVALID, "negative window budget");
-    pb_plan* pl = new (std::nothrow) pb_plan();
+    PbPlanOwner pl(new (std::nothrow) pb_plan());
     if (!pl) return pb_fail(PB_ERR_INVALID, "out of host memory");
     pb_params_of_request(pl->P, pb_to_end(dst), rot3x3, n_rot, pb_to_end(src));
     pl->P.win_budget = PB_WINLDS_MAX;
@@ -1679,13 +1718,10 @@ int pb_plan_create_ex(const pb_proj* dst, const double* rot3x3, int n_rot, const
     if (hipGetDeviceCount(&ndev) != hipSuccess) ndev = 0;
     (void)hipGetLastError();
     if (ndev > 0 && !(flags & PB_PLAN_DEFER)) {
-        const int rc = pb_plan_prepare_full(pl, flags, win_budget);
-        if (rc != PB_OK) {
-            pb_plan_destroy(pl);
-            return rc;
-        }
+        const int rc = pb_plan_prepare_full(pl.get(), flags, win_budget);
+        if (rc != PB_OK) return rc;
     }
-    *out = pl;
+    *out = pl.release();
     return PB_OK;
 }
 
@@ -1734,7 +1770,7 @@ int pb_plan_prepare(pb_plan* plan, unsigned flags, int win_budget) {
 
 int pb_plan_set_window_budget(pb_plan* plan, int win_budget) {
     if (!plan || win_budget <= 0) return pb_fail(PB_ERR_INVALID, "null plan or non-positive budget");
-    if (!(plan->fast_ready || plan->dbl_ready)) return pb_fail(PB_ERR_UNSUPPORTED, "the plan has no tile tables (not prepared, or a geometry without a fast path)");
+    if (!(plan->cert.fast_ready || plan->cert.dbl_ready)) return pb_fail(PB_ERR_UNSUPPORTED, "the plan has no tile tables (not prepared, or a geometry without a fast path)");
     int dev = -1;
     PB_HIP(hipGetDevice(&dev));
     if (dev != plan->device) return pb_fail(PB_ERR_INVALID, "plan was prepared on another device; create one plan per device");
@@ -1750,29 +1786,9 @@ int pb_plan_timing(const pb_plan* plan, double* prepare_ms, double* tune_ms) {
 
 void pb_plan_destroy(pb_plan* plan) {
     if (!plan) return;
-    // ONE wait (launches of the plan may still be in flight on the caller's streams), then every table back to the cache
-    if (plan->table || plan->table_r || plan->ltable || plan->P_dev || plan->sep_rows) pb_wait_device(plan->device);
-    pb_tmp_free(plan->table);
-    pb_tmp_free(plan->fail_tiles);
-    pb_tmp_free(plan->fix_px);
-    pb_tmp_free(plan->idx_tab);
-    pb_tmp_free(plan->fix_idx);
-    pb_sep_release(plan);
-    pb_tmp_free(plan->sep_rows);
-    pb_tmp_free(plan->sep_cols);
-    pb_tmp_free(plan->table_r);
-    pb_tmp_free(plan->lat_tab);
-    pb_tmp_free(plan->dbl_tile_fix);
-    pb_tmp_free(plan->dbl_px_fix);
-    pb_tmp_free(plan->saved_l);
-    pb_tmp_free(plan->saved_r);
-    pb_tmp_free(plan->ltable);
-    pb_tmp_free(plan->ltable_bil);
-    pb_tmp_free(plan->bil_dbl_tables);
-    pb_tmp_free(plan->P_dev);
-    pb_tmp_free(plan->bil_tiles);
-    pb_tmp_free(plan->bil_xy);
-    pb_tmp_free(plan->bil_fix_xy);
+    // ONE wait (launches of the plan may still be in flight on the caller's streams), then its groups give their blocks back to the
+    // cache; a plan that owns none (deferred and never prepared, or without tables) touches no HIP call
+    if (plan->holds()) pb_wait_device(plan->device);
     delete plan;
 }
 
@@ -1783,45 +1799,44 @@ int pb_plan_dst_shape(const pb_plan* plan, int* height, int* width) {
     return PB_OK;
 }
 int pb_plan_bilinear_float64_tiles(const pb_plan* plan) {
-    if (!plan || !(plan->fast_ready || plan->dbl_ready)) return 0;
-    if (!plan->bil_tiles) return (int)plan->n_tiles;  // (created with PB_PLAN_NO_BILINEAR and not asked since: pb_remap_bilinear_u8 runs the per-pixel float64 kernels)
-    if (plan->bil_xy) return 0;  // every tile the models cannot serve has its exact coordinates in the plan's table
-    return (int)(plan->n_fail_tiles + (plan->bil_tiles ? plan->n_bil_tiles : 0u));
+    if (!plan || !(plan->cert.fast_ready || plan->cert.dbl_ready)) return 0;
+    if (!plan->bil.tiles) return (int)plan->cert.n_tiles;  // (created with PB_PLAN_NO_BILINEAR and not asked since: pb_remap_bilinear_u8 runs the per-pixel float64 kernels)
+    if (plan->bil.xy) return 0;  // every tile the models cannot serve has its exact coordinates in the plan's table
+    return (int)(plan->cert.n_fail_tiles + (plan->bil.tiles ? plan->bil.n_tiles : 0u));
 }
 int pb_plan_bilinear_tile_mix(const pb_plan* plan, long long mix[8]) {
     if (!plan || !mix) return pb_fail(PB_ERR_INVALID, "null argument");
     for (int k = 0; k < 8; ++k) mix[k] = 0;
-    if (!(plan->fast_ready || plan->dbl_ready) || !plan->ltable_bil || plan->launch_groups_bil == 0) return PB_OK;
+    if (!(plan->cert.fast_ready || plan->cert.dbl_ready) || !plan->bil.lt.entries || plan->bil.lt.groups == 0) return PB_OK;
     if (plan->device >= 0) {
         int dev = -1;
         PB_HIP(hipGetDevice(&dev));
         if (dev != plan->device) return pb_fail(PB_ERR_INVALID, "plan was prepared on another device");
     }
     // the entries the bilinear launch's waves read, classified as the kernel takes them (pb_bilinear_mix_kernel)
-    unsigned* counters = nullptr;
-    PB_HIP(pb_tmp_alloc((void**)&counters, 8 * sizeof(unsigned)));
+    PbBlock<unsigned> counters;
+    PB_HIP(counters.alloc(8));
     hipError_t e = hipMemsetAsync(counters, 0, 8 * sizeof(unsigned), 0);
     if (e == hipSuccess) {
-        const unsigned n_slots = 4u * plan->launch_groups_bil;
-        hipLaunchKernelGGL(pb_bilinear_mix_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, 0, plan->ltable_bil, n_slots, counters);
+        const unsigned n_slots = 4u * plan->bil.lt.groups;
+        hipLaunchKernelGGL(pb_bilinear_mix_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, 0, plan->bil.lt.entries, n_slots, counters);
         unsigned res[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         e = hipMemcpy(res, counters, sizeof(res), hipMemcpyDeviceToHost);
         for (int k = 0; k < 8; ++k) mix[k] = res[k];
     }
     if (e != hipSuccess) (void)hipDeviceSynchronize();
-    pb_tmp_free(counters);
     PB_HIP(e);
     return PB_OK;
 }
 int pb_plan_bilinear_launch_shape(const pb_plan* plan, int* lds_bytes, int* workgroups_per_frame) {
     if (!plan || !lds_bytes || !workgroups_per_frame) return pb_fail(PB_ERR_INVALID, "null argument");
-    const bool tiles = (plan->fast_ready || plan->dbl_ready) && plan->ltable_bil && plan->launch_groups_bil > 0;
-    *lds_bytes = tiles ? (int)plan->bil_pool_bytes : 0;
+    const bool tiles = (plan->cert.fast_ready || plan->cert.dbl_ready) && plan->bil.lt.entries && plan->bil.lt.groups > 0;
+    *lds_bytes = tiles ? (int)plan->bil.pool_bytes : 0;
     *workgroups_per_frame = tiles ? (int)pb_bil_groups(plan) : 0;
     return PB_OK;
 }
 int pb_plan_window_budget(const pb_plan* plan) {
-    return (plan && (plan->fast_ready || plan->dbl_ready)) ? plan->P.win_budget : 0;
+    return (plan && (plan->cert.fast_ready || plan->cert.dbl_ready)) ? plan->P.win_budget : 0;
 }
 int pb_plan_src_shape(const pb_plan* plan, int* height, int* width) {
     if (!plan || !height || !width) return pb_fail(PB_ERR_INVALID, "null argument");
@@ -1859,7 +1874,7 @@ int pb_remap_u8v(const pb_plan* plan, const uint8_t* const* src_dev, uint8_t* co
     }
     // the VEC instantiations of the two windowed kernels: frame f's pointers from a by-value table, at most PB_MAX_VFRAMES per launch
     const PbParams& P = plan->P;
-    const unsigned gpf = plan->launch_groups;
+    const unsigned gpf = plan->nearest.lt.groups;
     for (int f0 = 0; f0 < n_frames; f0 += PB_MAX_VFRAMES) {
         const int nf = n_frames - f0 < PB_MAX_VFRAMES ? n_frames - f0 : PB_MAX_VFRAMES;
         PbFrameTab tab;
@@ -1870,14 +1885,14 @@ int pb_remap_u8v(const pb_plan* plan, const uint8_t* const* src_dev, uint8_t* co
         const dim3 grid(gpf * (unsigned)nf), block(64 * PB_TILE_WAVES);
         if (r.kind == PbRoute::DOUBLE)
             pb_pick_wmode(plan, [&](auto W) {
-                hipLaunchKernelGGL((pb_hot_double_kernel<W.value, true, true>), grid, block, pb_window_lds_bytes(P, 8), st, P, plan->table, plan->table_r,
-                                   plan->ltable, pb_sep_rows(plan), plan->lat_tab, plan->fix_px, plan->dbl_px_fix, plan->dbl_tile_fix, tab.src[0], tab.dst[0], nf,
+                hipLaunchKernelGGL((pb_hot_double_kernel<W.value, true, true>), grid, block, pb_window_lds_bytes(P, 8), st, P, plan->cert.table, plan->cert.table_r,
+                                   plan->nearest.lt.entries, pb_sep_rows(plan), plan->cert.lat_tab, plan->cert.fix_px, plan->cert.dbl_px_fix, plan->cert.dbl_tile_fix, tab.src[0], tab.dst[0], nf,
                                    0ull, 0ull, gpf, 1, tab);
             });
         else
             pb_pick_kind(P, [&](auto K) {
-                hipLaunchKernelGGL((pb_hot_win_kernel<K.value, true>), grid, block, pb_window_lds_bytes(P), st, (const PbParams*)plan->P_dev, pb_hot_of_host(P),
-                                   plan->ltable, tab.src[0], tab.dst[0], gpf, 0ull, 0ull, plan->idx_tab, plan->fix_px, plan->fix_idx, (unsigned)nf, tab);
+                hipLaunchKernelGGL((pb_hot_win_kernel<K.value, true>), grid, block, pb_window_lds_bytes(P), st, (const PbParams*)plan->nearest.P_dev, pb_hot_of_host(P),
+                                   plan->nearest.lt.entries, tab.src[0], tab.dst[0], gpf, 0ull, 0ull, plan->cert.idx_tab, plan->cert.fix_px, plan->cert.fix_idx, (unsigned)nf, tab);
             });
     }
     PB_HIP(hipGetLastError());
@@ -1959,19 +1974,19 @@ __attribute__((visibility("default"))) int pb_debug_trace(unsigned long long* ou
 }
 __attribute__((visibility("default"))) int pb_debug_trace_frame(const pb_plan* plan, int frame) {
     // record the waves of frame `frame` of a batch launch (4-wave workgroups); frame < 0: whole launches (single frames)
-    const unsigned wpf = (plan && frame >= 0) ? plan->launch_groups : 0xFFFFFFFFu, f = frame >= 0 ? (unsigned)frame : 0u;
+    const unsigned wpf = (plan && frame >= 0) ? plan->nearest.lt.groups : 0xFFFFFFFFu, f = frame >= 0 ? (unsigned)frame : 0u;
     if (hipMemcpyToSymbol(HIP_SYMBOL(pb_trace_wpf), &wpf, sizeof(wpf)) != hipSuccess) return -1;
     return hipMemcpyToSymbol(HIP_SYMBOL(pb_trace_frame), &f, sizeof(f)) == hipSuccess ? 0 : -1;
 }
 __attribute__((visibility("default"))) int pb_debug_copy_table_r(const pb_plan* plan, void* host, size_t bytes) {  // the right eye's table of a double-fisheye plan
-    if (!plan || !plan->table_r) return -1;
-    const size_t have = (size_t)plan->n_tiles * sizeof(PbTileEntry);
-    return hipMemcpy(host, plan->table_r, bytes < have ? bytes : have, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
+    if (!plan || !plan->cert.table_r) return -1;
+    const size_t have = (size_t)plan->cert.n_tiles * sizeof(PbTileEntry);
+    return hipMemcpy(host, plan->cert.table_r, bytes < have ? bytes : have, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
 }
 __attribute__((visibility("default"))) int pb_debug_copy_table(const pb_plan* plan, void* host, size_t bytes) {
-    if (!plan || !plan->table) return -1;
-    const size_t have = (size_t)plan->n_tiles * sizeof(PbTileEntry);
-    return hipMemcpy(host, plan->table, bytes < have ? bytes : have, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
+    if (!plan || !plan->cert.table) return -1;
+    const size_t have = (size_t)plan->cert.n_tiles * sizeof(PbTileEntry);
+    return hipMemcpy(host, plan->cert.table, bytes < have ? bytes : have, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
 }
 #endif
 
@@ -1986,16 +2001,16 @@ int pb_plan_info(const pb_plan* plan, int* fast_path_enabled, long long* stats7,
     long long* stats5 = stats7;
     if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
     if (fast_path_enabled)
-        *fast_path_enabled = (pb_use_fast(plan) || ((plan->sep_ready || plan->dbl_ready) && plan->mode != PB_MODE_FAITHFUL)) ? 1 : 0;
+        *fast_path_enabled = (pb_use_fast(plan) || ((plan->cert.sep_ready || plan->cert.dbl_ready) && plan->mode != PB_MODE_FAITHFUL)) ? 1 : 0;
     if (stats5) {
-        const bool have = plan->fast_ready || plan->dbl_ready;  // a double source counts both eyes' tables
-        stats5[0] = have ? (long long)plan->n_tiles : -1;
-        stats5[1] = have ? (long long)plan->n_fail_tiles : -1;
-        stats5[2] = have ? (long long)plan->n_fix_px : -1;
-        stats5[3] = have ? plan->diff_pixels : -1;
-        stats5[4] = have ? (long long)plan->n_lean_tiles : -1;
-        stats5[5] = have ? (long long)plan->n_black_tiles : -1;
-        stats5[6] = have ? (long long)plan->n_direct_tiles : -1;
+        const bool have = plan->cert.fast_ready || plan->cert.dbl_ready;  // a double source counts both eyes' tables
+        stats5[0] = have ? (long long)plan->cert.n_tiles : -1;
+        stats5[1] = have ? (long long)plan->cert.n_fail_tiles : -1;
+        stats5[2] = have ? (long long)plan->cert.n_fix_px : -1;
+        stats5[3] = have ? plan->cert.diff_pixels : -1;
+        stats5[4] = have ? (long long)plan->cert.n_lean_tiles : -1;
+        stats5[5] = have ? (long long)plan->cert.n_black_tiles : -1;
+        stats5[6] = have ? (long long)plan->cert.n_direct_tiles : -1;
     }
     if (thresholds4) {
         thresholds4[0] = plan->P.inv_lo[0];
@@ -2206,26 +2221,27 @@ const uint32_t PB_BLOB_MAGIC = 0x4C504250u;  // "PBPL"
 const uint32_t PB_BLOB_VERSION = 5;  // 4: tile flags carry PB_TILE_COARSE; 5: ... and the walk bits of the bilinear table slots; the header names the math flavour
 
 struct PbSection {
-    void** ptr;
+    PbBlockAny* block;
     size_t bytes;
 };
-// the plan's device tables and their sizes (0 = absent), in blob order
-void pb_plan_sections(pb_plan* pl, PbSection sec[13]) {
-    const size_t nt = pl->n_tiles, nf = pl->n_fail_tiles ? pl->n_fail_tiles : 1, np = pl->n_fix_px ? pl->n_fix_px : 1;
-    const bool tiles = pl->fast_ready || pl->dbl_ready;
-    sec[0] = {(void**)&pl->table, tiles ? nt * sizeof(PbTileEntry) : 0};
-    sec[1] = {(void**)&pl->table_r, pl->dbl_ready ? nt * sizeof(PbTileEntry) : 0};
-    sec[2] = {(void**)&pl->fail_tiles, tiles ? nf * sizeof(int32_t) : 0};
-    sec[3] = {(void**)&pl->fix_px, tiles ? np * sizeof(int32_t) : 0};
-    sec[4] = {(void**)&pl->idx_tab, pl->fast_ready ? nf * PB_TILE * PB_TILE * sizeof(int32_t) : 0};
-    sec[5] = {(void**)&pl->fix_idx, pl->fast_ready ? np * sizeof(int32_t) : 0};
-    sec[6] = {(void**)&pl->sep_rows, pl->sep_rows ? (size_t)pl->P.dst.height * sizeof(PbSepRow) : 0};
-    sec[7] = {(void**)&pl->sep_cols, pl->sep_cols ? (size_t)pl->P.dst.width * sizeof(PbSepCol) : 0};
-    sec[8] = {(void**)&pl->dbl_tile_fix, pl->dbl_ready ? nf * PB_TILE * PB_TILE * sizeof(PbDoubleFix) : 0};
-    sec[9] = {(void**)&pl->dbl_px_fix, pl->dbl_ready ? np * sizeof(PbDoubleFix) : 0};
-    sec[10] = {(void**)&pl->lat_tab, (size_t)pl->n_lat_tiles * PB_LAT_TILE_DOUBLES * sizeof(double)};
-    sec[11] = {(void**)&pl->saved_l, tiles ? nt * sizeof(int32_t) : 0};
-    sec[12] = {(void**)&pl->saved_r, pl->dbl_ready ? nt * sizeof(int32_t) : 0};
+// the plan's certified tables and their sizes (0 = absent), in blob order.  sep_rows / sep_cols: whether the two optional sections are
+// there - the writing side says what it holds, the reading side what the blob's header records.
+void pb_plan_sections(PbCertified& c, const PbParams& P, bool sep_rows, bool sep_cols, PbSection sec[13]) {
+    const size_t nt = c.n_tiles, nf = c.n_fail_tiles ? c.n_fail_tiles : 1, np = c.n_fix_px ? c.n_fix_px : 1;
+    const bool tiles = c.fast_ready || c.dbl_ready;
+    sec[0] = {&c.table, tiles ? nt * sizeof(PbTileEntry) : 0};
+    sec[1] = {&c.table_r, c.dbl_ready ? nt * sizeof(PbTileEntry) : 0};
+    sec[2] = {&c.fail_tiles, tiles ? nf * sizeof(int32_t) : 0};
+    sec[3] = {&c.fix_px, tiles ? np * sizeof(int32_t) : 0};
+    sec[4] = {&c.idx_tab, c.fast_ready ? nf * PB_TILE * PB_TILE * sizeof(int32_t) : 0};
+    sec[5] = {&c.fix_idx, c.fast_ready ? np * sizeof(int32_t) : 0};
+    sec[6] = {&c.sep_rows, sep_rows ? (size_t)P.dst.height * sizeof(PbSepRow) : 0};
+    sec[7] = {&c.sep_cols, sep_cols ? (size_t)P.dst.width * sizeof(PbSepCol) : 0};
+    sec[8] = {&c.dbl_tile_fix, c.dbl_ready ? nf * PB_TILE * PB_TILE * sizeof(PbDoubleFix) : 0};
+    sec[9] = {&c.dbl_px_fix, c.dbl_ready ? np * sizeof(PbDoubleFix) : 0};
+    sec[10] = {&c.lat_tab, (size_t)c.n_lat_tiles * PB_LAT_TILE_DOUBLES * sizeof(double)};
+    sec[11] = {&c.saved_l, tiles ? nt * sizeof(int32_t) : 0};
+    sec[12] = {&c.saved_r, c.dbl_ready ? nt * sizeof(int32_t) : 0};
 }
 uint64_t pb_fnv1a(const uint8_t* p, size_t n) {
     uint64_t h = 1469598103934665603ull;
@@ -2241,10 +2257,10 @@ extern "C" {
 
 int pb_plan_serialize(const pb_plan* plan_c, void* buf, size_t capacity, size_t* size_out) {
     if (!plan_c || !size_out) return pb_fail(PB_ERR_INVALID, "null argument");
-    pb_plan* pl = const_cast<pb_plan*>(plan_c);  // sections are described through member addresses; nothing is modified
-    if (!(pl->fast_ready || pl->dbl_ready || pl->sep_ready)) return pb_fail(PB_ERR_UNSUPPORTED, "the plan holds no device tables (not prepared)");
+    pb_plan* pl = const_cast<pb_plan*>(plan_c);  // sections are described through the blocks' addresses; nothing is modified
+    if (!(pl->cert.fast_ready || pl->cert.dbl_ready || pl->cert.sep_ready)) return pb_fail(PB_ERR_UNSUPPORTED, "the plan holds no device tables (not prepared)");
     PbSection sec[13];
-    pb_plan_sections(pl, sec);
+    pb_plan_sections(pl->cert, pl->P, pl->cert.sep_rows.holds(), pl->cert.sep_cols.holds(), sec);
     size_t total = sizeof(PbBlobHeader) + sizeof(PbParams);
     for (int i = 0; i < 13; ++i) total += sec[i].bytes;
     *size_out = total;
@@ -2260,10 +2276,10 @@ int pb_plan_serialize(const pb_plan* plan_c, void* buf, size_t capacity, size_t*
     h.version = PB_BLOB_VERSION;
     h.params_size = (uint32_t)sizeof(PbParams);
     h.entry_size = (uint32_t)sizeof(PbTileEntry);
-    h.fast_ready = pl->fast_ready; h.sep_ready = pl->sep_ready; h.dbl_ready = pl->dbl_ready; h.reserved = pl->walk | (PB_MATH_FLAVOUR << 8);
-    h.n_tiles = pl->n_tiles; h.n_fail_tiles = pl->n_fail_tiles; h.n_fix_px = pl->n_fix_px; h.n_lean_tiles = pl->n_lean_tiles;
-    h.n_black_tiles = pl->n_black_tiles; h.n_direct_tiles = pl->n_direct_tiles; h.n_row_weight_tiles = pl->n_row_weight_tiles;
-    h.n_lat_tiles = pl->n_lat_tiles; h.diff_pixels = pl->diff_pixels;
+    h.fast_ready = pl->cert.fast_ready; h.sep_ready = pl->cert.sep_ready; h.dbl_ready = pl->cert.dbl_ready; h.reserved = pl->walk | (PB_MATH_FLAVOUR << 8);
+    h.n_tiles = pl->cert.n_tiles; h.n_fail_tiles = pl->cert.n_fail_tiles; h.n_fix_px = pl->cert.n_fix_px; h.n_lean_tiles = pl->cert.n_lean_tiles;
+    h.n_black_tiles = pl->cert.n_black_tiles; h.n_direct_tiles = pl->cert.n_direct_tiles; h.n_row_weight_tiles = pl->cert.n_row_weight_tiles;
+    h.n_lat_tiles = pl->cert.n_lat_tiles; h.diff_pixels = pl->cert.diff_pixels;
     uint8_t* q = out + sizeof(PbBlobHeader);
     memcpy(q, &pl->P, sizeof(PbParams));
     q += sizeof(PbParams);
@@ -2271,8 +2287,8 @@ int pb_plan_serialize(const pb_plan* plan_c, void* buf, size_t capacity, size_t*
     for (int i = 0; i < 13; ++i) {
         h.section_bytes[i] = sec[i].bytes;
         if (!sec[i].bytes) continue;
-        if (!*sec[i].ptr) return pb_fail(PB_ERR_INVALID, "inconsistent plan: a table is missing");
-        PB_HIP(hipMemcpy(q, *sec[i].ptr, sec[i].bytes, hipMemcpyDeviceToHost));
+        if (!sec[i].block->holds()) return pb_fail(PB_ERR_INVALID, "inconsistent plan: a table is missing");
+        PB_HIP(hipMemcpy(q, sec[i].block->bytes(), sec[i].bytes, hipMemcpyDeviceToHost));
         q += sec[i].bytes;
     }
     h.checksum = pb_fnv1a(out + sizeof(PbBlobHeader), total - sizeof(PbBlobHeader));
@@ -2295,17 +2311,17 @@ int pb_plan_deserialize(const void* buf, size_t size, pb_plan** out) {
     if (((h.reserved >> 8) & 0xFF) != PB_MATH_FLAVOUR)
         return pb_fail(PB_ERR_UNSUPPORTED, PB_MATH_FLAVOUR ? "serialized plan was made by libphotonbend_hip.so (the AVX-512 / SVML math flavour); this is libphotonbend_hip_libm.so"
                                                             : "serialized plan was made by libphotonbend_hip_libm.so (glibc's asin / acos / atan / tan); this is libphotonbend_hip.so");
-    pb_plan* pl = new (std::nothrow) pb_plan();
+    PbPlanOwner pl(new (std::nothrow) pb_plan());
     if (!pl) return pb_fail(PB_ERR_INVALID, "out of host memory");
     memcpy(&pl->P, in + sizeof(PbBlobHeader), sizeof(PbParams));
-    pl->fast_ready = h.fast_ready; pl->sep_ready = h.sep_ready; pl->dbl_ready = h.dbl_ready;
-    pb_sep_setup(pl);
+    pl->cert.fast_ready = h.fast_ready; pl->cert.sep_ready = h.sep_ready; pl->cert.dbl_ready = h.dbl_ready;
+    pb_sep_setup(pl->cert);
     pl->walk = ((h.reserved & 0xFF) <= 3) ? (h.reserved & 0xFF) : 0;
-    pl->n_tiles = h.n_tiles; pl->n_fail_tiles = h.n_fail_tiles; pl->n_fix_px = h.n_fix_px; pl->n_lean_tiles = h.n_lean_tiles;
-    pl->n_black_tiles = h.n_black_tiles; pl->n_direct_tiles = h.n_direct_tiles; pl->n_row_weight_tiles = h.n_row_weight_tiles;
-    pl->n_lat_tiles = h.n_lat_tiles; pl->diff_pixels = h.diff_pixels;
+    pl->cert.n_tiles = h.n_tiles; pl->cert.n_fail_tiles = h.n_fail_tiles; pl->cert.n_fix_px = h.n_fix_px; pl->cert.n_lean_tiles = h.n_lean_tiles;
+    pl->cert.n_black_tiles = h.n_black_tiles; pl->cert.n_direct_tiles = h.n_direct_tiles; pl->cert.n_row_weight_tiles = h.n_row_weight_tiles;
+    pl->cert.n_lat_tiles = h.n_lat_tiles; pl->cert.diff_pixels = h.diff_pixels;
     pl->mode = PB_MODE_AUTO;
-    const bool tiles = pl->fast_ready || pl->dbl_ready;
+    const bool tiles = pl->cert.fast_ready || pl->cert.dbl_ready;
     // the derived half of the parameter block must be what THIS build derives from the blob's own request (a blob whose tables
     // were made for other constants is foreign, whatever its checksum says)
     bool ok = pl->P.n_rot >= 0 && pl->P.n_rot <= PB_MAX_ROTATIONS;
@@ -2322,55 +2338,34 @@ int pb_plan_deserialize(const void* buf, size_t size, pb_plan** out) {
         pb_params_of_request(Q, ends[0], &pl->P.R[0][0], pl->P.n_rot, ends[1]);
         ok = ok && pb_same_request(Q, pl->P);
     }
-    ok = ok && (!tiles || pl->n_tiles == pb_num_tiles(pl->P)) && pl->n_fail_tiles <= 2u * pl->n_tiles + 1u &&
+    ok = ok && (!tiles || pl->cert.n_tiles == pb_num_tiles(pl->P)) && pl->cert.n_fail_tiles <= 2u * pl->cert.n_tiles + 1u &&
               pl->P.win_budget >= PB_DIRECT_LDS_BYTES && pl->P.win_budget <= PB_WINLDS_MAX && (pl->P.win_budget & 15) == 0 &&
               pl->P.n_rot >= 0 && pl->P.n_rot <= PB_MAX_ROTATIONS;
-    // section presence is decided by pointers on the writing side: reproduce it from the recorded sizes
     PbSection sec[13];
-    static uint8_t present_tag;  // any non-null value
-    if (h.section_bytes[6]) pl->sep_rows = reinterpret_cast<PbSepRow*>(&present_tag);
-    if (h.section_bytes[7]) pl->sep_cols = reinterpret_cast<PbSepCol*>(&present_tag);
-    pb_plan_sections(pl, sec);
-    pl->sep_rows = nullptr;
-    pl->sep_cols = nullptr;
+    pb_plan_sections(pl->cert, pl->P, h.section_bytes[6] != 0, h.section_bytes[7] != 0, sec);
     size_t total = sizeof(PbBlobHeader) + sizeof(PbParams);
     for (int i = 0; i < 13; ++i) {
         ok = ok && h.section_bytes[i] == sec[i].bytes;
         total += h.section_bytes[i];
     }
-    if (!ok || total != size) {
-        delete pl;
-        return pb_fail(PB_ERR_INVALID, "serialized plan is inconsistent (sizes do not match its geometry)");
-    }
+    if (!ok || total != size) return pb_fail(PB_ERR_INVALID, "serialized plan is inconsistent (sizes do not match its geometry)");
     int rc = PB_OK;
     if (hipGetDevice(&pl->device) != hipSuccess) rc = PB_ERR_HIP;
     const uint8_t* q = in + sizeof(PbBlobHeader) + sizeof(PbParams);
     for (int i = 0; i < 13 && rc == PB_OK; ++i) {
         if (!sec[i].bytes) continue;
-        if (pb_tmp_alloc(sec[i].ptr, sec[i].bytes) != hipSuccess || hipMemcpy(*sec[i].ptr, q, sec[i].bytes, hipMemcpyHostToDevice) != hipSuccess)
+        if (sec[i].block->alloc_bytes(sec[i].bytes) != hipSuccess || hipMemcpy(sec[i].block->bytes(), q, sec[i].bytes, hipMemcpyHostToDevice) != hipSuccess)
             rc = PB_ERR_HIP;
         q += sec[i].bytes;
     }
-    if (rc != PB_OK) {
-        g_err = std::string("plan upload failed: ") + hipGetErrorString(hipGetLastError());
-        pb_plan_destroy(pl);
-        return rc;
-    }
-    if (pb_tmp_alloc((void**)&pl->P_dev, sizeof(PbParams)) != hipSuccess || hipMemcpy(pl->P_dev, &pl->P, sizeof(PbParams), hipMemcpyHostToDevice) != hipSuccess) {
-        pb_plan_destroy(pl);
+    if (rc != PB_OK) return pb_fail(rc, std::string("plan upload failed: ") + hipGetErrorString(hipGetLastError()));
+    if (pl->nearest.P_dev.alloc(1) != hipSuccess || hipMemcpy(pl->nearest.P_dev, &pl->P, sizeof(PbParams), hipMemcpyHostToDevice) != hipSuccess)
         return pb_fail(PB_ERR_HIP, "plan upload failed: parameter block");
-    }
-    if ((pl->dbl_ready || pl->fast_ready) && pb_build_bilinear_list(pl) != PB_OK) {
-        pb_plan_destroy(pl);
-        return PB_ERR_HIP;
-    }
-    rc = pb_build_bilinear_launch(pl);  // derived state: rebuilt, not stored
-    if (rc == PB_OK) rc = pb_apply_budget(pl, pl->P.win_budget);
-    if (rc != PB_OK) {
-        pb_plan_destroy(pl);
-        return rc;
-    }
-    *out = pl;
+    if ((pl->cert.dbl_ready || pl->cert.fast_ready) && pb_build_bilinear_list(pl.get()) != PB_OK) return PB_ERR_HIP;
+    rc = pb_build_bilinear_launch(pl.get());  // derived state: rebuilt, not stored
+    if (rc == PB_OK) rc = pb_apply_budget(pl.get(), pl->P.win_budget);
+    if (rc != PB_OK) return rc;
+    *out = pl.release();
     return PB_OK;
 }
 
@@ -2749,13 +2744,13 @@ int pb_remap_ss_u8(const pb_plan* plan, int n, int interpolation, const uint8_t*
     hipStream_t st = (hipStream_t)stream;
     const bool aligned = pb_aligned16(src_dev, src_frame_stride);
     if (pb_route(plan, interpolation, n, flags, aligned).kind == PbRoute::SS_FUSED) {
-        const unsigned gpf = plan->launch_groups;
+        const unsigned gpf = plan->nearest.lt.groups;
         pb_each_launch(src_dev, dst_dev, n_frames, src_frame_stride, dst_frame_stride, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
             pb_pick_kind(P, [&](auto K) {
                 pb_pick<2, 4>(n == 2, [&](auto NS) {
                     hipLaunchKernelGGL((pb_ss_win_kernel<K.value, NS.value>), dim3(gpf * (unsigned)nf), dim3(64 * PB_TILE_WAVES), pb_window_lds_bytes(P), st,
-                                       (const PbParams*)plan->P_dev, pb_hot_of_host(P), plan->ltable, sf, df, gpf, (unsigned long long)src_frame_stride,
-                                       (unsigned long long)dst_frame_stride, plan->idx_tab, plan->fix_px, plan->fix_idx);
+                                       (const PbParams*)plan->nearest.P_dev, pb_hot_of_host(P), plan->nearest.lt.entries, sf, df, gpf, (unsigned long long)src_frame_stride,
+                                       (unsigned long long)dst_frame_stride, plan->cert.idx_tab, plan->cert.fix_px, plan->cert.fix_idx);
                 });
             });
         });
