@@ -60,6 +60,8 @@ SUPERSAMPLE_FACTORS = (1, 2, 4)
 # the largest map any pb_proj may describe (photonbend_hip.hip, pb_end_ok): h * w <= (2^31 - 1) / 4
 MAX_PROJ_PIXELS = 0x7FFFFFFF // 4
 KIND_CAMERA, KIND_DOUBLE, KIND_PANO = 0, 1, 2
+KIND_CUBE = 5  # a cube map (2N, 3N): no lens, like a panorama (3 and 4 are the library's own eye kinds)
+LENSLESS_KINDS = (KIND_PANO, KIND_CUBE)  # their pb_proj.lens / fov / magnitude / f_distance are ignored
 LENS_IDS = {
     "equidistant": 0,
     "equisolid": 1,
@@ -91,7 +93,7 @@ class pb_proj(C.Structure):
         """What identifies this projection in a cache - also one that outlives the process: a registered polynomial lens is named
         by its coefficients, never by its process-local id."""
         lens = self.lens
-        if self.kind != KIND_PANO and lens >= LENS_POLYNOMIAL_BASE:
+        if self.kind not in LENSLESS_KINDS and lens >= LENS_POLYNOMIAL_BASE:
             lens = ("polynomial",) + lens_polynomial_info(lens)
         return (self.kind, lens, self.height, self.width, self.fov, self.magnitude, self.f_distance)
 

@@ -32,6 +32,7 @@ from .. import _hostpipe
 from .. import _native as nat
 from ._coordmap import CoordinateMap
 from .lens import Lens, lens_id
+from ..utils import _cubemap_n
 
 _PLAN_CACHE: "OrderedDict" = OrderedDict()  # key -> [plan, uses, prepared, pending preparation]; least recently used first
 _PLAN_CACHE_MAX = 64
@@ -303,7 +304,7 @@ class _GpuProjection:
         returns the n x n block means at this image's size.  1 (the default) is the plain map."""
         n = nat.check_supersample(supersample)
         proj = self._proj_ss(n)
-        if proj.kind != nat.KIND_PANO and proj.lens == nat.LENS_CUSTOM:
+        if proj.kind not in nat.LENSLESS_KINDS and proj.lens == nat.LENS_CUSTOM:
             return CoordinateMap.from_array(proj, self._custom_coordinate_map(proj), supersample=n)
         return CoordinateMap(proj, supersample=n)
 
@@ -320,7 +321,7 @@ class _GpuProjection:
         if (n * p.height) * (n * p.width) > nat.MAX_PROJ_PIXELS:
             raise ValueError(f"supersample={n} of a {p.height} x {p.width} destination is a {n * p.height} x {n * p.width} map: beyond the "
                              f"projection limit of {nat.MAX_PROJ_PIXELS} pixels")
-        if p.kind == nat.KIND_PANO:
+        if p.kind in nat.LENSLESS_KINDS:  # (a cube of face size n N: N / 2 scales exactly)
             return nat.make_proj(p.kind, n * p.height, n * p.width)
         mag = p.magnitude * n
         return nat.make_proj(p.kind, n * p.height, n * p.width, p.lens, p.fov, mag, mag / self._forward_half_fov())
@@ -332,7 +333,7 @@ class _GpuProjection:
     def _distance_planes(self, src: nat.pb_proj, dev_map):
         """forward_lens(latitude) * f_distance per pixel for a source Lens of user callables (None, None for a built-in lens)."""
         dl = dr = None
-        if src.kind != nat.KIND_PANO and src.lens == nat.LENS_CUSTOM:
+        if src.kind not in nat.LENSLESS_KINDS and src.lens == nat.LENS_CUSTOM:
             # forward_function is host Python by definition: latitude plane down, distances up (projection.py:251)
             lat = np.ascontiguousarray(nat.to_host(dev_map)[..., 0])
             planes = self._source_distances(lat)
@@ -391,7 +392,7 @@ class _GpuProjection:
         src = self._proj("src")
         h, w, tail, dt = _image_info(self.image)
         rgb8 = tail == (3,) and dt == np.dtype(np.uint8)
-        custom_src = src.kind != nat.KIND_PANO and src.lens == nat.LENS_CUSTOM
+        custom_src = src.kind not in nat.LENSLESS_KINDS and src.lens == nat.LENS_CUSTOM
         lazy = isinstance(coordinate_map, CoordinateMap) and coordinate_map.is_lazy
         nat.check_interpolation(interpolation)
         interpolating = interpolation != "nearest"  # (bilinear or catmull-rom)
@@ -486,7 +487,7 @@ class _GpuProjection:
             raise ValueError(f"a ({mh}, {mw}) coordinate map is not divisible by supersample={n}")
         lazy = isinstance(coordinate_map, CoordinateMap) and coordinate_map.is_lazy
         rgb8 = tail == (3,) and dt == np.dtype(np.uint8)
-        custom_src = src.kind != nat.KIND_PANO and src.lens == nat.LENS_CUSTOM
+        custom_src = src.kind not in nat.LENSLESS_KINDS and src.lens == nat.LENS_CUSTOM
         on_device = nat.is_device_array(self.image)
         rotations = coordinate_map.rotations if lazy else ()
         if interpolation == "bilinear" and len(rotations) > nat.PB_MAX_ROTATIONS:
@@ -647,6 +648,31 @@ class PanoramaImage(_GpuProjection):
     def _proj(self, role: str = "src") -> nat.pb_proj:
         h, w = _shape_hw(self.image)
         return nat.make_proj(nat.KIND_PANO, h, w)
+
+
+class CubemapImage(_GpuProjection):
+    """A cube map: six N x N faces in one (2N, 3N) + trailing image - top row left, front, right; bottom row up, back, down; no padding,
+    no mirroring.  No reference counterpart; defined THROUGH the reference: face k is
+    ``CameraImage(N x N, fov = 2 pi / 3, rectilinear())`` with ``f_distance`` set to exactly N / 2, behind one rotation whose matrix has the
+    face's right, forward and up vectors as its columns (``utils.cubemap_face_rotation``).  As a destination its coordinate map is that
+    already face-rotated map (no pixel is invalid; the caller's rotations come after it); as a source the direction's largest component
+    picks the face and the face camera's truncating sampler the texel.  The interpolated modes clamp their taps to the selected face:
+    seams are not filtered across faces.  ``process_coordinate_map`` leaves the caller's map unmodified.
+
+    Attributes: image, face_size."""
+
+    def __init__(self, image_arr) -> None:
+        self.image = image_arr
+        self.face_size = cubemap_face_size(tuple(image_arr.shape))
+
+    def _proj(self, role: str = "src") -> nat.pb_proj:
+        h, w = _shape_hw(self.image)
+        return nat.make_proj(nat.KIND_CUBE, h, w)
+
+
+def cubemap_face_size(shape) -> int:
+    """N of a cube map's array shape (2N, 3N) + trailing; ValueError for any other shape."""
+    return _cubemap_n(tuple(shape))  # (the one shape rule: utils, which the face helpers use too)
 
 
 def map_projection(coordinate_map):

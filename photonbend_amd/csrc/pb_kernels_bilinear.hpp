@@ -135,6 +135,8 @@ struct PbBilinear {
         bool live;
         int by, bx;    // integer bases keep the float32 tap arithmetic exact enough: s - base is in [-1, 1)
         float ty, tx;
+        int face;       // a cube source (the float64 definition on the selected face): the face and the position on it
+        double fy, fx;
     };
     template <int SRC_KIND>
     static __device__ __forceinline__ Px prepare(const PbParams& P, const PbCoord& c);
@@ -144,9 +146,9 @@ struct PbBilinear {
                                                    int cmin, bool mirror);
 };
 template <class FILTER, int SRC_KIND, typename SAMPLE>
-__global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_interp_kernel(const PbParams P, double* __restrict__ map, unsigned total, const double* __restrict__ dist_l,
-                                                                 const double* __restrict__ dist_r, const SAMPLE* __restrict__ img, void* __restrict__ out,
-                                                                 int channels) {
+__device__ __forceinline__ void pb_sample_map_interp_px(const PbParams& P, double* __restrict__ map, unsigned total, const double* __restrict__ dist_l,
+                                                        const double* __restrict__ dist_r, const SAMPLE* __restrict__ img, void* __restrict__ out,
+                                                        int channels) {
     const unsigned p = blockIdx.x * PB_BLOCK + threadIdx.x;
     if (p >= total) return;
     double* a = map + 3ull * p;
@@ -163,6 +165,23 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_interp_kernel(const Pb
         SAMPLE* o = static_cast<SAMPLE*>(out) + (unsigned long long)p * (unsigned)channels;
         for (int ch = 0; ch < channels; ++ch)
             o[ch] = live ? (SAMPLE)FILTER::template sample64<SAMPLE, true>(img, fy, fx, h, w, 0, w, false, channels, ch) : (SAMPLE)0;
+        return;
+    }
+    if (SRC_KIND == PB_KIND_CUBE) {
+        // the camera definition on the selected face, the taps clamped to that face's N x N rectangle: the face as an image of its own
+        // (N rows of pitch w) - seams are not filtered across faces.  The caller's map is left as it is.
+        PbCoord c;
+        c.lat = inv ? 0.0 : lat;
+        c.lon = inv ? 0.0 : lon;
+        c.inv = inv;
+        c.face = 0;
+        const PbCubePos q = pb_src_cube_pos(P, c);
+        const int n = pb_cube_n(P.src);
+        const bool live = !inv && pb_live_in(q.fy, q.fx, 1.0e300, n, n);
+        const SAMPLE* face = img + ((unsigned long long)pb_cube_row0(q.face, n) * (unsigned)w + (unsigned)pb_cube_col0(q.face, n)) * (unsigned)channels;
+        SAMPLE* o = static_cast<SAMPLE*>(out) + (unsigned long long)p * (unsigned)channels;
+        for (int ch = 0; ch < channels; ++ch)
+            o[ch] = live ? (SAMPLE)FILTER::template sample64<SAMPLE, false>(face, q.fy, q.fx, n, w, 0, n, false, channels, ch) : (SAMPLE)0;
         return;
     }
     double sl, cl;
@@ -191,6 +210,19 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_interp_kernel(const Pb
         const double r = live_r ? FILTER::template sample64<SAMPLE, false>(img, fyr, fxr, h, w, wl, wl + wr, true, channels, ch) : 0.0;
         o[ch] = inv ? (uint8_t)0 : (uint8_t)pb_cvt_u8(l * fl + r * fr);
     }
+}
+
+template <class FILTER, int SRC_KIND, typename SAMPLE>
+__global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_interp_kernel(const PbParams P, double* __restrict__ map, unsigned total, const double* __restrict__ dist_l,
+                                                                 const double* __restrict__ dist_r, const SAMPLE* __restrict__ img, void* __restrict__ out,
+                                                                 int channels) {
+    pb_sample_map_interp_px<FILTER, SRC_KIND, SAMPLE>(P, map, total, dist_l, dist_r, img, out, channels);
+}
+// ... from a cube source (a kernel of its own name: the instantiations of the one above are counted per filter by tests/test_isa_catmull_rom.py)
+template <class FILTER, typename SAMPLE>
+__global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_interp_cube_kernel(const PbParams P, double* __restrict__ map, unsigned total, const SAMPLE* __restrict__ img,
+                                                                      void* __restrict__ out, int channels) {
+    pb_sample_map_interp_px<FILTER, PB_KIND_CUBE, SAMPLE>(P, map, total, nullptr, nullptr, img, out, channels);
 }
 
 // ---- exact coordinate tables ------------------------------------------------------------------------------------------------
@@ -845,11 +877,11 @@ __global__ __launch_bounds__(64 * WAVES, PB_BIL_WPE) void pb_bilinear_hot_kernel
 // 1.0e9), the taps are pb_bilinear_taps' float32.  all_pixels: every pixel of the image; else the listed tiles and the fix pixels
 // (pb_pick_pixel; n_tiles: fail_tiles' first n_fail_only and more_tiles' together).
 template <class FILTER, int SRC_KIND>
-__global__ __launch_bounds__(PB_BLOCK) void pb_interp_fix_kernel(const PbParams P, const int32_t* __restrict__ fail_tiles, int all_pixels,
-                                                                 const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,
-                                                                 unsigned long long src_stride, unsigned long long dst_stride, int n_tiles = 0,
-                                                                 const int32_t* __restrict__ fix_px = nullptr, int n_fix_px = 0,
-                                                                 const int32_t* __restrict__ more_tiles = nullptr, int n_fail_only = 0) {
+__device__ __forceinline__ void pb_interp_fix_px(const PbParams& P, const int32_t* __restrict__ fail_tiles, int all_pixels,
+                                                 const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,
+                                                 unsigned long long src_stride, unsigned long long dst_stride, int n_tiles,
+                                                 const int32_t* __restrict__ fix_px, int n_fix_px,
+                                                 const int32_t* __restrict__ more_tiles, int n_fail_only) {
     PbPixelPick k;
     if (!pb_pick_pixel(P, all_pixels != 0, fail_tiles, n_fail_only, more_tiles, n_tiles, fix_px, n_fix_px, k) || !k.inside) return;
     const typename FILTER::Px q = FILTER::template prepare<SRC_KIND>(P, pb_rotate_all(P, pb_dst_coord(P, k.i, k.j)));
@@ -857,8 +889,38 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_interp_fix_kernel(const PbParams 
     for (int f = 0; f < n_frames; ++f)
         pb_store_px(dst + (unsigned long long)f * dst_stride + 3 * p, FILTER::template sample<SRC_KIND>(P, q, src + (unsigned long long)f * src_stride));
 }
+template <class FILTER, int SRC_KIND>
+__global__ __launch_bounds__(PB_BLOCK) void pb_interp_fix_kernel(const PbParams P, const int32_t* __restrict__ fail_tiles, int all_pixels,
+                                                                 const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,
+                                                                 unsigned long long src_stride, unsigned long long dst_stride, int n_tiles = 0,
+                                                                 const int32_t* __restrict__ fix_px = nullptr, int n_fix_px = 0,
+                                                                 const int32_t* __restrict__ more_tiles = nullptr, int n_fail_only = 0) {
+    pb_interp_fix_px<FILTER, SRC_KIND>(P, fail_tiles, all_pixels, src, dst, n_frames, src_stride, dst_stride, n_tiles, fix_px, n_fix_px, more_tiles, n_fail_only);
+}
+// A cube source's interpolated modes (INTERP_FLOAT64, every pixel): the definition per pixel on the selected face, float64 (a kernel of its
+// own name: the instantiations of the one above are counted per filter by tests/test_isa_catmull_rom.py)
+template <class FILTER>
+__global__ __launch_bounds__(PB_BLOCK) void pb_interp_cube_kernel(const PbParams P, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,
+                                                                  unsigned long long src_stride, unsigned long long dst_stride) {
+    pb_interp_fix_px<FILTER, PB_KIND_CUBE>(P, nullptr, 1, src, dst, n_frames, src_stride, dst_stride, 0, nullptr, 0, nullptr, 0);
+}
 template <int SRC_KIND>
 __device__ __forceinline__ PbBilinear::Px PbBilinear::prepare(const PbParams& P, const PbCoord& c) {
+    if (SRC_KIND == PB_KIND_CUBE) {  // the float64 definition (sample64) on the selected face: its bytes exactly
+        Px q;
+        q.by = q.bx = 0;
+        q.ty = q.tx = 0.0f;
+        q.live = false;
+        q.face = 0;
+        q.fy = q.fx = 0.0;
+        if (c.inv) return q;
+        const PbCubePos h = pb_src_cube_pos(P, c);
+        q.face = h.face;
+        q.fy = h.fy;
+        q.fx = h.fx;
+        q.live = pb_live_in(h.fy, h.fx, 1.0e300, pb_cube_n(P.src), pb_cube_n(P.src));
+        return q;
+    }
     double f0, f1;
     pb_src_pretrunc<SRC_KIND>(P, c, f0, f1);
     Px q;
@@ -872,6 +934,15 @@ __device__ __forceinline__ PbBilinear::Px PbBilinear::prepare(const PbParams& P,
 }
 template <int SRC_KIND>
 __device__ __forceinline__ unsigned PbBilinear::sample(const PbParams& P, const Px& q, const uint8_t* __restrict__ s) {
+    if (SRC_KIND == PB_KIND_CUBE) {
+        if (!q.live) return 0u;
+        const int n = pb_cube_n(P.src);
+        const uint8_t* face = s + 3ull * ((unsigned long long)pb_cube_row0(q.face, n) * (unsigned)P.src.width + (unsigned)pb_cube_col0(q.face, n));
+        unsigned out = 0;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) out |= (unsigned)sample64<uint8_t, false>(face, q.fy, q.fx, n, P.src.width, 0, n, false, 3, ch) << (8 * ch);
+        return out;
+    }
     return q.live ? pb_bilinear_taps<SRC_KIND>(P, s, q.ty, q.tx, q.by, q.bx) : 0u;
 }
 

@@ -65,10 +65,23 @@ struct PbCatmullRom {
     struct Px {
         bool live;
         double fy, fx;
+        int face;  // a cube source: the selected face ((fy, fx) is the position on it)
     };
     template <int SRC_KIND>
     static __device__ __forceinline__ Px prepare(const PbParams& P, const PbCoord& c) {
         Px q;
+        q.face = 0;
+        if (SRC_KIND == PB_KIND_CUBE) {
+            q.fy = q.fx = 0.0;
+            q.live = false;
+            if (c.inv) return q;
+            const PbCubePos h = pb_src_cube_pos(P, c);
+            q.face = h.face;
+            q.fy = h.fy;
+            q.fx = h.fx;
+            q.live = pb_live_in(h.fy, h.fx, 1.0e300, pb_cube_n(P.src), pb_cube_n(P.src));
+            return q;
+        }
         if (SRC_KIND == PB_KIND_PANO) {
             q.fy = c.lat / P.src_hseg;
             q.fx = c.lon / P.src_wseg + P.src_half_w;
@@ -85,6 +98,11 @@ struct PbCatmullRom {
     }
     template <int SRC_KIND>
     static __device__ __forceinline__ unsigned sample(const PbParams& P, const Px& q, const uint8_t* __restrict__ s) {
+        if (SRC_KIND == PB_KIND_CUBE) {  // the face as an image of its own (N rows of pitch w): the taps stay on it
+            const int n = pb_cube_n(P.src);
+            const uint8_t* face = s + 3ull * ((unsigned long long)pb_cube_row0(q.face, n) * (unsigned)P.src.width + (unsigned)pb_cube_col0(q.face, n));
+            return q.live ? rgb<false>(face, q.fy, q.fx, n, P.src.width, 0, n, false) : 0u;
+        }
         return q.live ? rgb<SRC_KIND == PB_KIND_PANO>(s, q.fy, q.fx, P.src.height, P.src.width, 0, P.src.width, false) : 0u;
     }
     static __device__ __forceinline__ unsigned eye(const PbParams& P, const uint8_t* __restrict__ s, double lat, double sl, double cl, int we, double cx,

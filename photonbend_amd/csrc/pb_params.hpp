@@ -105,6 +105,10 @@ static inline void pb_derive(PbParams& P) {
         if (d.kind == PB_KIND_DOUBLE) {
             const double half = (double)P.dst_half_w;
             P.dst_x0 = -half / 2 + 0.5;
+        } else if (d.kind == PB_KIND_CUBE) {  // the face camera's first samples (N x N: projection.py:177-180)
+            const double N = (double)(d.height / 2);
+            P.dst_x0 = -N / 2 + 0.5;
+            P.dst_y0 = N / 2 - 0.5;
         } else {
             P.dst_x0 = -W / 2 + 0.5;
         }
@@ -129,6 +133,10 @@ static inline void pb_derive(PbParams& P) {
         if (s.kind == PB_KIND_DOUBLE) {
             P.src_cx = (double)P.src_eye_w / 2 - 0.5;
             P.src_cx_r = (double)P.src_eye_w_right / 2 - 0.5;
+        } else if (s.kind == PB_KIND_CUBE) {  // the face camera's centre (N x N: projection.py:274)
+            const double N = (double)(s.height / 2);
+            P.src_cy = N / 2 - 0.5;
+            P.src_cx = P.src_cx_r = N / 2 - 0.5;
         } else {
             P.src_cx = w / 2 - 0.5;
             P.src_cx_r = P.src_cx;

@@ -26,6 +26,7 @@
 struct PbCoord {
     double lat, lon;
     bool inv;
+    int face;  // a cube DESTINATION's face of the pixel (0..5: left, front, right, up, back, down), read by pb_rotate_all alone
 };
 
 // ---- NumPy / x86 cast semantics ------------------------------------------------
@@ -107,16 +108,59 @@ __device__ __forceinline__ double pb_lens_inverse(const PbParams& P, double r) {
 // |x| == |y| and the axes, where the pre-truncation longitude coordinate of a pano source is an exact integer (SURVEY 7 hard part 2).
 __device__ __forceinline__ double pb_atan2(double y, double x) { return pb_arg_np(y, x); }
 
+// ---- the cube map (PB_KIND_CUBE) ---------------------------------------------
+// A cube of face size N is a (2N, 3N) frame of six N x N faces - top row left, front, right; bottom row up, back, down - and face k is
+// the reference's CameraImage(N x N, fov = 2 pi / 3, rectilinear()) with f_distance N / 2 behind ONE rotate_coordinate_map whose matrix
+// M_k has the face's (right, forward, up) world unit vectors as its columns: exact 0 and +-1, determinant +1.  The parameter block holds
+// a cube end as that camera (lens rectilinear, fov 2 pi / 3, f_distance N / 2: pb_to_end), so the camera formulas of both stages run
+// unchanged on the face-local pixel; what is the cube's own is below.
+// PB_CUBE_CODE[k]: the nine entries of M_k, row-major, two bits each - 0: +0.0, 1: +1.0, 2: -1.0.
+__device__ static const unsigned PB_CUBE_CODE[6] = {
+    // left  r = +x, f = -z, u = +y : { 1, 0, 0,  0, 0, 1,  0,-1, 0}
+    1u | (1u << 10) | (2u << 14),
+    // front r = +z, f = +x, u = +y : { 0, 1, 0,  0, 0, 1,  1, 0, 0}
+    (1u << 2) | (1u << 10) | (1u << 12),
+    // right r = -x, f = +z, u = +y : {-1, 0, 0,  0, 0, 1,  0, 1, 0}
+    2u | (1u << 10) | (1u << 14),
+    // up    r = +z, f = +y, u = -x : { 0, 0,-1,  0, 1, 0,  1, 0, 0}
+    (2u << 4) | (1u << 8) | (1u << 12),
+    // back  r = -z, f = -x, u = +y : { 0,-1, 0,  0, 0, 1, -1, 0, 0}
+    (2u << 2) | (1u << 10) | (2u << 12),
+    // down  r = +z, f = -y, u = +x : { 0, 0, 1,  0,-1, 0,  1, 0, 0}
+    (1u << 4) | (2u << 8) | (1u << 12),
+};
+// entry (row, col) of M_face (TRANSPOSED: of its transpose), as the float64 the reference's matmul multiplies by
+template <bool TRANSPOSED>
+__device__ __forceinline__ double pb_cube_entry(int face, int row, int col) {
+    const unsigned code = (PB_CUBE_CODE[face] >> (2 * (TRANSPOSED ? col * 3 + row : row * 3 + col))) & 3u;
+    return code == 0u ? 0.0 : (code == 1u ? 1.0 : -1.0);
+}
+template <bool TRANSPOSED>
+__device__ __forceinline__ void pb_cube_matrix(int face, double M[9]) {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) M[e] = pb_cube_entry<TRANSPOSED>(face, e / 3, e % 3);
+}
+__device__ __forceinline__ int pb_cube_n(const PbEnd& e) { return e.height >> 1; }  // (pb_end_ok: height = 2N, width = 3N)
+
 // ---- stage A ---------------------------------------------------------------------
 __device__ __forceinline__ PbCoord pb_dst_coord(const PbParams& P, int i, int j) {
     PbCoord c;
     const PbEnd& d = P.dst;
+    c.face = 0;
     if (d.kind == PB_KIND_PANO) {
         // linspace: k * step + start (two roundings), last sample = stop
         c.lat = (i == d.height - 1 && d.height > 1) ? PB_PI : ((double)i * P.pano_lat_step + 0.0);
         c.lon = (j == d.width - 1 && d.width > 1) ? P.pano_lon_stop : ((double)j * P.pano_lon_step + P.pano_lon_start);
         c.inv = false;
         return c;
+    }
+    if (d.kind == PB_KIND_CUBE) {
+        // the face and the pixel on it: the face's camera map follows (dst_x0 / dst_y0 / f_distance / fov are the face camera's, and
+        // lat <= atan(sqrt(2) (N - 1) / N) < fov / 2: no pixel is invalid); its rotation is pb_rotate_all's first
+        const int n = pb_cube_n(d), fr = i >= n, fc = (j >= n) + (j >= 2 * n);
+        i -= fr ? n : 0;
+        j -= fc * n;
+        c.face = fr * 3 + fc;
     }
     double x, y;
     y = P.dst_y0 - (double)i;  // exact: i * (-1.0) + (H/2 - 0.5)
@@ -152,10 +196,18 @@ __device__ __forceinline__ PbCoord pb_dst_coord_real(const PbParams& P, double f
     PbCoord c;
     const PbEnd& d = P.dst;
     c.inv = false;
+    c.face = 0;
     if (d.kind == PB_KIND_PANO) {
         c.lat = fi * P.pano_lat_step;
         c.lon = fj * P.pano_lon_step + P.pano_lon_start;
         return c;
+    }
+    if (d.kind == PB_KIND_CUBE) {  // (a tile's nodes are pixel centres of the tile: one face, or the tile is listed as failed)
+        const double n = (double)pb_cube_n(d);
+        const int fr = fi >= n, fc = (fj >= n) + (fj >= 2.0 * n);
+        fi -= fr ? n : 0.0;
+        fj -= (double)fc * n;
+        c.face = fr * 3 + fc;
     }
     double x;
     const double y = P.dst_y0 - fi;
@@ -181,6 +233,76 @@ __device__ __forceinline__ PbCoord pb_dst_coord_real(const PbParams& P, double f
 #define PB_KIND_EYE_L 3
 #define PB_KIND_EYE_R 4
 
+// ---- stage C of a cube SOURCE --------------------------------------------------------------------------------
+// The incoming (lat, lon) is the map after all rotations.  v = (x, y, z) exactly as pb_rotate forms it; the largest |component| picks the
+// axis (x if |x| >= |y| and |x| >= |z|, otherwise y if |y| >= |z|, otherwise z) and its sign bit the face: +x front, -x back, +y up,
+// -y down, +z right, -z left.  The sample is the face camera's for the map after one more rotate_coordinate_map with M_face transposed:
+// arccos / atan2 of the permuted vector, np.tan, np.exp(1j lon), truncation toward zero - (-1, 0) -> 0 included.  A NaN falls through
+// both comparisons to the z axis, as the NumPy definition's masks do.
+struct PbCubePos {
+    int face;       // 0..5: left, front, right, up, back, down
+    double fy, fx;  // pre-truncation position on the face (face-local pixels)
+};
+__device__ __forceinline__ int pb_cube_face_of(double x, double y, double z) {
+    const double a = fabs(x), b = fabs(y), c = fabs(z);
+    if (a >= b && a >= c) return (__double_as_longlong(x) < 0) ? 4 : 1;
+    if (b >= c) return (__double_as_longlong(y) < 0) ? 5 : 3;
+    return (__double_as_longlong(z) < 0) ? 0 : 2;
+}
+__device__ __forceinline__ PbCubePos pb_src_cube_pos(const PbParams& P, const PbCoord& c) {
+    PbCubePos q;
+    const double s = pb_sin_np(c.lat), yy = pb_cos_np(c.lat);  // rotation.py:129-131
+    double sl, cl;
+    pb_expi_np(c.lon, &sl, &cl);
+    const double x = cl * s, z = sl * s;
+    q.face = pb_cube_face_of(x, yy, z);
+    double M[9];
+    pb_cube_matrix<true>(q.face, M);
+    const double vx = fma(M[2], z, fma(M[0], x, M[1] * yy));  // np.matmul's order, as in pb_rotate
+    const double vy = fma(M[5], z, fma(M[3], x, M[4] * yy));
+    const double vz = fma(M[8], z, fma(M[6], x, M[7] * yy));
+    const double lat = pb_acos_np(vy), lon = pb_atan2(vz, vx);
+    const double t = pb_tan_np(lat);                                             // lens.py:97-103
+    const double dist = ((lat < 0.0 || lat > P.rect_max) ? __builtin_nan("") : t) * P.src.f_distance;
+    pb_expi_np(lon, &sl, &cl);                                                   // projection.py:252
+    q.fy = ((sl * dist) * -1.0) + P.src_cy;
+    q.fx = (cl * dist) + P.src_cx;
+    return q;
+}
+// the face's first row / column in the frame
+__device__ __forceinline__ int pb_cube_row0(int face, int n) { return face >= 3 ? n : 0; }
+__device__ __forceinline__ int pb_cube_col0(int face, int n) { return (face >= 3 ? face - 3 : face) * n; }
+// linear index into the full (2N, 3N) frame, or -1; f0 / f1: the pre-truncation position in FRAME coordinates
+__device__ __forceinline__ int pb_src_cube_index_pre(const PbParams& P, const PbCoord& c, double& f0, double& f1) {
+    f0 = f1 = 0.0;
+    if (c.inv) return -1;  // (the reference zeroes such entries, samples, then paints them black)
+    const PbCubePos q = pb_src_cube_pos(P, c);
+    const int n = pb_cube_n(P.src), r0 = pb_cube_row0(q.face, n), c0 = pb_cube_col0(q.face, n);
+    f0 = q.fy + (double)r0;
+    f1 = q.fx + (double)c0;
+    const long long y = pb_cvt_i64(q.fy), x = pb_cvt_i64(q.fx);
+    if (y >= n || y < 0 || x >= n || x < 0) return -1;
+    return ((int)y + r0) * P.src.width + (int)x + c0;
+}
+__device__ __forceinline__ int pb_src_cube_index(const PbParams& P, const PbCoord& c) {
+    double f0, f1;
+    return pb_src_cube_index_pre(P, c, f0, f1);
+}
+// the same position in frame coordinates by plain real arithmetic (model building only, like pb_dst_coord_real): on the selected face
+// tan(lat') cos(lon') = right / forward and tan(lat') sin(lon') = up / forward
+__device__ __forceinline__ void pb_src_cube_real(const PbParams& P, const PbCoord& c, double& f0, double& f1) {
+    double sl, cl;
+    sincos(c.lon, &sl, &cl);
+    const double s = sin(c.lat), yy = cos(c.lat), x = cl * s, z = sl * s;
+    const int face = pb_cube_face_of(x, yy, z);
+    double M[9];
+    pb_cube_matrix<true>(face, M);
+    const double r = M[0] * x + M[1] * yy + M[2] * z, f = M[3] * x + M[4] * yy + M[5] * z, u = M[6] * x + M[7] * yy + M[8] * z;
+    const int n = pb_cube_n(P.src);
+    f0 = ((u / f) * P.src.f_distance) * -1.0 + P.src_cy + (double)pb_cube_row0(face, n);
+    f1 = (r / f) * P.src.f_distance + P.src_cx + (double)pb_cube_col0(face, n);
+}
+
 // columns of the frame a source kind may sample: [cmin, cmax)
 template <int SRC_KIND>
 __device__ __forceinline__ void pb_src_col_range(const PbParams& P, int& cmin, int& cmax) {
@@ -194,6 +316,9 @@ __device__ __forceinline__ void pb_src_pretrunc(const PbParams& P, const PbCoord
     if (SRC_KIND == PB_KIND_PANO) {
         f0 = c.lat / P.src_hseg;
         f1 = c.lon / P.src_wseg + P.src_half_w;
+    } else if (SRC_KIND == PB_KIND_CUBE) {  // frame coordinates of the position on the selected face
+        if (SMOOTH) pb_src_cube_real(P, c, f0, f1);
+        else (void)pb_src_cube_index_pre(P, c, f0, f1);
     } else if (SRC_KIND == PB_KIND_EYE_R) {
         // the right eye looks backwards (projection.py:426-427) and is mirrored: sampled column =
         // eye_w + (eye_w_right - 1 - x) with x = trunc(re + cx_r), i.e. floor(w - (re + cx_r)) wherever that
@@ -238,24 +363,34 @@ __device__ __forceinline__ bool pb_dst_inv_pred(const PbParams& P, long long n4,
 }
 
 // ---- stage B ---------------------------------------------------------------------
+// the direction of a map entry, v = (x, yy, z)   rotation.py:129-132
+__device__ __forceinline__ void pb_rotate_vec(const PbCoord& c, double& x, double& yy, double& z) {
+    double s, sl, cl;
+    s = pb_sin_np(c.lat);           // np.sin(lat), np.cos(lat): two calls in the reference, two functions in libm   rotation.py:129-131
+    yy = pb_cos_np(c.lat);
+    pb_expi_np(c.lon, &sl, &cl);  // np.exp(lon * 1j)
+    x = cl * s;                     // rotation.py:130-132
+    z = sl * s;
+}
+// ... and the map entry of a rotated direction
+__device__ __forceinline__ PbCoord pb_rotate_back(PbCoord c, double vx, double vy, double vz) {
+    c.lat = pb_acos_np(vy);   // rotation.py:158 (NumPy's SIMD arccos, bit for bit: pb_math_np.hpp)
+    c.lon = pb_atan2(vz, vx); // rotation.py:159-164
+    return c;
+}
 __device__ __forceinline__ PbCoord pb_rotate(const double* __restrict__ R, PbCoord c) {
     if (c.inv) {  // rotation.py:125, :168-175
         c.lat = 0.0;
         c.lon = 0.0;
         return c;
     }
-    double s, yy, sl, cl;
-    s = pb_sin_np(c.lat);           // np.sin(lat), np.cos(lat): two calls in the reference, two functions in libm   rotation.py:129-131
-    yy = pb_cos_np(c.lat);
-    pb_expi_np(c.lon, &sl, &cl);  // np.exp(lon * 1j)
-    const double x = cl * s, z = sl * s;  // rotation.py:130-132
+    double x, yy, z;
+    pb_rotate_vec(c, x, yy, z);
     // accumulation order of the BLAS behind np.matmul (probe)
     const double vx = fma(R[2], z, fma(R[0], x, R[1] * yy));
     const double vy = fma(R[5], z, fma(R[3], x, R[4] * yy));
     const double vz = fma(R[8], z, fma(R[6], x, R[7] * yy));
-    c.lat = pb_acos_np(vy);   // rotation.py:158 (NumPy's SIMD arccos, bit for bit: pb_math_np.hpp)
-    c.lon = pb_atan2(vz, vx); // rotation.py:159-164
-    return c;
+    return pb_rotate_back(c, vx, vy, vz);
 }
 
 // The whole rotation chain of one pixel.  ROT = the number of rotations when the caller knows it at COMPILE time (0 or 1: what the
@@ -269,12 +404,42 @@ template <int ROT = PB_ROT_ANY>
 __device__ __forceinline__ PbCoord pb_rotate_all(const PbParams& P, PbCoord c) {
     if (ROT == 0) return c;
     if (ROT == 1) return pb_rotate(P.R[0], c);
-    for (int k = 0; k < P.n_rot; ++k) c = pb_rotate(P.R[k], c);
+    // A cube destination's map is the face-rotated one: M_face, a constant of the kind, runs first and takes none of the caller's
+    // PB_MAX_ROTATIONS slots (such plans always come here: pb_rot_count).  The loop holds ONE copy of the rotation's transcendental
+    // halves; only the nine multiply-adds between them come twice - the caller's matrix from the parameter block (scalar operands), the
+    // face's from its code (per lane: a tile may straddle faces).
+    for (int k = (P.dst.kind == PB_KIND_CUBE) ? -1 : 0; k < P.n_rot; ++k) {
+        if (c.inv) {  // (pb_rotate's: rotation.py:125, :168-175)
+            c.lat = 0.0;
+            c.lon = 0.0;
+            continue;
+        }
+        double x, yy, z, vx, vy, vz;
+        pb_rotate_vec(c, x, yy, z);
+        if (k < 0) {
+            const int f = c.face;
+            vx = fma(pb_cube_entry<false>(f, 0, 2), z, fma(pb_cube_entry<false>(f, 0, 0), x, pb_cube_entry<false>(f, 0, 1) * yy));
+            vy = fma(pb_cube_entry<false>(f, 1, 2), z, fma(pb_cube_entry<false>(f, 1, 0), x, pb_cube_entry<false>(f, 1, 1) * yy));
+            vz = fma(pb_cube_entry<false>(f, 2, 2), z, fma(pb_cube_entry<false>(f, 2, 0), x, pb_cube_entry<false>(f, 2, 1) * yy));
+        } else {
+            const double* __restrict__ R = P.R[k];
+            vx = fma(R[2], z, fma(R[0], x, R[1] * yy));
+            vy = fma(R[5], z, fma(R[3], x, R[4] * yy));
+            vz = fma(R[8], z, fma(R[6], x, R[7] * yy));
+        }
+        c = pb_rotate_back(c, vx, vy, vz);
+    }
     return c;
 }
-// launches kernel<KIND, ROT> for the plan's rotation count
-#define PB_LAUNCH_BY_ROT(n_rot, kernel, KIND, ...)                                      \
+// the rotation count PB_LAUNCH_BY_ROT instantiates for: a cube destination's chain always holds a rotation, and only the run-time loop
+// above knows the face's
+static inline int pb_rot_count(const PbParams& P) { return P.dst.kind == PB_KIND_CUBE ? PB_MAX_ROTATIONS + 1 : P.n_rot; }
+// launches kernel<KIND, ROT> for the plan's rotation count.  It takes the PARAMETER BLOCK, not a count: the compile-time instantiations
+// (ROT 0 and 1) know nothing of a cube destination's face rotation, and this macro - the only way those instantiations are launched - is
+// where a cube destination is kept away from them.
+#define PB_LAUNCH_BY_ROT(P_, kernel, KIND, ...)                                         \
     do {                                                                                \
+        const int n_rot = pb_rot_count(P_);                                             \
         if ((n_rot) == 0) hipLaunchKernelGGL((kernel<KIND, 0>), __VA_ARGS__);           \
         else if ((n_rot) == 1) hipLaunchKernelGGL((kernel<KIND, 1>), __VA_ARGS__);      \
         else hipLaunchKernelGGL((kernel<KIND, PB_ROT_ANY>), __VA_ARGS__);               \

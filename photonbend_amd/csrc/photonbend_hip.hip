@@ -499,16 +499,17 @@ static int pb_poly_register(const PbPoly& L, int* lens_out) {
 }
 
 enum { PB_ROLE_DST = 1, PB_ROLE_SRC = 2, PB_ROLE_CUSTOM_OK = 4 };
+static bool pb_has_lens(int kind) { return kind != PB_KIND_PANO && kind != PB_KIND_CUBE; }  // (their pb_proj.lens / fov / f_distance are ignored)
 static bool pb_end_ok(const pb_proj* p, std::string& why, int role = PB_ROLE_DST | PB_ROLE_SRC) {
     if (!p) {
         why = "null pb_proj";
         return false;
     }
-    if (p->kind < PB_KIND_CAMERA || p->kind > PB_KIND_PANO) {
+    if ((p->kind < PB_KIND_CAMERA || p->kind > PB_KIND_PANO) && p->kind != PB_KIND_CUBE) {
         why = "pb_proj.kind out of range";
         return false;
     }
-    if (p->kind != PB_KIND_PANO && (p->lens < PB_LENS_EQUIDISTANT || p->lens > PB_LENS_THOBY) && !pb_poly_lookup(p->lens, nullptr) &&
+    if (pb_has_lens(p->kind) && (p->lens < PB_LENS_EQUIDISTANT || p->lens > PB_LENS_THOBY) && !pb_poly_lookup(p->lens, nullptr) &&
         !((role & PB_ROLE_CUSTOM_OK) && p->lens == PB_LENS_CUSTOM)) {
         why = p->lens == PB_LENS_CUSTOM ? "PB_LENS_CUSTOM is valid only where the host supplies the lens values (pb_index_from_map_i32 with distance planes)"
                                         : p->lens >= PB_LENS_POLYNOMIAL_BASE ? "pb_proj.lens is not a registered polynomial lens of this process (pb_lens_polynomial)"
@@ -529,6 +530,10 @@ static bool pb_end_ok(const pb_proj* p, std::string& why, int role = PB_ROLE_DST
         why = "a double-fisheye frame needs at least two columns";
         return false;
     }
+    if (p->kind == PB_KIND_CUBE && ((p->height & 1) || p->width != 3 * (p->height / 2))) {
+        why = "a cube map is a (2N, 3N) frame: six N x N faces in a 3 x 2 grid";
+        return false;
+    }
     return true;
 }
 
@@ -544,11 +549,18 @@ static PbEndX pb_to_end(const pb_proj* p) {
     PbEnd& e = x.e;
     e.kind = p->kind;
     e.lens = (p->kind == PB_KIND_PANO) ? PB_LENS_EQUIDISTANT : p->lens;
-    if (p->kind != PB_KIND_PANO && pb_poly_lookup(p->lens, &x.poly)) e.lens = PB_LENS_POLYNOMIAL;
+    if (pb_has_lens(p->kind) && pb_poly_lookup(p->lens, &x.poly)) e.lens = PB_LENS_POLYNOMIAL;
     e.height = p->height;
     e.width = p->width;
     e.fov = p->fov;
     e.f_distance = p->f_distance;
+    if (p->kind == PB_KIND_CUBE) {
+        // a face IS CameraImage(N x N, fov = 2 pi / 3, rectilinear()) with f_distance set to exactly N / 2: the block holds
+        // that camera, whatever the caller left in the ignored fields
+        e.lens = PB_LENS_RECTILINEAR;
+        e.fov = 2 * PB_PI / 3;
+        e.f_distance = (double)(p->height / 2) / 2;
+    }
     return x;
 }
 
@@ -584,6 +596,9 @@ static bool pb_fast_possible(const PbParams& P) {
 // the cast gives 0 whatever the sample - no restriction.)
 static bool pb_bilinear_tiles_allowed(const PbParams& P) {
     // (below 180 degrees the band turns inside out; it exists down to 179.5 degrees, with factors from 1 up to 0.5 deg / (180 deg - fov))
+    // THE place that says a cube source has no tile tables in the interpolated modes (the definition per pixel on the selected face, DESIGN
+    // 3.10): the table builders ask here, and pb_route follows from the tables' absence
+    if (P.src.kind == PB_KIND_CUBE) return false;
     return !(P.src.kind == PB_KIND_DOUBLE && P.mrg_range != 0.0 && fabs(P.mrg_range) < 0.999 * (PB_PI / 180.0));  // (181 / 179 degrees themselves: tiles)
 }
 #define PB_INTERP_CATMULL_ROM 2  // (a routing id of this file only: the supersampled entry points take PB_INTERP_NEAREST and PB_INTERP_BILINEAR)
@@ -596,14 +611,28 @@ static void pb_pick(bool first, F&& f) {
     if (first) f(PbInt<A>());
     else f(PbInt<B>());
 }
+// The SRC_KIND of the MODEL-evaluating kernels (hot, window, supersampled, interpolated tile kernels) of a single source.  A cube source
+// runs the camera's: what those kernels evaluate is a certified tile model, a frame-wide bounds test and the camera's truncation edge, and
+// pb_certify_kernel<PB_KIND_CUBE> compares that very evaluation with the cube's float64 chain for every pixel.
 template <class F>
-static void pb_pick_kind(const PbParams& P, F&& f) {  // (single sources)
+static void pb_pick_kind(const PbParams& P, F&& f) {
     pb_pick<PB_KIND_PANO, PB_KIND_CAMERA>(P.src.kind == PB_KIND_PANO, f);
 }
+// ... and of the kernels that run the float64 chain of a single source: a cube's own
 template <class F>
-static void pb_pick_any_kind(const PbParams& P, F&& f) {
+static void pb_pick_exact_kind(const PbParams& P, F&& f) {
+    if (P.src.kind == PB_KIND_CUBE) f(PbInt<PB_KIND_CUBE>());
+    else pb_pick_kind(P, f);
+}
+template <class F>
+static void pb_pick_lensed_kind(const PbParams& P, F&& f) {  // (every source but a cube, whose kernels of the caller have names of their own)
     if (P.src.kind == PB_KIND_DOUBLE) f(PbInt<PB_KIND_DOUBLE>());
     else pb_pick_kind(P, f);
+}
+template <class F>
+static void pb_pick_any_kind(const PbParams& P, F&& f) {  // (float64 chain, any source)
+    if (P.src.kind == PB_KIND_DOUBLE) f(PbInt<PB_KIND_DOUBLE>());
+    else pb_pick_exact_kind(P, f);
 }
 template <class F>
 static void pb_pick_filter(int filter, F&& f) {  // (the FILTER of the shared sampler kernels, pb_kernels_bilinear.hpp)
@@ -685,7 +714,11 @@ static int pb_plan_prepare_on_device(pb_plan* pl) {
     PB_HIP(scratch.alloc(16));
     int rc = PB_OK;
     do {
-        if (P.dst.kind != PB_KIND_PANO) {
+        if (P.dst.kind == PB_KIND_CUBE) {
+            // no pixel of a cube is invalid (the largest incidence angle on a face is below 54.74 degrees, fov / 2 is 60): thresholds no
+            // (2x)^2 + (2y)^2 reaches, so that the tile code's integer validity test never fires
+            for (int sd = 0; sd < 2; ++sd) P.inv_lo[sd] = P.inv_hi[sd] = (int64_t)1 << 62;
+        } else if (P.dst.kind != PB_KIND_PANO) {
             hipLaunchKernelGGL(pb_threshold_kernel, dim3(1), dim3(128), 0, 0, P, scratch);
             // (a chain of ~10 dependent square roots and arcsines, and the kernel's launch: a single source's tile tables are allocated meanwhile)
             if (P.src.kind != PB_KIND_DOUBLE && pb_fast_possible(P)) {
@@ -726,10 +759,10 @@ static int pb_plan_prepare_on_device(pb_plan* pl) {
             const double* col_sc = (P.dst.kind == PB_KIND_PANO && P.n_rot == 0 && c.sep_cols) ? reinterpret_cast<const double*>(c.sep_cols.get()) : nullptr;
             hipLaunchKernelGGL(pb_model_kernel<PB_KIND_EYE_L>, grid, block, 0, 0, P, c.table);
             hipLaunchKernelGGL(pb_window_kernel<PB_KIND_EYE_L>, grid, block, 0, 0, P, c.table);
-            PB_LAUNCH_BY_ROT(P.n_rot, pb_certify_kernel, PB_KIND_EYE_L, grid, block, 0, 0, P, c.table, c.fail_tiles, c.fix_px, cap, counters, col_sc);
+            PB_LAUNCH_BY_ROT(P, pb_certify_kernel, PB_KIND_EYE_L, grid, block, 0, 0, P, c.table, c.fail_tiles, c.fix_px, cap, counters, col_sc);
             hipLaunchKernelGGL(pb_model_kernel<PB_KIND_EYE_R>, grid, block, 0, 0, P, c.table_r);
             hipLaunchKernelGGL(pb_window_kernel<PB_KIND_EYE_R>, grid, block, 0, 0, P, c.table_r);
-            PB_LAUNCH_BY_ROT(P.n_rot, pb_certify_kernel, PB_KIND_EYE_R, grid, block, 0, 0, P, c.table_r, c.fail_tiles, c.fix_px, cap, counters, col_sc);
+            PB_LAUNCH_BY_ROT(P, pb_certify_kernel, PB_KIND_EYE_R, grid, block, 0, 0, P, c.table_r, c.fail_tiles, c.fix_px, cap, counters, col_sc);
             hipLaunchKernelGGL(pb_count_flags_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, 0, c.table, ntiles, counters);
             hipLaunchKernelGGL(pb_count_flags_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, 0, c.table_r, ntiles, counters);
             const unsigned lat_capacity = ntiles < 65536u ? ntiles : 65536u;  // <= 512 MiB of latitudes
@@ -784,14 +817,19 @@ static int pb_plan_prepare_on_device(pb_plan* pl) {
         if (P.src.kind == PB_KIND_PANO) {
             hipLaunchKernelGGL(pb_model_kernel<PB_KIND_PANO>, grid, block, 0, 0, P, c.table);
             hipLaunchKernelGGL(pb_window_kernel<PB_KIND_PANO>, grid, block, 0, 0, P, c.table);
-            PB_LAUNCH_BY_ROT(P.n_rot, pb_certify_kernel, PB_KIND_PANO, grid, block, 0, 0, P, c.table, c.fail_tiles, c.fix_px, cap, counters);
+            PB_LAUNCH_BY_ROT(P, pb_certify_kernel, PB_KIND_PANO, grid, block, 0, 0, P, c.table, c.fail_tiles, c.fix_px, cap, counters);
+        } else if (P.src.kind == PB_KIND_CUBE) {
+            // tiles whose pixels fall on more than one face get no usable model from their 25 nodes and fail certification by themselves
+            hipLaunchKernelGGL(pb_model_kernel<PB_KIND_CUBE>, grid, block, 0, 0, P, c.table);
+            hipLaunchKernelGGL(pb_window_kernel<PB_KIND_CUBE>, grid, block, 0, 0, P, c.table);
+            PB_LAUNCH_BY_ROT(P, pb_certify_kernel, PB_KIND_CUBE, grid, block, 0, 0, P, c.table, c.fail_tiles, c.fix_px, cap, counters);
         } else {
             PbBlock<double> col_sc;  // (unrotated panorama destination: one sine / cosine per column instead of one per pixel)
             if (P.dst.kind == PB_KIND_PANO && P.n_rot == 0 && col_sc.alloc((size_t)P.dst.width * 2) == hipSuccess)
                 hipLaunchKernelGGL(pb_col_sincos_kernel, dim3((P.dst.width + 255) / 256), dim3(256), 0, 0, P, col_sc);
             hipLaunchKernelGGL(pb_model_kernel<PB_KIND_CAMERA>, grid, block, 0, 0, P, c.table);
             hipLaunchKernelGGL(pb_window_kernel<PB_KIND_CAMERA>, grid, block, 0, 0, P, c.table);
-            PB_LAUNCH_BY_ROT(P.n_rot, pb_certify_kernel, PB_KIND_CAMERA, grid, block, 0, 0, P, c.table, c.fail_tiles, c.fix_px, cap, counters, (const double*)col_sc);
+            PB_LAUNCH_BY_ROT(P, pb_certify_kernel, PB_KIND_CAMERA, grid, block, 0, 0, P, c.table, c.fail_tiles, c.fix_px, cap, counters, (const double*)col_sc);
             if (col_sc) (void)hipDeviceSynchronize();  // (the block goes back at the end of this scope)
         }
         PB_STAGE("enqueue+colsync");
@@ -812,7 +850,7 @@ static int pb_plan_prepare_on_device(pb_plan* pl) {
                 c.fix_idx.alloc((size_t)(np ? np : 1)) != hipSuccess) { rc = PB_ERR_HIP; break; }
             const unsigned blocks = 4u * nf + (np + PB_BLOCK - 1) / PB_BLOCK;
             if (blocks) {
-                pb_pick_kind(P, [&](auto K) {
+                pb_pick_exact_kind(P, [&](auto K) {
                     hipLaunchKernelGGL(pb_fix_tables_kernel<K.value>, dim3(blocks), dim3(PB_BLOCK), 0, 0, P, c.table, c.fail_tiles, (int)nf, c.fix_px,
                                        (int)np, c.idx_tab, c.fix_idx);
                 });
@@ -910,6 +948,7 @@ static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned fl
             return (bil && tiled && pl->cert.dbl_ready && pl->bil.lt.entries && pl->bil.tiles && pl->bil.dbl_tables)
                        ? PbRoute{PbRoute::BIL_DOUBLE, windows, interpolation}
                        : PbRoute{PbRoute::INTERP_DOUBLE_FLOAT64, false, interpolation};
+        // (a cube source never has bil.tiles - pb_bilinear_tiles_allowed - and so takes INTERP_FLOAT64: the definition per pixel on the selected face)
         return (pb_use_fast(pl) && pl->bil.lt.entries && pl->bil.tiles) ? PbRoute{PbRoute::INTERP_TILES, bil && windows, interpolation}
                                                                     : PbRoute{PbRoute::INTERP_FLOAT64, false, interpolation};
     }
@@ -984,7 +1023,7 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
         case PbRoute::FLOAT64: {
             const int dst_aligned = (((uintptr_t)dst | ds) & 3u) == 0;
             pb_pick_any_kind(P, [&](auto K) {
-                PB_LAUNCH_BY_ROT(P.n_rot, pb_remap_kernel, K.value, dim3(pb_blocks((npx + PB_PX - 1) / PB_PX)), dim3(PB_BLOCK), 0, st, P, src, dst, n_frames,
+                PB_LAUNCH_BY_ROT(P, pb_remap_kernel, K.value, dim3(pb_blocks((npx + PB_PX - 1) / PB_PX)), dim3(PB_BLOCK), 0, st, P, src, dst, n_frames,
                                  ss, ds, dst_aligned);
             });
             break;
@@ -1064,6 +1103,12 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
             });
             break;
         case PbRoute::INTERP_FLOAT64:
+            if (P.src.kind == PB_KIND_CUBE) {
+                pb_pick_filter(r.filter, [&](auto F) {
+                    hipLaunchKernelGGL(pb_interp_cube_kernel<decltype(F)>, dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, src, dst, n_frames, ss, ds);
+                });
+                break;
+            }
             pb_pick_kind(P, [&](auto K) {
                 pb_pick_filter(r.filter, [&](auto F) {
                     hipLaunchKernelGGL((pb_interp_fix_kernel<decltype(F), K.value>), dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, nullptr, 1, src, dst,
@@ -1604,7 +1649,7 @@ static int pb_plan_prepare_full(pb_plan* pl, unsigned flags, int win_budget) {
     if (pl->cert.fast_ready || pl->cert.dbl_ready || pl->cert.sep_ready || pl->device >= 0) {
         // already prepared: the budget may change, and the opt-in bilinear mode's tables may be asked for (PB_PLAN_BILINEAR) by a plan
         // that was created without them
-        if ((flags & PB_PLAN_BILINEAR) && (pl->cert.fast_ready || pl->cert.dbl_ready) && !pl->bil.tiles) {
+        if ((flags & PB_PLAN_BILINEAR) && (pl->cert.fast_ready || pl->cert.dbl_ready) && !pl->bil.tiles && pb_bilinear_tiles_allowed(pl->P)) {
             pl->bil_wanted = 1;
             int rc = pb_build_bilinear_list(pl);
             if (rc == PB_OK) rc = pb_build_bilinear_launch(pl);
@@ -1926,7 +1971,7 @@ int pb_index_map_i32(const pb_plan* plan, int32_t* idx_dev, double* weights_dev,
         pb_launch_direct<1>(plan, nullptr, nullptr, 0, 0, 0, idx_dev, st);
     else
         pb_pick_any_kind(P, [&](auto K) {
-            PB_LAUNCH_BY_ROT(P.n_rot, pb_index_kernel, K.value, dim3(blocks), dim3(PB_BLOCK), 0, st, P, idx_dev, weights_dev);
+            PB_LAUNCH_BY_ROT(P, pb_index_kernel, K.value, dim3(blocks), dim3(PB_BLOCK), 0, st, P, idx_dev, weights_dev);
         });
     PB_HIP(hipGetLastError());
     return PB_OK;
@@ -2032,7 +2077,8 @@ int pb_coordmap_f64(const pb_proj* dst, double* map_dev, void* stream) {
     P.poly_dst = P.poly_src = d.poly;
     pb_derive(P);
     const unsigned blocks = pb_blocks((unsigned long long)P.dst.height * P.dst.width);
-    hipLaunchKernelGGL(pb_coordmap_kernel, dim3(blocks), dim3(PB_BLOCK), 0, (hipStream_t)stream, P, map_dev);
+    if (P.dst.kind == PB_KIND_CUBE) hipLaunchKernelGGL(pb_coordmap_cube_kernel, dim3(blocks), dim3(PB_BLOCK), 0, (hipStream_t)stream, P, map_dev);
+    else hipLaunchKernelGGL(pb_coordmap_kernel, dim3(blocks), dim3(PB_BLOCK), 0, (hipStream_t)stream, P, map_dev);
     PB_HIP(hipGetLastError());
     return PB_OK;
 }
@@ -2072,10 +2118,10 @@ static int pb_map_stage(bool null_argument, const pb_proj* src, unsigned roles, 
     return PB_OK;
 }
 static int pb_map_planes_ok(const pb_proj* src, const double* dist_l_dev, const double* dist_r_dev) {
-    if (src->kind != PB_KIND_PANO && src->lens == PB_LENS_CUSTOM && !dist_l_dev)
+    if (pb_has_lens(src->kind) && src->lens == PB_LENS_CUSTOM && !dist_l_dev)
         return pb_fail(PB_ERR_INVALID, "a PB_LENS_CUSTOM source needs the host-evaluated distance plane(s)");
     if (src->kind == PB_KIND_DOUBLE && dist_l_dev && !dist_r_dev) return pb_fail(PB_ERR_INVALID, "a double source needs both distance planes");
-    if (src->kind == PB_KIND_PANO && (dist_l_dev || dist_r_dev)) return pb_fail(PB_ERR_INVALID, "a panorama source has no lens");
+    if (!pb_has_lens(src->kind) && (dist_l_dev || dist_r_dev)) return pb_fail(PB_ERR_INVALID, src->kind == PB_KIND_CUBE ? "a cube source has no lens" : "a panorama source has no lens");
     return PB_OK;
 }
 
@@ -2090,7 +2136,14 @@ static int pb_sample_map_px(int filter, const pb_proj* src, double* map_dev, int
     const unsigned total = (unsigned)height * (unsigned)width;
     const auto launch = [&](auto* sample) {  // (the sample type: uint8_t or uint16_t)
         using SAMPLE = std::remove_pointer_t<decltype(sample)>;
-        pb_pick_any_kind(P, [&](auto K) {
+        if (P.src.kind == PB_KIND_CUBE) {
+            pb_pick_filter(filter, [&](auto F) {
+                hipLaunchKernelGGL((pb_sample_map_interp_cube_kernel<decltype(F), SAMPLE>), dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, (hipStream_t)stream, P, map_dev,
+                                   total, static_cast<const SAMPLE*>(img_dev), out_dev, channels);
+            });
+            return;
+        }
+        pb_pick_lensed_kind(P, [&](auto K) {
             pb_pick_filter(filter, [&](auto F) {
                 hipLaunchKernelGGL((pb_sample_map_interp_kernel<decltype(F), K.value, SAMPLE>), dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, (hipStream_t)stream,
                                    P, map_dev, total, dist_l_dev, dist_r_dev, static_cast<const SAMPLE*>(img_dev), out_dev, channels);
@@ -2533,7 +2586,7 @@ int pb_bcast_params(pb_comm* comm, pb_proj* dst, double* rot3x3, int* n_rot, pb_
             const pb_proj* ends[2] = {dst, src};
             for (int e = 0; e < 2; ++e) {
                 PbPoly L;
-                if (ends[e]->kind == PB_KIND_PANO || ends[e]->lens < PB_LENS_POLYNOMIAL_BASE) continue;
+                if (!pb_has_lens(ends[e]->kind) || ends[e]->lens < PB_LENS_POLYNOMIAL_BASE) continue;
                 if (!pb_poly_lookup(ends[e]->lens, &L)) {  // an id the root never registered must not travel: another rank's registry
                     block[0] = -1.0;                       // may hold a different lens under it - every rank returns PB_ERR_INVALID
                     break;
@@ -2561,7 +2614,7 @@ int pb_bcast_params(pb_comm* comm, pb_proj* dst, double* rot3x3, int* n_rot, pb_
     // ... and the receiver (the root included) registers them and writes ITS id into the projection it returns
     pb_proj* ends[2] = {dst, src};
     for (int e = 0; e < 2; ++e) {
-        if (ends[e]->kind == PB_KIND_PANO || ends[e]->lens != PB_LENS_POLYNOMIAL_BASE) continue;
+        if (!pb_has_lens(ends[e]->kind) || ends[e]->lens != PB_LENS_POLYNOMIAL_BASE) continue;
         int id = 0;
         const int rc = pb_lens_polynomial(block + PB_BLOCK_POLY + 5 * e, block[PB_BLOCK_POLY + 5 * e + 4], &id);
         if (rc != PB_OK) return rc;

@@ -49,13 +49,13 @@ def _proj_to_list(p: nat.pb_proj) -> List[float]:
 
 
 def _is_polynomial(p: nat.pb_proj) -> bool:
-    return p.kind != nat.KIND_PANO and p.lens >= nat.LENS_POLYNOMIAL_BASE
+    return p.kind not in nat.LENSLESS_KINDS and p.lens >= nat.LENS_POLYNOMIAL_BASE
 
 
 def _proj_from_list(v: Sequence[float], poly: Sequence[float] = ()) -> nat.pb_proj:
     """(the receiving rank registers a polynomial lens's coefficients and uses ITS id)"""
     lens = int(v[1])
-    if int(v[0]) != nat.KIND_PANO and lens >= nat.LENS_POLYNOMIAL_BASE:
+    if int(v[0]) not in nat.LENSLESS_KINDS and lens >= nat.LENS_POLYNOMIAL_BASE:
         if len(poly) != _POLY_FIELDS or not float(poly[4]) > 0.0:  # (a packed lens has max_theta > 0; zeros: the sender packed none)
             raise nat.PbError("corrupt parameter block (polynomial lens without coefficients)")
         lens = nat.lens_polynomial([float(x) for x in poly[:4]], float(poly[4]))

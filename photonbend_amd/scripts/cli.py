@@ -1,4 +1,5 @@
-"""The three photonbend commands on top of the GPU core - SURVEY 8 f-2.
+"""The three photonbend commands on top of the GPU core - SURVEY 8 f-2 - and two of our own beside them: pano-to-cubemap and
+cubemap-to-pano (the cube map is a (2N, 3N) image of six faces: left, front, right over up, back, down).
 
 Same command names, options and rules as the reference CLI (photonbend/scripts/main.py:28-35,
 commands/make_photo.py:52-141, alter_photo.py:51-162, make_pano.py:54-149, commands/__init__.py:53-191):
@@ -21,7 +22,7 @@ from PIL import Image
 from .. import core
 from .. import _native as nat
 from ..core.lens import equidistant, equisolid, orthographic, polynomial, rectilinear, stereographic
-from ..core.projection import CameraImage, DoubleCameraImage, PanoramaImage
+from ..core.projection import CameraImage, CubemapImage, DoubleCameraImage, PanoramaImage
 from ..core.rotation import Rotation
 from ..utils import to_radians
 
@@ -273,6 +274,64 @@ def make_pano(input_image, itype, lens, fov, output_image, rotation, size, super
     source = camera_object(itype, photo, radians_fov(fov, itype), lens, magnitude_for(itype, photo.shape))
     h = photo.shape[0] if size is None else size
     destiny = PanoramaImage(np.zeros((h, int(h * 2), 3), np.uint8))  # make_pano.py:142-149
+    run_chain(source, destiny, rotation, out, int(supersample), **_sampler(interpolation))
+
+
+def _cubemap_common(fn):
+    """-r, --interpolation and --supersample of the two cube map commands: the existing options under the existing rules."""
+    fn = click.option("-r", "--rotation", type=click.FLOAT, nargs=3, multiple=True, default=[], help=ROTATION_HELP)(fn)
+    fn = click.option("--supersample", type=click.Choice(["1", "2", "4"]), default="1", show_default=True,
+                      help="Antialiasing: each output pixel is the mean of n x n samples (1 = off).")(fn)
+    fn = click.option("--interpolation", type=click.Choice(list(INTERPOLATIONS)), default="nearest", show_default=True,
+                      help="The sampler: nearest, bilinear or catmull-rom (sharp when magnifying; not with --supersample).  From a cube map "
+                           "the interpolating samplers stay on one face: seams are not filtered, and the half texel along each face's top and "
+                           "left edge comes out black (thin dark seam lines; nearest has none).")(fn)
+    return fn
+
+
+@main.command("pano-to-cubemap")
+@click.argument("input_image", type=click.Path(exists=True, path_type=Path))
+@click.option("--face-size", type=click.INT, default=None, help="The side N of a face in pixels; the output is 3N wide and 2N high. [default: input height // 2]")
+@_cubemap_common
+@click.argument("output_image", type=click.Path(exists=False, path_type=Path))
+def pano_to_cubemap(input_image, face_size, output_image, rotation, supersample, interpolation):
+    """Make a cube map out of a panorama.
+
+    \b
+    INPUT is the path to the source panorama.
+    OUTPUT is the desired path of the cube map: six faces in a 3 x 2 grid, left, front, right over up, back, down.
+    """
+    out = checked_output(output_image)
+    pano = open_image(input_image)
+    n = pano.shape[0] // 2 if face_size is None else face_size
+    if n < 1:
+        raise click.BadParameter("a face needs at least one pixel", param_hint="--face-size")
+    destiny = CubemapImage(np.zeros((2 * n, 3 * n, 3), np.uint8))
+    run_chain(PanoramaImage(pano), destiny, rotation, out, int(supersample), **_sampler(interpolation))
+
+
+@main.command("cubemap-to-pano")
+@click.argument("input_image", type=click.Path(exists=True, path_type=Path))
+@click.option("--height", type=click.INT, default=None, help="The vertical size of the panorama (its width is twice that). [default: 2 x the face size]")
+@_cubemap_common
+@click.argument("output_image", type=click.Path(exists=False, path_type=Path))
+def cubemap_to_pano(input_image, height, output_image, rotation, supersample, interpolation):
+    """Make a panorama out of a cube map.
+
+    \b
+    INPUT is the path to the source cube map: a 3N x 2N image of six faces, left, front, right over up, back, down.
+    OUTPUT is the desired path of the destiny panorama.
+    """
+    out = checked_output(output_image)
+    cube = open_image(input_image)
+    try:
+        source = CubemapImage(cube)
+    except ValueError as exc:
+        raise click.UsageError(f"{input_image}: {exc}")
+    h = 2 * source.face_size if height is None else height
+    if h < 1:
+        raise click.BadParameter("a panorama needs at least one row", param_hint="--height")
+    destiny = PanoramaImage(np.zeros((h, 2 * h, 3), np.uint8))
     run_chain(source, destiny, rotation, out, int(supersample), **_sampler(interpolation))
 
 

@@ -1,10 +1,66 @@
 """Angle helpers and the panorama -> photo size rule, with the reference's operation order
-(photonbend/utils/__init__.py:27-118).  Host scalars only; nothing here touches a pixel."""
+(photonbend/utils/__init__.py:27-118), and the cube map's face layout (no reference counterpart).  Host scalars and array views only;
+nothing here computes a pixel."""
 
 import math
-from typing import Callable, Tuple
+from typing import Callable, Dict, Tuple
 
-__all__ = ["to_radians", "to_degrees", "calculate_size_panorama_to_photo"]
+__all__ = ["to_radians", "to_degrees", "calculate_size_panorama_to_photo", "CUBEMAP_FACES", "cubemap_faces", "cubemap_from_faces",
+           "cubemap_face_rotation"]
+
+# the six faces of a cube map in frame order: face k occupies rows (k // 3) N ... and columns (k % 3) N ... of the (2N, 3N) image
+CUBEMAP_FACES = ("left", "front", "right", "up", "back", "down")
+# face -> its (right, forward, up) world unit vectors; world axes are the rotation's: +x the panorama's centre column, +y its zenith,
+# +z 90 degrees to the right of centre
+_CUBEMAP_TRIPLES = {
+    "left": ((1, 0, 0), (0, 0, -1), (0, 1, 0)),
+    "front": ((0, 0, 1), (1, 0, 0), (0, 1, 0)),
+    "right": ((-1, 0, 0), (0, 0, 1), (0, 1, 0)),
+    "up": ((0, 0, 1), (0, 1, 0), (-1, 0, 0)),
+    "back": ((0, 0, -1), (-1, 0, 0), (0, 1, 0)),
+    "down": ((0, 0, 1), (0, -1, 0), (1, 0, 0)),
+}
+
+
+def cubemap_face_rotation(name: str):
+    """The 3 x 3 float64 matrix of a face: its right, forward and up vectors as columns (exact 0 and +-1, determinant +1).  A face of a
+    cube map is a 120-degree rectilinear camera of focal distance N / 2 behind a rotation with this matrix."""
+    import numpy as np
+
+    if name not in _CUBEMAP_TRIPLES:
+        raise KeyError(f"no cube map face {name!r}: the faces are {', '.join(CUBEMAP_FACES)}")
+    return np.array(_CUBEMAP_TRIPLES[name], dtype=np.float64).T + 0.0  # (+ 0.0: no negative zeros)
+
+
+def _cubemap_n(shape) -> int:
+    h, w = (int(shape[0]), int(shape[1])) if len(shape) >= 2 else (0, 0)
+    n = h // 2
+    if n < 1 or h != 2 * n or w != 3 * n:
+        raise ValueError(f"a cube map has shape (2N, 3N) + trailing: six N x N faces in a 3 x 2 grid, got {tuple(shape)}")
+    return n
+
+
+def cubemap_faces(image) -> Dict[str, "object"]:
+    """name -> the face's N x N (+ trailing) VIEW of a cube map image (an ndarray or anything sliceable the same way)."""
+    n = _cubemap_n(tuple(image.shape))
+    return {name: image[(k // 3) * n:(k // 3 + 1) * n, (k % 3) * n:(k % 3 + 1) * n] for k, name in enumerate(CUBEMAP_FACES)}
+
+
+def cubemap_from_faces(faces):
+    """The (2N, 3N) + trailing cube map of six equal square faces (a mapping by name): cubemap_faces' inverse, in NumPy.  Other layouts
+    (6 x 1, 1 x 6, a cross) are rearrangements of the same six arrays on the host."""
+    import numpy as np
+
+    missing = [name for name in CUBEMAP_FACES if name not in faces]
+    if missing or len(faces) != 6:
+        raise ValueError(f"a cube map needs exactly the faces {', '.join(CUBEMAP_FACES)}")
+    arrs = [np.asarray(faces[name]) for name in CUBEMAP_FACES]
+    first = arrs[0]
+    if first.ndim < 2 or first.shape[0] != first.shape[1] or first.shape[0] < 1:
+        raise ValueError(f"cube map faces are square, got {first.shape}")
+    if any(a.shape != first.shape or a.dtype != first.dtype for a in arrs):
+        raise ValueError("cube map faces must share one shape and sample type")
+    return np.concatenate([np.concatenate(arrs[:3], axis=1), np.concatenate(arrs[3:], axis=1)], axis=0)
 
 
 def to_radians(degrees: float) -> float:
