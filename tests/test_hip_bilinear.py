@@ -15,6 +15,7 @@ from oracle.synth import synth_frame
 from photonbend_amd import _native as nat
 from tests import helpers as H
 from tests.cases import Case, cam, case_by_name, dbl, full_cases, inscribed, pano
+from tests.interp_cases import TINY_BILINEAR
 
 pytestmark = pytest.mark.gpu
 
@@ -268,17 +269,7 @@ def test_a_stitch_with_a_merge_band_under_one_degree_runs_the_float64_kernels(fo
     assert torch.equal(plan.remap(frame), near64)
 
 
-_TINY = [
-    Case("tiny_pano_2x4", cam(33, 35, "equidistant", 180), pano(2, 4)),
-    Case("tiny_pano_3x6", cam(40, 40, "equidistant", 360, inscribed(40)), pano(3, 6)),
-    Case("tiny_cam_3x3", pano(5, 9), cam(3, 3, "equisolid", 180, inscribed(3))),
-    Case("tiny_cam_2x2", pano(64, 128), cam(2, 2, "equidistant", 180, inscribed(2))),
-    Case("tiny_double_2x4", pano(40, 80), dbl(2, 4, "equidistant", 190)),
-    Case("tiny_dst_1x1", cam(1, 1, "equidistant", 180, 0.5), pano(8, 16)),
-    Case("tiny_dst_1x2", pano(1, 2), pano(8, 16), [(10, 20, 30)]),
-    Case("tiny_pano_1x2", pano(70, 140), pano(1, 2)),
-    Case("tiny_pano_2x3", cam(64, 64, "rectilinear", 100, inscribed(64)), pano(2, 3)),
-]
+_TINY = TINY_BILINEAR  # (shared with tests/test_hip_catmull_rom_tiles.py, which adds sources and destinations for a 4 x 4 footprint)
 
 
 @pytest.mark.parametrize("case", _TINY, ids=lambda c: c.name)
