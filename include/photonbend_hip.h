@@ -15,13 +15,17 @@
  *                      -> src.process_coordinate_map()  chained lazily
  *                      (core/__init__.py:66-92)
  *   pb_remap_u8        that chain, fused: one work-item per output pixel
+ *   pb_remap_px        the same for the other arrays the reference's fancy indexing takes - grey (H, W),
+ *                      RGBA, 16-bit samples: pixels of 1, 2, 4, 6 or 8 bytes - in one launch
+ *                      (image[positions], projection.py:234-243, :545-546)
  *   pb_index_map_i32   the integer coordinate map inside process_coordinate_map
  *                      (projection.py:254-259, :545)
  *   pb_coordmap_f64    get_coordinate_map()  (projection.py:147, :341, :487)
  *   pb_rotate_f64      Rotation.rotate_coordinate_map()  (core/rotation.py:102-176)
  *   pb_sample_map_u8   process_coordinate_map(ndarray)  (projection.py:197, :408, :515)
  *
- * Images are uint8 (H, W, 3) RGB, row-major, tightly packed (core/__init__.py:31-36).
+ * Images are uint8 (H, W, 3) RGB, row-major, tightly packed (core/__init__.py:31-36); pb_remap_px, pb_gather_px and
+ * pb_gather_blend_u8 take the other layouts the reference accepts.
  * Coordinate maps are float64 (H, W, 3) = (latitude, longitude, invalid flag)
  * (core/__init__.py:42-49).  Angles are radians.
  */
@@ -245,6 +249,26 @@ int pb_remap_u8(const pb_plan* plan, const uint8_t* src_dev, uint8_t* dst_dev, i
  * pointer not 16-byte aligned), deferred plans and PB_MODE_FAITHFUL / PB_MODE_FAST_DIRECT run as n_frames single launches.
  * Replaces: a host loop over process_coordinate_map() (core/__init__.py:66-92) on separately allocated arrays. */
 int pb_remap_u8v(const pb_plan* plan, const uint8_t* const* src_dev, uint8_t* const* dst_dev, int n_frames, void* stream);
+
+/* pb_remap_u8 for frames whose pixel is not three bytes (ABI 5, additive): grey (bytes_per_px 1), 16-bit grey or two
+ * uint8 channels (2), RGBA (4), 16-bit RGB (6), 16-bit RGBA (8).  The reference's nearest sampler never looks inside a pixel - it copies
+ * bytes_per_px bytes from the plan's certified source index - so the bytes are those of pb_index_map_i32 + pb_gather_px, in ONE launch
+ * of the tile kernel pb_px_hot_kernel whatever n_frames, without an index map in memory.  pb_remap_u8's contract: the same argument
+ * checks and messages, strides in bytes (0: packed frames of bytes_per_px * h * w), asynchronous on `stream`, never allocates or
+ * synchronises (graph-capture safe).
+ *   bytes_per_px == 3            exactly pb_remap_u8 (same route, same bytes);
+ *   outside {1, 2, 3, 4, 6, 8}   PB_ERR_INVALID;
+ *   alignment                    frame pointers and strides must be multiples of min(4, bytes_per_px & -bytes_per_px) bytes - 1, 2, 4, 2, 4
+ *                                for 1, 2, 4, 6, 8 - else PB_ERR_INVALID, before any launch;
+ *   PB_ERR_UNSUPPORTED           (nothing is written; use pb_index_map_i32 + pb_gather_px) for plans the tile kernel does not serve:
+ *                                deferred plans, PB_MODE_FAITHFUL, double-fisheye sources (their blend is sample-typed:
+ *                                pb_gather_blend_u8), plans without device state, sources of 32768 px a side or more, and frames of
+ *                                bytes_per_px * h * w >= 2^31 bytes (the kernel's source byte offsets are 32-bit).
+ * pb_remap_px_supported: 1 when pb_remap_px takes `plan` with this pixel size, 0 when it would return PB_ERR_UNSUPPORTED, negative on
+ * bad arguments - a caller chooses its path without provoking the error. */
+int pb_remap_px(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, size_t src_frame_stride,
+                size_t dst_frame_stride, int bytes_per_px, void* stream);
+int pb_remap_px_supported(const pb_plan* plan, int bytes_per_px);
 
 /* OPT-IN extension with no reference counterpart (the reference samples nearest-by-truncation only):
  * bilinear interpolation at the reference's pre-truncation coordinate (pixel k covers [k, k+1), centre

@@ -157,21 +157,45 @@ def _ss_bytes(plan, supersample: int, interpolation: str, src_ptr: int) -> int:
     return 0 if supersample == 1 else plan.supersample_workspace_bytes(supersample, interpolation, src_ptr=src_ptr)
 
 
+def _px_format(plan, a: np.ndarray, interpolation: str, supersample: int) -> tuple:
+    """(trailing shape, dtype, bytes per pixel) of a frame (h, w, *tail) for `plan`: uint8 (h, w, 3), or - nearest, not supersampled - any
+    dtype and tail whose pixel is one of nat.PX_SIZES bytes (Plan.launch's bytes_per_px: pb_remap_px).  ValueError otherwise."""
+    sh = (plan.src.height, plan.src.width)
+    tail, dt = tuple(a.shape[2:]), a.dtype
+    if a.ndim < 2 or tuple(a.shape[:2]) != sh:
+        raise ValueError(f"frames must be {sh + (3,)} uint8 (or {sh} + trailing dimensions with pixels of {nat.PX_SIZES} bytes), got {dt} {tuple(a.shape)}")
+    if dt == np.uint8 and tail == (3,):
+        return tail, dt, 3
+    bpp = int(np.prod(tail, dtype=np.int64)) * dt.itemsize
+    if bpp not in nat.PX_SIZES or interpolation != "nearest" or supersample != 1:
+        raise ValueError(f"frames must be uint8 {sh + (3,)} - or, for nearest sampling without supersampling, {sh} + trailing dimensions with "
+                         f"pixels of {nat.PX_SIZES} bytes -, got {dt} {tuple(a.shape)}")
+    return tail, dt, bpp
+
+
+def _px_kw(bpp: int) -> dict:
+    """Plan.launch's pixel size - passed only when it is not the uint8 RGB call."""
+    return {} if bpp == 3 else {"bytes_per_px": bpp}
+
+
 def remap_ndarray(plan: nat.Plan, image: np.ndarray, interpolation: str = "nearest", device: int | None = None, supersample: int = 1) -> np.ndarray:
     """One frame: uint8 (h, w, 3) ndarray -> fresh uint8 (H, W, 3) ndarray (upload, ONE kernel launch, download).  ``supersample`` n: `plan`
     is the n x destination's and the result (H / n, W / n, 3) holds the n x n block means (``Plan.launch``).  ``interpolation``: "nearest",
-    "bilinear" or "catmull-rom" (not supersampled)."""
+    "bilinear" or "catmull-rom" (not supersampled).  Nearest without supersampling also takes (h, w, *tail) frames of any dtype whose
+    pixel is 1, 2, 4, 6 or 8 bytes - grey, RGBA, 16-bit samples - and returns (H, W, *tail) of that dtype (pb_remap_px: a plan
+    ``Plan.px_supported`` refuses is a PbError)."""
     nat.check_interpolation(interpolation, supersample)
     oh, ow = _out_shape(plan, supersample)
+    tail, dt, bpp = _px_format(plan, image, interpolation, supersample)
     nat.require_gpu()
     pipe = pipe_for(device)
     with nat.on_device(pipe.device):
         d_in = pipe.device_buffer("in", image.nbytes)
-        d_out = pipe.device_buffer("out", 3 * oh * ow)
+        d_out = pipe.device_buffer("out", bpp * oh * ow)
         ws = pipe.take_workspace(_ss_bytes(plan, supersample, interpolation, d_in.data_ptr()))
         pipe.upload(image, d_in)
-        plan.launch(d_in.data_ptr(), d_out.data_ptr(), 1, pipe.stream.handle, interpolation, **_ss_kw(supersample, ws))
-        out = pipe.download(d_out, (oh, ow, 3), np.uint8)
+        plan.launch(d_in.data_ptr(), d_out.data_ptr(), 1, pipe.stream.handle, interpolation, **_ss_kw(supersample, ws), **_px_kw(bpp))
+        out = pipe.download(d_out, (oh, ow) + tail, dt)
         pipe.stream.sync()
         pipe.give_workspace(ws)
     return out
@@ -182,18 +206,17 @@ def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, i
     """Streams host-resident frames through one plan: while frame k + 1 uploads on the H2D stream, the remap kernel of frame k stores its
     output over PCIe straight into frame k's result ndarray (page-locked, device-visible), through `depth` rotating device input
     buffers.  Yields uint8 (H, W, 3) ndarrays in order (page-locked, recycled when dropped).  ``supersample`` n: `plan` is the n x
-    destination's, the results are (H / n, W / n, 3) block means - the fused kernel stores only those over PCIe."""
+    destination's, the results are (H / n, W / n, 3) block means - the fused kernel stores only those over PCIe.  Nearest without
+    supersampling also takes frames (h, w, *tail) of any dtype whose pixel is 1, 2, 4, 6 or 8 bytes (``remap_ndarray``): all frames of a
+    call share the first frame's format, and the results are (H, W, *tail) of that dtype."""
     nat.check_interpolation(interpolation, supersample)
     oh, ow = _out_shape(plan, supersample)
     nat.require_gpu()
     depth = max(2, int(depth))
     dev = nat.current_device()
     pipe = pipe_for(dev)
-    sh = (plan.src.height, plan.src.width, 3)
-    dh = (oh, ow, 3)
-    n_in = int(np.prod(sh))
-    d_in = pipe.take_ring(n_in, depth)
-    ws = pipe.take_workspace(_ss_bytes(plan, supersample, interpolation, d_in[0].data_ptr()))  # (used in s_run's order, frame after frame)
+    fmt = sh = dh = d_in = ws = None  # the call's pixel format, frame shapes, ring and workspace: known with the first frame
+    n_in = bpp = 0
     s_up, s_run = Stream(), Stream()
     uploaded = [Event() for _ in range(depth)]
     computed = [Event() for _ in range(depth)]
@@ -212,14 +235,20 @@ def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, i
     try:
         for frame in frames:
             a = np.asarray(frame)
-            if a.dtype != np.uint8 or tuple(a.shape) != sh:
-                raise ValueError(f"frames must be uint8 {sh}, got {a.dtype} {tuple(a.shape)}")
+            if fmt is None:
+                tail, dt, bpp = fmt = _px_format(plan, a, interpolation, supersample)
+                sh, dh = (plan.src.height, plan.src.width) + tail, (oh, ow) + tail
+                n_in = a.nbytes
+                d_in = pipe.take_ring(n_in, depth)
+                ws = pipe.take_workspace(_ss_bytes(plan, supersample, interpolation, d_in[0].data_ptr()))  # (used in s_run's order, frame after frame)
+            if a.dtype != fmt[1] or tuple(a.shape) != sh:
+                raise ValueError(f"frames must be {fmt[1]} {sh}, got {a.dtype} {tuple(a.shape)}")
             slot = k % depth  # (free: the previous turn delivered its result, below)
             direct = pipe.upload(a, d_in[slot], s_up)
             uploaded[slot].record(s_up)
             s_run.wait(uploaded[slot])
-            out = results[slot] = PINNED.ndarray(dh, np.uint8)
-            plan.launch(d_in[slot].data_ptr(), out.ctypes.data, 1, s_run.handle, interpolation, **_ss_kw(supersample, ws))
+            out = results[slot] = PINNED.ndarray(dh, fmt[1])
+            plan.launch(d_in[slot].data_ptr(), out.ctypes.data, 1, s_run.handle, interpolation, **_ss_kw(supersample, ws), **_px_kw(bpp))
             computed[slot].record(s_run)
             pending.append(slot)
             if direct and ahead is not None:
@@ -243,5 +272,6 @@ def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, i
         # (a caller that stops early: nothing of the pipeline may still be reading its frames or writing the results it was not given)
         s_up.sync()
         s_run.sync()
-        pipe.give_ring(n_in, d_in)
+        if d_in is not None:
+            pipe.give_ring(n_in, d_in)
         pipe.give_workspace(ws)

@@ -128,6 +128,8 @@ SIGNATURES = {
     "pb_plan_matches": (C.c_int, [_VP, C.POINTER(pb_proj), C.POINTER(C.c_double), C.c_int, C.POINTER(pb_proj)]),
     "pb_remap_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_u8v": (C.c_int, [_VP, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, _VP]),
+    "pb_remap_px": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, C.c_int, _VP]),
+    "pb_remap_px_supported": (C.c_int, [_VP, C.c_int]),
     "pb_remap_bilinear_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_catmull_rom_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_ss_workspace": (C.c_int, [_VP, C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_size_t)]),
@@ -222,6 +224,24 @@ def check_interpolation(interpolation: str, supersample: int = 1) -> int:
     if n > 1 and interpolation not in INTERP_IDS:
         raise ValueError(f"{interpolation} sampling is not supersampled: pass supersample=1")
     return n
+
+
+PX_SIZES = (1, 2, 3, 4, 6, 8)  # bytes per pixel pb_remap_px takes: grey8, grey16 / two uint8 channels, RGB8, RGBA8, RGB16, RGBA16
+
+
+def px_align(bytes_per_px: int) -> int:
+    """The alignment pb_remap_px asks of frame pointers and strides: min(4, B & -B) bytes."""
+    return min(4, bytes_per_px & -bytes_per_px)
+
+
+def pixel_bytes(shape, dtype, hw) -> int:
+    """Bytes per pixel of an (h, w, *tail) or (N, h, w, *tail) array of `dtype` for a plan whose source (or destination) is hw = (h, w);
+    0 when the leading dimensions are not that."""
+    shp = tuple(int(v) for v in shape)
+    for lead in (2, 3):
+        if len(shp) >= lead and shp[lead - 2:lead] == tuple(hw):
+            return int(np.prod(shp[lead:], dtype=np.int64)) * np.dtype(dtype).itemsize
+    return 0
 
 
 def check_supersample(n) -> int:
@@ -521,14 +541,21 @@ class Plan:
 
     # -- launches (device arrays in, device arrays out: CUDA tensors or DeviceArrays; on the current stream unless told otherwise)
     def launch(self, src_ptr: int, dst_ptr: int, n_frames: int = 1, stream: int | None = None, interpolation: str = "nearest",
-               src_stride: int = 0, dst_stride: int = 0, supersample: int = 1, generic: bool = False, workspace=None) -> None:
+               src_stride: int = 0, dst_stride: int = 0, supersample: int = 1, generic: bool = False, workspace=None, bytes_per_px: int = 3) -> None:
         """The raw call: n_frames frames at src_ptr / dst_ptr (device addresses, strides in bytes, 0 = packed) on `stream`.
         ``supersample`` n in (2, 4): this plan is the n x destination's and each output frame is (H / n, W / n, 3), the n x n block
         means (pb_remap_ss_u8; ``generic`` forces its generic path).  ``workspace``: a device array of at least
         ``supersample_workspace_bytes(...)`` bytes the caller owns (allocate it outside a graph capture and keep it per stream); without
         one, a call that needs it takes a temporary buffer - from PyTorch's stream-ordered allocator where torch is installed, else a
-        DeviceArray that is freed after the call (on a stream other than the default one the call then synchronises that stream)."""
+        DeviceArray that is freed after the call (on a stream other than the default one the call then synchronises that stream).
+        ``bytes_per_px``: the frames' pixel size, one of PX_SIZES (pb_remap_px; nearest, not supersampled); 3 is the uint8 RGB call."""
         n = check_interpolation(interpolation, supersample)
+        if bytes_per_px != 3:
+            if interpolation != "nearest" or n != 1:
+                raise ValueError("frames of other than 3-byte pixels take nearest sampling without supersampling")
+            self._gated(load().pb_remap_px, self._h, src_ptr, dst_ptr, int(n_frames), int(src_stride), int(dst_stride), int(bytes_per_px),
+                        current_stream() if stream is None else stream)
+            return
         if interpolation != "nearest":
             self.ensure_bilinear()  # (catmull-rom reads the bilinear mode's tables too)
         st = current_stream() if stream is None else stream
@@ -619,6 +646,46 @@ class Plan:
         if out is not None:
             return out
         return o if batched else o[0]
+
+    def px_supported(self, bytes_per_px: int) -> bool:
+        """Whether ``remap_px`` / ``launch(bytes_per_px=...)`` takes this plan with this pixel size (pb_remap_px_supported): a prepared plan
+        of a single source in a tile mode.  A size outside PX_SIZES is a PbError.  Needs no GPU."""
+        r = load().pb_remap_px_supported(self._h, int(bytes_per_px))
+        if r < 0:
+            check(r)
+        return r == 1
+
+    def remap_px(self, src, out=None):
+        """The nearest remap of frames of any pixel layout (pb_remap_px): src is a device array (h, w, *tail) or (N, h, w, *tail) of any
+        dtype whose pixel - tail x itemsize - is 1, 2, 3, 4, 6 or 8 bytes (grey, grey16, RGB, RGBA, RGB16, RGBA16) -> (H, W, *tail) /
+        (N, H, W, *tail) of the same dtype and kind, in ONE launch.  A plan ``px_supported`` refuses is a PbError (no fallback)."""
+        sh, dh = (self.src.height, self.src.width), (self.dst.height, self.dst.width)
+        if not is_device_array(src):
+            raise PbError(f"source frames must be device arrays (CUDA tensors or DeviceArrays), got {type(src).__name__}")
+        tens = is_tensor(src)
+        shp = tuple(int(v) for v in src.shape)
+        dt = torch_dtype_np(src.dtype) if tens else np.dtype(src.dtype)
+        bpp = pixel_bytes(shp, dt, sh)
+        if bpp not in PX_SIZES:
+            raise PbError(f"source frames must be ({sh[0]}, {sh[1]}, ...) or (N, {sh[0]}, {sh[1]}, ...) with pixels of {PX_SIZES} bytes, got {shp} {dt}")
+        batched = shp[:2] != sh
+        tail = shp[3:] if batched else shp[2:]
+        n = shp[0] if batched else 1
+        oshape = ((n,) if batched else ()) + dh + tail
+        require_gpu()
+        s = src.contiguous() if tens else src
+        if out is None:
+            o = empty(oshape, dt, like=s)
+        else:
+            o = out
+            odt = (torch_dtype_np(o.dtype) if is_tensor(o) else np.dtype(o.dtype)) if is_device_array(o) else None
+            if odt != dt or tuple(o.shape) != oshape or is_tensor(o) != tens or (tens and not o.is_contiguous()):
+                raise PbError(f"out must be a contiguous device array {oshape} {dt} of the source's kind")
+            if tens and (not o.is_cuda or o.device != s.device):
+                raise PbError(f"out must live on the source's device ({s.device}), got {o.device}")
+        with _on(s):
+            self.launch(s.data_ptr(), o.data_ptr(), n, None, bytes_per_px=bpp)
+        return o
 
     def remap_each(self, srcs, outs=None, stream: int | None = None):
         """A batch of SEPARATELY ALLOCATED frames (a ring of buffers) in one launch (``pb_remap_u8v``): srcs / outs are

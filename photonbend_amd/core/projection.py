@@ -370,9 +370,10 @@ class _GpuProjection:
         per channel the round-half-to-even mean of each n x n block of what this call returns for the map at n = 1 (same side effects).
         1 is exactly the plain call.
 
-        uint8 (H, W, 3) images with built-in lenses take the fused kernel (one launch, no map in memory); any other
-        image the reference accepts - grey (H, W), RGBA, 16-bit samples - and sources whose lens is made of user
-        callables go through the integer index map and a gather (same indices, same bytes as the reference).
+        uint8 (H, W, 3) images with built-in lenses take the fused kernel (one launch, no map in memory); so do the other images the
+        reference accepts whose pixel is 1, 2, 4, 6 or 8 bytes - grey (H, W), RGBA, 16-bit samples - on a single source, from the
+        second use of a geometry on (pb_remap_px; same bytes).  The first use, double-fisheye sources, other pixel sizes and sources
+        whose lens is made of user callables go through the integer index map and a gather (same indices, same bytes as the reference).
 
         ``interpolation="bilinear"`` is an opt-in extension with no reference counterpart (the reference truncates to the nearest
         pixel).  A lazy map + a uint8 RGB image + built-in lenses take the tile kernels (one launch); a materialised or edited map, a
@@ -425,14 +426,33 @@ class _GpuProjection:
             if src.kind == nat.KIND_PANO:
                 coordinate_map.note_invalid_zeroed()  # projection.py:534-536
             return out
+        # grey, RGBA, 16-bit ... pixels of a supported size through the tile kernel of pixel sizes (pb_remap_px): one launch
+        # where the plan takes it (Plan.px_supported: prepared, single source) - else, and for the first call of a geometry (a deferred
+        # plan), double-fisheye sources, other pixel sizes and misaligned views, the index map + gather below
+        bpp = int(np.prod(tail, dtype=np.int64)) * dt.itemsize
+        px = (not fused and not interpolating and lazy and not too_many and not custom_src and src.kind != nat.KIND_DOUBLE and bpp in nat.PX_SIZES)
+        plan = None
+        if px and not on_device:
+            # ndarray in, fresh ndarray out, like the uint8 RGB user above: upload, ONE launch, download
+            nat.require_gpu()
+            plan = _plan_for(coordinate_map.dst_proj, rotations, src, eager=False)
+            if plan.px_supported(bpp):
+                out = _hostpipe.remap_ndarray(plan, np.ascontiguousarray(self.image))
+                if src.kind == nat.KIND_PANO:
+                    coordinate_map.note_invalid_zeroed()  # projection.py:534-536
+                return out
         img = _device_image(self.image, h, w) if fused else _device_bytes(self.image)
         dev = img.device if nat.is_tensor(img) else None
         if lazy and not too_many and not custom_src and (fused or not interpolating):
             # bilinear taps come from the tile models: that mode needs the prepared plan from the first use on
-            plan = _plan_for(coordinate_map.dst_proj, rotations, src, device=dev, eager=interpolation != "nearest")
+            if plan is None:  # (asked for ONCE per call: the second use of a geometry prepares it)
+                plan = _plan_for(coordinate_map.dst_proj, rotations, src, device=dev, eager=interpolation != "nearest")
             with nat.on_device(nat.device_index_of(img)):
                 if fused:
                     out = plan.remap(img, interpolation=interpolation)
+                elif px and plan.px_supported(bpp) and img.data_ptr() % nat.px_align(bpp) == 0:
+                    oh, ow = (int(v) for v in tuple(coordinate_map.shape)[:2])
+                    out = _typed(plan.remap_px(img), tail, dt, oh, ow)
                 else:
                     idx, wts = plan.index_map(weights=True, device=dev) if src.kind == nat.KIND_DOUBLE else (plan.index_map(device=dev), None)
                     out = self._gather(src, idx, wts, img, tail, dt)

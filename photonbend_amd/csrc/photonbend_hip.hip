@@ -36,6 +36,7 @@
 #include "pb_kernels_bilinear.hpp"
 #include "pb_kernels_supersample.hpp"
 #include "pb_kernels_catmull_rom.hpp"
+#include "pb_kernels_px.hpp"
 
 #define PB_DOUBLE_FRAMES_PER_WAVE 1  // frames a double-source wave loops over (the rest of a batch is a grid dimension)
 
@@ -611,6 +612,17 @@ static void pb_pick(bool first, F&& f) {
     if (first) f(PbInt<A>());
     else f(PbInt<B>());
 }
+// pb_px_hot_kernel's BPP (PB_PX_SIZES without 3, which is pb_hot_win_kernel's)
+template <class F>
+static void pb_pick_px_size(int bpp, F&& f) {
+    switch (bpp) {
+        case 1: f(PbInt<1>()); break;
+        case 2: f(PbInt<2>()); break;
+        case 4: f(PbInt<4>()); break;
+        case 6: f(PbInt<6>()); break;
+        default: f(PbInt<8>()); break;
+    }
+}
 // The SRC_KIND of the MODEL-evaluating kernels (hot, window, supersampled, interpolated tile kernels) of a single source.  A cube source
 // runs the camera's: what those kernels evaluate is a certified tile model, a frame-wide bounds test and the camera's truncation edge, and
 // pb_certify_kernel<PB_KIND_CUBE> compares that very evaluation with the cube's float64 chain for every pixel.
@@ -892,20 +904,28 @@ static int pb_check_device(const pb_plan* plan) {
 // The arguments of every frame-launching entry point, in this order: null plan / frames, the frame count (0: PB_OK and nothing to
 // launch - callers return), the plan's device, the frame strides (0: tightly packed; the defaults are filled in here and nowhere
 // else).  n: the supersample factor - an output frame is H/n x W/n of the plan's destination.  tables: src / dst are pb_remap_u8v's
-// pointer tables, which may be null when there are no frames.
+// pointer tables, which may be null when there are no frames.  bpp: bytes per pixel (pb_remap_px; 3 everywhere else) - one of
+// PB_PX_SIZES, frames and strides aligned to pb_px_align(bpp).
+static bool pb_px_size_ok(int bpp) { return bpp == 1 || bpp == 2 || bpp == 3 || bpp == 4 || bpp == 6 || bpp == 8; }
+static unsigned pb_px_align(int bpp) { return (unsigned)std::min(4, bpp & -bpp); }
 static int pb_check_frames(const pb_plan* plan, const void* src, const void* dst, int n_frames, int n, size_t& src_stride, size_t& dst_stride,
-                           bool tables = false) {
+                           bool tables = false, int bpp = 3) {
     if (!plan || ((!src || !dst) && (n_frames > 0 || !tables))) return pb_fail(PB_ERR_INVALID, "null argument");
     if (n_frames < 0) return pb_fail(PB_ERR_INVALID, "negative frame count");
+    if (!pb_px_size_ok(bpp)) return pb_fail(PB_ERR_INVALID, "bytes_per_px outside {1, 2, 3, 4, 6, 8}");
     if (n_frames == 0) return PB_OK;
     const int rc = pb_check_device(plan);
     if (rc != PB_OK) return rc;
     const PbParams& P = plan->P;
-    const unsigned long long src_bytes = 3ull * P.src.height * P.src.width, dst_bytes = 3ull * ((unsigned)P.dst.height / n) * ((unsigned)P.dst.width / n);
+    const unsigned long long B = (unsigned long long)bpp;
+    const unsigned long long src_bytes = B * P.src.height * P.src.width, dst_bytes = B * ((unsigned)P.dst.height / n) * ((unsigned)P.dst.width / n);
     if (!src_stride) src_stride = src_bytes;
     if (!dst_stride) dst_stride = dst_bytes;
     if (dst_stride < dst_bytes) return pb_fail(PB_ERR_INVALID, "dst_frame_stride smaller than a frame");
     if (n_frames > 1 && src_stride < src_bytes) return pb_fail(PB_ERR_INVALID, "src_frame_stride smaller than a frame");
+    const unsigned a = pb_px_align(bpp);  // (1 for three-byte pixels)
+    if (!tables && ((((uintptr_t)src | (uintptr_t)dst) | src_stride | dst_stride) & (a - 1u)))
+        return pb_fail(PB_ERR_INVALID, "frame pointers and strides must be multiples of " + std::to_string(a) + " bytes for " + std::to_string(bpp) + "-byte pixels");
     return PB_OK;
 }
 
@@ -928,13 +948,23 @@ struct PbRoute {
         INTERP_DOUBLE_FLOAT64,  // bilinear / catmull-rom: pb_interp_double_kernel<filter>
         SS_FUSED,            // supersampled: pb_ss_win_kernel
         SS_GENERIC,          // supersampled: frame by frame the route of n = 1 into a workspace, then pb_box_reduce_kernel
+        PX,                  // nearest, pixels of bpp != 3 bytes (pb_remap_px): pb_px_hot_kernel
+        PX_NONE,             // ... on a plan that kernel does not serve: nothing is launched (PB_ERR_UNSUPPORTED)
     } kind;
     bool windows;                    // BIL_DOUBLE / bilinear INTERP_TILES: LEAN tiles gather from LDS windows
     int filter = PB_INTERP_NEAREST;  // the INTERP_* routes: PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM
+    int bpp = 3;                     // PX: bytes per pixel
 };
 static bool pb_aligned16(const void* src, unsigned long long stride) { return ((((uintptr_t)src) | stride) & 15u) == 0; }
-static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned flags, bool aligned) {
+static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned flags, bool aligned, int bpp = 3) {
     const PbParams& P = pl->P;
+    if (bpp != 3) {
+        // the tile kernel of the nearest plan's launch-order table, or nothing: no window, so no alignment beyond the pixel's own
+        // (pb_check_frames); fast_ready says single source, prepared, device state; generic tiles pack row and column in 16 bits each
+        const bool px = interpolation == PB_INTERP_NEAREST && n == 1 && pb_use_fast(pl) && pl->nearest.lt.entries && pl->nearest.P_dev &&
+                        P.src.width < 32768 && P.src.height < 32768;
+        return {px ? PbRoute::PX : PbRoute::PX_NONE, false, PB_INTERP_NEAREST, bpp};
+    }
     if (n > 1) {
         const bool fused = interpolation == PB_INTERP_NEAREST && !(flags & PB_SS_GENERIC) && pb_route(pl, interpolation, 1, 0, aligned).kind == PbRoute::WIN;
         return {fused ? PbRoute::SS_FUSED : PbRoute::SS_GENERIC, false};
@@ -1044,6 +1074,23 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
         case PbRoute::DIRECT:
             pb_launch_direct<0>(pl, src, dst, n_frames, ss, ds, nullptr, st);
             break;
+        case PbRoute::PX: {
+            // launched like WIN: the nearest launch-order table, frames of a batch as a grid dimension; static LDS (the regrouping buffer)
+            const unsigned gpf = pl->nearest.lt.groups;
+            pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
+                pb_pick_kind(P, [&](auto K) {
+                    pb_pick_px_size(r.bpp, [&](auto B) {
+                        hipLaunchKernelGGL((pb_px_hot_kernel<K.value, B.value>), dim3(gpf * (unsigned)nf), dim3(64 * PB_TILE_WAVES), 0, st,
+                                           (const PbParams*)pl->nearest.P_dev, pb_hot_of_host(P), pl->nearest.lt.entries, sf, df, gpf, ss, ds, pl->cert.idx_tab,
+                                           pl->cert.fix_px, pl->cert.fix_idx);
+                    });
+                });
+            });
+            break;
+        }
+        case PbRoute::PX_NONE:
+            return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_px takes prepared plans of a single source in a tile mode (not deferred, not PB_MODE_FAITHFUL, not "
+                                               "double-fisheye, sources below 32768 px a side): use pb_index_map_i32 + pb_gather_px");
         case PbRoute::BIL_DOUBLE: {
             // the per-eye tile models of the nearest mode's plan + the exact coordinate tables: one wave per tile
             const unsigned gpf = pb_bil_groups(pl);
@@ -1896,6 +1943,30 @@ int pb_remap_u8(const pb_plan* plan, const uint8_t* src_dev, uint8_t* dst_dev, i
     if (rc != PB_OK || n_frames == 0) return rc;
     return pb_launch(plan, pb_route(plan, PB_INTERP_NEAREST, 1, 0, pb_aligned16(src_dev, src_frame_stride)), src_dev, dst_dev, n_frames,
                      src_frame_stride, dst_frame_stride, (hipStream_t)stream);
+}
+
+// pixels of bytes_per_px != 3 on plans the tile kernel serves; 3 is pb_remap_u8 itself
+static bool pb_px_frames_fit(const pb_plan* plan, int bpp) {  // 32-bit source byte offsets (pb_kernels_px.hpp)
+    const PbParams& P = plan->P;
+    const unsigned long long B = (unsigned long long)bpp;
+    return B * P.src.height * P.src.width < (1ull << 31) && B * P.dst.height * P.dst.width < (1ull << 31);
+}
+int pb_remap_px(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, size_t src_frame_stride, size_t dst_frame_stride,
+                int bytes_per_px, void* stream) {
+    const int rc = pb_check_frames(plan, src_dev, dst_dev, n_frames, 1, src_frame_stride, dst_frame_stride, false, bytes_per_px);
+    if (rc != PB_OK || n_frames == 0) return rc;
+    const uint8_t* s = static_cast<const uint8_t*>(src_dev);
+    uint8_t* d = static_cast<uint8_t*>(dst_dev);
+    if (bytes_per_px != 3 && !pb_px_frames_fit(plan, bytes_per_px))
+        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_px takes frames below 2^31 bytes: use pb_index_map_i32 + pb_gather_px");
+    return pb_launch(plan, pb_route(plan, PB_INTERP_NEAREST, 1, 0, pb_aligned16(s, src_frame_stride), bytes_per_px), s, d, n_frames, src_frame_stride,
+                     dst_frame_stride, (hipStream_t)stream);
+}
+int pb_remap_px_supported(const pb_plan* plan, int bytes_per_px) {
+    if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
+    if (!pb_px_size_ok(bytes_per_px)) return pb_fail(PB_ERR_INVALID, "bytes_per_px outside {1, 2, 3, 4, 6, 8}");
+    if (bytes_per_px == 3) return 1;
+    return pb_route(plan, PB_INTERP_NEAREST, 1, 0, false, bytes_per_px).kind == PbRoute::PX && pb_px_frames_fit(plan, bytes_per_px);
 }
 
 int pb_remap_u8v(const pb_plan* plan, const uint8_t* const* src_dev, uint8_t* const* dst_dev, int n_frames, void* stream) {
