@@ -166,7 +166,7 @@ def _px_format(plan, a: np.ndarray, interpolation: str, supersample: int) -> tup
         raise ValueError(f"frames must be {sh + (3,)} uint8 (or {sh} + trailing dimensions with pixels of {nat.PX_SIZES} bytes), got {dt} {tuple(a.shape)}")
     if dt == np.uint8 and tail == (3,):
         return tail, dt, 3
-    bpp = int(np.prod(tail, dtype=np.int64)) * dt.itemsize
+    bpp = nat.tail_bytes(tail, dt)
     if bpp not in nat.PX_SIZES or interpolation != "nearest" or supersample != 1:
         raise ValueError(f"frames must be uint8 {sh + (3,)} - or, for nearest sampling without supersampling, {sh} + trailing dimensions with "
                          f"pixels of {nat.PX_SIZES} bytes -, got {dt} {tuple(a.shape)}")

@@ -234,13 +234,21 @@ def px_align(bytes_per_px: int) -> int:
     return min(4, bytes_per_px & -bytes_per_px)
 
 
+def tail_bytes(tail, dtype) -> int:
+    """Bytes per pixel of frames whose shape after (h, w) is `tail`: the one place a trailing shape and a dtype become a byte count."""
+    n = np.dtype(dtype).itemsize
+    for v in tail:  # (no NumPy reduction: every facade call asks)
+        n *= int(v)
+    return n
+
+
 def pixel_bytes(shape, dtype, hw) -> int:
     """Bytes per pixel of an (h, w, *tail) or (N, h, w, *tail) array of `dtype` for a plan whose source (or destination) is hw = (h, w);
     0 when the leading dimensions are not that."""
     shp = tuple(int(v) for v in shape)
     for lead in (2, 3):
         if len(shp) >= lead and shp[lead - 2:lead] == tuple(hw):
-            return int(np.prod(shp[lead:], dtype=np.int64)) * np.dtype(dtype).itemsize
+            return tail_bytes(shp[lead:], dtype)
     return 0
 
 

@@ -24,7 +24,7 @@ import os
 import threading
 from abc import abstractmethod
 from collections import OrderedDict
-from typing import Protocol, Union
+from typing import NamedTuple, Protocol, Sequence, Union
 
 import numpy as np
 
@@ -208,17 +208,12 @@ def _device_image(image, height: int, width: int):
         if image.dtype != np.uint8 or tuple(image.shape) != (height, width, 3):
             raise ValueError(f"image must be uint8 ({height}, {width}, 3), got {image.dtype} {tuple(image.shape)}")
         return image
-    a = _checked_rgb8(image, height, width)
-    return _upload(a)
-
-
-def _checked_rgb8(image, height: int, width: int) -> np.ndarray:
     a = np.asarray(image)
     if a.dtype != np.uint8:
         raise TypeError(f"images are uint8 (H, W, 3) RGB arrays (core/__init__.py:31-36), got {a.dtype}")
     if tuple(a.shape) != (height, width, 3):
         raise ValueError(f"image must have shape ({height}, {width}, 3), got {tuple(a.shape)}")
-    return a
+    return _upload(a)
 
 
 def _check_map_tensor(cmap, device=None) -> None:
@@ -251,33 +246,24 @@ class ProjectionImage(Protocol):
         ...
 
 
-def _image_info(image):
-    """(height, width, trailing shape, numpy dtype) of an image array or tensor.  The reference fancy-indexes whatever
-    array it is given (projection.py:234-243, :545-546): grey (H, W), RGB, RGBA (H, W, 4), 8- or 16-bit samples."""
-    shp = tuple(int(v) for v in image.shape)
-    if len(shp) < 2:
-        raise ValueError("an image needs at least (height, width)")
-    if nat.is_tensor(image):
-        dt = nat.torch.empty(0, dtype=image.dtype).numpy().dtype
-    elif isinstance(image, nat.DeviceArray):
-        dt = image.dtype
-    else:
-        dt = np.asarray(image).dtype
-    return shp[0], shp[1], shp[2:], np.dtype(dt)
+def _sample_dtype(image) -> np.dtype:
+    """The numpy dtype of a device array's, a tensor's or an array-like's samples."""
+    if isinstance(image, nat.DeviceArray):
+        return image.dtype
+    return np.dtype(nat.torch_dtype_np(image.dtype) if nat.is_tensor(image) else np.asarray(image).dtype)
 
 
-def _device_bytes(image, device=None):
+def _device_bytes(image, c: _Call):
     """The image's pixels as a contiguous uint8 device array (h, w, bytes per pixel)."""
     nat.require_gpu()
-    h, w, tail, dt = _image_info(image)
-    bpp = int(np.prod(tail, dtype=np.int64)) * dt.itemsize
+    h, w, bpp = c.height, c.width, c.bpp
     if nat.is_tensor(image):
         t = image if image.is_cuda else image.cuda()
         return t.contiguous().view(nat.torch.uint8).reshape(h, w, bpp)
     if isinstance(image, nat.DeviceArray):
         return image.view(np.uint8, (h, w, bpp))
     a = np.ascontiguousarray(image)
-    return _upload(a.view(np.uint8).reshape(h, w, bpp), device)
+    return _upload(a.view(np.uint8).reshape(h, w, bpp))
 
 
 def _typed(out, tail, dt: np.dtype, H: int, W: int):
@@ -343,11 +329,6 @@ class _GpuProjection:
                 dr = _upload(np.ascontiguousarray(planes[1], dtype=np.float64), dev)
         return dl, dr
 
-    def _index_from_map(self, src: nat.pb_proj, dev_map):
-        """int32 source indices (and float64 weights for a double source) of a materialised map on the device."""
-        dl, dr = self._distance_planes(src, dev_map)
-        return nat.index_from_map(src, dev_map, dl, dr)
-
     def _gather(self, src: nat.pb_proj, idx, weights, img_bytes, tail, dt: np.dtype):
         """index map -> output pixels, any channel count / sample width; returns a CUDA tensor of the output dtype."""
         H, W = (idx.shape[-2], idx.shape[-1])
@@ -363,177 +344,189 @@ class _GpuProjection:
 
     def process_coordinate_map(self, coordinate_map, interpolation: str = "nearest", supersample=None):
         """Maps this image's pixels through ``coordinate_map`` and returns the new image
-        (projection.py:197-245, :408-462, :515-547).
+        (projection.py:197-245, :408-462, :515-547): an ndarray image gives a fresh ndarray, a device image a device array.
 
         ``supersample``: None takes the map's own (``get_coordinate_map(supersample=n)``; 1 for a plain array or tensor); an explicit
         n in (2, 4) declares that the map holds n x n samples per output pixel.  The result is then (map_H / n, map_W / n) + trailing:
         per channel the round-half-to-even mean of each n x n block of what this call returns for the map at n = 1 (same side effects).
         1 is exactly the plain call.
 
-        uint8 (H, W, 3) images with built-in lenses take the fused kernel (one launch, no map in memory); so do the other images the
-        reference accepts whose pixel is 1, 2, 4, 6 or 8 bytes - grey (H, W), RGBA, 16-bit samples - on a single source, from the
-        second use of a geometry on (pb_remap_px; same bytes).  The first use, double-fisheye sources, other pixel sizes and sources
-        whose lens is made of user callables go through the integer index map and a gather (same indices, same bytes as the reference).
+        ``interpolation``: "nearest" is the reference's truncating sample, for every image the reference accepts (grey, RGB, RGBA, 8- or
+        16-bit samples ...), bit for bit.  "bilinear" and "catmull-rom" (4 x 4 footprint, Keys' cubic weights, a = -0.5; not
+        supersampled) are opt-in extensions with no reference counterpart, for 8- and 16-bit unsigned samples.
 
-        ``interpolation="bilinear"`` is an opt-in extension with no reference counterpart (the reference truncates to the nearest
-        pixel).  A lazy map + a uint8 RGB image + built-in lenses take the tile kernels (one launch); a materialised or edited map, a
-        grey / RGBA / 16-bit image or a Lens of user callables take the mode's definition per pixel from the map
-        (pb_sample_map_bilinear_px) - same definition, float64 arithmetic.
-
-        ``interpolation="catmull-rom"`` (opt-in): the same with a 4 x 4 footprint and Keys' cubic weights (a = -0.5) - sharp
-        where the source is magnified.  Served like bilinear (pb_remap_catmull_rom_u8 / pb_sample_map_catmull_rom_px); not supersampled."""
+        Which kernels serve a call - one fused launch, the tile kernel of pixel sizes, an index map and a gather, the mode's definition
+        per pixel from a materialised map - is decided in one place, ``_route``; DESIGN 3.12 lists its rows.  The bytes do not depend on it."""
         n = nat.check_interpolation(interpolation, _map_supersample(coordinate_map, supersample))
-        if n == 1:
-            return self._process(coordinate_map, interpolation)
-        return self._process_ss(coordinate_map, interpolation, n)
+        call = self._call(coordinate_map, interpolation, n)
+        return self._run(call, _route(call), coordinate_map)
 
-    def _process(self, coordinate_map, interpolation: str = "nearest", device_out: bool = False):
-        """process_coordinate_map at n = 1; ``device_out``: the result stays on the device whatever the image is (the generic supersampled
-        path reduces it there)."""
-        src = self._proj("src")
-        h, w, tail, dt = _image_info(self.image)
-        rgb8 = tail == (3,) and dt == np.dtype(np.uint8)
-        custom_src = src.kind not in nat.LENSLESS_KINDS and src.lens == nat.LENS_CUSTOM
-        lazy = isinstance(coordinate_map, CoordinateMap) and coordinate_map.is_lazy
-        nat.check_interpolation(interpolation)
-        interpolating = interpolation != "nearest"  # (bilinear or catmull-rom)
-        if interpolating:
-            if dt not in (np.dtype(np.uint8), np.dtype(np.uint16)):
-                raise NotImplementedError(f"{interpolation} sampling takes 8- or 16-bit unsigned samples, got {dt}")
-            if src.kind == nat.KIND_DOUBLE and len(tail) != 1:
-                # (the reference's blend cannot broadcast (H, W) samples against its (H, W, 1) factor maps either)
-                H_, W_ = tuple(coordinate_map.shape[:2])
-                raise ValueError(f"operands could not be broadcast together with shapes ({H_},{W_}) ({H_},{W_},1)")
-        on_device = nat.is_device_array(self.image) or device_out  # the pixels live on the device: so does the result
-        fused = rgb8 and not custom_src
-        rotations = coordinate_map.rotations if lazy else ()
-        if interpolating and lazy and len(rotations) > nat.PB_MAX_ROTATIONS:
-            # The reference applies any number of -r rotations one after the other (scripts/commands/make_photo.py:128-131).  A chain
-            # longer than one fused plan takes leaves the plan for the materialised-map kernels, which only truncate; in THIS mode
-            # (our own definition, no reference bits to keep) the chain folds into one matrix product R_k ... R_1 instead.
-            folded = np.eye(3)
-            for r in rotations:
-                folded = np.asarray(r, dtype=np.float64).reshape(3, 3) @ folded
-            rotations = [folded]
-        too_many = lazy and len(rotations) > nat.PB_MAX_ROTATIONS
-        if fused and not on_device and lazy and not too_many:
-            # THE path of a user who swapped imports: ndarray in, fresh ndarray out - upload, ONE fused launch, download, on the
-            # package's own device buffers, stream and page-locked memory (_hostpipe.py; no PyTorch involved)
-            nat.require_gpu()
-            a = _checked_rgb8(self.image, h, w)
-            plan = _plan_for(coordinate_map.dst_proj, rotations, src, eager=interpolation != "nearest")
-            out = _hostpipe.remap_ndarray(plan, a, interpolation)
-            if src.kind == nat.KIND_PANO:
-                coordinate_map.note_invalid_zeroed()  # projection.py:534-536
-            return out
-        # grey, RGBA, 16-bit ... pixels of a supported size through the tile kernel of pixel sizes (pb_remap_px, DESIGN 3.11): one launch
-        # where the plan takes it (Plan.px_supported: prepared, single source) - else, and for the first call of a geometry (a deferred
-        # plan), double-fisheye sources, other pixel sizes and misaligned views, the index map + gather below
-        bpp = int(np.prod(tail, dtype=np.int64)) * dt.itemsize
-        px = (not fused and not interpolating and lazy and not too_many and not custom_src and src.kind != nat.KIND_DOUBLE and bpp in nat.PX_SIZES)
-        plan = None
-        if px and not on_device:
-            # ndarray in, fresh ndarray out, like the uint8 RGB user above: upload, ONE launch, download
-            nat.require_gpu()
-            plan = _plan_for(coordinate_map.dst_proj, rotations, src, eager=False)
-            if plan.px_supported(bpp):
-                out = _hostpipe.remap_ndarray(plan, np.ascontiguousarray(self.image))
-                if src.kind == nat.KIND_PANO:
-                    coordinate_map.note_invalid_zeroed()  # projection.py:534-536
-                return out
-        img = _device_image(self.image, h, w) if fused else _device_bytes(self.image)
-        dev = img.device if nat.is_tensor(img) else None
-        if lazy and not too_many and not custom_src and (fused or not interpolating):
-            # bilinear taps come from the tile models: that mode needs the prepared plan from the first use on
-            if plan is None:  # (asked for ONCE per call: the second use of a geometry prepares it)
-                plan = _plan_for(coordinate_map.dst_proj, rotations, src, device=dev, eager=interpolation != "nearest")
-            with nat.on_device(nat.device_index_of(img)):
-                if fused:
-                    out = plan.remap(img, interpolation=interpolation)
-                elif px and plan.px_supported(bpp) and img.data_ptr() % nat.px_align(bpp) == 0:
-                    oh, ow = (int(v) for v in tuple(coordinate_map.shape)[:2])
-                    out = _typed(plan.remap_px(img), tail, dt, oh, ow)
-                else:
-                    idx, wts = plan.index_map(weights=True, device=dev) if src.kind == nat.KIND_DOUBLE else (plan.index_map(device=dev), None)
-                    out = self._gather(src, idx, wts, img, tail, dt)
-            if src.kind == nat.KIND_PANO:
-                coordinate_map.note_invalid_zeroed()  # projection.py:534-536
-            return out if on_device else _to_host(out)
-        # a materialised map: the caller's tensor / ndarray, or a recipe that has to become one (more rotations than one
-        # fused plan takes: the reference accepts any number of -r options; a source lens evaluated on the host)
-        host = None
-        with nat.on_device(nat.device_index_of(img)):
-            if nat.is_device_array(coordinate_map):
-                _check_map_tensor(coordinate_map, dev)
-                dmap = coordinate_map
-            elif lazy:
-                dmap = coordinate_map.device_tensor()
-                if src.kind == nat.KIND_PANO:
-                    coordinate_map.note_invalid_zeroed()
-            else:
-                host = coordinate_map.materialize() if isinstance(coordinate_map, CoordinateMap) else coordinate_map
-                if not (isinstance(host, np.ndarray) and host.dtype == np.float64 and host.ndim == 3 and host.shape[2] == 3):
-                    raise TypeError("coordinate_map must be a float64 array of shape (H, W, 3)")
-                dmap = _upload(host, dev)
-            if interpolating:
-                # the mode's definition per pixel from the map (pb_sample_map_bilinear_px): a materialised or edited map, any image
-                # layout, a source Lens of user callables - everything the tile kernels do not take
-                dl, dr = self._distance_planes(src, dmap)
-                channels = int(np.prod(tail, dtype=np.int64))
-                out = nat.sample_map_interp(interpolation, src, dmap, img, channels, dt, dl, dr)
-                out_dt = np.dtype(np.uint8) if src.kind == nat.KIND_DOUBLE else dt
-                H_, W_ = int(dmap.shape[0]), int(dmap.shape[1])
-                out = out.reshape((H_, W_) + tuple(tail)) if nat.is_tensor(out) else out.view(out_dt, (H_, W_) + tuple(tail))
-            elif fused:
-                out = nat.sample_map(src, dmap, img)
-            else:
-                idx, wts = self._index_from_map(src, dmap)
-                out = self._gather(src, idx, wts, img, tail, dt)
-            if host is not None and src.kind == nat.KIND_PANO:
-                host[...] = nat.to_host(dmap)  # the in-place zeroing of invalid pixels
-            return out if on_device else _to_host(out)
-
-    def _process_ss(self, coordinate_map, interpolation: str, n: int):
-        """The supersampled result.  A lazy map + a uint8 RGB image + built-in lenses: ONE pb_remap_ss_u8 call on the
-        n x plan (the fused kernel where the plan takes it, else its generic path); anything else: the n = 1 call's result on the device,
-        then pb_box_reduce."""
-        src = self._proj("src")
-        h, w, tail, dt = _image_info(self.image)
-        nat.check_interpolation(interpolation, n)
-        if dt not in (np.dtype(np.uint8), np.dtype(np.uint16)):
-            raise NotImplementedError(f"supersampling takes 8- or 16-bit unsigned samples, got {dt}")
-        mh, mw = (int(v) for v in tuple(coordinate_map.shape)[:2])
-        if mh % n or mw % n:
-            raise ValueError(f"a ({mh}, {mw}) coordinate map is not divisible by supersample={n}")
-        lazy = isinstance(coordinate_map, CoordinateMap) and coordinate_map.is_lazy
-        rgb8 = tail == (3,) and dt == np.dtype(np.uint8)
-        custom_src = src.kind not in nat.LENSLESS_KINDS and src.lens == nat.LENS_CUSTOM
-        on_device = nat.is_device_array(self.image)
-        rotations = coordinate_map.rotations if lazy else ()
-        if interpolation == "bilinear" and len(rotations) > nat.PB_MAX_ROTATIONS:
-            return self._process_ss_generic(coordinate_map, interpolation, n, on_device)  # (the folded chain: _process's own rule)
-        if not (lazy and rgb8 and not custom_src and len(rotations) <= nat.PB_MAX_ROTATIONS):
-            return self._process_ss_generic(coordinate_map, interpolation, n, on_device)
-        nat.require_gpu()
-        if not on_device:
-            a = _checked_rgb8(self.image, h, w)
-            plan = _plan_for(coordinate_map.dst_proj, rotations, src, eager=interpolation != "nearest")
-            out = _hostpipe.remap_ndarray(plan, a, interpolation, supersample=n)
+    def _call(self, coordinate_map, interpolation: str, n: int) -> _Call:
+        """The facts of one process_coordinate_map call, gathered once.  The reference fancy-indexes whatever array it is given
+        (projection.py:234-243, :545-546): grey (H, W), RGB, RGBA (H, W, 4), 8- or 16-bit samples."""
+        src, image = self._proj("src"), self.image  # (_proj has seen to it that the image has a height and a width)
+        if isinstance(image, np.ndarray):
+            shp, dt, on_device = image.shape, image.dtype, False
         else:
-            img = _device_image(self.image, h, w)
-            dev = img.device if nat.is_tensor(img) else None
-            plan = _plan_for(coordinate_map.dst_proj, rotations, src, device=dev, eager=interpolation != "nearest")
-            with nat.on_device(nat.device_index_of(img)):
-                out = plan.remap(img, interpolation=interpolation, supersample=n)
-        if src.kind == nat.KIND_PANO:
+            shp, dt, on_device = tuple(map(int, image.shape)), _sample_dtype(image), nat.is_device_array(image)
+        if isinstance(coordinate_map, CoordinateMap):
+            kind = "lazy" if coordinate_map.is_lazy else "coordmap"
+        else:
+            kind = "device" if nat.is_device_array(coordinate_map) else "ndarray"
+        custom = src.kind not in nat.LENSLESS_KINDS and src.lens == nat.LENS_CUSTOM
+        return _Call(src, custom, shp[0], shp[1], shp[2:], dt, nat.tail_bytes(shp[2:], dt), on_device, kind,
+                     getattr(coordinate_map, "shape", ()), coordinate_map.rotations if kind == "lazy" else (), interpolation, n)
+
+    def _run(self, c: _Call, r: _Route, coordinate_map):
+        if r.name.startswith("HOST_"):
+            return self._run_host(c, r, coordinate_map)
+        if r.name == "SS_GENERIC":  # the n = 1 result on the device, then the box filter
+            full = self._run(c, r.inner, coordinate_map)
+            with nat.on_device(nat.device_index_of(full)):
+                out = nat.box_reduce(full, c.supersample)
+            return out if r.device_out else _to_host(out)
+        return (self._run_map if r.name.startswith("MAP_") else self._run_plan)(c, r, coordinate_map)
+
+    def _run_host(self, c: _Call, r: _Route, coordinate_map):
+        """THE path of a user who swapped imports: ndarray in, fresh ndarray out - upload, ONE launch, download, on the package's own
+        device buffers, stream and page-locked memory (_hostpipe.py; no PyTorch involved)."""
+        nat.require_gpu()
+        plan = _plan_for(coordinate_map.dst_proj, r.rotations, c.src, eager=r.eager)
+        if r.name == "HOST_PX" and not plan.px_supported(c.bpp):
+            return self._run_plan(c, r._replace(name=r.fallback), coordinate_map, plan)  # (the first use of a geometry: a deferred plan)
+        out = _hostpipe.remap_ndarray(plan, np.ascontiguousarray(self.image), c.interpolation, supersample=r.supersample)
+        if c.src.kind == nat.KIND_PANO:
             coordinate_map.note_invalid_zeroed()  # projection.py:534-536
         return out
 
-    def _process_ss_generic(self, coordinate_map, interpolation: str, n: int, on_device: bool):
-        full = self._process(coordinate_map, interpolation, device_out=True)
-        with nat.on_device(nat.device_index_of(full)):
-            out = nat.box_reduce(full, n)
-        return out if on_device else _to_host(out)
+    def _run_plan(self, c: _Call, r: _Route, coordinate_map, plan=None):
+        """The image on the device through the geometry's plan: ``Plan.remap``, ``Plan.remap_px`` or its index map and a gather.  `plan`: the
+        one a host route already asked for - ``_plan_for`` counts uses (the second use of a geometry prepares it): ONCE per call."""
+        fused = r.name in ("DEV_RGB8", "SS_FUSED")
+        img = _device_image(self.image, c.height, c.width) if fused else _device_bytes(self.image, c)
+        dev = img.device if nat.is_tensor(img) else None
+        if plan is None:
+            plan = _plan_for(coordinate_map.dst_proj, r.rotations, c.src, device=dev, eager=r.eager)
+        with nat.on_device(nat.device_index_of(img)):
+            if fused:
+                out = plan.remap(img, interpolation=c.interpolation, supersample=r.supersample)
+            elif r.name == "DEV_PX" and plan.px_supported(c.bpp) and img.data_ptr() % nat.px_align(c.bpp) == 0:
+                out = _typed(plan.remap_px(img), c.tail, c.dt, *c.map_shape[:2])
+            else:  # PLAN_GATHER - and DEV_PX's fallback: a deferred plan, a misaligned view
+                idx, wts = plan.index_map(weights=True, device=dev) if c.double_src else (plan.index_map(device=dev), None)
+                out = self._gather(c.src, idx, wts, img, c.tail, c.dt)
+        if c.src.kind == nat.KIND_PANO:
+            coordinate_map.note_invalid_zeroed()  # projection.py:534-536
+        return out if r.device_out else _to_host(out)
+
+    def _run_map(self, c: _Call, r: _Route, coordinate_map):
+        """A materialised map: the caller's device array or ndarray, or a recipe that has to become one (more rotations than one fused plan
+        takes: the reference accepts any number of -r options; a source lens evaluated on the host; an interpolated grey / RGBA / 16-bit image)."""
+        img = _device_image(self.image, c.height, c.width) if c.fused else _device_bytes(self.image, c)
+        dev = img.device if nat.is_tensor(img) else None
+        host = None
+        with nat.on_device(nat.device_index_of(img)):
+            if c.map_kind == "device":
+                _check_map_tensor(coordinate_map, dev)
+                dmap = coordinate_map
+            elif c.map_kind == "lazy":
+                dmap = coordinate_map.device_tensor()
+            else:
+                host = coordinate_map.materialize() if c.map_kind == "coordmap" else coordinate_map
+                if not (isinstance(host, np.ndarray) and host.dtype == np.float64 and host.ndim == 3 and host.shape[2] == 3):
+                    raise TypeError("coordinate_map must be a float64 array of shape (H, W, 3)")
+                dmap = _upload(host, dev)
+            if r.name == "MAP_INTERP":  # the mode's definition per pixel from the map (pb_sample_map_bilinear_px / _catmull_rom_px)
+                dl, dr = self._distance_planes(c.src, dmap)
+                out = nat.sample_map_interp(c.interpolation, c.src, dmap, img, c.bpp // c.dt.itemsize, c.dt, dl, dr)
+                out = _typed(out, c.tail, np.dtype(np.uint8) if c.double_src else c.dt, int(dmap.shape[0]), int(dmap.shape[1]))
+            elif r.name == "MAP_RGB8":
+                out = nat.sample_map(c.src, dmap, img)
+            else:  # int32 source indices (and float64 weights for a double source) of the map, then the gather
+                idx, wts = nat.index_from_map(c.src, dmap, *self._distance_planes(c.src, dmap))
+                out = self._gather(c.src, idx, wts, img, c.tail, c.dt)
+            if c.src.kind == nat.KIND_PANO:  # the in-place zeroing of invalid pixels: a recipe remembers it, a host map gets it written back
+                if c.map_kind == "lazy":
+                    coordinate_map.note_invalid_zeroed()
+                elif host is not None:
+                    host[...] = nat.to_host(dmap)
+            return out if r.device_out else _to_host(out)
+
+
+class _Call(NamedTuple):
+    """What a process_coordinate_map call is made of: everything ``_route`` decides from and the executors work with."""
+
+    src: nat.pb_proj  # the source projection (this image's)
+    custom_src: bool  # its Lens is made of user callables: the host evaluates it
+    height: int
+    width: int
+    tail: tuple  # the image's shape after (height, width)
+    dt: np.dtype
+    bpp: int  # bytes per pixel
+    on_device: bool  # the image is a device array
+    map_kind: str  # "lazy" (a recipe), "coordmap" (a materialised CoordinateMap), "ndarray" (anything else on the host), "device"
+    map_shape: tuple
+    rotations: Sequence  # a recipe's
+    interpolation: str
+    supersample: int
+
+    @property
+    def double_src(self) -> bool:
+        return self.src.kind == nat.KIND_DOUBLE
+
+    @property
+    def fused(self) -> bool:  # what pb_remap_u8 and pb_sample_map_u8 take: uint8 RGB through a built-in lens
+        return self.bpp == 3 and self.tail == (3,) and self.dt == _SAMPLES_8_16[0] and not self.custom_src
+
+
+class _Route(NamedTuple):
+    name: str  # a row of DESIGN 3.12
+    fallback: Union[str, None]  # the row that serves the call when the plan refuses this one (asked once the plan exists)
+    rotations: Sequence  # for _plan_for
+    eager: bool  # for _plan_for: the interpolating modes read the tile models from the first use on
+    device_out: bool  # the result stays on the device
+    supersample: int = 1  # for the launch
+    inner: Union["_Route", None] = None  # SS_GENERIC: the n = 1 route whose result it reduces
+
+
+_SAMPLES_8_16 = (np.dtype(np.uint8), np.dtype(np.uint16))
+
+
+def _route(c: _Call, device_out: bool = False) -> _Route:
+    """The facade's one routing decision, the counterpart of the library's pb_route: from the facts of a call the route, what
+    it passes on, and the argument errors that come before any device work.  Pure: no device, no plan, no library."""
+    n, interpolating, rotations, fused = c.supersample, c.interpolation != "nearest", c.rotations, c.fused
+    if n > 1:
+        if c.dt not in _SAMPLES_8_16:
+            raise NotImplementedError(f"supersampling takes 8- or 16-bit unsigned samples, got {c.dt}")
+        if c.map_shape[0] % n or c.map_shape[1] % n:
+            raise ValueError(f"a ({c.map_shape[0]}, {c.map_shape[1]}) coordinate map is not divisible by supersample={n}")
+    if interpolating:
+        if c.dt not in _SAMPLES_8_16:
+            raise NotImplementedError(f"{c.interpolation} sampling takes 8- or 16-bit unsigned samples, got {c.dt}")
+        if c.double_src and len(c.tail) != 1:
+            # (the reference's blend cannot broadcast (H, W) samples against its (H, W, 1) factor maps either)
+            raise ValueError(f"operands could not be broadcast together with shapes ({c.map_shape[0]},{c.map_shape[1]}) ({c.map_shape[0]},{c.map_shape[1]},1)")
+    stay, lazy = c.on_device or device_out, c.map_kind == "lazy"
+    if n > 1 and not (lazy and fused and len(rotations) <= nat.PB_MAX_ROTATIONS):
+        return _Route("SS_GENERIC", None, rotations, False, stay, inner=_route(c._replace(supersample=1), device_out=True))
+    if interpolating and len(rotations) > nat.PB_MAX_ROTATIONS:
+        # The reference applies any number of -r rotations one after the other (scripts/commands/make_photo.py:128-131).  A chain longer
+        # than one fused plan takes leaves the plan for the materialised-map kernels, which only truncate; in an interpolating mode (our
+        # own definition, no reference bits to keep) the chain folds into one matrix product R_k ... R_1 instead.
+        folded = np.eye(3)
+        for m in rotations:
+            folded = np.asarray(m, dtype=np.float64).reshape(3, 3) @ folded
+        rotations = (folded,)
+    planned = lazy and len(rotations) <= nat.PB_MAX_ROTATIONS and (fused or not c.custom_src)  # the geometry has a plan
+    if planned and fused:
+        name = "SS_FUSED" if n > 1 and stay else "DEV_RGB8" if stay else "HOST_RGB8"
+        return _Route(name, None, rotations, interpolating, stay, n)
+    if planned and not interpolating:
+        if not c.double_src and c.bpp in nat.PX_SIZES:  # the tile kernel of pixel sizes where the plan takes it (Plan.px_supported)
+            return _Route("DEV_PX" if stay else "HOST_PX", "PLAN_GATHER", rotations, False, stay)
+        return _Route("PLAN_GATHER", None, rotations, False, stay)
+    return _Route("MAP_INTERP" if interpolating else "MAP_RGB8" if fused else "MAP_GATHER", None, rotations, False, stay)
 
 
 def _map_supersample(coordinate_map, supersample) -> int:
