@@ -26,24 +26,7 @@ except ImportError:  # the NumPy workflow needs no torch
 
 from ._device import DeviceArray
 from . import build as _build
-
-
-def host_math_flavour() -> str:
-    """Which code THIS host's NumPy runs for np.arcsin / arccos / arctan / tan - and so which bits the reference would print here:
-    "svml" (NumPy's AVX-512 kernels: x86-64 Linux with AVX512_SKX) or "libm" (everything else: the platform's libm).  PB_MATH_FLAVOUR
-    overrides.  The library is loaded in the same flavour (include/photonbend_hip.h, "MATH FLAVOURS")."""
-    env = os.environ.get("PB_MATH_FLAVOUR", "").lower()
-    if env in ("svml", "libm"):
-        return env
-    try:
-        try:
-            from numpy._core._multiarray_umath import __cpu_features__ as feats
-        except ImportError:
-            from numpy.core._multiarray_umath import __cpu_features__ as feats
-    except Exception:
-        return "svml"
-    return "svml" if feats.get("AVX512_SKX") else "libm"
-
+from .build import host_math_flavour  # (the build picks the diagnostic library's flavour by it too)
 
 MATH_FLAVOUR = host_math_flavour()
 # PB_LIB_PATH: another build of the same sources (A/B experiments, the diagnostic build); else the product library of the host's flavour

@@ -145,3 +145,33 @@ def pb_plan_private(case: Case, **kw):
     src, cmap = pb_chain(case, image=np.zeros((case.src[1], case.src[2], 3), np.uint8))
     kw.setdefault("bilinear", True)  # (most private plans are the bilinear tests': the mode's tables at creation, as the C ABI's default does)
     return nat.Plan(cmap.dst_proj, cmap.rotations, src._proj(), **kw)
+
+
+# oracle/check_math.cpp is the HOST build of the device math header: its flags are part of what the tests that run it mean - every multiply
+# and add rounded separately, fma() a hardware FMA - so they are written down here and nowhere else in the suite
+CHECK_MATH_FLAGS = ("-O2", "-ffp-contract=off", "-mfma")
+CHECK_MATH_SANITIZER_FLAGS = ("-O1", "-g", "-ffp-contract=off", "-mfma", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined")
+_CHECK_MATH = {}
+
+
+def check_math(sanitizers: bool = False):
+    """-> (the stand-alone checker compiled from oracle/check_math.cpp, g++'s CompletedProcess: the caller decides what a failed compile means).
+    Compiled once per process, plain and with the sanitizers, into a directory removed at exit; skips the calling test where there is no g++."""
+    import atexit
+    import shutil
+    import subprocess
+    import tempfile
+
+    import pytest
+
+    gxx = shutil.which("g++")
+    if not gxx:
+        pytest.skip("no g++")
+    if sanitizers not in _CHECK_MATH:
+        tmp = tempfile.mkdtemp(prefix="pb_check_math_")
+        atexit.register(shutil.rmtree, tmp, ignore_errors=True)
+        exe = os.path.join(tmp, "check_math_san" if sanitizers else "check_math")
+        src = os.path.join(os.path.dirname(os.path.dirname(GOLD)), "oracle", "check_math.cpp")
+        flags = CHECK_MATH_SANITIZER_FLAGS if sanitizers else CHECK_MATH_FLAGS
+        _CHECK_MATH[sanitizers] = (exe, subprocess.run([gxx, *flags, "-o", exe, src], capture_output=True, text=True))
+    return _CHECK_MATH[sanitizers]

@@ -4,24 +4,14 @@ whether the compiler keeps the entry in SGPRs or drags it through VGPR lanes (v_
 spelling of an unrelated `if` - +40 % vector instructions per wave, c5 bilinear 80 -> 91 us, same pixels, every test green.  Nothing but
 the listing shows it, so the listing is pinned here: VGPRs (occupancy), scratch, float64 in the float32 kernels, and the lane traffic."""
 
-import importlib.util
-import os
-import shutil
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import kernel_listing
 
 
 @pytest.fixture(scope="module")
-def stats(tmp_path_factory):
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("needs hipcc")
-    spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "experiments", "r6", "isa_stats.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    rows = mod.kernel_stats(out=str(tmp_path_factory.mktemp("isa") / "pb.s"))
-    return {r["name"]: r for r in rows}
+def stats():
+    return kernel_listing.stats()
 
 
 def _pick(stats, prefix):

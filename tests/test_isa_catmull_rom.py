@@ -1,24 +1,14 @@
 """The Catmull-Rom tile kernel's budget, read from the compiler's listing of the product build (like test_isa_supersample.py): no scratch,
 no float64, and no tile entry dragged through VGPR lanes (DESIGN 3.4 "A finding worth its own line")."""
 
-import importlib.util
-import os
-import shutil
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import kernel_listing
 
 
 @pytest.fixture(scope="module")
-def stats(tmp_path_factory):
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("needs hipcc")
-    spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "experiments", "r6", "isa_stats.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    rows = mod.kernel_stats(out=str(tmp_path_factory.mktemp("isa") / "pb.s"))
-    return {r["name"]: r for r in rows}
+def stats():
+    return kernel_listing.stats()
 
 
 def test_tile_kernel_budget(stats):

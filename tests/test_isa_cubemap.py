@@ -5,14 +5,12 @@ a hot kernel ever appear it is held to the camera's registers, without scratch o
 cube's own instantiations of the per-pixel kernels and the cube destination's map kernel - and must not spill or lose waves against
 the camera's."""
 
-import importlib.util
-import os
 import re
-import shutil
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import kernel_listing
+
 CUBE, CAMERA = 5, 0  # PB_KIND_CUBE, PB_KIND_CAMERA (include/photonbend_hip.h)
 HOT = ("pb_hot_win_kernel", "pb_hot_kernel", "pb_ss_win_kernel", "pb_bilinear_hot_kernel", "pb_catmull_rom_hot_kernel")
 # kernels of the float64 chain that exist per source kind: the template argument that is the kind
@@ -30,14 +28,8 @@ NAMED = {
 
 
 @pytest.fixture(scope="module")
-def stats(tmp_path_factory):
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("needs hipcc")
-    spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "experiments", "r6", "isa_stats.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    rows = mod.kernel_stats(out=str(tmp_path_factory.mktemp("isa") / "pb.s"))
-    return {r["name"]: r for r in rows}
+def stats():
+    return kernel_listing.stats()
 
 
 def _split(name):

@@ -2,27 +2,19 @@
 instantiations, no scratch, no float64, the tile entry in scalar registers, at least four waves per SIMD - and the listing's own figures
 per pixel size, pinned."""
 
-import importlib.util
-import os
 import re
-import shutil
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import kernel_listing
+
 # VGPRs and waves per SIMD of the listing, per bytes per pixel (both source kinds alike; recorded in DESIGN 3.11)
 PINNED = {1: (64, 7), 2: (64, 7), 4: (64, 7), 6: (80, 6), 8: (89, 5)}
 
 
 @pytest.fixture(scope="module")
-def stats(tmp_path_factory):
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("needs hipcc")
-    spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "experiments", "r6", "isa_stats.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    rows = mod.kernel_stats(out=str(tmp_path_factory.mktemp("isa") / "pb.s"))
-    return {r["name"]: r for r in rows}
+def stats():
+    return kernel_listing.stats()
 
 
 def _px(stats):

@@ -3,13 +3,9 @@ csrc/pb_stages.hpp, which every kernel of the float64 chain inlines), read from 
 test_isa_budget.py: no scratch, and no fewer waves per SIMD than before the lens was added.  The hot kernels never evaluate a lens;
 their budgets are pinned by test_isa_budget.py, test_isa_supersample.py and test_isa_catmull_rom.py."""
 
-import importlib.util
-import os
-import shutil
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import kernel_listing
 
 # waves per SIMD ("Occupancy" in the listing) of every kernel that inlines pb_lens_forward / pb_lens_inverse, read from the listing of
 # commit 34dda95 ("Share one sampler path between bilinear and Catmull-Rom"), the last one without the polynomial lens - same flags
@@ -91,14 +87,8 @@ PARENT_INSTRUCTIONS = {"pb_coordmap_kernel": 1449, "pb_threshold_kernel": 1511}
 
 
 @pytest.fixture(scope="module")
-def stats(tmp_path_factory):
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("needs hipcc")
-    spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "experiments", "r6", "isa_stats.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    rows = mod.kernel_stats(out=str(tmp_path_factory.mktemp("isa") / "pb.s"))
-    return {r["name"]: r for r in rows}
+def stats():
+    return kernel_listing.stats()
 
 
 def test_float64_kernels_keep_their_occupancy_and_have_no_scratch(stats):

@@ -2,24 +2,14 @@
 pb_hot_win_kernel's tile code and adds the n x n reduction: it must stay inside the same register budget - 64 VGPRs, seven waves per SIMD -
 or it loses the latency hiding the windowed tiles live on."""
 
-import importlib.util
-import os
-import shutil
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import kernel_listing
 
 
 @pytest.fixture(scope="module")
-def stats(tmp_path_factory):
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("needs hipcc")
-    spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "experiments", "r6", "isa_stats.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    rows = mod.kernel_stats(out=str(tmp_path_factory.mktemp("isa") / "pb.s"))
-    return {r["name"]: r for r in rows}
+def stats():
+    return kernel_listing.stats()
 
 
 def _pick(stats, prefix):

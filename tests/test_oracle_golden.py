@@ -119,18 +119,13 @@ def test_numpy_and_glibc_functions_are_restated_bit_for_bit(fn, tmp_path):
     (tests/golden/npmath.npz): np.arcsin / np.arccos / np.arctan / np.tan (NumPy's AVX-512 kernels), np.sin / np.cos / np.exp(x * 1j) /
     np.log(z).imag (glibc 2.35) - what rotation.py:129-164, lens.py:71-335 and projection.py:193, :252 run there - on 40 000 arguments
     per function.  Not a tolerance: every bit, NaN for NaN.  Where this machine's NumPy IS that NumPy, a million fresh arguments too."""
-    import shutil
     import subprocess
 
     from tests import npmath_args
 
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("no g++")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = str(tmp_path / "check_math")
-    res = subprocess.run([gxx, "-O2", "-ffp-contract=off", "-mfma", "-o", exe, os.path.join(root, "oracle", "check_math.cpp")], capture_output=True, text=True)
+    exe, res = H.check_math()
     assert res.returncode == 0, res.stderr
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     gold = np.load(os.path.join(root, "tests", "golden", "npmath.npz"))
     code = npmath_args.FUNCTIONS.index(fn)
     src, dst = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
@@ -212,20 +207,14 @@ def test_restated_math_is_clean_under_the_sanitizers(tmp_path):
     """The host build of csrc/pb_math.hpp under AddressSanitizer + UndefinedBehaviorSanitizer (GPU sanitizers are not available on this pool:
     the CPU build is where table indices, shifts and conversions get checked): the whole fixture plus infinities, huge, tiny and
     out-of-domain arguments through all eight functions, no finding, same bits as the plain build."""
-    import shutil
     import subprocess
 
     from tests import npmath_args
 
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("no g++")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = str(tmp_path / "check_math_san")
-    res = subprocess.run([gxx, "-O1", "-g", "-ffp-contract=off", "-mfma", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe,
-                          os.path.join(root, "oracle", "check_math.cpp")], capture_output=True, text=True)
+    exe, res = H.check_math(sanitizers=True)
     if res.returncode != 0:
         pytest.skip("no sanitizer runtime here: " + res.stderr.strip()[-160:])
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     gold = np.load(os.path.join(root, "tests", "golden", "npmath.npz"))
     wild = np.array([np.inf, -np.inf, 1e308, -1e308, 1.7e308, 5e-324, -5e-324, 2.0 ** 1023, 1e9, 65537.0, 1.05e8, np.nan, 0.0, -0.0])
     src, dst = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
@@ -268,18 +257,13 @@ def test_second_math_flavour_is_libms_bit_for_bit(fn, tmp_path):
     rotation.py:158) on the fixture's 40 000 arguments per function - every bit - and, on a glibc 2.35 x86-64 host, against this
     machine's own libm on a million fresh arguments (tan: the main path, |x| < 2^27)."""
     import ctypes
-    import shutil
     import subprocess
 
     from tests import npmath_args
 
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("no g++")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = str(tmp_path / "check_math")
-    res = subprocess.run([gxx, "-O2", "-ffp-contract=off", "-mfma", "-o", exe, os.path.join(root, "oracle", "check_math.cpp")], capture_output=True, text=True)
+    exe, res = H.check_math()
     assert res.returncode == 0, res.stderr
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     gold = np.load(os.path.join(root, "tests", "golden", "npmath_libm.npz"))
     code = 8 + ["arcsin", "arccos", "arctan", "tan"].index(fn)
     src, dst = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
