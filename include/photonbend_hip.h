@@ -292,6 +292,27 @@ int pb_remap_bilinear_u8(const pb_plan* plan, const uint8_t* src_dev, uint8_t* d
 int pb_remap_catmull_rom_u8(const pb_plan* plan, const uint8_t* src_dev, uint8_t* dst_dev, int n_frames,
                             size_t src_frame_stride, size_t dst_frame_stride, void* stream);
 
+/* ROTATION TRACKS (ABI 5, additive): a batch in which every frame has rotations of its own - stabilising or reframing a
+ * 360-degree video, a turntable - in ONE launch.  Frame f receives exactly the bytes the matching single-plan call (pb_remap_u8,
+ * pb_remap_bilinear_u8, pb_remap_catmull_rom_u8 by `interpolation`) writes for frame f alone from a plan of the same dst and src in
+ * PB_MODE_FAITHFUL whose rotation chain is this plan's own n_rot rotations followed by frame f's n_rot_per_frame.  Rotations are applied
+ * one after another, arccos / atan2 between them, as Rotation.rotate_coordinate_map does (core/rotation.py:102-176); nothing is folded.
+ * Nearest: the reference's own output for that chain; the interpolating modes: their float64 per-pixel definition.
+ *   rot3x3_dev       DEVICE memory, 8-byte aligned: float64 [n_frames][n_rot_per_frame][9], row-major 3 x 3 = Rotation.rotation_matrix.
+ *                    The kernel reads it when the stream runs the launch: it must stay alive and unchanged until then.
+ *   interpolation    PB_INTERP_NEAREST, PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM.
+ * The plan's tables are never read (they are certified for another chain): a deferred plan, a prepared one, any mode, with or without the
+ * bilinear mode's tables or device state are served alike - the float64 chain per pixel, the part no frame changes (the destination's
+ * inverse projection, a cube destination's face rotation, the plan's own rotations) once per pixel and chunk of frames.  All source and
+ * destination kinds.  pb_remap_u8's contract: its argument checks and messages, strides in bytes (0: packed), asynchronous on `stream`;
+ * never allocates, never synchronises, never copies the table (graph-capture safe).  PB_ERR_INVALID before any launch: a null or misaligned
+ * table, n_rot_per_frame < 1, n_rot + n_rot_per_frame > PB_MAX_ROTATIONS, an interpolation outside the three.  n_frames == 0: PB_OK, no launch. */
+#define PB_INTERP_NEAREST 0
+#define PB_INTERP_BILINEAR 1
+#define PB_INTERP_CATMULL_ROM 2
+int pb_remap_track_u8(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, int interpolation, const uint8_t* src_dev, uint8_t* dst_dev,
+                      int n_frames, size_t src_frame_stride, size_t dst_frame_stride, void* stream);
+
 /* SUPERSAMPLED REMAPPING (ABI 5, additive).  Output pixel (i, j) is, per channel, the round-half-to-even mean of the n x n block
  * S[n i : n i + n, n j : n j + n] of S = the remap of the n x destination: the same kind and lens with image (n H, n W) and, for a camera,
  * magnitude n x (a double fisheye's magnitude = height / 2 scales by itself); n in {2, 4}, a power of two, so its f_distance is exactly
@@ -308,9 +329,7 @@ int pb_remap_catmull_rom_u8(const pb_plan* plan, const uint8_t* src_dev, uint8_t
  *   pb_box_reduce         the generic kernel on its own: (n_frames, n height, n width, channels) samples of sample_bytes (1 or 2) bytes ->
  *                         (n_frames, height, width, channels), tightly packed.
  * n outside {2, 4}, indivisible dimensions and n x frames beyond the projection limit (n^2 h w < 2^29) are PB_ERR_INVALID. */
-#define PB_INTERP_NEAREST 0
-#define PB_INTERP_BILINEAR 1
-#define PB_SS_GENERIC 1u
+#define PB_SS_GENERIC 1u /* (PB_INTERP_NEAREST, PB_INTERP_BILINEAR: above) */
 int pb_remap_ss_workspace(const pb_plan* plan, int n, int interpolation, unsigned flags, size_t* bytes);
 int pb_remap_ss_u8(const pb_plan* plan, int n, int interpolation, const uint8_t* src_dev, uint8_t* dst_dev, int n_frames, size_t src_frame_stride,
                    size_t dst_frame_stride, void* workspace_dev, size_t workspace_bytes, unsigned flags, void* stream);

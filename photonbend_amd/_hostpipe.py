@@ -202,16 +202,25 @@ def remap_ndarray(plan: nat.Plan, image: np.ndarray, interpolation: str = "neare
 
 
 def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, interpolation: str = "nearest",
-                 supersample: int = 1) -> Iterator[np.ndarray]:
+                 supersample: int = 1, track=None) -> Iterator[np.ndarray]:
     """Streams host-resident frames through one plan: while frame k + 1 uploads on the H2D stream, the remap kernel of frame k stores its
     output over PCIe straight into frame k's result ndarray (page-locked, device-visible), through `depth` rotating device input
     buffers.  Yields uint8 (H, W, 3) ndarrays in order (page-locked, recycled when dropped).  ``supersample`` n: `plan` is the n x
     destination's, the results are (H / n, W / n, 3) block means - the fused kernel stores only those over PCIe.  Nearest without
     supersampling also takes frames (h, w, *tail) of any dtype whose pixel is 1, 2, 4, 6 or 8 bytes (``remap_ndarray``): all frames of a
-    call share the first frame's format, and the results are (H, W, *tail) of that dtype."""
+    call share the first frame's format, and the results are (H, W, *tail) of that dtype.  ``track``: ``nat.rotation_table``'s result - a
+    rotation per frame (uint8 RGB, not supersampled): the table is uploaded once before the first frame (a device array is used in place)
+    and frame f is a one-frame ``Plan.launch_track`` that points at entry f; a frame beyond the table is a ValueError at that frame."""
     nat.check_interpolation(interpolation, supersample)
+    if track is not None and supersample != 1:
+        raise ValueError("a rotation track is not supersampled: pass supersample=1")
     oh, ow = _out_shape(plan, supersample)
     nat.require_gpu()
+    tab = n_tab = k_tab = None
+    if track is not None:
+        tab, n_tab, k_tab = track
+        if isinstance(tab, np.ndarray):  # (synchronous, once: every launch below finds the whole table on the device)
+            tab = DeviceArray(tab.shape, np.float64).copy_from_host(tab)
     depth = max(2, int(depth))
     dev = nat.current_device()
     pipe = pipe_for(dev)
@@ -248,7 +257,14 @@ def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, i
             uploaded[slot].record(s_up)
             s_run.wait(uploaded[slot])
             out = results[slot] = PINNED.ndarray(dh, fmt[1])
-            plan.launch(d_in[slot].data_ptr(), out.ctypes.data, 1, s_run.handle, interpolation, **_ss_kw(supersample, ws), **_px_kw(bpp))
+            if tab is None:
+                plan.launch(d_in[slot].data_ptr(), out.ctypes.data, 1, s_run.handle, interpolation, **_ss_kw(supersample, ws), **_px_kw(bpp))
+            else:
+                if k >= n_tab:
+                    raise ValueError(f"frame {k} has no rotation: the table holds {n_tab}")
+                if bpp != 3:
+                    raise ValueError(f"a rotation track takes uint8 {sh[:2] + (3,)} frames, got {a.dtype} {tuple(a.shape)}")
+                plan.launch_track(tab.data_ptr() + k * k_tab * nat.TRACK_MATRIX_BYTES, k_tab, d_in[slot].data_ptr(), out.ctypes.data, 1, s_run.handle, interpolation)
             computed[slot].record(s_run)
             pending.append(slot)
             if direct and ahead is not None:

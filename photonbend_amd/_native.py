@@ -115,6 +115,7 @@ SIGNATURES = {
     "pb_remap_px_supported": (C.c_int, [_VP, C.c_int]),
     "pb_remap_bilinear_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_catmull_rom_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
+    "pb_remap_track_u8": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_ss_workspace": (C.c_int, [_VP, C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_size_t)]),
     "pb_remap_ss_u8": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP, C.c_size_t, C.c_uint, _VP]),
     "pb_box_reduce": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
@@ -207,6 +208,41 @@ def check_interpolation(interpolation: str, supersample: int = 1) -> int:
     if n > 1 and interpolation not in INTERP_IDS:
         raise ValueError(f"{interpolation} sampling is not supersampled: pass supersample=1")
     return n
+
+
+TRACK_INTERP_IDS = {"nearest": 0, "bilinear": 1, "catmull-rom": 2}  # pb_remap_track_u8's PB_INTERP_* ids
+TRACK_MATRIX_BYTES = 72  # one row-major 3 x 3 float64 matrix of a rotation table
+
+
+def rotation_table(rotations, n_rot: int = 0):
+    """A rotation track as pb_remap_track_u8 takes it -> (table, N, k): N frames of k rotations each, applied in order behind a plan's own
+    ``n_rot``.  ``rotations``: a float64 ndarray (N, 3, 3) or (N, k, 3, 3) - returned C-contiguous as (N, k, 3, 3), for upload -, a device
+    array of float64 of either shape (contiguous; returned as it is, used in place), or a sequence of ``Rotation`` objects / 3 x 3
+    matrices (one per frame).  ValueError for any other shape or dtype, for k < 1 and for n_rot + k > PB_MAX_ROTATIONS.  Needs no GPU."""
+    if is_device_array(rotations):
+        tab = rotations
+        dt = torch_dtype_np(tab.dtype) if is_tensor(tab) else np.dtype(tab.dtype)
+        if is_tensor(tab) and not tab.is_contiguous():
+            raise ValueError("a device rotation table must be contiguous")
+    else:
+        if not isinstance(rotations, np.ndarray):
+            try:
+                rotations = [getattr(r, "rotation_matrix", r) for r in rotations]
+            except TypeError:
+                raise ValueError(f"rotations must be an array (N, 3, 3) or (N, k, 3, 3) or a sequence of Rotation objects, got {type(rotations).__name__}") from None
+            rotations = np.asarray(rotations) if len(rotations) else np.empty((0, 3, 3), np.float64)
+        tab, dt = rotations, rotations.dtype
+    shp = tuple(int(v) for v in tab.shape)
+    if dt != np.float64:
+        raise ValueError(f"a rotation table holds float64 matrices, got {dt}")
+    if len(shp) not in (3, 4) or shp[-2:] != (3, 3):
+        raise ValueError(f"a rotation table has shape (N, 3, 3) or (N, k, 3, 3), got {shp}")
+    n, k = shp[0], (shp[1] if len(shp) == 4 else 1)
+    if k < 1 or int(n_rot) + k > PB_MAX_ROTATIONS:
+        raise ValueError(f"{k} rotations per frame behind the plan's {int(n_rot)}: between 1 and {PB_MAX_ROTATIONS - int(n_rot)} fit (PB_MAX_ROTATIONS = {PB_MAX_ROTATIONS})")
+    if isinstance(tab, np.ndarray):
+        tab = np.ascontiguousarray(tab).reshape(n, k, 3, 3)
+    return tab, n, k
 
 
 PX_SIZES = (1, 2, 3, 4, 6, 8)  # bytes per pixel pb_remap_px takes: grey8, grey16 / two uint8 channels, RGB8, RGBA8, RGB16, RGBA16
@@ -637,6 +673,57 @@ class Plan:
         if out is not None:
             return out
         return o if batched else o[0]
+
+    def launch_track(self, table_ptr: int, n_rot_per_frame: int, src_ptr: int, dst_ptr: int, n_frames: int = 1, stream: int | None = None,
+                     interpolation: str = "nearest", src_stride: int = 0, dst_stride: int = 0) -> None:
+        """The raw rotation-track call (pb_remap_track_u8): frame f of n_frames is remapped with this plan's own rotations followed by the
+        ``n_rot_per_frame`` matrices at table_ptr + f * n_rot_per_frame * 72 (device memory, float64, row-major 3 x 3), in one launch on
+        `stream`.  The table must stay alive and unchanged until the stream has run the launch."""
+        if interpolation not in TRACK_INTERP_IDS:
+            raise ValueError(f"interpolation must be one of {', '.join(map(repr, TRACK_INTERP_IDS))}, got {interpolation!r}")
+        self._gated(load().pb_remap_track_u8, self._h, table_ptr, int(n_rot_per_frame), TRACK_INTERP_IDS[interpolation], src_ptr, dst_ptr, int(n_frames),
+                    int(src_stride), int(dst_stride), current_stream() if stream is None else stream)
+
+    def remap_track(self, src, rotations, out=None, interpolation: str = "nearest", stream: int | None = None):
+        """A batch with a rotation per frame in ONE launch: src uint8 device array (N, h, w, 3) -> (N, H, W, 3); frame f is what a plan of
+        this one's rotations followed by ``rotations[f]`` gives in MODE_FAITHFUL.  ``rotations``: see ``rotation_table`` - an ndarray
+        (N, 3, 3) / (N, k, 3, 3) or a sequence of ``Rotation`` objects is uploaded; a float64 device array is used in place (keep it
+        alive and unchanged until the stream has run the launch).  Shapes, dtypes and counts are checked before any device work."""
+        if interpolation not in TRACK_INTERP_IDS:
+            raise ValueError(f"interpolation must be one of {', '.join(map(repr, TRACK_INTERP_IDS))}, got {interpolation!r}")
+        if not is_device_array(src):
+            raise PbError(f"source frames must be uint8 device arrays (CUDA tensors or DeviceArrays), got {type(src).__name__}")
+        tens = is_tensor(src)
+        shp = tuple(int(v) for v in src.shape)
+        u8 = (src.dtype == torch.uint8) if tens else (src.dtype == np.uint8)
+        if not u8 or len(shp) != 4 or shp[1:] != (self.src.height, self.src.width, 3):
+            raise PbError(f"source frames must be uint8 (N, {self.src.height}, {self.src.width}, 3), got {shp} {src.dtype}")
+        n = shp[0]
+        tab, n_tab, k = rotation_table(rotations, self.n_rot)
+        if n_tab != n:
+            raise ValueError(f"{n} frames need {n} rotations, the table holds {n_tab}")
+        oshape = (n, self.dst.height, self.dst.width, 3)
+        if out is not None:
+            ok = is_device_array(out) and is_tensor(out) == tens and tuple(out.shape) == oshape
+            ok = ok and ((out.dtype == torch.uint8 and out.is_contiguous()) if tens else out.dtype == np.uint8)
+            if not ok:
+                raise PbError(f"out must be a contiguous uint8 device array {oshape} of the source's kind")
+            if tens and out.device != src.device:
+                raise PbError(f"out must live on the source's device ({src.device}), got {out.device}")
+        require_gpu()
+        s = src.contiguous() if tens else src
+        o = empty(oshape, np.uint8, like=s) if out is None else out
+        if n == 0:
+            return o
+        with _on(s):
+            st = current_stream() if stream is None else stream
+            uploaded = isinstance(tab, np.ndarray)
+            if uploaded:  # (synchronous: the table is on the device before the launch is queued)
+                tab = torch.from_numpy(tab).to(s.device) if tens else DeviceArray(tab.shape, np.float64).copy_from_host(tab)
+            self.launch_track(tab.data_ptr(), k, s.data_ptr(), o.data_ptr(), n, st, interpolation)
+            if uploaded and tens and int(st or 0) != current_stream():
+                check(load().pb_stream_sync(st))  # (the table goes back to torch's allocator, which orders its reuse on the current stream only)
+        return o
 
     def px_supported(self, bytes_per_px: int) -> bool:
         """Whether ``remap_px`` / ``launch(bytes_per_px=...)`` takes this plan with this pixel size (pb_remap_px_supported): a prepared plan

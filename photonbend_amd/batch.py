@@ -27,10 +27,18 @@ def plan_for(dst_image, rotations, src_image, supersample: int = 1) -> nat.Plan:
 
 
 def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, interpolation: str = "nearest",
-                 supersample: int = 1) -> Iterator[np.ndarray]:
+                 supersample: int = 1, rotations=None) -> Iterator[np.ndarray]:
     """Remaps an iterable of uint8 (h, w, 3) ndarrays with ``plan``; yields uint8 (H, W, 3) ndarrays in order
     (``_hostpipe.remap_frames``: upload stream + launch stream, page-locked results the kernel writes directly, no PyTorch).
     ``supersample`` n: ``plan`` came from ``plan_for(..., supersample=n)``; the frames are (H, W, 3) block means of its n x output.
-    ``interpolation``: "nearest", "bilinear" or "catmull-rom" (not supersampled) - checked here, before the first frame."""
-    nat.check_interpolation(interpolation, supersample)
-    return _hostpipe.remap_frames(plan, frames, depth, interpolation, supersample)
+    ``interpolation``: "nearest", "bilinear" or "catmull-rom" (not supersampled) - checked here, before the first frame.
+    ``rotations``: a rotation track (``core.rotation_track``, an array (N, 3, 3) / (N, k, 3, 3), a float64 device array or a sequence
+    of ``Rotation`` objects) - frame f is remapped with the plan's own rotations followed by entry f's (``Plan.remap_track``); the table
+    is uploaded once, before the first frame; a frame beyond its length is a ValueError at that frame; not supersampled."""
+    n = nat.check_interpolation(interpolation, supersample)
+    table = None
+    if rotations is not None:
+        if n > 1:
+            raise ValueError("a rotation track is not supersampled: pass supersample=1")
+        table = nat.rotation_table(rotations, plan.n_rot)
+    return _hostpipe.remap_frames(plan, frames, depth, interpolation, supersample, table)

@@ -15,3 +15,4 @@ pixel; a *ProjectionImage* offers ``get_coordinate_map()`` and
 from . import lens, projection, rotation  # noqa: F401
 from ._coordmap import CoordinateMap  # noqa: F401
 from .projection import CubemapImage  # noqa: F401
+from .rotation import rotation_track  # noqa: F401

@@ -53,3 +53,16 @@ class Rotation:
         out = nat.rotate(self.rotation_matrix, dev)
         host[...] = nat.to_host(dev)  # the in-place zeroing of invalid pixels
         return nat.to_host(out)
+
+
+def rotation_track(angles) -> np.ndarray:
+    """(N, 3) pitch, yaw, roll in radians, one triple per frame -> float64 (N, 3, 3): row k is ``Rotation(*angles[k]).rotation_matrix``,
+    bit for bit (it is made by that very code) - the table ``Plan.remap_track`` and ``batch.remap_frames(rotations=...)`` take for a
+    stabilised or reframed video."""
+    a = np.asarray(angles)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError(f"angles must have shape (N, 3): pitch, yaw, roll per frame, got {a.shape}")
+    out = np.empty((a.shape[0], 3, 3), np.float64)
+    for k in range(a.shape[0]):
+        out[k] = Rotation(a[k, 0], a[k, 1], a[k, 2]).rotation_matrix
+    return out

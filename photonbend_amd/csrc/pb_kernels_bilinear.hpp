@@ -976,10 +976,9 @@ __device__ __forceinline__ unsigned PbBilinear::eye(const PbParams& P, const uin
 // One output pixel from a double-fisheye source, from the float64 chain: the reference's blend (projection.py:439-460) of the two eyes'
 // rounded samples, each eye sampled like a camera source on its half of the frame (the right one mirrored).  (Whole inside the frame loop
 // of its callers: with the chain hoisted out of it by hand both filters' kernels need 256 VGPRs and more, one wave per SIMD.)
+// (pb_interp_double_at: from the chain's map entry - a rotation track's frames rotate it further first, pb_kernels_track.hpp)
 template <class FILTER>
-__device__ __forceinline__ unsigned pb_interp_double_px(const PbParams& P, int i, int j, const uint8_t* __restrict__ s) {
-    PbCoord c = pb_dst_coord(P, i, j);
-    c = pb_rotate_all(P, c);
+__device__ __forceinline__ unsigned pb_interp_double_at(const PbParams& P, const PbCoord& c, const uint8_t* __restrict__ s) {
     if (c.inv) return 0u;
     const double lat_r = (c.lat * -1.0) + PB_PI;  // projection.py:426-427
     const double fl = pb_merge_factor(P, c.lat), fr = pb_merge_factor(P, lat_r);
@@ -989,6 +988,10 @@ __device__ __forceinline__ unsigned pb_interp_double_px(const PbParams& P, int i
     const unsigned r = FILTER::eye(P, s, lat_r, sl, cl, P.src_eye_w_right, P.src_cx_r, P.src_eye_w, true);
     return pb_blend_u8(l & 0xFF, r & 0xFF, fl, fr) | (pb_blend_u8((l >> 8) & 0xFF, (r >> 8) & 0xFF, fl, fr) << 8) |
            (pb_blend_u8((l >> 16) & 0xFF, (r >> 16) & 0xFF, fl, fr) << 16);
+}
+template <class FILTER>
+__device__ __forceinline__ unsigned pb_interp_double_px(const PbParams& P, int i, int j, const uint8_t* __restrict__ s) {
+    return pb_interp_double_at<FILTER>(P, pb_rotate_all(P, pb_dst_coord(P, i, j)), s);
 }
 template <class FILTER>
 __global__ __launch_bounds__(PB_BLOCK) void pb_interp_double_kernel(const PbParams P, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,

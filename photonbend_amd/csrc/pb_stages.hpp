@@ -378,18 +378,23 @@ __device__ __forceinline__ PbCoord pb_rotate_back(PbCoord c, double vx, double v
     c.lon = pb_atan2(vz, vx); // rotation.py:159-164
     return c;
 }
+// "rotate by this matrix", spelled once: R (row-major 3 x 3, rotation.py:100) times the direction, in the accumulation order of the BLAS
+// behind np.matmul (probe).  R is the plan's matrix in the parameter block or a rotation track's in device memory (uniform
+// address: scalar operands either way).
+__device__ __forceinline__ void pb_rotate_mul(const double* R, double x, double yy, double z, double& vx, double& vy, double& vz) {
+    vx = fma(R[2], z, fma(R[0], x, R[1] * yy));
+    vy = fma(R[5], z, fma(R[3], x, R[4] * yy));
+    vz = fma(R[8], z, fma(R[6], x, R[7] * yy));
+}
 __device__ __forceinline__ PbCoord pb_rotate(const double* __restrict__ R, PbCoord c) {
     if (c.inv) {  // rotation.py:125, :168-175
         c.lat = 0.0;
         c.lon = 0.0;
         return c;
     }
-    double x, yy, z;
+    double x, yy, z, vx, vy, vz;
     pb_rotate_vec(c, x, yy, z);
-    // accumulation order of the BLAS behind np.matmul (probe)
-    const double vx = fma(R[2], z, fma(R[0], x, R[1] * yy));
-    const double vy = fma(R[5], z, fma(R[3], x, R[4] * yy));
-    const double vz = fma(R[8], z, fma(R[6], x, R[7] * yy));
+    pb_rotate_mul(R, x, yy, z, vx, vy, vz);
     return pb_rotate_back(c, vx, vy, vz);
 }
 
@@ -423,9 +428,7 @@ __device__ __forceinline__ PbCoord pb_rotate_all(const PbParams& P, PbCoord c) {
             vz = fma(pb_cube_entry<false>(f, 2, 2), z, fma(pb_cube_entry<false>(f, 2, 0), x, pb_cube_entry<false>(f, 2, 1) * yy));
         } else {
             const double* __restrict__ R = P.R[k];
-            vx = fma(R[2], z, fma(R[0], x, R[1] * yy));
-            vy = fma(R[5], z, fma(R[3], x, R[4] * yy));
-            vz = fma(R[8], z, fma(R[6], x, R[7] * yy));
+            pb_rotate_mul(R, x, yy, z, vx, vy, vz);
         }
         c = pb_rotate_back(c, vx, vy, vz);
     }

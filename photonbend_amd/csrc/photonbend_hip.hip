@@ -6,6 +6,7 @@
 //   pb_kernels_double.hpp    hot kernel for double-fisheye sources (one tile table per eye, weight classes)
 //   pb_kernels_sep.hpp       separable tables for the unrotated stitch (row factors; unaligned-frame fallback)
 //   pb_kernels_bilinear.hpp  opt-in bilinear sampling
+//   pb_kernels_track.hpp     rotation tracks: a rotation per frame in one launch of the float64 chain
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared ...
 // (-ffp-contract=off is REQUIRED: the reference rounds every multiply and add
@@ -37,6 +38,7 @@
 #include "pb_kernels_supersample.hpp"
 #include "pb_kernels_catmull_rom.hpp"
 #include "pb_kernels_px.hpp"
+#include "pb_kernels_track.hpp"
 
 #define PB_DOUBLE_FRAMES_PER_WAVE 1  // frames a double-source wave loops over (the rest of a batch is a grid dimension)
 
@@ -602,7 +604,7 @@ static bool pb_bilinear_tiles_allowed(const PbParams& P) {
     if (P.src.kind == PB_KIND_CUBE) return false;
     return !(P.src.kind == PB_KIND_DOUBLE && P.mrg_range != 0.0 && fabs(P.mrg_range) < 0.999 * (PB_PI / 180.0));  // (181 / 179 degrees themselves: tiles)
 }
-#define PB_INTERP_CATMULL_ROM 2  // (a routing id of this file only: the supersampled entry points take PB_INTERP_NEAREST and PB_INTERP_BILINEAR)
+// (PB_INTERP_CATMULL_ROM: the third id, which pb_remap_track_u8 takes; the supersampled entry points take PB_INTERP_NEAREST and PB_INTERP_BILINEAR)
 // Template arguments from run-time values: f(PbInt<A>()) if `first`, else f(PbInt<B>()) - the kernel's KIND, its waves per workgroup,
 // the supersample factor.
 template <int V>
@@ -2029,6 +2031,51 @@ int pb_remap_catmull_rom_u8(const pb_plan* plan, const uint8_t* src_dev, uint8_t
     if (rc != PB_OK || n_frames == 0) return rc;
     return pb_launch(plan, pb_route(plan, PB_INTERP_CATMULL_ROM, 1, 0, pb_aligned16(src_dev, src_frame_stride)), src_dev, dst_dev, n_frames,
                      src_frame_stride, dst_frame_stride, (hipStream_t)stream);
+}
+
+// A rotation track: the float64 chain of the plan's parameter block with frame f's matrices behind the plan's own.  No route:
+// no table of the plan is certified for these chains, so every plan state takes the same kernels.
+int pb_remap_track_u8(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, int interpolation, const uint8_t* src_dev, uint8_t* dst_dev,
+                      int n_frames, size_t src_frame_stride, size_t dst_frame_stride, void* stream) {
+    const int rc = pb_check_frames(plan, src_dev, dst_dev, n_frames, 1, src_frame_stride, dst_frame_stride);
+    if (rc != PB_OK) return rc;
+    if (!rot3x3_dev) return pb_fail(PB_ERR_INVALID, "null rotation table");
+    if ((uintptr_t)rot3x3_dev & 7u) return pb_fail(PB_ERR_INVALID, "the rotation table must be 8-byte aligned");
+    if (n_rot_per_frame < 1) return pb_fail(PB_ERR_INVALID, "n_rot_per_frame must be at least 1");
+    const PbParams& P = plan->P;
+    if (n_rot_per_frame > PB_MAX_ROTATIONS - P.n_rot)
+        return pb_fail(PB_ERR_INVALID, "the plan's " + std::to_string(P.n_rot) + " rotations and " + std::to_string(n_rot_per_frame) + " per frame exceed PB_MAX_ROTATIONS (" +
+                                           std::to_string(PB_MAX_ROTATIONS) + ")");
+    if (interpolation != PB_INTERP_NEAREST && interpolation != PB_INTERP_BILINEAR && interpolation != PB_INTERP_CATMULL_ROM)
+        return pb_fail(PB_ERR_INVALID, "interpolation must be PB_INTERP_NEAREST, PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM");
+    if (n_frames == 0) return PB_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned long long npx = (unsigned long long)P.dst.height * P.dst.width;
+    const int fpc = std::max(1, pb_knob("PB_TRACK_FRAMES", PB_TRACK_FRAMES));  // (the knob: the diagnostic build's, for the measurement of DESIGN 3.13)
+    const int per_launch = 65535 * fpc;  // frames are chunked over the grid's y, which ends at 65535
+    for (int f0 = 0; f0 < n_frames; f0 += per_launch) {
+        const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
+        const double* rot = rot3x3_dev + 9ull * (unsigned)n_rot_per_frame * (unsigned)f0;
+        const uint8_t* s = src_dev + (unsigned long long)f0 * src_frame_stride;
+        uint8_t* d = dst_dev + (unsigned long long)f0 * dst_frame_stride;
+        const unsigned chunks = (unsigned)((nf + fpc - 1) / fpc);
+        if (interpolation == PB_INTERP_NEAREST) {
+            const int dst_aligned = (((uintptr_t)dst_dev | dst_frame_stride) & 3u) == 0;
+            pb_pick_any_kind(P, [&](auto K) {
+                hipLaunchKernelGGL((pb_track_kernel<K.value>), dim3(pb_blocks((npx + PB_PX - 1) / PB_PX), chunks), dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d,
+                                   nf, (unsigned long long)src_frame_stride, (unsigned long long)dst_frame_stride, dst_aligned);
+            });
+        } else {
+            pb_pick_any_kind(P, [&](auto K) {
+                pb_pick_filter(interpolation, [&](auto F) {
+                    hipLaunchKernelGGL((pb_track_interp_kernel<K.value, decltype(F)>), dim3(pb_blocks(npx), chunks), dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d,
+                                       nf, (unsigned long long)src_frame_stride, (unsigned long long)dst_frame_stride);
+                });
+            });
+        }
+    }
+    PB_HIP(hipGetLastError());
+    return PB_OK;
 }
 
 int pb_index_map_i32(const pb_plan* plan, int32_t* idx_dev, double* weights_dev, void* stream) {
