@@ -57,10 +57,16 @@ typedef enum pb_kind {
     PB_KIND_DOUBLE = 1, /* DoubleCameraImage  projection.py:277 */
     PB_KIND_PANO = 2,   /* PanoramaImage      projection.py:465 */
     /* (3 and 4 are taken inside the library: the two eyes of a double-fisheye source as sources of their own) */
-    PB_KIND_CUBE = 5    /* a cube map (additive, ABI 5): no reference class - six rectilinear CameraImage faces of 120
+    PB_KIND_CUBE = 5,   /* a cube map (additive, ABI 5): no reference class - six rectilinear CameraImage faces of 120
                            degrees with f_distance N / 2, each behind a fixed rotation, in one (2N, 3N) frame: top row left, front,
                            right - bottom row up, back, down.  height = 2N, width = 3N; lens, fov, magnitude and f_distance are
                            ignored, as for a panorama.  A destination and a source wherever the other kinds are. */
+    /* (6 and 7 stay refused, as they always were) */
+    PB_KIND_EAC = 8     /* an equi-angular cube map (additive, ABI 5): PB_KIND_CUBE's frame, faces, face selection and
+                           truncation, but the position on a face is proportional to the ANGLE from the face centre, not to its
+                           tangent: with half = N / 2 a centred face coordinate c of this kind is the plain cube's
+                           tan((c / half) * (pi / 4)) * half, and back (atan(c / half) * (4 / pi)) * half.  Same shape rule, same
+                           ignored fields; a destination and a source wherever PB_KIND_CUBE is. */
 } pb_kind;
 
 /* core/lens.py factories :341-401 */
@@ -80,7 +86,7 @@ typedef enum pb_lens {
  * bits are the caller's; the kernels never recompute it. */
 typedef struct pb_proj {
     int32_t kind;      /* pb_kind */
-    int32_t lens;      /* pb_lens (ignored for PB_KIND_PANO and PB_KIND_CUBE) */
+    int32_t lens;      /* pb_lens (ignored for PB_KIND_PANO, PB_KIND_CUBE and PB_KIND_EAC) */
     int32_t height;
     int32_t width;
     double fov;        /* radians; the per-sensor fov for PB_KIND_DOUBLE */

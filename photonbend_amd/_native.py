@@ -44,7 +44,8 @@ SUPERSAMPLE_FACTORS = (1, 2, 4)
 MAX_PROJ_PIXELS = 0x7FFFFFFF // 4
 KIND_CAMERA, KIND_DOUBLE, KIND_PANO = 0, 1, 2
 KIND_CUBE = 5  # a cube map (2N, 3N): no lens, like a panorama (3 and 4 are the library's own eye kinds)
-LENSLESS_KINDS = (KIND_PANO, KIND_CUBE)  # their pb_proj.lens / fov / magnitude / f_distance are ignored
+KIND_EAC = 8  # an equi-angular cube map: the cube's frame and shape rule, face positions proportional to the angle
+LENSLESS_KINDS = (KIND_PANO, KIND_CUBE, KIND_EAC)  # their pb_proj.lens / fov / magnitude / f_distance are ignored
 LENS_IDS = {
     "equidistant": 0,
     "equisolid": 1,

@@ -672,15 +672,24 @@ class CubemapImage(_GpuProjection):
     picks the face and the face camera's truncating sampler the texel.  The interpolated modes clamp their taps to the selected face:
     seams are not filtered across faces.  ``process_coordinate_map`` leaves the caller's map unmodified.
 
-    Attributes: image, face_size."""
+    ``mapping``: "gnomonic" (the default) is that cube; "equiangular" is the equi-angular cube map 360-degree video ships in -
+    the same frame, faces and rules, but the position on a face is proportional to the angle from the face centre instead of its tangent:
+    with half = N / 2 a centred face coordinate c stands for the gnomonic ``tan((c / half) * (pi / 4)) * half``.
 
-    def __init__(self, image_arr) -> None:
+    Attributes: image, face_size, mapping."""
+
+    MAPPINGS = {"gnomonic": nat.KIND_CUBE, "equiangular": nat.KIND_EAC}
+
+    def __init__(self, image_arr, mapping: str = "gnomonic") -> None:
+        if not isinstance(mapping, str) or mapping not in self.MAPPINGS:
+            raise ValueError(f"a cube map's mapping is one of {' or '.join(repr(m) for m in self.MAPPINGS)}, got {mapping!r}")
         self.image = image_arr
         self.face_size = cubemap_face_size(tuple(image_arr.shape))
+        self.mapping = mapping
 
     def _proj(self, role: str = "src") -> nat.pb_proj:
         h, w = _shape_hw(self.image)
-        return nat.make_proj(nat.KIND_CUBE, h, w)
+        return nat.make_proj(self.MAPPINGS[self.mapping], h, w)
 
 
 def cubemap_face_size(shape) -> int:

@@ -167,7 +167,7 @@ __device__ __forceinline__ void pb_sample_map_interp_px(const PbParams& P, doubl
             o[ch] = live ? (SAMPLE)FILTER::template sample64<SAMPLE, true>(img, fy, fx, h, w, 0, w, false, channels, ch) : (SAMPLE)0;
         return;
     }
-    if (SRC_KIND == PB_KIND_CUBE) {
+    if (pb_is_cube(SRC_KIND)) {
         // the camera definition on the selected face, the taps clamped to that face's N x N rectangle: the face as an image of its own
         // (N rows of pitch w) - seams are not filtered across faces.  The caller's map is left as it is.
         PbCoord c;
@@ -175,7 +175,7 @@ __device__ __forceinline__ void pb_sample_map_interp_px(const PbParams& P, doubl
         c.lon = inv ? 0.0 : lon;
         c.inv = inv;
         c.face = 0;
-        const PbCubePos q = pb_src_cube_pos(P, c);
+        const PbCubePos q = pb_src_cube_pos<SRC_KIND == PB_KIND_EAC>(P, c);
         const int n = pb_cube_n(P.src);
         const bool live = !inv && pb_live_in(q.fy, q.fx, 1.0e300, n, n);
         const SAMPLE* face = img + ((unsigned long long)pb_cube_row0(q.face, n) * (unsigned)w + (unsigned)pb_cube_col0(q.face, n)) * (unsigned)channels;
@@ -223,6 +223,12 @@ template <class FILTER, typename SAMPLE>
 __global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_interp_cube_kernel(const PbParams P, double* __restrict__ map, unsigned total, const SAMPLE* __restrict__ img,
                                                                       void* __restrict__ out, int channels) {
     pb_sample_map_interp_px<FILTER, PB_KIND_CUBE, SAMPLE>(P, map, total, nullptr, nullptr, img, out, channels);
+}
+// ... and from an equi-angular cube source
+template <class FILTER, typename SAMPLE>
+__global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_interp_eac_kernel(const PbParams P, double* __restrict__ map, unsigned total, const SAMPLE* __restrict__ img,
+                                                                     void* __restrict__ out, int channels) {
+    pb_sample_map_interp_px<FILTER, PB_KIND_EAC, SAMPLE>(P, map, total, nullptr, nullptr, img, out, channels);
 }
 
 // ---- exact coordinate tables ------------------------------------------------------------------------------------------------
@@ -904,9 +910,15 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_interp_cube_kernel(const PbParams
                                                                   unsigned long long src_stride, unsigned long long dst_stride) {
     pb_interp_fix_px<FILTER, PB_KIND_CUBE>(P, nullptr, 1, src, dst, n_frames, src_stride, dst_stride, 0, nullptr, 0, nullptr, 0);
 }
+// ... and an equi-angular cube source's
+template <class FILTER>
+__global__ __launch_bounds__(PB_BLOCK) void pb_interp_eac_kernel(const PbParams P, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,
+                                                                 unsigned long long src_stride, unsigned long long dst_stride) {
+    pb_interp_fix_px<FILTER, PB_KIND_EAC>(P, nullptr, 1, src, dst, n_frames, src_stride, dst_stride, 0, nullptr, 0, nullptr, 0);
+}
 template <int SRC_KIND>
 __device__ __forceinline__ PbBilinear::Px PbBilinear::prepare(const PbParams& P, const PbCoord& c) {
-    if (SRC_KIND == PB_KIND_CUBE) {  // the float64 definition (sample64) on the selected face: its bytes exactly
+    if (pb_is_cube(SRC_KIND)) {  // the float64 definition (sample64) on the selected face: its bytes exactly
         Px q;
         q.by = q.bx = 0;
         q.ty = q.tx = 0.0f;
@@ -914,7 +926,7 @@ __device__ __forceinline__ PbBilinear::Px PbBilinear::prepare(const PbParams& P,
         q.face = 0;
         q.fy = q.fx = 0.0;
         if (c.inv) return q;
-        const PbCubePos h = pb_src_cube_pos(P, c);
+        const PbCubePos h = pb_src_cube_pos<SRC_KIND == PB_KIND_EAC>(P, c);
         q.face = h.face;
         q.fy = h.fy;
         q.fx = h.fx;
@@ -934,7 +946,7 @@ __device__ __forceinline__ PbBilinear::Px PbBilinear::prepare(const PbParams& P,
 }
 template <int SRC_KIND>
 __device__ __forceinline__ unsigned PbBilinear::sample(const PbParams& P, const Px& q, const uint8_t* __restrict__ s) {
-    if (SRC_KIND == PB_KIND_CUBE) {
+    if (pb_is_cube(SRC_KIND)) {
         if (!q.live) return 0u;
         const int n = pb_cube_n(P.src);
         const uint8_t* face = s + 3ull * ((unsigned long long)pb_cube_row0(q.face, n) * (unsigned)P.src.width + (unsigned)pb_cube_col0(q.face, n));

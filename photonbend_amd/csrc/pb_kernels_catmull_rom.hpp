@@ -71,11 +71,11 @@ struct PbCatmullRom {
     static __device__ __forceinline__ Px prepare(const PbParams& P, const PbCoord& c) {
         Px q;
         q.face = 0;
-        if (SRC_KIND == PB_KIND_CUBE) {
+        if (pb_is_cube(SRC_KIND)) {
             q.fy = q.fx = 0.0;
             q.live = false;
             if (c.inv) return q;
-            const PbCubePos h = pb_src_cube_pos(P, c);
+            const PbCubePos h = pb_src_cube_pos<SRC_KIND == PB_KIND_EAC>(P, c);
             q.face = h.face;
             q.fy = h.fy;
             q.fx = h.fx;
@@ -98,7 +98,7 @@ struct PbCatmullRom {
     }
     template <int SRC_KIND>
     static __device__ __forceinline__ unsigned sample(const PbParams& P, const Px& q, const uint8_t* __restrict__ s) {
-        if (SRC_KIND == PB_KIND_CUBE) {  // the face as an image of its own (N rows of pitch w): the taps stay on it
+        if (pb_is_cube(SRC_KIND)) {  // the face as an image of its own (N rows of pitch w): the taps stay on it
             const int n = pb_cube_n(P.src);
             const uint8_t* face = s + 3ull * ((unsigned long long)pb_cube_row0(q.face, n) * (unsigned)P.src.width + (unsigned)pb_cube_col0(q.face, n));
             return q.live ? rgb<false>(face, q.fy, q.fx, n, P.src.width, 0, n, false) : 0u;

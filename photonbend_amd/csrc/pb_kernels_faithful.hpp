@@ -16,7 +16,7 @@
 // ----------------------------------------------------------------------------------
 template <int ROT = PB_ROT_ANY>
 __device__ __forceinline__ PbCoord pb_chain(const PbParams& P, int i, int j) {
-    return pb_rotate_all<ROT>(P, pb_dst_coord(P, i, j));
+    return pb_rotate_all<ROT>(P, pb_dst_coord<ROT>(P, i, j));
 }
 
 __device__ __forceinline__ unsigned pb_load_px(const uint8_t* __restrict__ src, int idx) {
@@ -70,7 +70,7 @@ __device__ __forceinline__ void pb_store_px4(uint8_t* __restrict__ out, unsigned
 // bound the run-time-rotation instantiation is 5 % faster and the unrotated camera one level; without it they are level and 3 % slower.
 #ifndef PB_FAITHFUL_WPE
 // (an unrotated cube source - 43 VGPRs - is held to eight like the unrotated camera source it is built from)
-#define PB_FAITHFUL_WPE(kind, rot) ((kind) == PB_KIND_DOUBLE ? 1 : (((kind) == PB_KIND_PANO && (rot) != 1) || (((kind) == PB_KIND_CAMERA || (kind) == PB_KIND_CUBE) && (rot) == 0)) ? 8 : 4)
+#define PB_FAITHFUL_WPE(kind, rot) ((kind) == PB_KIND_DOUBLE ? 1 : (((kind) == PB_KIND_PANO && (rot) != 1) || (((kind) == PB_KIND_CAMERA || pb_is_cube(kind)) && (rot) == 0)) ? 8 : 4)
 #endif
 #ifndef PB_FAITHFUL_UNROLL  // pixels of a work-item whose float64 chains the compiler may interleave
 #define PB_FAITHFUL_UNROLL 4
@@ -106,8 +106,8 @@ __global__ __launch_bounds__(PB_BLOCK, PB_FAITHFUL_WPE(SRC_KIND, ROT)) void pb_r
                 idx[k] = pb_src_pano_index(P, c);
             } else if (SRC_KIND == PB_KIND_CAMERA) {
                 idx[k] = pb_src_camera_index(P, c);
-            } else if (SRC_KIND == PB_KIND_CUBE) {
-                idx[k] = pb_src_cube_index(P, c);
+            } else if (pb_is_cube(SRC_KIND)) {
+                idx[k] = pb_src_cube_index<SRC_KIND == PB_KIND_EAC>(P, c);
             } else {
                 const PbDoubleTap t = pb_src_double_taps(P, c);
                 idx[k] = t.il;
@@ -159,8 +159,8 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_index_kernel(const PbParams P, in
         out[p] = pb_src_pano_index(P, c);
     } else if (SRC_KIND == PB_KIND_CAMERA) {
         out[p] = pb_src_camera_index(P, c);
-    } else if (SRC_KIND == PB_KIND_CUBE) {
-        out[p] = pb_src_cube_index(P, c);
+    } else if (pb_is_cube(SRC_KIND)) {
+        out[p] = pb_src_cube_index<SRC_KIND == PB_KIND_EAC>(P, c);
     } else {
         const PbDoubleTap t = pb_src_double_taps(P, c);
         out[p] = t.il;
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_coordmap_kernel(const PbParams P,
     if (p >= total) return;
     const unsigned W = (unsigned)P.dst.width;
     const unsigned i = p / W, j = p - i * W;
-    const PbCoord c = pb_dst_coord(P, (int)i, (int)j);
+    const PbCoord c = pb_dst_coord<0>(P, (int)i, (int)j);  // (never a cube: pb_coordmap_cube_kernel)
     double* o = out + 3ull * p;
     o[0] = c.lat;
     o[1] = c.lon;
@@ -243,8 +243,8 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_sample_map_kernel(const PbParams 
         v = pb_load_px(src, pb_src_pano_index(P, c));
     } else if (SRC_KIND == PB_KIND_CAMERA) {
         v = pb_load_px(src, pb_src_camera_index(P, c));
-    } else if (SRC_KIND == PB_KIND_CUBE) {  // (the caller's map stays as it is: the zeroing of invalid entries happens in a copy)
-        v = pb_load_px(src, pb_src_cube_index(P, c));
+    } else if (pb_is_cube(SRC_KIND)) {  // (the caller's map stays as it is: the zeroing of invalid entries happens in a copy)
+        v = pb_load_px(src, pb_src_cube_index<SRC_KIND == PB_KIND_EAC>(P, c));
     } else {
         const PbDoubleTap t = pb_src_double_taps(P, c);
         const unsigned l = pb_load_px(src, t.il), r = pb_load_px(src, t.ir);
@@ -301,8 +301,8 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_index_from_map_kernel(const PbPar
         } else {
             out[p] = pb_src_camera_index(P, c);
         }
-    } else if (SRC_KIND == PB_KIND_CUBE) {
-        out[p] = pb_src_cube_index(P, c);
+    } else if (pb_is_cube(SRC_KIND)) {
+        out[p] = pb_src_cube_index<SRC_KIND == PB_KIND_EAC>(P, c);
     } else {
         PbDoubleTap t;
         if (dist_l) {

@@ -23,7 +23,7 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_sep_tables_kernel(const PbParams 
                                                                  PbSepCol* __restrict__ cols) {
     const int t = blockIdx.x * PB_BLOCK + threadIdx.x;
     if (t < P.dst.height) {
-        const PbCoord c = pb_dst_coord(P, t, 0);
+        const PbCoord c = pb_dst_coord<0>(P, t, 0);  // (<0>: a panorama destination - never a cube's, whose warp lives in pb_dst_coord<PB_ROT_ANY> alone)
         const double lat_r = (c.lat * -1.0) + PB_PI;  // projection.py:426-427
         PbSepRow r;
         r.dist_l = pb_lens_forward(P, c.lat) * P.src.f_distance;  // projection.py:251
@@ -34,7 +34,7 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_sep_tables_kernel(const PbParams 
     }
     const int j = t - P.dst.height;
     if (j >= 0 && j < P.dst.width) {
-        const PbCoord c = pb_dst_coord(P, 0, j);
+        const PbCoord c = pb_dst_coord<0>(P, 0, j);  // (as above)
         PbSepCol q;
         pb_expi_np(c.lon, &q.sl, &q.cl);
         cols[j] = q;
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_sep_check_kernel(const PbParams P
     const unsigned p = blockIdx.x * PB_BLOCK + threadIdx.x;
     if (p >= total) return;
     const unsigned i = p / (unsigned)P.dst.width, j = p - i * (unsigned)P.dst.width;
-    PbCoord c = pb_dst_coord(P, (int)i, (int)j);
+    PbCoord c = pb_dst_coord<0>(P, (int)i, (int)j);  // (<0>: the separable path exists for unrotated panorama destinations only - never a cube's)
     const PbDoubleTap t = pb_src_double_taps(P, c);
     int il, ir;
     const PbSepRow R = rows[i];

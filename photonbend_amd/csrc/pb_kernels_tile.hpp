@@ -1140,7 +1140,7 @@ __global__ __launch_bounds__(64 * PB_TILE_WAVES) void pb_model_kernel(const PbPa
     bool bad = node && !(fabs(f0) < 1.0e9 && fabs(f1) < 1.0e9);  // NaN / inf / absurd: no model
     // a double-destination tile that straddles the two eyes has no single model
     if (P.dst.kind == PB_KIND_DOUBLE && X0 < P.dst_half_w && X0 + PB_TILE > P.dst_half_w) bad = true;
-    if (P.dst.kind == PB_KIND_CUBE) {  // ... and so has a cube-destination tile that straddles two faces
+    if (pb_is_cube(P.dst.kind)) {  // ... and so has a cube-destination tile that straddles two faces
         const int n = pb_cube_n(P.dst), X1 = min(X0 + PB_TILE, P.dst.width) - 1, Y1 = min(Y0 + PB_TILE, P.dst.height) - 1;
         if (X0 / n != X1 / n || Y0 / n != Y1 / n) bad = true;
     }
@@ -1232,7 +1232,7 @@ __global__ __launch_bounds__(64 * PB_TILE_WAVES) void pb_window_kernel(const PbP
     if (not_plain != 0 || w >= 32768 || h >= 32768) return;
     // invalid destination pixels only (the rest plain): the MASKED class, single sources only (the two-eye paths do not know it)
     const bool masked = n_invalid != 0;
-    if (masked && SRC_KIND != PB_KIND_PANO && SRC_KIND != PB_KIND_CAMERA && SRC_KIND != PB_KIND_CUBE) return;
+    if (masked && SRC_KIND != PB_KIND_PANO && SRC_KIND != PB_KIND_CAMERA && !pb_is_cube(SRC_KIND)) return;
     int lr0 = rmin - 1, lc0 = cmin - 1, rows = rmax - rmin + 3, cols = cmax - cmin + 3;
     if (masked) {
         // a ring tile's valid pixels reach the LAST rows / columns of the source (a fisheye's rim is the panorama's pole row): the
@@ -1290,7 +1290,7 @@ __global__ void pb_count_flags_kernel(const PbTileEntry* __restrict__ table, uns
 __global__ void pb_col_sincos_kernel(const PbParams P, double* __restrict__ col_sc) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= P.dst.width) return;
-    const PbCoord c = pb_dst_coord(P, 0, j);
+    const PbCoord c = pb_dst_coord<0>(P, 0, j);  // (a panorama destination)
     pb_expi_np(c.lon, &col_sc[2 * j + 1], &col_sc[2 * j]);
 }
 
@@ -1342,7 +1342,7 @@ __global__ __launch_bounds__(64 * PB_TILE_WAVES, PB_CERTIFY_WPE) void pb_certify
                 const int fast = pb_model_px<SRC_KIND>(P, R, xh, k);
                 PbCoord cc = {0.0, 0.0, false};
                 if (!(PB_CERT_ABL & 1)) {
-                    cc = pb_rotate_all<ROT>(P, pb_dst_coord(P, i, j));
+                    cc = pb_rotate_all<ROT>(P, pb_dst_coord<ROT>(P, i, j));
                 }
                 // the faithful index and the faithful pre-truncation coordinate from ONE evaluation of the longitude's sine / cosine
                 int exact;
@@ -1352,8 +1352,8 @@ __global__ __launch_bounds__(64 * PB_TILE_WAVES, PB_CERTIFY_WPE) void pb_certify
                 } else if (SRC_KIND == PB_KIND_PANO) {
                     exact = pb_src_pano_index(P, cc);
                     if (exact >= 0) pb_src_pretrunc<PB_KIND_PANO>(P, cc, f0, f1);
-                } else if (SRC_KIND == PB_KIND_CUBE) {
-                    exact = pb_src_cube_index_pre(P, cc, f0, f1);
+                } else if (pb_is_cube(SRC_KIND)) {
+                    exact = pb_src_cube_index_pre<SRC_KIND == PB_KIND_EAC>(P, cc, f0, f1);
                 } else {
                     double sl, cl;
                     if (col_sc) {  // (unrotated panorama destination: the column's table entry IS pb_sincos_cr(cc.lon))

@@ -43,7 +43,7 @@ template <int SRC_KIND>
 __device__ __forceinline__ unsigned pb_track_px(const PbParams& P, const PbCoord& c, const uint8_t* __restrict__ s) {
     if (SRC_KIND == PB_KIND_PANO) return pb_load_px(s, pb_src_pano_index(P, c));
     if (SRC_KIND == PB_KIND_CAMERA) return pb_load_px(s, pb_src_camera_index(P, c));
-    if (SRC_KIND == PB_KIND_CUBE) return pb_load_px(s, pb_src_cube_index(P, c));
+    if (pb_is_cube(SRC_KIND)) return pb_load_px(s, pb_src_cube_index<SRC_KIND == PB_KIND_EAC>(P, c));
     const PbDoubleTap t = pb_src_double_taps(P, c);
     const unsigned l = pb_load_px(s, t.il), r = pb_load_px(s, t.ir);
     if (c.inv) return 0u;  // final_image[invalid_map] = 0, projection.py:460
@@ -54,9 +54,8 @@ __device__ __forceinline__ unsigned pb_track_px(const PbParams& P, const PbCoord
 // pb_remap_kernel's layout: PB_PX consecutive output pixels per work-item, three dword stores where the frame is 4-byte aligned, bytes
 // otherwise, every store clipped to the image.  grid: (quads of the image / PB_BLOCK, chunks of fpc frames).
 template <int SRC_KIND>
-__global__ __launch_bounds__(PB_BLOCK, PB_TRACK_WPE(SRC_KIND)) void pb_track_kernel(const PbParams P, const double* __restrict__ rot, int k_rot, int fpc,
-                                                                                   const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,
-                                                                                   unsigned long long src_stride, unsigned long long dst_stride, int aligned) {
+__device__ __forceinline__ void pb_track_body(const PbParams& P, const double* __restrict__ rot, int k_rot, int fpc, const uint8_t* __restrict__ src,
+                                              uint8_t* __restrict__ dst, int n_frames, unsigned long long src_stride, unsigned long long dst_stride, int aligned) {
     const unsigned total = (unsigned)P.dst.height * (unsigned)P.dst.width;
     const unsigned g = blockIdx.x * PB_BLOCK + threadIdx.x;
     const unsigned p0 = g * PB_PX;
@@ -103,14 +102,26 @@ __global__ __launch_bounds__(PB_BLOCK, PB_TRACK_WPE(SRC_KIND)) void pb_track_ker
         pb_store_px4(d, p0, a, count, aligned != 0);
     }
 }
+template <int SRC_KIND>
+__global__ __launch_bounds__(PB_BLOCK, PB_TRACK_WPE(SRC_KIND)) void pb_track_kernel(const PbParams P, const double* __restrict__ rot, int k_rot, int fpc,
+                                                                                   const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,
+                                                                                   unsigned long long src_stride, unsigned long long dst_stride, int aligned) {
+    pb_track_body<SRC_KIND>(P, rot, k_rot, fpc, src, dst, n_frames, src_stride, dst_stride, aligned);
+}
+// ... of an equi-angular cube source (a kernel of its own name: the instantiations of the one above are listed per source kind by
+// tests/test_isa_track.py)
+__global__ __launch_bounds__(PB_BLOCK, PB_TRACK_WPE(PB_KIND_EAC)) void pb_track_eac_kernel(const PbParams P, const double* __restrict__ rot, int k_rot, int fpc,
+                                                                                          const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,
+                                                                                          unsigned long long src_stride, unsigned long long dst_stride, int aligned) {
+    pb_track_body<PB_KIND_EAC>(P, rot, k_rot, fpc, src, dst, n_frames, src_stride, dst_stride, aligned);
+}
 
 // The interpolating modes: the same structure around the definition's own device functions - FILTER::prepare / FILTER::sample as
 // pb_interp_fix_kernel and pb_interp_cube_kernel run them over every pixel, pb_interp_double_at as pb_interp_double_kernel does.  One
 // pixel per work-item, like those.
 template <int SRC_KIND, class FILTER>
-__global__ __launch_bounds__(PB_BLOCK) void pb_track_interp_kernel(const PbParams P, const double* __restrict__ rot, int k_rot, int fpc,
-                                                                   const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,
-                                                                   unsigned long long src_stride, unsigned long long dst_stride) {
+__device__ __forceinline__ void pb_track_interp_body(const PbParams& P, const double* __restrict__ rot, int k_rot, int fpc, const uint8_t* __restrict__ src,
+                                                     uint8_t* __restrict__ dst, int n_frames, unsigned long long src_stride, unsigned long long dst_stride) {
     PbPixelPick k;
     if (!pb_pick_pixel(P, true, nullptr, 0, nullptr, 0, nullptr, 0, k)) return;
     const PbCoord base = pb_chain<PB_ROT_ANY>(P, k.i, k.j);
@@ -128,4 +139,16 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_track_interp_kernel(const PbParam
         }
         pb_store_px(dst + (unsigned long long)f * dst_stride + 3ull * k.p, v);
     }
+}
+template <int SRC_KIND, class FILTER>
+__global__ __launch_bounds__(PB_BLOCK) void pb_track_interp_kernel(const PbParams P, const double* __restrict__ rot, int k_rot, int fpc,
+                                                                   const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,
+                                                                   unsigned long long src_stride, unsigned long long dst_stride) {
+    pb_track_interp_body<SRC_KIND, FILTER>(P, rot, k_rot, fpc, src, dst, n_frames, src_stride, dst_stride);
+}
+template <class FILTER>
+__global__ __launch_bounds__(PB_BLOCK) void pb_track_interp_eac_kernel(const PbParams P, const double* __restrict__ rot, int k_rot, int fpc,
+                                                                       const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,
+                                                                       unsigned long long src_stride, unsigned long long dst_stride) {
+    pb_track_interp_body<PB_KIND_EAC, FILTER>(P, rot, k_rot, fpc, src, dst, n_frames, src_stride, dst_stride);
 }

@@ -43,6 +43,9 @@ PB_HD static inline double pb_poly_dp(const PbPoly& L, double t) {
     const double t2 = t * t;
     return 1.0 + t2 * (L.d[0] + t2 * (L.d[1] + t2 * (L.d[2] + t2 * L.d[3])));
 }
+// "this end is a cube": the plain cube map and the equi-angular one share the frame, the faces, the face rotation
+// and the face camera; everything that treats an end as a cube asks here
+PB_HD constexpr bool pb_is_cube(int kind) { return kind == PB_KIND_CUBE || kind == PB_KIND_EAC; }
 #define PB_POLY_NEWTON_STEPS 10  // a constant of the definition: host and device, scalar and array agree to the bit
 
 struct PbParams {
@@ -105,7 +108,7 @@ static inline void pb_derive(PbParams& P) {
         if (d.kind == PB_KIND_DOUBLE) {
             const double half = (double)P.dst_half_w;
             P.dst_x0 = -half / 2 + 0.5;
-        } else if (d.kind == PB_KIND_CUBE) {  // the face camera's first samples (N x N: projection.py:177-180)
+        } else if (pb_is_cube(d.kind)) {  // the face camera's first samples (N x N: projection.py:177-180)
             const double N = (double)(d.height / 2);
             P.dst_x0 = -N / 2 + 0.5;
             P.dst_y0 = N / 2 - 0.5;
@@ -133,7 +136,7 @@ static inline void pb_derive(PbParams& P) {
         if (s.kind == PB_KIND_DOUBLE) {
             P.src_cx = (double)P.src_eye_w / 2 - 0.5;
             P.src_cx_r = (double)P.src_eye_w_right / 2 - 0.5;
-        } else if (s.kind == PB_KIND_CUBE) {  // the face camera's centre (N x N: projection.py:274)
+        } else if (pb_is_cube(s.kind)) {  // the face camera's centre (N x N: projection.py:274)
             const double N = (double)(s.height / 2);
             P.src_cy = N / 2 - 0.5;
             P.src_cx = P.src_cx_r = N / 2 - 0.5;

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pb_math.hpp"
+#include "pb_eac.hpp"
 #include "pb_params.hpp"
 
 struct PbCoord {
@@ -141,8 +142,16 @@ __device__ __forceinline__ void pb_cube_matrix(int face, double M[9]) {
     for (int e = 0; e < 9; ++e) M[e] = pb_cube_entry<TRANSPOSED>(face, e / 3, e % 3);
 }
 __device__ __forceinline__ int pb_cube_n(const PbEnd& e) { return e.height >> 1; }  // (pb_end_ok: height = 2N, width = 3N)
+// An equi-angular cube (PB_KIND_EAC) is that cube with pb_eac.hpp's two functions between the face pixel and the face
+// camera: a destination warps its mesh coordinates before the camera's formulas, a source unwarps the camera's position before the
+// truncation.  f_distance of either end is N / 2 exactly (pb_to_end): the `half` of both functions.
 
 // ---- stage A ---------------------------------------------------------------------
+// ROT: the caller's compile-time rotation count (pb_rotate_all below).  A cube destination only ever runs the PB_ROT_ANY instantiations
+// (pb_rot_count), so an equi-angular destination's two np.tan are compiled into those alone - the ROT 0 and 1 kernels hold no
+// tangent of it - and both axes go through ONE rolled copy of pb_tan_np.
+#define PB_ROT_ANY (-1)
+template <int ROT = PB_ROT_ANY>
 __device__ __forceinline__ PbCoord pb_dst_coord(const PbParams& P, int i, int j) {
     PbCoord c;
     const PbEnd& d = P.dst;
@@ -154,7 +163,7 @@ __device__ __forceinline__ PbCoord pb_dst_coord(const PbParams& P, int i, int j)
         c.inv = false;
         return c;
     }
-    if (d.kind == PB_KIND_CUBE) {
+    if (pb_is_cube(d.kind)) {
         // the face and the pixel on it: the face's camera map follows (dst_x0 / dst_y0 / f_distance / fov are the face camera's, and
         // lat <= atan(sqrt(2) (N - 1) / N) < fov / 2: no pixel is invalid); its rotation is pb_rotate_all's first
         const int n = pb_cube_n(d), fr = i >= n, fc = (j >= n) + (j >= 2 * n);
@@ -172,6 +181,14 @@ __device__ __forceinline__ PbCoord pb_dst_coord(const PbParams& P, int i, int j)
         if (right) x = -x;  // projection.py:394
     } else {
         x = (double)j + P.dst_x0;
+    }
+    if (ROT == PB_ROT_ANY && d.kind == PB_KIND_EAC) {  // the mesh vectors become warp(x), warp(y); the camera's own code follows
+#pragma clang loop unroll(disable)
+        for (int a = 0; a < 2; ++a) {  // (x, y) -> (y, warp(x)) -> (warp(x), warp(y))
+            const double w = pb_eac_warp(x, d.f_distance);
+            x = y;
+            y = w;
+        }
     }
     const double dist = sqrt(x * x + y * y) / d.f_distance;  // projection.py:186, :375
     double lat = pb_lens_inverse(P, dist);
@@ -202,15 +219,14 @@ __device__ __forceinline__ PbCoord pb_dst_coord_real(const PbParams& P, double f
         c.lon = fj * P.pano_lon_step + P.pano_lon_start;
         return c;
     }
-    if (d.kind == PB_KIND_CUBE) {  // (a tile's nodes are pixel centres of the tile: one face, or the tile is listed as failed)
+    if (pb_is_cube(d.kind)) {  // (a tile's nodes are pixel centres of the tile: one face, or the tile is listed as failed)
         const double n = (double)pb_cube_n(d);
         const int fr = fi >= n, fc = (fj >= n) + (fj >= 2.0 * n);
         fi -= fr ? n : 0.0;
         fj -= (double)fc * n;
         c.face = fr * 3 + fc;
     }
-    double x;
-    const double y = P.dst_y0 - fi;
+    double x, y = P.dst_y0 - fi;
     bool right = false;
     if (d.kind == PB_KIND_DOUBLE) {
         right = fj >= (double)P.dst_half_w;
@@ -218,6 +234,10 @@ __device__ __forceinline__ PbCoord pb_dst_coord_real(const PbParams& P, double f
         if (right) x = -x;
     } else {
         x = fj + P.dst_x0;
+    }
+    if (d.kind == PB_KIND_EAC) {  // the smooth form of pb_eac_warp
+        x = tan((x / d.f_distance) * PB_EAC_Q) * d.f_distance;
+        y = tan((y / d.f_distance) * PB_EAC_Q) * d.f_distance;
     }
     const double dist = sqrt(x * x + y * y) / d.f_distance;
     double lat = pb_lens_inverse<true>(P, dist);
@@ -249,6 +269,9 @@ __device__ __forceinline__ int pb_cube_face_of(double x, double y, double z) {
     if (b >= c) return (__double_as_longlong(y) < 0) ? 5 : 3;
     return (__double_as_longlong(z) < 0) ? 0 : 2;
 }
+// EAC: the source is equi-angular (SRC_KIND == PB_KIND_EAC: a template argument, so the plain cube's instantiations hold no trace of it) -
+// the camera's position on the face, centred, goes through pb_eac_unwarp before the centre is added
+template <bool EAC>
 __device__ __forceinline__ PbCubePos pb_src_cube_pos(const PbParams& P, const PbCoord& c) {
     PbCubePos q;
     const double s = pb_sin_np(c.lat), yy = pb_cos_np(c.lat);  // rotation.py:129-131
@@ -265,18 +288,28 @@ __device__ __forceinline__ PbCubePos pb_src_cube_pos(const PbParams& P, const Pb
     const double t = pb_tan_np(lat);                                             // lens.py:97-103
     const double dist = ((lat < 0.0 || lat > P.rect_max) ? __builtin_nan("") : t) * P.src.f_distance;
     pb_expi_np(lon, &sl, &cl);                                                   // projection.py:252
-    q.fy = ((sl * dist) * -1.0) + P.src_cy;
-    q.fx = (cl * dist) + P.src_cx;
+    double re = cl * dist, im = sl * dist;
+    if (EAC) {
+#pragma clang loop unroll(disable)
+        for (int a = 0; a < 2; ++a) {  // (re, im) -> (im, unwarp(re)) -> (unwarp(re), unwarp(im)): one copy of pb_atan_np
+            const double w = pb_eac_unwarp(re, P.src.f_distance);
+            re = im;
+            im = w;
+        }
+    }
+    q.fy = (im * -1.0) + P.src_cy;
+    q.fx = re + P.src_cx;
     return q;
 }
 // the face's first row / column in the frame
 __device__ __forceinline__ int pb_cube_row0(int face, int n) { return face >= 3 ? n : 0; }
 __device__ __forceinline__ int pb_cube_col0(int face, int n) { return (face >= 3 ? face - 3 : face) * n; }
 // linear index into the full (2N, 3N) frame, or -1; f0 / f1: the pre-truncation position in FRAME coordinates
+template <bool EAC>
 __device__ __forceinline__ int pb_src_cube_index_pre(const PbParams& P, const PbCoord& c, double& f0, double& f1) {
     f0 = f1 = 0.0;
     if (c.inv) return -1;  // (the reference zeroes such entries, samples, then paints them black)
-    const PbCubePos q = pb_src_cube_pos(P, c);
+    const PbCubePos q = pb_src_cube_pos<EAC>(P, c);
     const int n = pb_cube_n(P.src), r0 = pb_cube_row0(q.face, n), c0 = pb_cube_col0(q.face, n);
     f0 = q.fy + (double)r0;
     f1 = q.fx + (double)c0;
@@ -284,12 +317,14 @@ __device__ __forceinline__ int pb_src_cube_index_pre(const PbParams& P, const Pb
     if (y >= n || y < 0 || x >= n || x < 0) return -1;
     return ((int)y + r0) * P.src.width + (int)x + c0;
 }
+template <bool EAC>
 __device__ __forceinline__ int pb_src_cube_index(const PbParams& P, const PbCoord& c) {
     double f0, f1;
-    return pb_src_cube_index_pre(P, c, f0, f1);
+    return pb_src_cube_index_pre<EAC>(P, c, f0, f1);
 }
 // the same position in frame coordinates by plain real arithmetic (model building only, like pb_dst_coord_real): on the selected face
 // tan(lat') cos(lon') = right / forward and tan(lat') sin(lon') = up / forward
+template <bool EAC>
 __device__ __forceinline__ void pb_src_cube_real(const PbParams& P, const PbCoord& c, double& f0, double& f1) {
     double sl, cl;
     sincos(c.lon, &sl, &cl);
@@ -299,8 +334,9 @@ __device__ __forceinline__ void pb_src_cube_real(const PbParams& P, const PbCoor
     pb_cube_matrix<true>(face, M);
     const double r = M[0] * x + M[1] * yy + M[2] * z, f = M[3] * x + M[4] * yy + M[5] * z, u = M[6] * x + M[7] * yy + M[8] * z;
     const int n = pb_cube_n(P.src);
-    f0 = ((u / f) * P.src.f_distance) * -1.0 + P.src_cy + (double)pb_cube_row0(face, n);
-    f1 = (r / f) * P.src.f_distance + P.src_cx + (double)pb_cube_col0(face, n);
+    const double ty = EAC ? atan(u / f) * PB_EAC_IQ : u / f, tx = EAC ? atan(r / f) * PB_EAC_IQ : r / f;  // (pb_eac_unwarp's smooth form)
+    f0 = (ty * P.src.f_distance) * -1.0 + P.src_cy + (double)pb_cube_row0(face, n);
+    f1 = tx * P.src.f_distance + P.src_cx + (double)pb_cube_col0(face, n);
 }
 
 // columns of the frame a source kind may sample: [cmin, cmax)
@@ -316,9 +352,9 @@ __device__ __forceinline__ void pb_src_pretrunc(const PbParams& P, const PbCoord
     if (SRC_KIND == PB_KIND_PANO) {
         f0 = c.lat / P.src_hseg;
         f1 = c.lon / P.src_wseg + P.src_half_w;
-    } else if (SRC_KIND == PB_KIND_CUBE) {  // frame coordinates of the position on the selected face
-        if (SMOOTH) pb_src_cube_real(P, c, f0, f1);
-        else (void)pb_src_cube_index_pre(P, c, f0, f1);
+    } else if (pb_is_cube(SRC_KIND)) {  // frame coordinates of the position on the selected face
+        if (SMOOTH) pb_src_cube_real<SRC_KIND == PB_KIND_EAC>(P, c, f0, f1);
+        else (void)pb_src_cube_index_pre<SRC_KIND == PB_KIND_EAC>(P, c, f0, f1);
     } else if (SRC_KIND == PB_KIND_EYE_R) {
         // the right eye looks backwards (projection.py:426-427) and is mirrored: sampled column =
         // eye_w + (eye_w_right - 1 - x) with x = trunc(re + cx_r), i.e. floor(w - (re + cx_r)) wherever that
@@ -404,7 +440,6 @@ __device__ __forceinline__ PbCoord pb_rotate(const double* __restrict__ R, PbCoo
 // loop-invariant code motion hoisted the hundred-odd float64 constants of the five transcendental kernels out of this loop (and out of
 // certification's pixel loop) and kept them live across the caller.  The build switches that pass off (build.py): 42-61 VGPRs with the
 // plain loop.  Instantiating the three float64 kernels per count on top of that is worth another 3-4 % on unrotated geometries.
-#define PB_ROT_ANY (-1)
 template <int ROT = PB_ROT_ANY>
 __device__ __forceinline__ PbCoord pb_rotate_all(const PbParams& P, PbCoord c) {
     if (ROT == 0) return c;
@@ -413,7 +448,7 @@ __device__ __forceinline__ PbCoord pb_rotate_all(const PbParams& P, PbCoord c) {
     // PB_MAX_ROTATIONS slots (such plans always come here: pb_rot_count).  The loop holds ONE copy of the rotation's transcendental
     // halves; only the nine multiply-adds between them come twice - the caller's matrix from the parameter block (scalar operands), the
     // face's from its code (per lane: a tile may straddle faces).
-    for (int k = (P.dst.kind == PB_KIND_CUBE) ? -1 : 0; k < P.n_rot; ++k) {
+    for (int k = pb_is_cube(P.dst.kind) ? -1 : 0; k < P.n_rot; ++k) {
         if (c.inv) {  // (pb_rotate's: rotation.py:125, :168-175)
             c.lat = 0.0;
             c.lon = 0.0;
@@ -436,7 +471,7 @@ __device__ __forceinline__ PbCoord pb_rotate_all(const PbParams& P, PbCoord c) {
 }
 // the rotation count PB_LAUNCH_BY_ROT instantiates for: a cube destination's chain always holds a rotation, and only the run-time loop
 // above knows the face's
-static inline int pb_rot_count(const PbParams& P) { return P.dst.kind == PB_KIND_CUBE ? PB_MAX_ROTATIONS + 1 : P.n_rot; }
+static inline int pb_rot_count(const PbParams& P) { return pb_is_cube(P.dst.kind) ? PB_MAX_ROTATIONS + 1 : P.n_rot; }
 // launches kernel<KIND, ROT> for the plan's rotation count.  It takes the PARAMETER BLOCK, not a count: the compile-time instantiations
 // (ROT 0 and 1) know nothing of a cube destination's face rotation, and this macro - the only way those instantiations are launched - is
 // where a cube destination is kept away from them.

@@ -132,7 +132,7 @@ __device__ __forceinline__ void pb_chain_real(const PbParams& P, double fi, doub
 template <int SRC_KIND>
 __device__ __forceinline__ int pb_exact_index_of(const PbParams& P, const PbCoord& c) {
     if (SRC_KIND == PB_KIND_PANO) return pb_src_pano_index(P, c);
-    if (SRC_KIND == PB_KIND_CUBE) return pb_src_cube_index(P, c);
+    if (pb_is_cube(SRC_KIND)) return pb_src_cube_index<SRC_KIND == PB_KIND_EAC>(P, c);
     double sl, cl;
     pb_expi_np(c.lon, &sl, &cl);
     return pb_src_index_sc<SRC_KIND>(P, c, sl, cl);  // (one eye of a double frame: that eye alone)

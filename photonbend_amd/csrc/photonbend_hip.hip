@@ -502,13 +502,13 @@ static int pb_poly_register(const PbPoly& L, int* lens_out) {
 }
 
 enum { PB_ROLE_DST = 1, PB_ROLE_SRC = 2, PB_ROLE_CUSTOM_OK = 4 };
-static bool pb_has_lens(int kind) { return kind != PB_KIND_PANO && kind != PB_KIND_CUBE; }  // (their pb_proj.lens / fov / f_distance are ignored)
+static bool pb_has_lens(int kind) { return kind != PB_KIND_PANO && !pb_is_cube(kind); }  // (their pb_proj.lens / fov / f_distance are ignored)
 static bool pb_end_ok(const pb_proj* p, std::string& why, int role = PB_ROLE_DST | PB_ROLE_SRC) {
     if (!p) {
         why = "null pb_proj";
         return false;
     }
-    if ((p->kind < PB_KIND_CAMERA || p->kind > PB_KIND_PANO) && p->kind != PB_KIND_CUBE) {
+    if ((p->kind < PB_KIND_CAMERA || p->kind > PB_KIND_PANO) && !pb_is_cube(p->kind)) {
         why = "pb_proj.kind out of range";
         return false;
     }
@@ -533,7 +533,7 @@ static bool pb_end_ok(const pb_proj* p, std::string& why, int role = PB_ROLE_DST
         why = "a double-fisheye frame needs at least two columns";
         return false;
     }
-    if (p->kind == PB_KIND_CUBE && ((p->height & 1) || p->width != 3 * (p->height / 2))) {
+    if (pb_is_cube(p->kind) && ((p->height & 1) || p->width != 3 * (p->height / 2))) {
         why = "a cube map is a (2N, 3N) frame: six N x N faces in a 3 x 2 grid";
         return false;
     }
@@ -557,7 +557,7 @@ static PbEndX pb_to_end(const pb_proj* p) {
     e.width = p->width;
     e.fov = p->fov;
     e.f_distance = p->f_distance;
-    if (p->kind == PB_KIND_CUBE) {
+    if (pb_is_cube(p->kind)) {
         // a face IS CameraImage(N x N, fov = 2 pi / 3, rectilinear()) with f_distance set to exactly N / 2: the block holds
         // that camera, whatever the caller left in the ignored fields
         e.lens = PB_LENS_RECTILINEAR;
@@ -601,7 +601,7 @@ static bool pb_bilinear_tiles_allowed(const PbParams& P) {
     // (below 180 degrees the band turns inside out; it exists down to 179.5 degrees, with factors from 1 up to 0.5 deg / (180 deg - fov))
     // THE place that says a cube source has no tile tables in the interpolated modes (the definition per pixel on the selected face, DESIGN
     // 3.10): the table builders ask here, and pb_route follows from the tables' absence
-    if (P.src.kind == PB_KIND_CUBE) return false;
+    if (pb_is_cube(P.src.kind)) return false;
     return !(P.src.kind == PB_KIND_DOUBLE && P.mrg_range != 0.0 && fabs(P.mrg_range) < 0.999 * (PB_PI / 180.0));  // (181 / 179 degrees themselves: tiles)
 }
 // (PB_INTERP_CATMULL_ROM: the third id, which pb_remap_track_u8 takes; the supersampled entry points take PB_INTERP_NEAREST and PB_INTERP_BILINEAR)
@@ -632,10 +632,15 @@ template <class F>
 static void pb_pick_kind(const PbParams& P, F&& f) {
     pb_pick<PB_KIND_PANO, PB_KIND_CAMERA>(P.src.kind == PB_KIND_PANO, f);
 }
-// ... and of the kernels that run the float64 chain of a single source: a cube's own
+// a cube source's mapping (P.src.kind is one of the two: pb_is_cube)
+template <class F>
+static void pb_pick_cube_kind(const PbParams& P, F&& f) {
+    pb_pick<PB_KIND_EAC, PB_KIND_CUBE>(P.src.kind == PB_KIND_EAC, f);
+}
+// ... and of the kernels that run the float64 chain of a single source: a cube's own, of either mapping
 template <class F>
 static void pb_pick_exact_kind(const PbParams& P, F&& f) {
-    if (P.src.kind == PB_KIND_CUBE) f(PbInt<PB_KIND_CUBE>());
+    if (pb_is_cube(P.src.kind)) pb_pick_cube_kind(P, f);
     else pb_pick_kind(P, f);
 }
 template <class F>
@@ -647,6 +652,28 @@ template <class F>
 static void pb_pick_any_kind(const PbParams& P, F&& f) {  // (float64 chain, any source)
     if (P.src.kind == PB_KIND_DOUBLE) f(PbInt<PB_KIND_DOUBLE>());
     else pb_pick_exact_kind(P, f);
+}
+// Kernels that carry a NAME per cube mapping instead of a template argument (the listing tests count the other sources' instantiations
+// per kind: pb_kernels_bilinear.hpp, pb_kernels_track.hpp) - the one place that maps a kind to them
+template <int KIND, class FILTER>
+static constexpr auto pb_interp_cube_kernel_of() {
+    if constexpr (KIND == PB_KIND_EAC) return &pb_interp_eac_kernel<FILTER>;
+    else return &pb_interp_cube_kernel<FILTER>;
+}
+template <int KIND, class FILTER, typename SAMPLE>
+static constexpr auto pb_sample_map_interp_cube_kernel_of() {
+    if constexpr (KIND == PB_KIND_EAC) return &pb_sample_map_interp_eac_kernel<FILTER, SAMPLE>;
+    else return &pb_sample_map_interp_cube_kernel<FILTER, SAMPLE>;
+}
+template <int KIND>
+static constexpr auto pb_track_kernel_of() {
+    if constexpr (KIND == PB_KIND_EAC) return &pb_track_eac_kernel;
+    else return &pb_track_kernel<KIND>;
+}
+template <int KIND, class FILTER>
+static constexpr auto pb_track_interp_kernel_of() {
+    if constexpr (KIND == PB_KIND_EAC) return &pb_track_interp_eac_kernel<FILTER>;
+    else return &pb_track_interp_kernel<KIND, FILTER>;
 }
 template <class F>
 static void pb_pick_filter(int filter, F&& f) {  // (the FILTER of the shared sampler kernels, pb_kernels_bilinear.hpp)
@@ -728,7 +755,7 @@ static int pb_plan_prepare_on_device(pb_plan* pl) {
     PB_HIP(scratch.alloc(16));
     int rc = PB_OK;
     do {
-        if (P.dst.kind == PB_KIND_CUBE) {
+        if (pb_is_cube(P.dst.kind)) {
             // no pixel of a cube is invalid (the largest incidence angle on a face is below 54.74 degrees, fov / 2 is 60): thresholds no
             // (2x)^2 + (2y)^2 reaches, so that the tile code's integer validity test never fires
             for (int sd = 0; sd < 2; ++sd) P.inv_lo[sd] = P.inv_hi[sd] = (int64_t)1 << 62;
@@ -832,11 +859,13 @@ static int pb_plan_prepare_on_device(pb_plan* pl) {
             hipLaunchKernelGGL(pb_model_kernel<PB_KIND_PANO>, grid, block, 0, 0, P, c.table);
             hipLaunchKernelGGL(pb_window_kernel<PB_KIND_PANO>, grid, block, 0, 0, P, c.table);
             PB_LAUNCH_BY_ROT(P, pb_certify_kernel, PB_KIND_PANO, grid, block, 0, 0, P, c.table, c.fail_tiles, c.fix_px, cap, counters);
-        } else if (P.src.kind == PB_KIND_CUBE) {
+        } else if (pb_is_cube(P.src.kind)) {
             // tiles whose pixels fall on more than one face get no usable model from their 25 nodes and fail certification by themselves
-            hipLaunchKernelGGL(pb_model_kernel<PB_KIND_CUBE>, grid, block, 0, 0, P, c.table);
-            hipLaunchKernelGGL(pb_window_kernel<PB_KIND_CUBE>, grid, block, 0, 0, P, c.table);
-            PB_LAUNCH_BY_ROT(P, pb_certify_kernel, PB_KIND_CUBE, grid, block, 0, 0, P, c.table, c.fail_tiles, c.fix_px, cap, counters);
+            pb_pick_cube_kind(P, [&](auto K) {
+                hipLaunchKernelGGL(pb_model_kernel<K.value>, grid, block, 0, 0, P, c.table);
+                hipLaunchKernelGGL(pb_window_kernel<K.value>, grid, block, 0, 0, P, c.table);
+                PB_LAUNCH_BY_ROT(P, pb_certify_kernel, K.value, grid, block, 0, 0, P, c.table, c.fail_tiles, c.fix_px, cap, counters);
+            });
         } else {
             PbBlock<double> col_sc;  // (unrotated panorama destination: one sine / cosine per column instead of one per pixel)
             if (P.dst.kind == PB_KIND_PANO && P.n_rot == 0 && col_sc.alloc((size_t)P.dst.width * 2) == hipSuccess)
@@ -1152,9 +1181,11 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
             });
             break;
         case PbRoute::INTERP_FLOAT64:
-            if (P.src.kind == PB_KIND_CUBE) {
-                pb_pick_filter(r.filter, [&](auto F) {
-                    hipLaunchKernelGGL(pb_interp_cube_kernel<decltype(F)>, dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, src, dst, n_frames, ss, ds);
+            if (pb_is_cube(P.src.kind)) {
+                pb_pick_cube_kind(P, [&](auto K) {
+                    pb_pick_filter(r.filter, [&](auto F) {
+                        hipLaunchKernelGGL((pb_interp_cube_kernel_of<K.value, decltype(F)>()), dim3(pb_blocks(npx)), dim3(PB_BLOCK), 0, st, P, src, dst, n_frames, ss, ds);
+                    });
                 });
                 break;
             }
@@ -2062,13 +2093,13 @@ int pb_remap_track_u8(const pb_plan* plan, const double* rot3x3_dev, int n_rot_p
         if (interpolation == PB_INTERP_NEAREST) {
             const int dst_aligned = (((uintptr_t)dst_dev | dst_frame_stride) & 3u) == 0;
             pb_pick_any_kind(P, [&](auto K) {
-                hipLaunchKernelGGL((pb_track_kernel<K.value>), dim3(pb_blocks((npx + PB_PX - 1) / PB_PX), chunks), dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d,
+                hipLaunchKernelGGL(pb_track_kernel_of<K.value>(), dim3(pb_blocks((npx + PB_PX - 1) / PB_PX), chunks), dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d,
                                    nf, (unsigned long long)src_frame_stride, (unsigned long long)dst_frame_stride, dst_aligned);
             });
         } else {
             pb_pick_any_kind(P, [&](auto K) {
                 pb_pick_filter(interpolation, [&](auto F) {
-                    hipLaunchKernelGGL((pb_track_interp_kernel<K.value, decltype(F)>), dim3(pb_blocks(npx), chunks), dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d,
+                    hipLaunchKernelGGL((pb_track_interp_kernel_of<K.value, decltype(F)>()), dim3(pb_blocks(npx), chunks), dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d,
                                        nf, (unsigned long long)src_frame_stride, (unsigned long long)dst_frame_stride);
                 });
             });
@@ -2195,7 +2226,7 @@ int pb_coordmap_f64(const pb_proj* dst, double* map_dev, void* stream) {
     P.poly_dst = P.poly_src = d.poly;
     pb_derive(P);
     const unsigned blocks = pb_blocks((unsigned long long)P.dst.height * P.dst.width);
-    if (P.dst.kind == PB_KIND_CUBE) hipLaunchKernelGGL(pb_coordmap_cube_kernel, dim3(blocks), dim3(PB_BLOCK), 0, (hipStream_t)stream, P, map_dev);
+    if (pb_is_cube(P.dst.kind)) hipLaunchKernelGGL(pb_coordmap_cube_kernel, dim3(blocks), dim3(PB_BLOCK), 0, (hipStream_t)stream, P, map_dev);
     else hipLaunchKernelGGL(pb_coordmap_kernel, dim3(blocks), dim3(PB_BLOCK), 0, (hipStream_t)stream, P, map_dev);
     PB_HIP(hipGetLastError());
     return PB_OK;
@@ -2239,7 +2270,7 @@ static int pb_map_planes_ok(const pb_proj* src, const double* dist_l_dev, const 
     if (pb_has_lens(src->kind) && src->lens == PB_LENS_CUSTOM && !dist_l_dev)
         return pb_fail(PB_ERR_INVALID, "a PB_LENS_CUSTOM source needs the host-evaluated distance plane(s)");
     if (src->kind == PB_KIND_DOUBLE && dist_l_dev && !dist_r_dev) return pb_fail(PB_ERR_INVALID, "a double source needs both distance planes");
-    if (!pb_has_lens(src->kind) && (dist_l_dev || dist_r_dev)) return pb_fail(PB_ERR_INVALID, src->kind == PB_KIND_CUBE ? "a cube source has no lens" : "a panorama source has no lens");
+    if (!pb_has_lens(src->kind) && (dist_l_dev || dist_r_dev)) return pb_fail(PB_ERR_INVALID, pb_is_cube(src->kind) ? "a cube source has no lens" : "a panorama source has no lens");
     return PB_OK;
 }
 
@@ -2254,10 +2285,12 @@ static int pb_sample_map_px(int filter, const pb_proj* src, double* map_dev, int
     const unsigned total = (unsigned)height * (unsigned)width;
     const auto launch = [&](auto* sample) {  // (the sample type: uint8_t or uint16_t)
         using SAMPLE = std::remove_pointer_t<decltype(sample)>;
-        if (P.src.kind == PB_KIND_CUBE) {
-            pb_pick_filter(filter, [&](auto F) {
-                hipLaunchKernelGGL((pb_sample_map_interp_cube_kernel<decltype(F), SAMPLE>), dim3(pb_blocks(total)), dim3(PB_BLOCK), 0, (hipStream_t)stream, P, map_dev,
-                                   total, static_cast<const SAMPLE*>(img_dev), out_dev, channels);
+        if (pb_is_cube(P.src.kind)) {
+            pb_pick_cube_kind(P, [&](auto K) {
+                pb_pick_filter(filter, [&](auto F) {
+                    hipLaunchKernelGGL((pb_sample_map_interp_cube_kernel_of<K.value, decltype(F), SAMPLE>()), dim3(pb_blocks(total)), dim3(PB_BLOCK), 0,
+                                       (hipStream_t)stream, P, map_dev, total, static_cast<const SAMPLE*>(img_dev), out_dev, channels);
+                });
             });
             return;
         }

@@ -1,5 +1,5 @@
-"""The three photonbend commands on top of the GPU core - SURVEY 8 f-2 - and two of our own beside them: pano-to-cubemap and
-cubemap-to-pano (the cube map is a (2N, 3N) image of six faces: left, front, right over up, back, down).
+"""The three photonbend commands on top of the GPU core - SURVEY 8 f-2 - and three of our own beside them: pano-to-cubemap,
+cubemap-to-pano and cubemap-to-cubemap (the cube map is a (2N, 3N) image of six faces: left, front, right over up, back, down).
 
 Same command names, options and rules as the reference CLI (photonbend/scripts/main.py:28-35,
 commands/make_photo.py:52-141, alter_photo.py:51-162, make_pano.py:54-149, commands/__init__.py:53-191):
@@ -289,12 +289,22 @@ def _cubemap_common(fn):
     return fn
 
 
+MAPPINGS = tuple(CubemapImage.MAPPINGS)
+MAPPING_HELP = ("How a face is laid out: gnomonic (the plain cube map: position proportional to the tangent of the angle from the face centre) or "
+                "equiangular (the equi-angular cube map of 360-degree video: position proportional to the angle itself).")
+
+
+def _mapping_option(*names):
+    return click.option(*names, type=click.Choice(list(MAPPINGS)), default="gnomonic", show_default=True, help=MAPPING_HELP)
+
+
 @main.command("pano-to-cubemap")
 @click.argument("input_image", type=click.Path(exists=True, path_type=Path))
 @click.option("--face-size", type=click.INT, default=None, help="The side N of a face in pixels; the output is 3N wide and 2N high. [default: input height // 2]")
+@_mapping_option("--mapping")
 @_cubemap_common
 @click.argument("output_image", type=click.Path(exists=False, path_type=Path))
-def pano_to_cubemap(input_image, face_size, output_image, rotation, supersample, interpolation):
+def pano_to_cubemap(input_image, face_size, output_image, rotation, supersample, interpolation, mapping):
     """Make a cube map out of a panorama.
 
     \b
@@ -306,16 +316,17 @@ def pano_to_cubemap(input_image, face_size, output_image, rotation, supersample,
     n = pano.shape[0] // 2 if face_size is None else face_size
     if n < 1:
         raise click.BadParameter("a face needs at least one pixel", param_hint="--face-size")
-    destiny = CubemapImage(np.zeros((2 * n, 3 * n, 3), np.uint8))
+    destiny = CubemapImage(np.zeros((2 * n, 3 * n, 3), np.uint8), mapping=mapping)
     run_chain(PanoramaImage(pano), destiny, rotation, out, int(supersample), **_sampler(interpolation))
 
 
 @main.command("cubemap-to-pano")
 @click.argument("input_image", type=click.Path(exists=True, path_type=Path))
 @click.option("--height", type=click.INT, default=None, help="The vertical size of the panorama (its width is twice that). [default: 2 x the face size]")
+@_mapping_option("--mapping")
 @_cubemap_common
 @click.argument("output_image", type=click.Path(exists=False, path_type=Path))
-def cubemap_to_pano(input_image, height, output_image, rotation, supersample, interpolation):
+def cubemap_to_pano(input_image, height, output_image, rotation, supersample, interpolation, mapping):
     """Make a panorama out of a cube map.
 
     \b
@@ -325,13 +336,40 @@ def cubemap_to_pano(input_image, height, output_image, rotation, supersample, in
     out = checked_output(output_image)
     cube = open_image(input_image)
     try:
-        source = CubemapImage(cube)
+        source = CubemapImage(cube, mapping=mapping)
     except ValueError as exc:
         raise click.UsageError(f"{input_image}: {exc}")
     h = 2 * source.face_size if height is None else height
     if h < 1:
         raise click.BadParameter("a panorama needs at least one row", param_hint="--height")
     destiny = PanoramaImage(np.zeros((h, 2 * h, 3), np.uint8))
+    run_chain(source, destiny, rotation, out, int(supersample), **_sampler(interpolation))
+
+
+@main.command("cubemap-to-cubemap")
+@click.argument("input_image", type=click.Path(exists=True, path_type=Path))
+@_mapping_option("--input-mapping")
+@_mapping_option("--output-mapping")
+@click.option("--face-size", type=click.INT, default=None, help="The side N of an output face in pixels. [default: the input's face size]")
+@_cubemap_common
+@click.argument("output_image", type=click.Path(exists=False, path_type=Path))
+def cubemap_to_cubemap(input_image, input_mapping, output_mapping, face_size, output_image, rotation, supersample, interpolation):
+    """Convert a cube map between the gnomonic and the equi-angular mapping, resize it or re-orient it.
+
+    \b
+    INPUT is the path to the source cube map: a 3N x 2N image of six faces, left, front, right over up, back, down.
+    OUTPUT is the desired path of the destiny cube map, in the same arrangement.
+    """
+    out = checked_output(output_image)
+    cube = open_image(input_image)
+    try:
+        source = CubemapImage(cube, mapping=input_mapping)
+    except ValueError as exc:
+        raise click.UsageError(f"{input_image}: {exc}")
+    n = source.face_size if face_size is None else face_size
+    if n < 1:
+        raise click.BadParameter("a face needs at least one pixel", param_hint="--face-size")
+    destiny = CubemapImage(np.zeros((2 * n, 3 * n, 3), np.uint8), mapping=output_mapping)
     run_chain(source, destiny, rotation, out, int(supersample), **_sampler(interpolation))
 
 
