@@ -276,6 +276,34 @@ int pb_remap_px(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_f
                 size_t dst_frame_stride, int bytes_per_px, void* stream);
 int pb_remap_px_supported(const pb_plan* plan, int bytes_per_px);
 
+/* 4:2:0 semi-planar video frames - NV12 (bytes_per_sample 1) and P010 / P016 (2) - in ONE launch of the tile kernel pb_nv12_hot_kernel
+ * whatever n_frames (ABI 5, additive).  A frame is a plane of height x width luma samples and, uv_offset bytes after its
+ * start, a plane of height/2 x width/2 interleaved (U, V) pairs; the rows of both planes are `pitch` bytes apart - the surface a hardware
+ * video decoder writes.  With idx the plan's index map (pb_index_map_i32):
+ *   luma     Y_out[y][x] = Y_src[r][c], (r, c) = divmod(idx[y][x], w); fill_yuv[0] where idx[y][x] < 0;
+ *   chroma   UV_out[i][j] = UV_src[r >> 1][c >> 1], (r, c) = divmod(idx[2i][2j], w) - the ANCHOR, the top-left pixel of the 2 x 2 block;
+ *            (fill_yuv[1], fill_yuv[2]) where idx[2i][2j] < 0.  Only the anchor decides, whatever the block's other pixels are.
+ * This is a NEAREST sample of chroma at the anchor's position: it can lie up to one luma pixel off the chroma sample's nominal siting,
+ * the order of what truncation does to luma.  No chroma interpolation is done.  The bytes are exact: those of the definition with
+ * the reference's own index map.
+ *   layouts (bytes; NULL, or a 0 member: the packed default)   pitch = S * width; uv_offset = pitch * height; frame_stride = uv_offset +
+ *                                pitch * height / 2.  Padding bytes are neither read nor written.
+ *   fill_yuv                     the samples of black pixels; NULL: video black, (16, 128, 128) << 8 * (S - 1).
+ *   PB_ERR_INVALID               before any launch, nothing is written: null plan or frames, bytes_per_sample outside {1, 2}, an odd
+ *                                dimension of source or destination, pitch < S * width, uv_offset < pitch * height, a frame_stride
+ *                                smaller than a frame, a pointer, pitch, offset or stride that is not a multiple of 2 * S (one pair).
+ *   PB_ERR_UNSUPPORTED           nothing is written - exactly the plans pb_remap_px refuses: deferred plans, PB_MODE_FAITHFUL,
+ *                                double-fisheye sources, plans without device state, sources of 32768 px a side or more; and frames
+ *                                whose byte span (uv_offset + pitch * height / 2) reaches 2^31 (the kernel's byte offsets are 32-bit) - a pitch
+ *                                or uv_offset of 2^31 or more among them, refused before any product is formed.
+ * Asynchronous on `stream`, never allocates or synchronises (graph-capture safe).
+ * pb_remap_nv12_supported: 1 when pb_remap_nv12 takes `plan` with packed frames of this sample size, 0 when it would return
+ * PB_ERR_UNSUPPORTED, negative on bad arguments. */
+typedef struct pb_nv12_layout { size_t pitch, uv_offset, frame_stride; } pb_nv12_layout;   /* bytes; 0 = packed default */
+int pb_remap_nv12(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout,
+                  const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3], void* stream);
+int pb_remap_nv12_supported(const pb_plan* plan, int bytes_per_sample);
+
 /* OPT-IN extension with no reference counterpart (the reference samples nearest-by-truncation only):
  * bilinear interpolation at the reference's pre-truncation coordinate (pixel k covers [k, k+1), centre
  * k + 0.5; taps clamped to the image, panorama columns wrap; round half to even).  Pixels the nearest mode

@@ -178,31 +178,67 @@ def _px_kw(bpp: int) -> dict:
     return {} if bpp == 3 else {"bytes_per_px": bpp}
 
 
-def remap_ndarray(plan: nat.Plan, image: np.ndarray, interpolation: str = "nearest", device: int | None = None, supersample: int = 1) -> np.ndarray:
+VIDEO_FORMATS = {"nv12": np.dtype(np.uint8), "p010": np.dtype(np.uint16)}  # 4:2:0 semi-planar frames (3h/2, w): Plan.launch_nv12
+
+
+def check_video_call(pixel_format: str, interpolation: str, supersample: int, track=None) -> np.dtype:
+    """The sample type of a video pixel format, for a call it can be part of: nearest, not supersampled, no rotation track (pb_remap_nv12).
+    ValueError otherwise.  THE place that says so: ``_video_format`` and ``batch.remap_frames`` (before its first frame) ask here."""
+    dt = VIDEO_FORMATS.get(pixel_format)
+    if dt is None:
+        raise ValueError(f"pixel_format must be None or one of {sorted(VIDEO_FORMATS)}, got {pixel_format!r}")
+    if interpolation != "nearest" or supersample != 1 or track is not None:
+        raise ValueError(f"{pixel_format} frames take nearest sampling without supersampling or a rotation track")
+    return dt
+
+
+def _video_format(plan, a: np.ndarray, pixel_format: str, interpolation: str, supersample: int, track=None) -> tuple:
+    """(result shape, dtype, bytes per sample) of a 4:2:0 semi-planar frame (3h/2, w) for `plan`.  The keyword is needed: such an array is
+    indistinguishable from a grey image.  ValueError otherwise."""
+    dt = check_video_call(pixel_format, interpolation, supersample, track)
+    h, w, H, W = plan.src.height, plan.src.width, plan.dst.height, plan.dst.width
+    if (h | w | H | W) & 1:
+        raise ValueError(f"{pixel_format} frames need even dimensions, the plan maps {h} x {w} to {H} x {W}")
+    if a.dtype != dt or tuple(a.shape) != (3 * h // 2, w):
+        raise ValueError(f"{pixel_format} frames must be {dt} {(3 * h // 2, w)}, got {a.dtype} {tuple(a.shape)}")
+    return (3 * H // 2, W), dt, dt.itemsize
+
+
+def remap_ndarray(plan: nat.Plan, image: np.ndarray, interpolation: str = "nearest", device: int | None = None, supersample: int = 1,
+                  pixel_format: str | None = None) -> np.ndarray:
     """One frame: uint8 (h, w, 3) ndarray -> fresh uint8 (H, W, 3) ndarray (upload, ONE kernel launch, download).  ``supersample`` n: `plan`
     is the n x destination's and the result (H / n, W / n, 3) holds the n x n block means (``Plan.launch``).  ``interpolation``: "nearest",
     "bilinear" or "catmull-rom" (not supersampled).  Nearest without supersampling also takes (h, w, *tail) frames of any dtype whose
     pixel is 1, 2, 4, 6 or 8 bytes - grey, RGBA, 16-bit samples - and returns (H, W, *tail) of that dtype (pb_remap_px: a plan
-    ``Plan.px_supported`` refuses is a PbError)."""
+    ``Plan.px_supported`` refuses is a PbError).  ``pixel_format`` "nv12" (uint8) or "p010" (uint16): the frame is a 4:2:0 semi-planar
+    video frame (3h/2, w) and the result (3H/2, W) (pb_remap_nv12, DESIGN 3.15: a plan ``Plan.nv12_supported`` refuses is a PbError)."""
     nat.check_interpolation(interpolation, supersample)
-    oh, ow = _out_shape(plan, supersample)
-    tail, dt, bpp = _px_format(plan, image, interpolation, supersample)
+    if pixel_format is None:
+        oh, ow = _out_shape(plan, supersample)
+        tail, dt, bpp = _px_format(plan, image, interpolation, supersample)
+        oshape, out_bytes = (oh, ow) + tail, bpp * oh * ow
+    else:
+        oshape, dt, bpp = _video_format(plan, image, pixel_format, interpolation, supersample)  # (bpp: bytes per sample)
+        out_bytes = bpp * oshape[0] * oshape[1]
     nat.require_gpu()
     pipe = pipe_for(device)
     with nat.on_device(pipe.device):
         d_in = pipe.device_buffer("in", image.nbytes)
-        d_out = pipe.device_buffer("out", bpp * oh * ow)
+        d_out = pipe.device_buffer("out", out_bytes)
         ws = pipe.take_workspace(_ss_bytes(plan, supersample, interpolation, d_in.data_ptr()))
         pipe.upload(image, d_in)
-        plan.launch(d_in.data_ptr(), d_out.data_ptr(), 1, pipe.stream.handle, interpolation, **_ss_kw(supersample, ws), **_px_kw(bpp))
-        out = pipe.download(d_out, (oh, ow) + tail, dt)
+        if pixel_format is None:
+            plan.launch(d_in.data_ptr(), d_out.data_ptr(), 1, pipe.stream.handle, interpolation, **_ss_kw(supersample, ws), **_px_kw(bpp))
+        else:
+            plan.launch_nv12(d_in.data_ptr(), d_out.data_ptr(), 1, pipe.stream.handle, bpp)
+        out = pipe.download(d_out, oshape, dt)
         pipe.stream.sync()
         pipe.give_workspace(ws)
     return out
 
 
 def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, interpolation: str = "nearest",
-                 supersample: int = 1, track=None) -> Iterator[np.ndarray]:
+                 supersample: int = 1, track=None, pixel_format: str | None = None) -> Iterator[np.ndarray]:
     """Streams host-resident frames through one plan: while frame k + 1 uploads on the H2D stream, the remap kernel of frame k stores its
     output over PCIe straight into frame k's result ndarray (page-locked, device-visible), through `depth` rotating device input
     buffers.  Yields uint8 (H, W, 3) ndarrays in order (page-locked, recycled when dropped).  ``supersample`` n: `plan` is the n x
@@ -210,8 +246,12 @@ def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, i
     supersampling also takes frames (h, w, *tail) of any dtype whose pixel is 1, 2, 4, 6 or 8 bytes (``remap_ndarray``): all frames of a
     call share the first frame's format, and the results are (H, W, *tail) of that dtype.  ``track``: ``nat.rotation_table``'s result - a
     rotation per frame (uint8 RGB, not supersampled): the table is uploaded once before the first frame (a device array is used in place)
-    and frame f is a one-frame ``Plan.launch_track`` that points at entry f; a frame beyond the table is a ValueError at that frame."""
+    and frame f is a one-frame ``Plan.launch_track`` that points at entry f; a frame beyond the table is a ValueError at that frame.
+    ``pixel_format`` "nv12" / "p010": the frames are 4:2:0 semi-planar video frames (3h/2, w) of uint8 / uint16 and the results (3H/2, W)
+    (``remap_ndarray``) - the same pipeline, page-locking and ring; None: everything above."""
     nat.check_interpolation(interpolation, supersample)
+    if pixel_format is not None:
+        check_video_call(pixel_format, interpolation, supersample, track)
     if track is not None and supersample != 1:
         raise ValueError("a rotation track is not supersampled: pass supersample=1")
     oh, ow = _out_shape(plan, supersample)
@@ -244,7 +284,12 @@ def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, i
     try:
         for frame in frames:
             a = np.asarray(frame)
-            if fmt is None:
+            if fmt is None and pixel_format is not None:
+                dh, dt, bpp = _video_format(plan, a, pixel_format, interpolation, supersample, track)  # (bpp: bytes per sample)
+                fmt, sh = ((), dt, bpp), tuple(a.shape)
+                n_in = a.nbytes
+                d_in = pipe.take_ring(n_in, depth)
+            elif fmt is None:
                 tail, dt, bpp = fmt = _px_format(plan, a, interpolation, supersample)
                 sh, dh = (plan.src.height, plan.src.width) + tail, (oh, ow) + tail
                 n_in = a.nbytes
@@ -257,7 +302,9 @@ def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, i
             uploaded[slot].record(s_up)
             s_run.wait(uploaded[slot])
             out = results[slot] = PINNED.ndarray(dh, fmt[1])
-            if tab is None:
+            if pixel_format is not None:
+                plan.launch_nv12(d_in[slot].data_ptr(), out.ctypes.data, 1, s_run.handle, bpp)
+            elif tab is None:
                 plan.launch(d_in[slot].data_ptr(), out.ctypes.data, 1, s_run.handle, interpolation, **_ss_kw(supersample, ws), **_px_kw(bpp))
             else:
                 if k >= n_tab:

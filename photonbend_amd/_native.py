@@ -114,6 +114,8 @@ SIGNATURES = {
     "pb_remap_u8v": (C.c_int, [_VP, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, _VP]),
     "pb_remap_px": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, C.c_int, _VP]),
     "pb_remap_px_supported": (C.c_int, [_VP, C.c_int]),
+    "pb_remap_nv12": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP]),
+    "pb_remap_nv12_supported": (C.c_int, [_VP, C.c_int]),
     "pb_remap_bilinear_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_catmull_rom_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_track_u8": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
@@ -247,6 +249,33 @@ def rotation_table(rotations, n_rot: int = 0):
 
 
 PX_SIZES = (1, 2, 3, 4, 6, 8)  # bytes per pixel pb_remap_px takes: grey8, grey16 / two uint8 channels, RGB8, RGBA8, RGB16, RGBA16
+
+
+class pb_nv12_layout(C.Structure):
+    """include/photonbend_hip.h: the plane layout of 4:2:0 semi-planar frames, in bytes; a 0 member is the packed default."""
+    _fields_ = [("pitch", C.c_size_t), ("uv_offset", C.c_size_t), ("frame_stride", C.c_size_t)]
+
+
+def nv12_layout(layout):
+    """None, a pb_nv12_layout, a dict or a (pitch, uv_offset, frame_stride) tuple -> a pb_nv12_layout or None."""
+    if layout is None or isinstance(layout, pb_nv12_layout):
+        return layout
+    if isinstance(layout, dict):
+        extra = set(layout) - {"pitch", "uv_offset", "frame_stride"}
+        if extra:
+            raise ValueError(f"unknown layout members {sorted(extra)}")
+        return pb_nv12_layout(int(layout.get("pitch", 0)), int(layout.get("uv_offset", 0)), int(layout.get("frame_stride", 0)))
+    pitch, uv_offset, frame_stride = layout
+    return pb_nv12_layout(int(pitch), int(uv_offset), int(frame_stride))
+
+
+def nv12_frame_bytes(layout, height: int, width: int, bytes_per_sample: int) -> tuple:
+    """(bytes one frame spans, frame stride) of a layout (None: packed) - the library's defaults, for buffer-size checks."""
+    l = layout or pb_nv12_layout()
+    pitch = l.pitch or bytes_per_sample * width
+    uv = l.uv_offset or pitch * height
+    span = uv + pitch * (height // 2)
+    return span, (l.frame_stride or span)
 
 
 def px_align(bytes_per_px: int) -> int:
@@ -764,6 +793,81 @@ class Plan:
                 raise PbError(f"out must live on the source's device ({s.device}), got {o.device}")
         with _on(s):
             self.launch(s.data_ptr(), o.data_ptr(), n, None, bytes_per_px=bpp)
+        return o
+
+    def nv12_supported(self, bytes_per_sample: int = 1) -> bool:
+        """Whether ``remap_nv12`` takes this plan with samples of this size (pb_remap_nv12_supported): the plans ``px_supported`` takes,
+        with even dimensions.  A size outside (1, 2) or an odd dimension is a PbError.  Needs no GPU."""
+        r = load().pb_remap_nv12_supported(self._h, int(bytes_per_sample))
+        if r < 0:
+            check(r)
+        return r == 1
+
+    def launch_nv12(self, src_ptr: int, dst_ptr: int, n_frames: int = 1, stream: int | None = None, bytes_per_sample: int = 1, fill=None,
+                    src_layout=None, dst_layout=None) -> None:
+        """The raw call (pb_remap_nv12): n_frames 4:2:0 semi-planar frames at src_ptr / dst_ptr on `stream`, layouts in bytes (None: packed),
+        ``fill`` the (Y, U, V) samples of black pixels (None: video black)."""
+        f = None if fill is None else (C.c_uint16 * 3)(*[int(v) for v in fill])
+        sl, dl = nv12_layout(src_layout), nv12_layout(dst_layout)
+        self._gated(load().pb_remap_nv12, self._h, src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl), None if dl is None else C.addressof(dl),
+                    int(bytes_per_sample), None if f is None else C.addressof(f), current_stream() if stream is None else stream)
+
+    def remap_nv12(self, src, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None):
+        """The nearest remap of NV12 (uint8) or P010 / P016 (uint16) video frames in ONE launch (pb_remap_nv12): luma moves
+        like a grey image, and the (U, V) pair of an output 2 x 2 block is the source pair at the block's top-left pixel's source position.
+        src: a device array (3h/2, w) or (N, 3h/2, w), packed - or, with ``src_layout``, any 1-D uint8 / uint16 device buffer that holds
+        the frames at that layout (then ``out`` is required with ``dst_layout``, or the result is packed).  -> (3H/2, W) / (N, 3H/2, W) of
+        src's kind and dtype.  ``fill``: (Y, U, V) for black pixels (None: 16, 128, 128 scaled to the sample size).  Layouts: a
+        (pitch, uv_offset, frame_stride) tuple, dict or pb_nv12_layout, in bytes, 0 = default.  A plan ``nv12_supported`` refuses is a
+        PbError (no fallback)."""
+        h, w, Hd, Wd = self.src.height, self.src.width, self.dst.height, self.dst.width
+        if not is_device_array(src):
+            raise PbError(f"source frames must be device arrays (CUDA tensors or DeviceArrays), got {type(src).__name__}")
+        if (h | w | Hd | Wd) & 1:
+            raise PbError("4:2:0 frames need even source and destination dimensions")
+        tens = is_tensor(src)
+        shp = tuple(int(v) for v in src.shape)
+        dt = torch_dtype_np(src.dtype) if tens else np.dtype(src.dtype)
+        if dt not in (np.dtype(np.uint8), np.dtype(np.uint16)):
+            raise PbError(f"NV12 frames are uint8 and P010 / P016 frames uint16, got {dt}")
+        S = dt.itemsize
+        sl, dl = nv12_layout(src_layout), nv12_layout(dst_layout)
+        if sl is None:
+            if len(shp) not in (2, 3) or shp[-2:] != (3 * h // 2, w):
+                raise PbError(f"packed source frames must be ({3 * h // 2}, {w}) or (N, {3 * h // 2}, {w}), got {shp}")
+            n = shp[0] if len(shp) == 3 else 1
+        else:
+            if len(shp) != 1:
+                raise PbError(f"frames at a layout come as a 1-D buffer, got {shp}")
+            span, stride = nv12_frame_bytes(sl, h, w, S)
+            n = 0 if shp[0] * S < span else (shp[0] * S - span) // stride + 1
+            if n < 1:
+                raise PbError(f"the source buffer holds {shp[0] * S} bytes, a frame at this layout spans {span}")
+        require_gpu()
+        s = src.contiguous() if tens else src
+        packed_out = ((n,) if len(shp) == 3 else ()) + (3 * Hd // 2, Wd)
+        if out is None:
+            if dl is not None:
+                raise PbError("a destination layout needs the `out` buffer it describes")
+            o = empty(packed_out if sl is None else (n, 3 * Hd // 2, Wd), dt, like=s)
+        else:
+            o = out
+            odt = (torch_dtype_np(o.dtype) if is_tensor(o) else np.dtype(o.dtype)) if is_device_array(o) else None
+            if odt != dt or is_tensor(o) != tens or (tens and not o.is_contiguous()):
+                raise PbError(f"out must be a contiguous {dt} device array of the source's kind")
+            oshp = tuple(int(v) for v in o.shape)
+            if dl is None:
+                if oshp not in (packed_out, (n, 3 * Hd // 2, Wd)):
+                    raise PbError(f"out must be {packed_out}, got {oshp}")
+            else:
+                span, stride = nv12_frame_bytes(dl, Hd, Wd, S)
+                have = int(np.prod(oshp)) * S
+                if have < (n - 1) * stride + span:
+                    raise PbError(f"out holds {have} bytes, {n} frames at this layout span {(n - 1) * stride + span}")
+            if tens and (not o.is_cuda or o.device != s.device):
+                raise PbError(f"out must live on the source's device ({s.device}), got {o.device}")
+        with _on(s):
+            self.launch_nv12(s.data_ptr(), o.data_ptr(), n, stream, S, fill, sl, dl)
         return o
 
     def remap_each(self, srcs, outs=None, stream: int | None = None):

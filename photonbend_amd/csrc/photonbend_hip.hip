@@ -38,6 +38,7 @@
 #include "pb_kernels_supersample.hpp"
 #include "pb_kernels_catmull_rom.hpp"
 #include "pb_kernels_px.hpp"
+#include "pb_kernels_nv12.hpp"
 #include "pb_kernels_track.hpp"
 
 #define PB_DOUBLE_FRAMES_PER_WAVE 1  // frames a double-source wave loops over (the rest of a batch is a grid dimension)
@@ -981,19 +982,22 @@ struct PbRoute {
         SS_GENERIC,          // supersampled: frame by frame the route of n = 1 into a workspace, then pb_box_reduce_kernel
         PX,                  // nearest, pixels of bpp != 3 bytes (pb_remap_px): pb_px_hot_kernel
         PX_NONE,             // ... on a plan that kernel does not serve: nothing is launched (PB_ERR_UNSUPPORTED)
+        NV12,                // nearest, 4:2:0 semi-planar frames (pb_remap_nv12): pb_nv12_hot_kernel
+        NV12_NONE,           // ... on a plan that kernel does not serve - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
     } kind;
     bool windows;                    // BIL_DOUBLE / bilinear INTERP_TILES: LEAN tiles gather from LDS windows
     int filter = PB_INTERP_NEAREST;  // the INTERP_* routes: PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM
-    int bpp = 3;                     // PX: bytes per pixel
+    int bpp = 3;                     // PX: bytes per pixel; NV12: bytes per sample
 };
 static bool pb_aligned16(const void* src, unsigned long long stride) { return ((((uintptr_t)src) | stride) & 15u) == 0; }
-static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned flags, bool aligned, int bpp = 3) {
+static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned flags, bool aligned, int bpp = 3, bool nv12 = false) {
     const PbParams& P = pl->P;
-    if (bpp != 3) {
+    if (bpp != 3 || nv12) {
         // the tile kernel of the nearest plan's launch-order table, or nothing: no window, so no alignment beyond the pixel's own
         // (pb_check_frames); fast_ready says single source, prepared, device state; generic tiles pack row and column in 16 bits each
         const bool px = interpolation == PB_INTERP_NEAREST && n == 1 && pb_use_fast(pl) && pl->nearest.lt.entries && pl->nearest.P_dev &&
                         P.src.width < 32768 && P.src.height < 32768;
+        if (nv12) return {px ? PbRoute::NV12 : PbRoute::NV12_NONE, false, PB_INTERP_NEAREST, bpp};  // (bpp: bytes per sample)
         return {px ? PbRoute::PX : PbRoute::PX_NONE, false, PB_INTERP_NEAREST, bpp};
     }
     if (n > 1) {
@@ -1054,8 +1058,9 @@ static void pb_launch_direct(const pb_plan* pl, const uint8_t* src, uint8_t* dst
 }
 
 // Launches a nearest or bilinear route (n = 1) for n_frames frames at strides ss / ds (pb_check_frames has filled them in).
+// nv12: the plane layouts and fills of the NV12 route (pb_remap_nv12), null everywhere else.
 static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* dst, int n_frames, unsigned long long ss, unsigned long long ds,
-                     hipStream_t st) {
+                     hipStream_t st, const PbNv12* nv12 = nullptr) {
     const PbParams& P = pl->P;
     const unsigned long long npx = (unsigned long long)P.dst.height * P.dst.width;
     switch (r.kind) {
@@ -1122,6 +1127,23 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
         case PbRoute::PX_NONE:
             return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_px takes prepared plans of a single source in a tile mode (not deferred, not PB_MODE_FAITHFUL, not "
                                                "double-fisheye, sources below 32768 px a side): use pb_index_map_i32 + pb_gather_px");
+        case PbRoute::NV12: {
+            // launched like PX: both planes of a tile by the tile's wave
+            const unsigned gpf = pl->nearest.lt.groups;
+            pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
+                pb_pick_kind(P, [&](auto K) {
+                    pb_pick<1, 2>(r.bpp == 1, [&](auto S) {
+                        hipLaunchKernelGGL((pb_nv12_hot_kernel<K.value, S.value>), dim3(gpf * (unsigned)nf), dim3(64 * PB_TILE_WAVES), 0, st,
+                                           (const PbParams*)pl->nearest.P_dev, pb_hot_of_host(P), pl->nearest.lt.entries, sf, df, gpf, ss, ds, pl->cert.idx_tab,
+                                           pl->cert.fix_px, pl->cert.fix_idx, *nv12);
+                    });
+                });
+            });
+            break;
+        }
+        case PbRoute::NV12_NONE:
+            return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_nv12 takes prepared plans of a single source in a tile mode (not deferred, not PB_MODE_FAITHFUL, not "
+                                               "double-fisheye, sources below 32768 px a side): use pb_index_map_i32 and gather the two planes");
         case PbRoute::BIL_DOUBLE: {
             // the per-eye tile models of the nearest mode's plan + the exact coordinate tables: one wave per tile
             const unsigned gpf = pb_bil_groups(pl);
@@ -2000,6 +2022,67 @@ int pb_remap_px_supported(const pb_plan* plan, int bytes_per_px) {
     if (!pb_px_size_ok(bytes_per_px)) return pb_fail(PB_ERR_INVALID, "bytes_per_px outside {1, 2, 3, 4, 6, 8}");
     if (bytes_per_px == 3) return 1;
     return pb_route(plan, PB_INTERP_NEAREST, 1, 0, false, bytes_per_px).kind == PbRoute::PX && pb_px_frames_fit(plan, bytes_per_px);
+}
+
+// 4:2:0 semi-planar frames.  Every check comes before the device is looked at and before any launch.
+struct PbNv12Frame {  // a resolved layout, in bytes
+    unsigned long long pitch, uv, span, stride;
+};
+static int pb_nv12_resolve(const char* what, const pb_nv12_layout* l, unsigned long long S, unsigned long long h, unsigned long long w, PbNv12Frame& f) {
+    const std::string n(what);
+    // (a frame must span less than 2^31 bytes to be served: a pitch or an offset at or beyond that is refused here, before anything is
+    //  multiplied - no product below can wrap, whatever the caller passes)
+    if (l && (l->pitch >= (1ull << 31) || l->uv_offset >= (1ull << 31)))
+        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_nv12 takes frames whose planes span less than 2^31 bytes (" + n + " pitch or uv_offset): use pb_index_map_i32 and gather the two planes");
+    f.pitch = (l && l->pitch) ? l->pitch : S * w;
+    if (f.pitch < S * w) return pb_fail(PB_ERR_INVALID, n + " pitch smaller than a row");
+    f.uv = (l && l->uv_offset) ? l->uv_offset : f.pitch * h;
+    if (f.uv < f.pitch * h) return pb_fail(PB_ERR_INVALID, n + " uv_offset smaller than the luma plane");
+    f.span = f.uv + f.pitch * (h / 2);
+    f.stride = (l && l->frame_stride) ? l->frame_stride : f.span;
+    if (f.stride < f.span) return pb_fail(PB_ERR_INVALID, n + " frame_stride smaller than a frame");
+    if ((f.pitch | f.uv | f.stride) % (2 * S))
+        return pb_fail(PB_ERR_INVALID, n + " pitch, uv_offset and frame_stride must be multiples of " + std::to_string(2 * S) + " bytes (one chroma pair)");
+    return PB_OK;
+}
+static bool pb_nv12_dims_even(const pb_plan* plan) {
+    const PbParams& P = plan->P;
+    return !((P.src.height | P.src.width | P.dst.height | P.dst.width) & 1);
+}
+static bool pb_nv12_served(const pb_plan* plan, int S) { return pb_route(plan, PB_INTERP_NEAREST, 1, 0, false, S, true).kind == PbRoute::NV12; }
+int pb_remap_nv12(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout,
+                  int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
+    if (!plan || !src_dev || !dst_dev) return pb_fail(PB_ERR_INVALID, "null argument");
+    if (n_frames < 0) return pb_fail(PB_ERR_INVALID, "negative frame count");
+    if (bytes_per_sample != 1 && bytes_per_sample != 2) return pb_fail(PB_ERR_INVALID, "bytes_per_sample outside {1, 2}");
+    if (!pb_nv12_dims_even(plan)) return pb_fail(PB_ERR_INVALID, "4:2:0 frames need even source and destination dimensions");
+    const PbParams& P = plan->P;
+    const unsigned long long S = (unsigned long long)bytes_per_sample;
+    PbNv12Frame fs, fd;
+    int rc = pb_nv12_resolve("source", src_layout, S, (unsigned long long)P.src.height, (unsigned long long)P.src.width, fs);
+    if (rc == PB_OK) rc = pb_nv12_resolve("destination", dst_layout, S, (unsigned long long)P.dst.height, (unsigned long long)P.dst.width, fd);
+    if (rc != PB_OK) return rc;
+    if (((uintptr_t)src_dev | (uintptr_t)dst_dev) % (2 * S))
+        return pb_fail(PB_ERR_INVALID, "frame pointers must be multiples of " + std::to_string(2 * S) + " bytes (one chroma pair)");
+    if (n_frames == 0) return PB_OK;
+    rc = pb_check_device(plan);
+    if (rc != PB_OK) return rc;
+    const PbRoute r = pb_route(plan, PB_INTERP_NEAREST, 1, 0, false, bytes_per_sample, true);
+    if (r.kind == PbRoute::NV12 && (fs.span >= (1ull << 31) || fd.span >= (1ull << 31)))
+        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_nv12 takes frames whose planes span less than 2^31 bytes: use pb_index_map_i32 and gather the two planes");
+    const unsigned sh = 8u * ((unsigned)S - 1u), smask = S == 1 ? 0xFFu : 0xFFFFu;
+    const unsigned fy = fill_yuv ? fill_yuv[0] & smask : 16u << sh, fu = fill_yuv ? fill_yuv[1] & smask : 128u << sh, fv = fill_yuv ? fill_yuv[2] & smask : 128u << sh;
+    const PbNv12 L = {(unsigned)fs.pitch, (unsigned)fs.uv, (unsigned)fd.pitch, (unsigned)fd.uv, fy, fu | (fv << (8u * (unsigned)S))};
+    return pb_launch(plan, r, static_cast<const uint8_t*>(src_dev), static_cast<uint8_t*>(dst_dev), n_frames, fs.stride, fd.stride, (hipStream_t)stream, &L);
+}
+int pb_remap_nv12_supported(const pb_plan* plan, int bytes_per_sample) {
+    if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
+    if (bytes_per_sample != 1 && bytes_per_sample != 2) return pb_fail(PB_ERR_INVALID, "bytes_per_sample outside {1, 2}");
+    if (!pb_nv12_dims_even(plan)) return pb_fail(PB_ERR_INVALID, "4:2:0 frames need even source and destination dimensions");
+    // (packed frames: 3/2 S h w bytes; a pitched layout's span is pb_remap_nv12's to check)
+    const PbParams& P = plan->P;
+    const unsigned long long S = (unsigned long long)bytes_per_sample;
+    return pb_nv12_served(plan, bytes_per_sample) && 3 * S * P.src.height * P.src.width / 2 < (1ull << 31) && 3 * S * P.dst.height * P.dst.width / 2 < (1ull << 31);
 }
 
 int pb_remap_u8v(const pb_plan* plan, const uint8_t* const* src_dev, uint8_t* const* dst_dev, int n_frames, void* stream) {

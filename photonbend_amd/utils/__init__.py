@@ -1,12 +1,12 @@
 """Angle helpers and the panorama -> photo size rule, with the reference's operation order
-(photonbend/utils/__init__.py:27-118), and the cube map's face layout (no reference counterpart).  Host scalars and array views only;
-nothing here computes a pixel."""
+(photonbend/utils/__init__.py:27-118), the cube map's face layout and the planes of a 4:2:0 semi-planar video frame (no reference
+counterparts).  Host scalars and array views only; nothing here computes a pixel."""
 
 import math
 from typing import Callable, Dict, Tuple
 
 __all__ = ["to_radians", "to_degrees", "calculate_size_panorama_to_photo", "CUBEMAP_FACES", "cubemap_faces", "cubemap_from_faces",
-           "cubemap_face_rotation"]
+           "cubemap_face_rotation", "nv12_planes", "nv12_frame"]
 
 # the six faces of a cube map in frame order: face k occupies rows (k // 3) N ... and columns (k % 3) N ... of the (2N, 3N) image
 CUBEMAP_FACES = ("left", "front", "right", "up", "back", "down")
@@ -61,6 +61,27 @@ def cubemap_from_faces(faces):
     if any(a.shape != first.shape or a.dtype != first.dtype for a in arrs):
         raise ValueError("cube map faces must share one shape and sample type")
     return np.concatenate([np.concatenate(arrs[:3], axis=1), np.concatenate(arrs[3:], axis=1)], axis=0)
+
+
+def nv12_planes(frame):
+    """(y, uv) VIEWS of a packed 4:2:0 semi-planar frame (3h/2, w) - NV12 (uint8) or P010 / P016 (uint16), an ndarray or anything
+    sliceable and reshapeable the same way: y is (h, w), uv is (h/2, w/2, 2) with uv[i, j] the (U, V) pair of luma block (2i, 2j)."""
+    shape = tuple(int(v) for v in frame.shape)
+    if len(shape) != 2 or shape[0] % 3 or shape[1] % 2 or shape[0] < 3 or (shape[0] // 3 * 2) % 2:
+        raise ValueError(f"a 4:2:0 semi-planar frame has shape (3h/2, w) with h and w even, got {shape}")
+    h, w = shape[0] // 3 * 2, shape[1]
+    return frame[:h], frame[h:].reshape(h // 2, w // 2, 2)
+
+
+def nv12_frame(y, uv):
+    """The packed (3h/2, w) frame of a luma plane (h, w) and a chroma plane (h/2, w/2, 2) of the same sample type: nv12_planes'
+    inverse, in NumPy."""
+    import numpy as np
+
+    y, uv = np.asarray(y), np.asarray(uv)
+    if y.ndim != 2 or y.shape[0] % 2 or y.shape[1] % 2 or uv.shape != (y.shape[0] // 2, y.shape[1] // 2, 2) or uv.dtype != y.dtype:
+        raise ValueError(f"a luma plane (h, w) with h and w even and a chroma plane (h/2, w/2, 2) of its sample type, got {y.shape} {y.dtype} and {uv.shape} {uv.dtype}")
+    return np.concatenate([y, uv.reshape(y.shape[0] // 2, y.shape[1])], axis=0)
 
 
 def to_radians(degrees: float) -> float:
