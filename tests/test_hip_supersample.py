@@ -47,6 +47,21 @@ def _workspace(plan, n, interp=0, flags=0):
     return need.value
 
 
+def _assert_route(plan, n, dev):
+    """The route of plan.remap(dev, supersample=n), asserted: a prepared single-source plan (info()["fast_path"]) takes the fused kernel -
+    no workspace for this very frame - unless its packed frame size 3 h w is no multiple of 16: pb_check_frames fills the stride in with
+    it, the plain route then is not the windowed kernel (pb_aligned16) and pb_route answers SS_GENERIC, one n x frame of workspace.
+    Returns the workspace bytes; plans without a fast path (deferred ones, double-fisheye sources) are generic by design."""
+    ws = plan.supersample_workspace_bytes(n, src_ptr=dev.data_ptr())
+    if plan.double_src or not plan.info()["fast_path"]:
+        return ws
+    if (3 * plan.src.height * plan.src.width) % 16:
+        assert ws == 3 * plan.dst.height * plan.dst.width and _workspace(plan, n) == 0
+    else:
+        assert ws == 0 and _workspace(plan, n) == 0, "a prepared single-source plan with 16-byte aligned frames must take SS_FUSED"
+    return ws
+
+
 def _check_oracle(got, want):
     if H.live_numpy_is_the_goldens_numpy():
         assert np.array_equal(got, want), f"{int((got != want).any(axis=-1).sum())} pixels differ from the oracle"
@@ -73,6 +88,7 @@ def test_small_cases_match_oracle(case, n):
         # the prepared n x plan on the device: the fused kernel where it takes the plan, and the forced generic path
         plan = _ss_plan(case, n)
         dev = torch.from_numpy(frame).cuda()
+        _assert_route(plan, n, dev)
         fused = plan.remap(dev, supersample=n).cpu().numpy()
         generic = plan.remap(dev, supersample=n, generic=True).cpu().numpy()
         assert np.array_equal(fused, got) and np.array_equal(generic, got)
@@ -99,6 +115,7 @@ def test_random_geometries_match_oracle(case):
     want = ss_ref.reference(case, n, frame)
     plan = _ss_plan(case, n)
     dev = torch.from_numpy(frame).cuda()
+    _assert_route(plan, n, dev)
     got = plan.remap(dev, supersample=n).cpu().numpy()
     assert np.array_equal(got, plan.remap(dev, supersample=n, generic=True).cpu().numpy())
     _check_oracle(got, want)
