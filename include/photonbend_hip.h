@@ -347,6 +347,26 @@ int pb_remap_catmull_rom_u8(const pb_plan* plan, const uint8_t* src_dev, uint8_t
 int pb_remap_track_u8(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, int interpolation, const uint8_t* src_dev, uint8_t* dst_dev,
                       int n_frames, size_t src_frame_stride, size_t dst_frame_stride, void* stream);
 
+/* ROTATION TRACKS FOR 4:2:0 SEMI-PLANAR VIDEO FRAMES (ABI 5, additive): NV12 / P010 / P016 frames, every frame with rotations
+ * of its own, both planes of all frames in as many launches as pb_remap_track_u8 makes.  Frame f receives exactly pb_remap_nv12's
+ * definition above with idx the index map of the chain "this plan's own n_rot rotations followed by the n_rot_per_frame matrices of table
+ * entry f", applied one after another as for pb_remap_track_u8 (nothing folded): luma like a grey image, the pair of an output 2 x 2 block
+ * from the source position of the block's top-left pixel, and only that anchor decides between pair and fill.  Equivalently: what
+ * pb_remap_nv12 writes for frame f alone from a prepared plan of that whole chain, wherever pb_remap_nv12_supported.
+ *   rot3x3_dev, n_rot_per_frame   pb_remap_track_u8's table: device memory, 8-byte aligned, read when the stream runs the launch.
+ *   layouts, bytes_per_sample, fill_yuv   pb_remap_nv12's.  Padding bytes are neither read nor written.
+ * The plan's tables are never read: a deferred plan, a prepared one and any mode are served alike.
+ *   PB_ERR_INVALID       before any launch, in this order: pb_remap_nv12's checks (null plan or frames, a negative count, bytes_per_sample,
+ *                        odd dimensions, the layouts, pointer alignment), then pb_remap_track_u8's (a null or misaligned table,
+ *                        n_rot_per_frame < 1, n_rot + n_rot_per_frame > PB_MAX_ROTATIONS).  n_frames == 0: PB_OK, no launch, no device.
+ *   PB_ERR_UNSUPPORTED   nothing is written: a double-fisheye source (its blend is sample-typed: convert to RGB8 and use
+ *                        pb_remap_track_u8); frames whose byte span reaches 2^31 or sources of 32768 px a side or more (a plan per frame,
+ *                        pb_index_map_i32 and a gather of the two planes).
+ * Asynchronous on `stream`; never allocates, never synchronises, never copies the table (graph-capture safe). */
+int pb_remap_track_nv12(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                        const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3],
+                        void* stream);
+
 /* SUPERSAMPLED REMAPPING (ABI 5, additive).  Output pixel (i, j) is, per channel, the round-half-to-even mean of the n x n block
  * S[n i : n i + n, n j : n j + n] of S = the remap of the n x destination: the same kind and lens with image (n H, n W) and, for a camera,
  * magnitude n x (a double fisheye's magnitude = height / 2 scales by itself); n in {2, 4}, a power of two, so its f_distance is exactly

@@ -119,6 +119,7 @@ SIGNATURES = {
     "pb_remap_bilinear_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_catmull_rom_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_track_u8": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
+    "pb_remap_track_nv12": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP]),
     "pb_remap_ss_workspace": (C.c_int, [_VP, C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_size_t)]),
     "pb_remap_ss_u8": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP, C.c_size_t, C.c_uint, _VP]),
     "pb_box_reduce": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
@@ -747,13 +748,26 @@ class Plan:
             return o
         with _on(s):
             st = current_stream() if stream is None else stream
-            uploaded = isinstance(tab, np.ndarray)
-            if uploaded:  # (synchronous: the table is on the device before the launch is queued)
-                tab = torch.from_numpy(tab).to(s.device) if tens else DeviceArray(tab.shape, np.float64).copy_from_host(tab)
+            tab, release = self._track_table(tab, s, st)
             self.launch_track(tab.data_ptr(), k, s.data_ptr(), o.data_ptr(), n, st, interpolation)
-            if uploaded and tens and int(st or 0) != current_stream():
-                check(load().pb_stream_sync(st))  # (the table goes back to torch's allocator, which orders its reuse on the current stream only)
+            release()
         return o
+
+    @staticmethod
+    def _track_table(tab, like, st):
+        """A rotation table on `like`'s device -> (table, release): an ndarray is uploaded (synchronously: it is on the device before the
+        launch is queued) and ``release()``, called after the launch on stream `st` is queued, makes its memory safe to reuse; a device
+        array is used in place."""
+        if not isinstance(tab, np.ndarray):
+            return tab, lambda: None
+        tens = is_tensor(like)
+        dev = torch.from_numpy(tab).to(like.device) if tens else DeviceArray(tab.shape, np.float64).copy_from_host(tab)
+
+        def release():
+            if tens and int(st or 0) != current_stream():
+                check(load().pb_stream_sync(st))  # (the table goes back to torch's allocator, which orders its reuse on the current stream only)
+
+        return dev, release
 
     def px_supported(self, bytes_per_px: int) -> bool:
         """Whether ``remap_px`` / ``launch(bytes_per_px=...)`` takes this plan with this pixel size (pb_remap_px_supported): a prepared plan
@@ -820,18 +834,24 @@ class Plan:
         src's kind and dtype.  ``fill``: (Y, U, V) for black pixels (None: 16, 128, 128 scaled to the sample size).  Layouts: a
         (pitch, uv_offset, frame_stride) tuple, dict or pb_nv12_layout, in bytes, 0 = default.  A plan ``nv12_supported`` refuses is a
         PbError (no fallback)."""
+        s, o, n, S, sl, dl = self._nv12_out(*self._nv12_source(src, src_layout), out, dst_layout)
+        with _on(s):
+            self.launch_nv12(s.data_ptr(), o.data_ptr(), n, stream, S, fill, sl, dl)
+        return o
+
+    def _nv12_source(self, src, src_layout):
+        """The source checks of ``remap_nv12`` and ``remap_track_nv12`` -> (src, its shape, dtype, layout, frame count).  Needs no GPU."""
         h, w, Hd, Wd = self.src.height, self.src.width, self.dst.height, self.dst.width
         if not is_device_array(src):
             raise PbError(f"source frames must be device arrays (CUDA tensors or DeviceArrays), got {type(src).__name__}")
         if (h | w | Hd | Wd) & 1:
             raise PbError("4:2:0 frames need even source and destination dimensions")
-        tens = is_tensor(src)
         shp = tuple(int(v) for v in src.shape)
-        dt = torch_dtype_np(src.dtype) if tens else np.dtype(src.dtype)
+        dt = torch_dtype_np(src.dtype) if is_tensor(src) else np.dtype(src.dtype)
         if dt not in (np.dtype(np.uint8), np.dtype(np.uint16)):
             raise PbError(f"NV12 frames are uint8 and P010 / P016 frames uint16, got {dt}")
         S = dt.itemsize
-        sl, dl = nv12_layout(src_layout), nv12_layout(dst_layout)
+        sl = nv12_layout(src_layout)
         if sl is None:
             if len(shp) not in (2, 3) or shp[-2:] != (3 * h // 2, w):
                 raise PbError(f"packed source frames must be ({3 * h // 2}, {w}) or (N, {3 * h // 2}, {w}), got {shp}")
@@ -843,6 +863,13 @@ class Plan:
             n = 0 if shp[0] * S < span else (shp[0] * S - span) // stride + 1
             if n < 1:
                 raise PbError(f"the source buffer holds {shp[0] * S} bytes, a frame at this layout spans {span}")
+        return src, shp, dt, sl, n
+
+    def _nv12_out(self, src, shp, dt, sl, n, out, dst_layout):
+        """... and their ``out`` checks (allocating it when None) -> (source, out, frame count, sample size, the two layouts)."""
+        Hd, Wd, S = self.dst.height, self.dst.width, dt.itemsize
+        tens = is_tensor(src)
+        dl = nv12_layout(dst_layout)
         require_gpu()
         s = src.contiguous() if tens else src
         packed_out = ((n,) if len(shp) == 3 else ()) + (3 * Hd // 2, Wd)
@@ -866,8 +893,34 @@ class Plan:
                     raise PbError(f"out holds {have} bytes, {n} frames at this layout span {(n - 1) * stride + span}")
             if tens and (not o.is_cuda or o.device != s.device):
                 raise PbError(f"out must live on the source's device ({s.device}), got {o.device}")
+        return s, o, n, S, sl, dl
+
+    def launch_track_nv12(self, table_ptr: int, n_rot_per_frame: int, src_ptr: int, dst_ptr: int, n_frames: int = 1, stream: int | None = None,
+                          bytes_per_sample: int = 1, fill=None, src_layout=None, dst_layout=None) -> None:
+        """The raw rotation-track call for video frames (pb_remap_track_nv12): ``launch_track``'s table, ``launch_nv12``'s frames, layouts
+        and fill.  The table must stay alive and unchanged until the stream has run the launch."""
+        f = None if fill is None else (C.c_uint16 * 3)(*[int(v) for v in fill])
+        sl, dl = nv12_layout(src_layout), nv12_layout(dst_layout)
+        self._gated(load().pb_remap_track_nv12, self._h, table_ptr, int(n_rot_per_frame), src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl),
+                    None if dl is None else C.addressof(dl), int(bytes_per_sample), None if f is None else C.addressof(f), current_stream() if stream is None else stream)
+
+    def remap_track_nv12(self, src, rotations, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None):
+        """NV12 (uint8) or P010 / P016 (uint16) video frames with a rotation per frame in ONE launch (pb_remap_track_nv12):
+        frame f is ``remap_nv12``'s definition with the index map of this plan's rotations followed by ``rotations[f]``.  ``src``, ``out``,
+        ``fill`` and the layouts follow ``remap_nv12``'s rules, ``rotations`` follows ``rotation_table``'s as for ``remap_track``; the frame
+        count must equal the table's (ValueError).  Any plan of a single source is served alike, a deferred one included.  Shapes, dtypes
+        and counts are checked before any device work."""
+        source = self._nv12_source(src, src_layout)
+        n = source[-1]
+        tab, n_tab, k = rotation_table(rotations, self.n_rot)
+        if n_tab != n:
+            raise ValueError(f"{n} frames need {n} rotations, the table holds {n_tab}")
+        s, o, n, S, sl, dl = self._nv12_out(*source, out, dst_layout)
         with _on(s):
-            self.launch_nv12(s.data_ptr(), o.data_ptr(), n, stream, S, fill, sl, dl)
+            st = current_stream() if stream is None else stream
+            tab, release = self._track_table(tab, s, st)
+            self.launch_track_nv12(tab.data_ptr(), k, s.data_ptr(), o.data_ptr(), n, st, S, fill, sl, dl)
+            release()
         return o
 
     def remap_each(self, srcs, outs=None, stream: int | None = None):

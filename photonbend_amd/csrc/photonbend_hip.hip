@@ -40,6 +40,7 @@
 #include "pb_kernels_px.hpp"
 #include "pb_kernels_nv12.hpp"
 #include "pb_kernels_track.hpp"
+#include "pb_kernels_track_nv12.hpp"
 
 #define PB_DOUBLE_FRAMES_PER_WAVE 1  // frames a double-source wave loops over (the rest of a batch is a grid dimension)
 
@@ -2050,30 +2051,42 @@ static bool pb_nv12_dims_even(const pb_plan* plan) {
     return !((P.src.height | P.src.width | P.dst.height | P.dst.width) & 1);
 }
 static bool pb_nv12_served(const pb_plan* plan, int S) { return pb_route(plan, PB_INTERP_NEAREST, 1, 0, false, S, true).kind == PbRoute::NV12; }
-int pb_remap_nv12(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout,
-                  int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
+// The arguments of the two 4:2:0 entry points (pb_remap_nv12, pb_remap_track_nv12), in this order: null plan / frames, the frame count,
+// the sample size, even dimensions, the two layouts, the pointers' alignment.  Resolves the layouts, and the fills in stored form.
+struct PbNv12Call {
+    PbNv12Frame fs, fd;
+    PbNv12 L;
+};
+static int pb_nv12_check(const pb_plan* plan, const void* src_dev, const void* dst_dev, int n_frames, const pb_nv12_layout* src_layout,
+                         const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3], PbNv12Call& c) {
     if (!plan || !src_dev || !dst_dev) return pb_fail(PB_ERR_INVALID, "null argument");
     if (n_frames < 0) return pb_fail(PB_ERR_INVALID, "negative frame count");
     if (bytes_per_sample != 1 && bytes_per_sample != 2) return pb_fail(PB_ERR_INVALID, "bytes_per_sample outside {1, 2}");
     if (!pb_nv12_dims_even(plan)) return pb_fail(PB_ERR_INVALID, "4:2:0 frames need even source and destination dimensions");
     const PbParams& P = plan->P;
     const unsigned long long S = (unsigned long long)bytes_per_sample;
-    PbNv12Frame fs, fd;
-    int rc = pb_nv12_resolve("source", src_layout, S, (unsigned long long)P.src.height, (unsigned long long)P.src.width, fs);
-    if (rc == PB_OK) rc = pb_nv12_resolve("destination", dst_layout, S, (unsigned long long)P.dst.height, (unsigned long long)P.dst.width, fd);
+    int rc = pb_nv12_resolve("source", src_layout, S, (unsigned long long)P.src.height, (unsigned long long)P.src.width, c.fs);
+    if (rc == PB_OK) rc = pb_nv12_resolve("destination", dst_layout, S, (unsigned long long)P.dst.height, (unsigned long long)P.dst.width, c.fd);
     if (rc != PB_OK) return rc;
     if (((uintptr_t)src_dev | (uintptr_t)dst_dev) % (2 * S))
         return pb_fail(PB_ERR_INVALID, "frame pointers must be multiples of " + std::to_string(2 * S) + " bytes (one chroma pair)");
-    if (n_frames == 0) return PB_OK;
+    const unsigned sh = 8u * ((unsigned)S - 1u), smask = S == 1 ? 0xFFu : 0xFFFFu;
+    const unsigned fy = fill_yuv ? fill_yuv[0] & smask : 16u << sh, fu = fill_yuv ? fill_yuv[1] & smask : 128u << sh, fv = fill_yuv ? fill_yuv[2] & smask : 128u << sh;
+    // (pitches and offsets are below 2^31: pb_nv12_resolve)
+    c.L = {(unsigned)c.fs.pitch, (unsigned)c.fs.uv, (unsigned)c.fd.pitch, (unsigned)c.fd.uv, fy, fu | (fv << (8u * (unsigned)S))};
+    return PB_OK;
+}
+int pb_remap_nv12(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout,
+                  int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
+    PbNv12Call c;
+    int rc = pb_nv12_check(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, bytes_per_sample, fill_yuv, c);
+    if (rc != PB_OK || n_frames == 0) return rc;
     rc = pb_check_device(plan);
     if (rc != PB_OK) return rc;
     const PbRoute r = pb_route(plan, PB_INTERP_NEAREST, 1, 0, false, bytes_per_sample, true);
-    if (r.kind == PbRoute::NV12 && (fs.span >= (1ull << 31) || fd.span >= (1ull << 31)))
+    if (r.kind == PbRoute::NV12 && (c.fs.span >= (1ull << 31) || c.fd.span >= (1ull << 31)))
         return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_nv12 takes frames whose planes span less than 2^31 bytes: use pb_index_map_i32 and gather the two planes");
-    const unsigned sh = 8u * ((unsigned)S - 1u), smask = S == 1 ? 0xFFu : 0xFFFFu;
-    const unsigned fy = fill_yuv ? fill_yuv[0] & smask : 16u << sh, fu = fill_yuv ? fill_yuv[1] & smask : 128u << sh, fv = fill_yuv ? fill_yuv[2] & smask : 128u << sh;
-    const PbNv12 L = {(unsigned)fs.pitch, (unsigned)fs.uv, (unsigned)fd.pitch, (unsigned)fd.uv, fy, fu | (fv << (8u * (unsigned)S))};
-    return pb_launch(plan, r, static_cast<const uint8_t*>(src_dev), static_cast<uint8_t*>(dst_dev), n_frames, fs.stride, fd.stride, (hipStream_t)stream, &L);
+    return pb_launch(plan, r, static_cast<const uint8_t*>(src_dev), static_cast<uint8_t*>(dst_dev), n_frames, c.fs.stride, c.fd.stride, (hipStream_t)stream, &c.L);
 }
 int pb_remap_nv12_supported(const pb_plan* plan, int bytes_per_sample) {
     if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
@@ -2147,12 +2160,8 @@ int pb_remap_catmull_rom_u8(const pb_plan* plan, const uint8_t* src_dev, uint8_t
                      src_frame_stride, dst_frame_stride, (hipStream_t)stream);
 }
 
-// A rotation track (DESIGN 3.13): the float64 chain of the plan's parameter block with frame f's matrices behind the plan's own.  No route:
-// no table of the plan is certified for these chains, so every plan state takes the same kernels.
-int pb_remap_track_u8(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, int interpolation, const uint8_t* src_dev, uint8_t* dst_dev,
-                      int n_frames, size_t src_frame_stride, size_t dst_frame_stride, void* stream) {
-    const int rc = pb_check_frames(plan, src_dev, dst_dev, n_frames, 1, src_frame_stride, dst_frame_stride);
-    if (rc != PB_OK) return rc;
+// a rotation table's checks, shared by the rotation-track entry points: null, alignment, the count per frame, the sum with the plan's own
+static int pb_track_table_check(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame) {
     if (!rot3x3_dev) return pb_fail(PB_ERR_INVALID, "null rotation table");
     if ((uintptr_t)rot3x3_dev & 7u) return pb_fail(PB_ERR_INVALID, "the rotation table must be 8-byte aligned");
     if (n_rot_per_frame < 1) return pb_fail(PB_ERR_INVALID, "n_rot_per_frame must be at least 1");
@@ -2160,12 +2169,25 @@ int pb_remap_track_u8(const pb_plan* plan, const double* rot3x3_dev, int n_rot_p
     if (n_rot_per_frame > PB_MAX_ROTATIONS - P.n_rot)
         return pb_fail(PB_ERR_INVALID, "the plan's " + std::to_string(P.n_rot) + " rotations and " + std::to_string(n_rot_per_frame) + " per frame exceed PB_MAX_ROTATIONS (" +
                                            std::to_string(PB_MAX_ROTATIONS) + ")");
+    return PB_OK;
+}
+// the frames of one launch of a rotation-track kernel: chunks of `fpc` frames over the grid's y, which ends at 65535
+static int pb_track_fpc() { return std::max(1, pb_knob("PB_TRACK_FRAMES", PB_TRACK_FRAMES)); }  // (the knob: the diagnostic build's, for the measurement of DESIGN 3.13)
+
+// A rotation track (DESIGN 3.13): the float64 chain of the plan's parameter block with frame f's matrices behind the plan's own.  No route:
+// no table of the plan is certified for these chains, so every plan state takes the same kernels.
+int pb_remap_track_u8(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, int interpolation, const uint8_t* src_dev, uint8_t* dst_dev,
+                      int n_frames, size_t src_frame_stride, size_t dst_frame_stride, void* stream) {
+    const int rc = pb_check_frames(plan, src_dev, dst_dev, n_frames, 1, src_frame_stride, dst_frame_stride);
+    if (rc != PB_OK) return rc;
+    if (int rt = pb_track_table_check(plan, rot3x3_dev, n_rot_per_frame)) return rt;
+    const PbParams& P = plan->P;
     if (interpolation != PB_INTERP_NEAREST && interpolation != PB_INTERP_BILINEAR && interpolation != PB_INTERP_CATMULL_ROM)
         return pb_fail(PB_ERR_INVALID, "interpolation must be PB_INTERP_NEAREST, PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM");
     if (n_frames == 0) return PB_OK;
     hipStream_t st = (hipStream_t)stream;
     const unsigned long long npx = (unsigned long long)P.dst.height * P.dst.width;
-    const int fpc = std::max(1, pb_knob("PB_TRACK_FRAMES", PB_TRACK_FRAMES));  // (the knob: the diagnostic build's, for the measurement of DESIGN 3.13)
+    const int fpc = pb_track_fpc();
     const int per_launch = 65535 * fpc;  // frames are chunked over the grid's y, which ends at 65535
     for (int f0 = 0; f0 < n_frames; f0 += per_launch) {
         const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
@@ -2187,6 +2209,42 @@ int pb_remap_track_u8(const pb_plan* plan, const double* rot3x3_dev, int n_rot_p
                 });
             });
         }
+    }
+    PB_HIP(hipGetLastError());
+    return PB_OK;
+}
+
+// A rotation track of 4:2:0 semi-planar frames: pb_remap_nv12's argument checks, then pb_remap_track_u8's table checks; the
+// launches are pb_remap_track_u8's, one per 65535 chunks of frames.
+int pb_remap_track_nv12(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                        const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
+    PbNv12Call c;
+    int rc = pb_nv12_check(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, bytes_per_sample, fill_yuv, c);
+    if (rc == PB_OK) rc = pb_track_table_check(plan, rot3x3_dev, n_rot_per_frame);
+    if (rc != PB_OK || n_frames == 0) return rc;
+    rc = pb_check_device(plan);
+    if (rc != PB_OK) return rc;
+    const PbParams& P = plan->P;
+    if (P.src.kind == PB_KIND_DOUBLE)
+        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_track_nv12 takes single sources (a double fisheye's blend is sample-typed): convert to RGB8 and use pb_remap_track_u8");
+    if (c.fs.span >= (1ull << 31) || c.fd.span >= (1ull << 31) || P.src.height >= 32768 || P.src.width >= 32768)
+        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_track_nv12 takes frames whose planes span less than 2^31 bytes and sources below 32768 px a side: use a plan per "
+                                           "frame with pb_index_map_i32 and gather the two planes");
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned long long quads = (unsigned long long)P.dst.height * (((unsigned)P.dst.width + PB_PX - 1) / PB_PX);
+    const int fpc = pb_track_fpc();
+    const int per_launch = 65535 * fpc;
+    for (int f0 = 0; f0 < n_frames; f0 += per_launch) {
+        const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
+        const double* rot = rot3x3_dev + 9ull * (unsigned)n_rot_per_frame * (unsigned)f0;
+        const uint8_t* s = static_cast<const uint8_t*>(src_dev) + (unsigned long long)f0 * c.fs.stride;
+        uint8_t* d = static_cast<uint8_t*>(dst_dev) + (unsigned long long)f0 * c.fd.stride;
+        const dim3 grid(pb_blocks(quads), (unsigned)((nf + fpc - 1) / fpc));
+        pb_pick_exact_kind(P, [&](auto K) {
+            pb_pick<1, 2>(bytes_per_sample == 1, [&](auto S) {
+                hipLaunchKernelGGL((pb_track_nv12_kernel<S.value, K.value>), grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride, c.fd.stride, c.L);
+            });
+        });
     }
     PB_HIP(hipGetLastError());
     return PB_OK;

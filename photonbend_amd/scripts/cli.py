@@ -373,5 +373,132 @@ def cubemap_to_cubemap(input_image, input_mapping, output_mapping, face_size, ou
     run_chain(source, destiny, rotation, out, int(supersample), **_sampler(interpolation))
 
 
+# ---- raw video frames ---------------------------------------------------------------------------
+PIX_FMTS = {"nv12": np.uint8, "p010": np.uint16}  # ffmpeg's -pix_fmt names of the two 4:2:0 semi-planar layouts
+TRACK_FRAMES = 4  # PB_TRACK_FRAMES (csrc/pb_kernels_track.hpp): --chunk is a multiple of it
+
+
+def _fail(message: str):
+    """A usage error of remap-nv12: the message on stderr (stdout may be the frame pipe), exit status 1."""
+    click.echo(f"Error: {message}", err=True)
+    sys.exit(1)
+
+
+def _read_track(path: Path) -> np.ndarray:
+    """A rotation track file: one `pitch yaw roll` line in degrees per frame (blank lines and # comments skipped) -> radians (N, 3)."""
+    rows = []
+    for n, line in enumerate(Path(path).read_text().splitlines(), 1):
+        line = line.split("#", 1)[0].strip()
+        if not line:
+            continue
+        try:
+            vals = [float(v) for v in line.split()]
+        except ValueError:
+            vals = []
+        if len(vals) != 3:
+            _fail(f"{path}:{n}: a rotation track line holds three numbers: pitch yaw roll in degrees")
+        rows.append([to_radians(v) for v in vals])
+    return np.array(rows, np.float64).reshape(-1, 3)
+
+
+def _read_exact(stream, nbytes: int) -> bytes:
+    """Up to nbytes from a file or a pipe: short only at the end of the input."""
+    parts, got = [], 0
+    while got < nbytes:
+        b = stream.read(nbytes - got)
+        if not b:
+            break
+        parts.append(b)
+        got += len(b)
+    return b"".join(parts)
+
+
+@main.command("remap-nv12")
+@click.argument("input_frames", metavar="INPUT", type=click.Path(path_type=Path, allow_dash=True))
+@click.argument("output_frames", metavar="OUTPUT", type=click.Path(path_type=Path, allow_dash=True))
+@click.option("--width", required=True, type=click.INT, help="The width of an input frame in pixels (even).")
+@click.option("--height", required=True, type=click.INT, help="The height of an input frame in pixels (even).")
+@click.option("--pix-fmt", type=click.Choice(list(PIX_FMTS)), default="nv12", show_default=True, help="The frames' layout, as ffmpeg names it.")
+@click.option("--type", "otype", type=click.Choice([t for t in TYPES if t != "double"]), default=None,
+              help="Make a photo: the type of the output image (with --lens and --fov). " + TYPE_HELP)
+@click.option("--lens", type=_lens_choice, default=None, help="With --type: the lens type of the output photo.")
+@_lens_parameters("--lens", "lens")
+@click.option("--fov", type=click.FLOAT, default=None, help="With --type: the lens field of view of the output photo in degrees.")
+@click.option("-s", "--size", type=click.INT, default=None, help="The vertical size of an output frame (even). [default: the input's]")
+@click.option("-r", "--rotation", type=click.FLOAT, nargs=3, multiple=True, default=[], help=ROTATION_HELP)
+@click.option("--rotations", "track", type=click.Path(exists=True, dir_okay=False, path_type=Path), default=None,
+              help="A rotation track: a text file of one `pitch yaw roll` line in degrees per frame, applied after every -r.")
+@click.option("--chunk", type=click.INT, default=8, show_default=True, help=f"Frames per launch, a multiple of {TRACK_FRAMES}.")
+def remap_nv12(input_frames, output_frames, width, height, pix_fmt, otype, lens, fov, size, rotation, track, chunk, lens_coefficients, lens_max_theta):
+    """Remap raw NV12 / P010 video frames of an equirectangular panorama, e.g. between two `ffmpeg -f rawvideo -pix_fmt nv12` pipes.
+
+    \b
+    INPUT is a file of packed frames, HEIGHT x WIDTH each; - is stdin.
+    OUTPUT receives the packed output frames; - is stdout.
+    By default the output is a panorama of the same size (--size H: H x 2H); with --type, --lens and --fov it is the photo make-photo would make.
+    """
+    dt = np.dtype(PIX_FMTS[pix_fmt])
+    if width < 2 or height < 2 or (width | height) & 1:
+        _fail(f"4:2:0 frames have even dimensions, got --width {width} --height {height}")
+    if size is not None and (size < 2 or size & 1):
+        _fail(f"4:2:0 frames have even dimensions, got --size {size}")
+    if chunk < TRACK_FRAMES or chunk % TRACK_FRAMES:
+        _fail(f"--chunk is a multiple of {TRACK_FRAMES}, got {chunk}")
+    if otype is None:
+        if lens is not None or fov is not None or lens_coefficients or lens_max_theta is not None:
+            raise click.UsageError("--lens / --fov and the lens parameters belong to a photo: give --type too")
+        h_out = height if size is None else size
+        destiny = PanoramaImage(np.zeros((h_out, width if size is None else 2 * h_out, 3), np.uint8))
+    else:
+        if lens is None or fov is None:
+            raise click.UsageError("a photo needs --type, --lens and --fov")
+        shape = camera_shape(otype, np.zeros((height, width, 3), np.uint8), size)
+        destiny = camera_object(otype, np.zeros(shape, np.uint8), radians_fov(fov, otype), lens_object(lens, lens_coefficients, lens_max_theta), magnitude_for(otype, shape))
+    cmap = destiny.get_coordinate_map()
+    for rot in rotation:
+        cmap = Rotation(*map(to_radians, rot)).rotate_coordinate_map(cmap)
+    dstp, srcp = cmap.dst_proj, PanoramaImage(np.zeros((height, width, 3), np.uint8))._proj("src")
+    if dstp.width & 1:
+        _fail(f"4:2:0 frames have even dimensions: the output would be {dstp.height} x {dstp.width}")
+    mats = None if track is None else core.rotation_track(_read_track(track))
+    frame_in, frame_out = 3 * height * width // 2 * dt.itemsize, 3 * dstp.height * dstp.width // 2 * dt.itemsize
+    piped = str(input_frames) == "-"
+    if not piped:  # a file's length is known: refuse before anything is written
+        if not input_frames.is_file():
+            _fail(f"{input_frames}: no such file")
+        total = input_frames.stat().st_size
+        if total % frame_in:
+            _fail(f"{input_frames}: {total} bytes are {total // frame_in} frames of {frame_in} bytes and a truncated one of {total % frame_in}")
+        if mats is not None and total // frame_in > len(mats):
+            _fail(f"{input_frames} holds {total // frame_in} frames, the rotation track {len(mats)} lines")
+    # without a track: a prepared plan and the tile kernel; with one: a deferred plan (its tables are never read) and the track kernel
+    plan = nat.Plan(dstp, list(cmap.rotations), srcp, bilinear=False) if mats is None else nat.Plan(dstp, list(cmap.rotations), srcp, defer=True)
+    fin = sys.stdin.buffer if piped else open(input_frames, "rb")
+    fout = sys.stdout.buffer if str(output_frames) == "-" else open(output_frames, "wb")
+    done = 0
+    try:
+        while True:
+            data = _read_exact(fin, chunk * frame_in)
+            n, rest = divmod(len(data), frame_in)
+            if mats is not None and done + n + (1 if rest else 0) > len(mats):
+                _fail(f"the input holds more than {len(mats)} frames, the rotation track {len(mats)} lines")
+            if n:  # upload, ONE launch, download
+                host = np.frombuffer(data, dt, n * frame_in // dt.itemsize).reshape(n, 3 * height // 2, width)
+                s = nat.to_device(host)
+                o = plan.remap_nv12(s) if mats is None else plan.remap_track_nv12(s, mats[done : done + n])
+                fout.write(nat.to_host(o).tobytes())
+                done += n
+            if rest:
+                _fail(f"the input ends with a truncated frame: {rest} of {frame_in} bytes after {done} whole frames")
+            if len(data) < chunk * frame_in:
+                break
+        fout.flush()
+    finally:
+        if fin is not sys.stdin.buffer:
+            fin.close()
+        if fout is not sys.stdout.buffer:
+            fout.close()
+
+
 if __name__ == "__main__":
     main()
