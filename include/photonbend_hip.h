@@ -304,6 +304,52 @@ int pb_remap_nv12(const pb_plan* plan, const void* src_dev, void* dst_dev, int n
                   const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3], void* stream);
 int pb_remap_nv12_supported(const pb_plan* plan, int bytes_per_sample);
 
+/* PLANAR video frames - yuv420p / yuv422p / yuv444p, their 10- and 16-bit forms, gbrp - in ONE launch of the tile kernel
+ * pb_planar_hot_kernel whatever n_frames (ABI 5, additive).  A frame is three planes of S-byte samples, S = bytes_per_sample:
+ * plane 0 of height x width samples at the frame's start, rows `pitch` bytes apart; planes 1 and 2 of (height >> cy) x (width >> cx)
+ * samples each, offset1 and offset2 bytes after the frame's start, rows `chroma_pitch` bytes apart.  (cx, cy) is (0, 0) for PB_PLANAR_444,
+ * (1, 0) for PB_PLANAR_422 and (1, 1) for PB_PLANAR_420.  With idx the plan's index map (pb_index_map_i32):
+ *   plane 0       P0_out[y][x] = P0_src[r][c], (r, c) = divmod(idx[y][x], w); fill[0] where idx[y][x] < 0 - pb_remap_px of the plane;
+ *   planes 1, 2   Pk_out[i][j] = Pk_src[r >> cy][c >> cx], (r, c) = divmod(idx[i << cy][j << cx], w) - the ANCHOR, the top-left pixel of
+ *                 the sample's block; fill[k] where the anchor's index is negative.  Only the anchor decides.
+ * A NEAREST sample of chroma at the anchor's position, as for pb_remap_nv12; no chroma interpolation.  At PB_PLANAR_420 planes 1 and 2,
+ * interleaved, are pb_remap_nv12's pairs.  At PB_PLANAR_444 every plane is a grey remap: gbrp is PB_PLANAR_444 with fill (0, 0, 0).  The
+ * bytes are exact: those of the definition with the reference's own index map.  Plane order (I420 against YV12, G-B-R) is a matter of
+ * offset1 and offset2 alone.
+ *   dimensions                   source and destination widths are multiples of 1 << cx, heights of 1 << cy: PB_PLANAR_444 takes any
+ *                                size, PB_PLANAR_422 odd heights.
+ *   layouts (bytes; NULL, or a 0 member: the packed default)   pitch = S * width; chroma_pitch = S * (width >> cx); offset1 = pitch *
+ *                                height; offset2 = offset1 + chroma_pitch * (height >> cy); frame_stride = the end of plane 2.  The planes
+ *                                may come in any order.  Padding bytes are neither read nor written.
+ *   fill                         the samples of black pixels, per plane; NULL: pb_remap_nv12's video black, (16, 128, 128) << 8 * (S - 1).
+ *   PB_ERR_INVALID               before any launch, nothing is written: null plan or frames, a negative count, bytes_per_sample outside
+ *                                {1, 2}, a subsampling outside the three, a dimension that breaks the rule above, a pitch smaller than a
+ *                                row, planes that overlap each other or plane 0, a plane that ends beyond frame_stride, a pointer, pitch,
+ *                                offset or stride that is not a multiple of S (a 1-byte plane may start anywhere).
+ *   PB_ERR_UNSUPPORTED           nothing is written - exactly the plans pb_remap_px and pb_remap_nv12 refuse: deferred plans,
+ *                                PB_MODE_FAITHFUL, double-fisheye sources, plans without device state, sources of 32768 px a side or more;
+ *                                and frames whose byte span (the end of the last plane) reaches 2^31 - a layout member of 2^31 or more
+ *                                among them, refused before any product is formed.
+ * Asynchronous on `stream`, never allocates or synchronises (graph-capture safe).
+ * pb_remap_planar_supported: 1 when pb_remap_planar takes `plan` with packed frames of this subsampling and sample size, 0 when it would
+ * return PB_ERR_UNSUPPORTED, negative on bad arguments.
+ * pb_remap_track_planar: ROTATION TRACKS for these frames - pb_remap_track_nv12's contract with the definition above: frame f receives it
+ * with idx the index map of the chain "this plan's own n_rot rotations followed by the n_rot_per_frame matrices of table entry f";
+ * equivalently what pb_remap_planar writes for frame f alone from a prepared plan of that whole chain, wherever pb_remap_planar_supported.
+ * The plan's tables are never read: a deferred plan, a prepared one and any mode are served alike.  PB_ERR_INVALID before any launch, in
+ * this order: pb_remap_planar's checks, then pb_remap_track_u8's table checks.  PB_ERR_UNSUPPORTED, nothing written: a double-fisheye
+ * source, frames whose byte span reaches 2^31, sources of 32768 px a side or more.  n_frames == 0: PB_OK, no launch, no device. */
+#define PB_PLANAR_444 0
+#define PB_PLANAR_422 1
+#define PB_PLANAR_420 2
+typedef struct pb_planar_layout { size_t pitch, chroma_pitch, offset1, offset2, frame_stride; } pb_planar_layout;  /* bytes; 0 = packed default */
+int pb_remap_planar(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_planar_layout* src_layout,
+                    const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample, const uint16_t fill[3], void* stream);
+int pb_remap_planar_supported(const pb_plan* plan, int subsampling, int bytes_per_sample);
+int pb_remap_track_planar(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                          const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample,
+                          const uint16_t fill[3], void* stream);
+
 /* OPT-IN extension with no reference counterpart (the reference samples nearest-by-truncation only):
  * bilinear interpolation at the reference's pre-truncation coordinate (pixel k covers [k, k+1), centre
  * k + 0.5; taps clamped to the image, panorama columns wrap; round half to even).  Pixels the nearest mode

@@ -185,8 +185,10 @@ def check_video_call(pixel_format: str, interpolation: str, supersample: int, tr
     """The sample type of a video pixel format, for a call it can be part of: nearest, not supersampled, no rotation track (pb_remap_nv12).
     ValueError otherwise.  THE place that says so: ``_video_format`` and ``batch.remap_frames`` (before its first frame) ask here."""
     dt = VIDEO_FORMATS.get(pixel_format)
+    if dt is None and pixel_format in nat.PLANAR_FORMATS:
+        dt = nat.PLANAR_FORMATS[pixel_format][0]
     if dt is None:
-        raise ValueError(f"pixel_format must be None or one of {sorted(VIDEO_FORMATS)}, got {pixel_format!r}")
+        raise ValueError(f"pixel_format must be None or one of {sorted(VIDEO_FORMATS) + sorted(nat.PLANAR_FORMATS)}, got {pixel_format!r}")
     if interpolation != "nearest" or supersample != 1 or track is not None:
         raise ValueError(f"{pixel_format} frames take nearest sampling without supersampling or a rotation track")
     return dt
@@ -197,11 +199,30 @@ def _video_format(plan, a: np.ndarray, pixel_format: str, interpolation: str, su
     indistinguishable from a grey image.  ValueError otherwise."""
     dt = check_video_call(pixel_format, interpolation, supersample, track)
     h, w, H, W = plan.src.height, plan.src.width, plan.dst.height, plan.dst.width
+    if pixel_format in nat.PLANAR_FORMATS:
+        # a planar frame (nat.PLANAR_FORMATS): a flat array of the three planes' samples - at 4:4:4 also (3, h, w)
+        sub = nat.PLANAR_FORMATS[pixel_format][1]
+        if not nat.planar_dims_ok(sub, (h, w), (H, W)):
+            raise ValueError(f"{nat.planar_dims_rule(sub, pixel_format)}, the plan maps {h} x {w} to {H} x {W}")
+        flat = (nat.planar_frame_samples(h, w, sub),)
+        cube = sub == nat.PLANAR_444 and tuple(a.shape) == (3, h, w)
+        if a.dtype != dt or not (cube or tuple(a.shape) == flat):
+            raise ValueError(f"{pixel_format} frames must be {dt} {flat}" + (f" or {(3, h, w)}" if sub == nat.PLANAR_444 else "") + f", got {a.dtype} {tuple(a.shape)}")
+        return ((3, H, W) if cube else (nat.planar_frame_samples(H, W, sub),)), dt, dt.itemsize
     if (h | w | H | W) & 1:
         raise ValueError(f"{pixel_format} frames need even dimensions, the plan maps {h} x {w} to {H} x {W}")
     if a.dtype != dt or tuple(a.shape) != (3 * h // 2, w):
         raise ValueError(f"{pixel_format} frames must be {dt} {(3 * h // 2, w)}, got {a.dtype} {tuple(a.shape)}")
     return (3 * H // 2, W), dt, dt.itemsize
+
+
+def _launch_video(plan, pixel_format: str, src_ptr: int, dst_ptr: int, stream: int, bps: int) -> None:
+    """One packed video frame: pb_remap_nv12 for the semi-planar formats, pb_remap_planar with the format's black for the planar ones."""
+    if pixel_format in VIDEO_FORMATS:
+        plan.launch_nv12(src_ptr, dst_ptr, 1, stream, bps)
+    else:
+        _, sub, fill = nat.PLANAR_FORMATS[pixel_format]
+        plan.launch_planar(src_ptr, dst_ptr, sub, 1, stream, bps, fill)
 
 
 def remap_ndarray(plan: nat.Plan, image: np.ndarray, interpolation: str = "nearest", device: int | None = None, supersample: int = 1,
@@ -211,7 +232,10 @@ def remap_ndarray(plan: nat.Plan, image: np.ndarray, interpolation: str = "neare
     "bilinear" or "catmull-rom" (not supersampled).  Nearest without supersampling also takes (h, w, *tail) frames of any dtype whose
     pixel is 1, 2, 4, 6 or 8 bytes - grey, RGBA, 16-bit samples - and returns (H, W, *tail) of that dtype (pb_remap_px: a plan
     ``Plan.px_supported`` refuses is a PbError).  ``pixel_format`` "nv12" (uint8) or "p010" (uint16): the frame is a 4:2:0 semi-planar
-    video frame (3h/2, w) and the result (3H/2, W) (pb_remap_nv12, DESIGN 3.15: a plan ``Plan.nv12_supported`` refuses is a PbError)."""
+    video frame (3h/2, w) and the result (3H/2, W) (pb_remap_nv12, DESIGN 3.15: a plan ``Plan.nv12_supported`` refuses is a PbError).
+    ``pixel_format`` one of ``nat.PLANAR_FORMATS`` - ffmpeg's "yuv420p", "yuv422p", "yuv444p", their "10le" / "16le" forms, "gbrp",
+    "gbrp16le": the frame is a planar frame, a flat array of its three planes' samples (``utils.planar_planes``; 4:4:4 also (3, h, w)),
+    and the result one of the destination's, black pixels the format's black (pb_remap_planar)."""
     nat.check_interpolation(interpolation, supersample)
     if pixel_format is None:
         oh, ow = _out_shape(plan, supersample)
@@ -219,7 +243,7 @@ def remap_ndarray(plan: nat.Plan, image: np.ndarray, interpolation: str = "neare
         oshape, out_bytes = (oh, ow) + tail, bpp * oh * ow
     else:
         oshape, dt, bpp = _video_format(plan, image, pixel_format, interpolation, supersample)  # (bpp: bytes per sample)
-        out_bytes = bpp * oshape[0] * oshape[1]
+        out_bytes = bpp * int(np.prod(oshape))
     nat.require_gpu()
     pipe = pipe_for(device)
     with nat.on_device(pipe.device):
@@ -230,7 +254,7 @@ def remap_ndarray(plan: nat.Plan, image: np.ndarray, interpolation: str = "neare
         if pixel_format is None:
             plan.launch(d_in.data_ptr(), d_out.data_ptr(), 1, pipe.stream.handle, interpolation, **_ss_kw(supersample, ws), **_px_kw(bpp))
         else:
-            plan.launch_nv12(d_in.data_ptr(), d_out.data_ptr(), 1, pipe.stream.handle, bpp)
+            _launch_video(plan, pixel_format, d_in.data_ptr(), d_out.data_ptr(), pipe.stream.handle, bpp)
         out = pipe.download(d_out, oshape, dt)
         pipe.stream.sync()
         pipe.give_workspace(ws)
@@ -248,7 +272,8 @@ def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, i
     rotation per frame (uint8 RGB, not supersampled): the table is uploaded once before the first frame (a device array is used in place)
     and frame f is a one-frame ``Plan.launch_track`` that points at entry f; a frame beyond the table is a ValueError at that frame.
     ``pixel_format`` "nv12" / "p010": the frames are 4:2:0 semi-planar video frames (3h/2, w) of uint8 / uint16 and the results (3H/2, W)
-    (``remap_ndarray``) - the same pipeline, page-locking and ring; None: everything above."""
+    (``remap_ndarray``) - the same pipeline, page-locking and ring; a planar format of ``nat.PLANAR_FORMATS``: flat planar frames
+    (``remap_ndarray``); None: everything above."""
     nat.check_interpolation(interpolation, supersample)
     if pixel_format is not None:
         check_video_call(pixel_format, interpolation, supersample, track)
@@ -303,7 +328,7 @@ def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, i
             s_run.wait(uploaded[slot])
             out = results[slot] = PINNED.ndarray(dh, fmt[1])
             if pixel_format is not None:
-                plan.launch_nv12(d_in[slot].data_ptr(), out.ctypes.data, 1, s_run.handle, bpp)
+                _launch_video(plan, pixel_format, d_in[slot].data_ptr(), out.ctypes.data, s_run.handle, bpp)
             elif tab is None:
                 plan.launch(d_in[slot].data_ptr(), out.ctypes.data, 1, s_run.handle, interpolation, **_ss_kw(supersample, ws), **_px_kw(bpp))
             else:

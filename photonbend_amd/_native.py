@@ -116,10 +116,13 @@ SIGNATURES = {
     "pb_remap_px_supported": (C.c_int, [_VP, C.c_int]),
     "pb_remap_nv12": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP]),
     "pb_remap_nv12_supported": (C.c_int, [_VP, C.c_int]),
+    "pb_remap_planar": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, _VP]),
+    "pb_remap_planar_supported": (C.c_int, [_VP, C.c_int, C.c_int]),
     "pb_remap_bilinear_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_catmull_rom_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_track_u8": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_track_nv12": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP]),
+    "pb_remap_track_planar": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, _VP]),
     "pb_remap_ss_workspace": (C.c_int, [_VP, C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_size_t)]),
     "pb_remap_ss_u8": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP, C.c_size_t, C.c_uint, _VP]),
     "pb_box_reduce": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
@@ -277,6 +280,102 @@ def nv12_frame_bytes(layout, height: int, width: int, bytes_per_sample: int) -> 
     uv = l.uv_offset or pitch * height
     span = uv + pitch * (height // 2)
     return span, (l.frame_stride or span)
+
+
+PLANAR_444, PLANAR_422, PLANAR_420 = 0, 1, 2  # include/photonbend_hip.h: PB_PLANAR_*
+PLANAR_SHIFTS = {PLANAR_444: (0, 0), PLANAR_422: (1, 0), PLANAR_420: (1, 1)}  # (cx, cy): planes 1 and 2 are (h >> cy, w >> cx)
+_PLANAR_NAMES = {"444": PLANAR_444, "4:4:4": PLANAR_444, "422": PLANAR_422, "4:2:2": PLANAR_422, "420": PLANAR_420, "4:2:0": PLANAR_420}
+_U8, _U16 = np.dtype(np.uint8), np.dtype(np.uint16)
+# THE table of planar pixel formats, by ffmpeg's -pix_fmt names: name -> (sample type, subsampling, the samples of black).  10-bit formats
+# carry their value in the low bits of a 16-bit sample; gbrp is planar RGB in the order G, B, R, black (0, 0, 0)
+PLANAR_FORMATS = {
+    "yuv420p": (_U8, PLANAR_420, (16, 128, 128)),
+    "yuv422p": (_U8, PLANAR_422, (16, 128, 128)),
+    "yuv444p": (_U8, PLANAR_444, (16, 128, 128)),
+    "yuv420p10le": (_U16, PLANAR_420, (64, 512, 512)),
+    "yuv422p10le": (_U16, PLANAR_422, (64, 512, 512)),
+    "yuv444p10le": (_U16, PLANAR_444, (64, 512, 512)),
+    "yuv420p16le": (_U16, PLANAR_420, (16 << 8, 128 << 8, 128 << 8)),
+    "yuv444p16le": (_U16, PLANAR_444, (16 << 8, 128 << 8, 128 << 8)),
+    "gbrp": (_U8, PLANAR_444, (0, 0, 0)),
+    "gbrp16le": (_U16, PLANAR_444, (0, 0, 0)),
+}
+
+
+def planar_subsampling(subsampling) -> int:
+    """PLANAR_444 / PLANAR_422 / PLANAR_420, or "444" / "4:4:4" and so on -> the PB_PLANAR_* id.  ValueError otherwise."""
+    if isinstance(subsampling, str) and subsampling in _PLANAR_NAMES:
+        return _PLANAR_NAMES[subsampling]
+    if not isinstance(subsampling, (str, bool)) and subsampling in PLANAR_SHIFTS:
+        return int(subsampling)
+    raise ValueError(f"subsampling must be PLANAR_444, PLANAR_422 or PLANAR_420 (or '444', '422', '420'), got {subsampling!r}")
+
+
+def planar_dims_rule(subsampling: int, name: str | None = None) -> str:
+    """The dimension rule of a subsampling, as the error messages say it - with a pixel format's name where there is one."""
+    what = name or {PLANAR_444: "4:4:4", PLANAR_422: "4:2:2", PLANAR_420: "4:2:0"}[subsampling]
+    return {PLANAR_444: f"{what} frames take any dimensions", PLANAR_422: f"{what} frames have even widths",
+            PLANAR_420: f"{what} frames have even widths and heights"}[subsampling]
+
+
+def planar_dims_ok(subsampling: int, *shapes) -> bool:
+    """Whether every (height, width) obeys the subsampling's rule: widths multiples of 1 << cx, heights of 1 << cy."""
+    cx, cy = PLANAR_SHIFTS[subsampling]
+    return not any((int(h) & cy) | (int(w) & cx) for h, w in shapes)
+
+
+def planar_frame_samples(height: int, width: int, subsampling: int) -> int:
+    """Samples of one packed planar frame: plane 0 and two planes (h >> cy, w >> cx)."""
+    cx, cy = PLANAR_SHIFTS[subsampling]
+    return height * width + 2 * (height >> cy) * (width >> cx)
+
+
+class pb_planar_layout(C.Structure):
+    """include/photonbend_hip.h: the plane layout of planar frames, in bytes; a 0 member is the packed default."""
+    _fields_ = [("pitch", C.c_size_t), ("chroma_pitch", C.c_size_t), ("offset1", C.c_size_t), ("offset2", C.c_size_t), ("frame_stride", C.c_size_t)]
+
+
+_PLANAR_MEMBERS = ("pitch", "chroma_pitch", "offset1", "offset2", "frame_stride")
+
+
+def planar_layout(layout):
+    """None, a pb_planar_layout, a dict or a (pitch, chroma_pitch, offset1, offset2, frame_stride) tuple -> a pb_planar_layout or None."""
+    if layout is None or isinstance(layout, pb_planar_layout):
+        return layout
+    if isinstance(layout, dict):
+        extra = set(layout) - set(_PLANAR_MEMBERS)
+        if extra:
+            raise ValueError(f"unknown layout members {sorted(extra)}")
+        return pb_planar_layout(*[int(layout.get(m, 0)) for m in _PLANAR_MEMBERS])
+    pitch, chroma_pitch, offset1, offset2, frame_stride = layout
+    return pb_planar_layout(int(pitch), int(chroma_pitch), int(offset1), int(offset2), int(frame_stride))
+
+
+def planar_frame_bytes(layout, height: int, width: int, bytes_per_sample: int, subsampling: int) -> tuple:
+    """(pitch, chroma_pitch, offset1, offset2, bytes one frame spans, frame stride) of a layout (None: packed) - the library's defaults and
+    its layout checks (pb_planar_resolve), for buffer-size checks and plane views.  PbError for a pitch smaller than a row, planes that
+    overlap, a plane beyond frame_stride and members that are no multiple of the sample size.  Needs no GPU."""
+    l = layout or pb_planar_layout()
+    S = int(bytes_per_sample)
+    cx, cy = PLANAR_SHIFTS[subsampling]
+    cw, ch = width >> cx, height >> cy
+    pitch = l.pitch or S * width
+    cpitch = l.chroma_pitch or S * cw
+    if pitch < S * width or cpitch < S * cw:
+        raise PbError("pitch smaller than a row")
+    e0 = pitch * (height - 1) + S * width if height else 0
+    ce = cpitch * (ch - 1) + S * cw if ch else 0
+    o1 = l.offset1 or pitch * height
+    o2 = l.offset2 or o1 + cpitch * ch
+    if o1 < e0 or o2 < e0 or (ce and (o1 + ce > o2 if o1 < o2 else o2 + ce > o1)):
+        raise PbError("the planes of a frame overlap")
+    span = max(o1, o2) + ce
+    stride = l.frame_stride or max(span, o2 + cpitch * ch)
+    if stride < span:
+        raise PbError("frame_stride smaller than a frame: a plane ends beyond it")
+    if any(v % S for v in (pitch, cpitch, o1, o2, stride)):
+        raise PbError(f"pitch, chroma_pitch, offsets and frame_stride must be multiples of {S} bytes (one sample)")
+    return pitch, cpitch, o1, o2, span, stride
 
 
 def px_align(bytes_per_px: int) -> int:
@@ -920,6 +1019,131 @@ class Plan:
             st = current_stream() if stream is None else stream
             tab, release = self._track_table(tab, s, st)
             self.launch_track_nv12(tab.data_ptr(), k, s.data_ptr(), o.data_ptr(), n, st, S, fill, sl, dl)
+            release()
+        return o
+
+    def planar_supported(self, subsampling, bytes_per_sample: int = 1) -> bool:
+        """Whether ``remap_planar`` takes this plan with this subsampling and sample size (pb_remap_planar_supported): the plans
+        ``px_supported`` takes.  A size outside (1, 2) or a dimension that breaks the subsampling's rule is a PbError.  Needs no GPU."""
+        r = load().pb_remap_planar_supported(self._h, planar_subsampling(subsampling), int(bytes_per_sample))
+        if r < 0:
+            check(r)
+        return r == 1
+
+    def launch_planar(self, src_ptr: int, dst_ptr: int, subsampling, n_frames: int = 1, stream: int | None = None, bytes_per_sample: int = 1, fill=None,
+                      src_layout=None, dst_layout=None) -> None:
+        """The raw call (pb_remap_planar): n_frames planar frames at src_ptr / dst_ptr on `stream`, layouts in bytes (None: packed),
+        ``fill`` the samples of black pixels per plane (None: video black)."""
+        f = None if fill is None else (C.c_uint16 * 3)(*[int(v) for v in fill])
+        sl, dl = planar_layout(src_layout), planar_layout(dst_layout)
+        self._gated(load().pb_remap_planar, self._h, src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl), None if dl is None else C.addressof(dl),
+                    planar_subsampling(subsampling), int(bytes_per_sample), None if f is None else C.addressof(f), current_stream() if stream is None else stream)
+
+    def remap_planar(self, src, subsampling, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None):
+        """The nearest remap of PLANAR video frames - three planes of uint8 or uint16 samples at 4:4:4, 4:2:2 or 4:2:0 - in ONE launch
+        (pb_remap_planar): plane 0 moves like a grey image, and a sample of planes 1 and 2 is the source sample at the source
+        position of its block's top-left pixel.  src: a flat device array of one packed frame, or (N, frame_samples) - a 4:2:0 or 4:2:2
+        frame is no rectangle; 4:4:4 also takes (3, h, w) / (N, 3, h, w) - or, with ``src_layout``, any 1-D buffer that holds the frames
+        at that layout (then ``out`` is required with ``dst_layout``, or the result is packed).  -> the same shape for the destination.
+        ``subsampling``: PLANAR_444 / PLANAR_422 / PLANAR_420 or "444" / "422" / "420".  ``fill``: the samples of black per plane (None:
+        16, 128, 128 scaled to the sample size).  Layouts: a (pitch, chroma_pitch, offset1, offset2, frame_stride) tuple, dict or
+        pb_planar_layout, in bytes, 0 = default.  A plan ``planar_supported`` refuses is a PbError (no fallback)."""
+        sub = planar_subsampling(subsampling)
+        s, o, n, S, sl, dl = self._planar_out(*self._planar_source(src, sub, src_layout), out, dst_layout)
+        with _on(s):
+            self.launch_planar(s.data_ptr(), o.data_ptr(), sub, n, stream, S, fill, sl, dl)
+        return o
+
+    def _planar_source(self, src, sub, src_layout):
+        """The source checks of ``remap_planar`` and ``remap_track_planar`` -> (src, subsampling, its shape, dtype, layout, frame count).
+        Needs no GPU."""
+        h, w, Hd, Wd = self.src.height, self.src.width, self.dst.height, self.dst.width
+        if not is_device_array(src):
+            raise PbError(f"source frames must be device arrays (CUDA tensors or DeviceArrays), got {type(src).__name__}")
+        if not planar_dims_ok(sub, (h, w), (Hd, Wd)):
+            raise PbError(f"{planar_dims_rule(sub)}, source and destination: the plan maps {h} x {w} to {Hd} x {Wd}")
+        shp = tuple(int(v) for v in src.shape)
+        dt = torch_dtype_np(src.dtype) if is_tensor(src) else np.dtype(src.dtype)
+        if dt not in (_U8, _U16):
+            raise PbError(f"planar frames hold uint8 or uint16 samples, got {dt}")
+        S = dt.itemsize
+        sl = planar_layout(src_layout)
+        ns = planar_frame_samples(h, w, sub)
+        if sl is None:
+            ok = (len(shp) in (1, 2) and shp[-1] == ns) or (sub == PLANAR_444 and len(shp) in (3, 4) and shp[-3:] == (3, h, w))
+            if not ok:
+                raise PbError(f"packed source frames must be ({ns},) or (N, {ns})" + (f", or (3, {h}, {w}) / (N, 3, {h}, {w})" if sub == PLANAR_444 else "") + f", got {shp}")
+            n = shp[0] if len(shp) in (2, 4) else 1
+        else:
+            if len(shp) != 1:
+                raise PbError(f"frames at a layout come as a 1-D buffer, got {shp}")
+            span, stride = planar_frame_bytes(sl, h, w, S, sub)[4:]
+            n = 0 if shp[0] * S < span else (shp[0] * S - span) // stride + 1
+            if n < 1:
+                raise PbError(f"the source buffer holds {shp[0] * S} bytes, a frame at this layout spans {span}")
+        return src, sub, shp, dt, sl, n
+
+    def _planar_out(self, src, sub, shp, dt, sl, n, out, dst_layout):
+        """... and their ``out`` checks (allocating it when None) -> (source, out, frame count, sample size, the two layouts)."""
+        Hd, Wd, S = self.dst.height, self.dst.width, dt.itemsize
+        tens = is_tensor(src)
+        dl = planar_layout(dst_layout)
+        if dl is not None:
+            planar_frame_bytes(dl, Hd, Wd, S, sub)
+        require_gpu()
+        s = src.contiguous() if tens else src
+        nd = planar_frame_samples(Hd, Wd, sub)
+        batched = len(shp) in (2, 4)
+        cube = sl is None and len(shp) >= 3  # (4:4:4 as (3, h, w))
+        packed_out = ((n,) if batched else ()) + ((3, Hd, Wd) if cube else (nd,))
+        if out is None:
+            if dl is not None:
+                raise PbError("a destination layout needs the `out` buffer it describes")
+            o = empty(packed_out if sl is None else (n, nd), dt, like=s)
+        else:
+            o = out
+            odt = (torch_dtype_np(o.dtype) if is_tensor(o) else np.dtype(o.dtype)) if is_device_array(o) else None
+            if odt != dt or is_tensor(o) != tens or (tens and not o.is_contiguous()):
+                raise PbError(f"out must be a contiguous {dt} device array of the source's kind")
+            oshp = tuple(int(v) for v in o.shape)
+            if dl is None:
+                if oshp not in (packed_out, (n, nd)):
+                    raise PbError(f"out must be {packed_out}, got {oshp}")
+            else:
+                span, stride = planar_frame_bytes(dl, Hd, Wd, S, sub)[4:]
+                have = int(np.prod(oshp)) * S
+                if have < (n - 1) * stride + span:
+                    raise PbError(f"out holds {have} bytes, {n} frames at this layout span {(n - 1) * stride + span}")
+            if tens and (not o.is_cuda or o.device != s.device):
+                raise PbError(f"out must live on the source's device ({s.device}), got {o.device}")
+        return s, o, n, S, sl, dl
+
+    def launch_track_planar(self, table_ptr: int, n_rot_per_frame: int, src_ptr: int, dst_ptr: int, subsampling, n_frames: int = 1, stream: int | None = None,
+                            bytes_per_sample: int = 1, fill=None, src_layout=None, dst_layout=None) -> None:
+        """The raw rotation-track call for planar frames (pb_remap_track_planar): ``launch_track``'s table, ``launch_planar``'s frames,
+        layouts and fill.  The table must stay alive and unchanged until the stream has run the launch."""
+        f = None if fill is None else (C.c_uint16 * 3)(*[int(v) for v in fill])
+        sl, dl = planar_layout(src_layout), planar_layout(dst_layout)
+        self._gated(load().pb_remap_track_planar, self._h, table_ptr, int(n_rot_per_frame), src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl),
+                    None if dl is None else C.addressof(dl), planar_subsampling(subsampling), int(bytes_per_sample), None if f is None else C.addressof(f),
+                    current_stream() if stream is None else stream)
+
+    def remap_track_planar(self, src, rotations, subsampling, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None):
+        """Planar video frames with a rotation per frame in ONE launch (pb_remap_track_planar): frame f is ``remap_planar``'s
+        definition with the index map of this plan's rotations followed by ``rotations[f]``.  ``src``, ``subsampling``, ``out``, ``fill``
+        and the layouts follow ``remap_planar``'s rules, ``rotations`` follows ``rotation_table``'s as for ``remap_track``; the frame count
+        must equal the table's (ValueError).  Any plan of a single source is served alike, a deferred one included.  Shapes, dtypes and
+        counts are checked before any device work."""
+        source = self._planar_source(src, planar_subsampling(subsampling), src_layout)
+        n = source[-1]
+        tab, n_tab, k = rotation_table(rotations, self.n_rot)
+        if n_tab != n:
+            raise ValueError(f"{n} frames need {n} rotations, the table holds {n_tab}")
+        s, o, n, S, sl, dl = self._planar_out(*source, out, dst_layout)
+        with _on(s):
+            st = current_stream() if stream is None else stream
+            tab, release = self._track_table(tab, s, st)
+            self.launch_track_planar(tab.data_ptr(), k, s.data_ptr(), o.data_ptr(), source[1], n, st, S, fill, sl, dl)
             release()
         return o
 

@@ -37,7 +37,9 @@ def remap_frames(plan: nat.Plan, frames: Iterable[np.ndarray], depth: int = 3, i
     is uploaded once, before the first frame; a frame beyond its length is a ValueError at that frame; not supersampled.
     ``pixel_format``: "nv12" (uint8) or "p010" (uint16) - the frames are 4:2:0 semi-planar video frames (3h/2, w), a luma plane over a
     plane of interleaved (U, V) pairs, and the results (3H/2, W), each in one launch (``Plan.remap_nv12``): nearest, not
-    supersampled, no rotation track, even dimensions.  The keyword is needed - such an array looks like a grey image.  None: as above."""
+    supersampled, no rotation track, even dimensions.  The keyword is needed - such an array looks like a grey image.  A planar format
+    of ``nat.PLANAR_FORMATS`` ("yuv420p", "yuv422p", "yuv444p", "yuv420p10le", ..., "gbrp"): the frames are flat arrays of three planes'
+    samples and so are the results (``Plan.remap_planar``), under the same conditions.  None: as above."""
     n = nat.check_interpolation(interpolation, supersample)
     if pixel_format is not None:  # (here, before the first frame: the pipeline below is a generator)
         _hostpipe.check_video_call(pixel_format, interpolation, n, rotations)

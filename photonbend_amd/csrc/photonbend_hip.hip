@@ -41,6 +41,8 @@
 #include "pb_kernels_nv12.hpp"
 #include "pb_kernels_track.hpp"
 #include "pb_kernels_track_nv12.hpp"
+#include "pb_kernels_planar.hpp"
+#include "pb_kernels_track_planar.hpp"
 
 #define PB_DOUBLE_FRAMES_PER_WAVE 1  // frames a double-source wave loops over (the rest of a batch is a grid dimension)
 
@@ -627,6 +629,16 @@ static void pb_pick_px_size(int bpp, F&& f) {
         default: f(PbInt<8>()); break;
     }
 }
+// pb_planar_hot_kernel's SUB (PB_PLANAR_444 / _422 / _420; pb_planar_check has refused everything else)
+template <class F>
+static void pb_pick_subsampling(int sub, F&& f) {
+    static_assert(PB_PLANAR_444 == PB_SUB_444 && PB_PLANAR_422 == PB_SUB_422 && PB_PLANAR_420 == PB_SUB_420, "the kernel's SUB is the header's constant");
+    switch (sub) {
+        case PB_PLANAR_444: f(PbInt<PB_SUB_444>()); break;
+        case PB_PLANAR_422: f(PbInt<PB_SUB_422>()); break;
+        default: f(PbInt<PB_SUB_420>()); break;
+    }
+}
 // The SRC_KIND of the MODEL-evaluating kernels (hot, window, supersampled, interpolated tile kernels) of a single source.  A cube source
 // runs the camera's: what those kernels evaluate is a certified tile model, a frame-wide bounds test and the camera's truncation edge, and
 // pb_certify_kernel<PB_KIND_CUBE> compares that very evaluation with the cube's float64 chain for every pixel.
@@ -985,20 +997,25 @@ struct PbRoute {
         PX_NONE,             // ... on a plan that kernel does not serve: nothing is launched (PB_ERR_UNSUPPORTED)
         NV12,                // nearest, 4:2:0 semi-planar frames (pb_remap_nv12): pb_nv12_hot_kernel
         NV12_NONE,           // ... on a plan that kernel does not serve - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
+        PLANAR,              // nearest, planar 4:4:4 / 4:2:2 / 4:2:0 frames (pb_remap_planar): pb_planar_hot_kernel
+        PLANAR_NONE,         // ... on a plan that kernel does not serve - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
     } kind;
     bool windows;                    // BIL_DOUBLE / bilinear INTERP_TILES: LEAN tiles gather from LDS windows
     int filter = PB_INTERP_NEAREST;  // the INTERP_* routes: PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM
-    int bpp = 3;                     // PX: bytes per pixel; NV12: bytes per sample
+    int bpp = 3;                     // PX: bytes per pixel; NV12, PLANAR: bytes per sample
+    int sub = 0;                     // PLANAR: the subsampling (PB_PLANAR_*)
 };
 static bool pb_aligned16(const void* src, unsigned long long stride) { return ((((uintptr_t)src) | stride) & 15u) == 0; }
-static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned flags, bool aligned, int bpp = 3, bool nv12 = false) {
+// planar: the subsampling of a pb_remap_planar call (PB_PLANAR_*), -1 everywhere else
+static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned flags, bool aligned, int bpp = 3, bool nv12 = false, int planar = -1) {
     const PbParams& P = pl->P;
-    if (bpp != 3 || nv12) {
+    if (bpp != 3 || nv12 || planar >= 0) {
         // the tile kernel of the nearest plan's launch-order table, or nothing: no window, so no alignment beyond the pixel's own
         // (pb_check_frames); fast_ready says single source, prepared, device state; generic tiles pack row and column in 16 bits each
         const bool px = interpolation == PB_INTERP_NEAREST && n == 1 && pb_use_fast(pl) && pl->nearest.lt.entries && pl->nearest.P_dev &&
                         P.src.width < 32768 && P.src.height < 32768;
         if (nv12) return {px ? PbRoute::NV12 : PbRoute::NV12_NONE, false, PB_INTERP_NEAREST, bpp};  // (bpp: bytes per sample)
+        if (planar >= 0) return {px ? PbRoute::PLANAR : PbRoute::PLANAR_NONE, false, PB_INTERP_NEAREST, bpp, planar};
         return {px ? PbRoute::PX : PbRoute::PX_NONE, false, PB_INTERP_NEAREST, bpp};
     }
     if (n > 1) {
@@ -1059,9 +1076,9 @@ static void pb_launch_direct(const pb_plan* pl, const uint8_t* src, uint8_t* dst
 }
 
 // Launches a nearest or bilinear route (n = 1) for n_frames frames at strides ss / ds (pb_check_frames has filled them in).
-// nv12: the plane layouts and fills of the NV12 route (pb_remap_nv12), null everywhere else.
+// nv12 / planar: the plane layouts and fills of the NV12 route (pb_remap_nv12) / the PLANAR route (pb_remap_planar), null everywhere else.
 static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* dst, int n_frames, unsigned long long ss, unsigned long long ds,
-                     hipStream_t st, const PbNv12* nv12 = nullptr) {
+                     hipStream_t st, const PbNv12* nv12 = nullptr, const PbPlanar* planar = nullptr) {
     const PbParams& P = pl->P;
     const unsigned long long npx = (unsigned long long)P.dst.height * P.dst.width;
     switch (r.kind) {
@@ -1145,6 +1162,25 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
         case PbRoute::NV12_NONE:
             return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_nv12 takes prepared plans of a single source in a tile mode (not deferred, not PB_MODE_FAITHFUL, not "
                                                "double-fisheye, sources below 32768 px a side): use pb_index_map_i32 and gather the two planes");
+        case PbRoute::PLANAR: {
+            // launched like NV12: the three planes of a tile by the tile's wave
+            const unsigned gpf = pl->nearest.lt.groups;
+            pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
+                pb_pick_kind(P, [&](auto K) {
+                    pb_pick<1, 2>(r.bpp == 1, [&](auto S) {
+                        pb_pick_subsampling(r.sub, [&](auto SUB) {
+                            hipLaunchKernelGGL((pb_planar_hot_kernel<K.value, S.value, SUB.value>), dim3(gpf * (unsigned)nf), dim3(64 * PB_TILE_WAVES), 0, st,
+                                               (const PbParams*)pl->nearest.P_dev, pb_hot_of_host(P), pl->nearest.lt.entries, sf, df, gpf, ss, ds, pl->cert.idx_tab,
+                                               pl->cert.fix_px, pl->cert.fix_idx, *planar);
+                        });
+                    });
+                });
+            });
+            break;
+        }
+        case PbRoute::PLANAR_NONE:
+            return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_planar takes prepared plans of a single source in a tile mode (not deferred, not PB_MODE_FAITHFUL, not "
+                                               "double-fisheye, sources below 32768 px a side): use pb_index_map_i32 and gather the three planes");
         case PbRoute::BIL_DOUBLE: {
             // the per-eye tile models of the nearest mode's plan + the exact coordinate tables: one wave per tile
             const unsigned gpf = pb_bil_groups(pl);
@@ -2098,6 +2134,100 @@ int pb_remap_nv12_supported(const pb_plan* plan, int bytes_per_sample) {
     return pb_nv12_served(plan, bytes_per_sample) && 3 * S * P.src.height * P.src.width / 2 < (1ull << 31) && 3 * S * P.dst.height * P.dst.width / 2 < (1ull << 31);
 }
 
+// Planar frames.  Every check comes before the device is looked at and before any launch.
+struct PbPlanarFrame {  // a resolved layout, in bytes
+    unsigned long long pitch, cpitch, o1, o2, span, stride;
+};
+static int pb_planar_resolve(const char* what, const pb_planar_layout* l, unsigned long long S, unsigned long long h, unsigned long long w, int cx, int cy,
+                             PbPlanarFrame& f) {
+    const std::string n(what);
+    // (a frame must span less than 2^31 bytes to be served: a member at or beyond that is refused here, before anything is multiplied -
+    //  no product below can wrap, whatever the caller passes)
+    if (l && (l->pitch >= (1ull << 31) || l->chroma_pitch >= (1ull << 31) || l->offset1 >= (1ull << 31) || l->offset2 >= (1ull << 31)))
+        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_planar takes frames whose planes span less than 2^31 bytes (" + n + " pitch, chroma_pitch, offset1 or offset2): use pb_index_map_i32 and gather the three planes");
+    const unsigned long long cw = w >> cx, ch = h >> cy;
+    f.pitch = (l && l->pitch) ? l->pitch : S * w;
+    if (f.pitch < S * w) return pb_fail(PB_ERR_INVALID, n + " pitch smaller than a row");
+    f.cpitch = (l && l->chroma_pitch) ? l->chroma_pitch : S * cw;
+    if (f.cpitch < S * cw) return pb_fail(PB_ERR_INVALID, n + " chroma_pitch smaller than a row of planes 1 and 2");
+    // a plane occupies [start, start + pitch * (rows - 1) + S * samples of a row): the padding after its last row belongs to nobody
+    const unsigned long long e0 = h ? f.pitch * (h - 1) + S * w : 0, ce = ch ? f.cpitch * (ch - 1) + S * cw : 0;
+    f.o1 = (l && l->offset1) ? l->offset1 : f.pitch * h;
+    f.o2 = (l && l->offset2) ? l->offset2 : f.o1 + f.cpitch * ch;
+    if (f.o1 < e0 || f.o2 < e0) return pb_fail(PB_ERR_INVALID, n + " planes overlap: plane 1 or 2 starts inside plane 0");
+    if (ce && (f.o1 < f.o2 ? f.o1 + ce > f.o2 : f.o2 + ce > f.o1)) return pb_fail(PB_ERR_INVALID, n + " planes overlap: planes 1 and 2");
+    f.span = std::max(f.o1, f.o2) + ce;
+    // (the packed default is the end of plane 2 when the planes come in order; in any order, the end of the last plane)
+    f.stride = (l && l->frame_stride) ? l->frame_stride : std::max(f.span, f.o2 + f.cpitch * ch);
+    if (f.stride < f.span) return pb_fail(PB_ERR_INVALID, n + " frame_stride smaller than a frame: a plane ends beyond it");
+    if ((f.pitch | f.cpitch | f.o1 | f.o2 | f.stride) % S)
+        return pb_fail(PB_ERR_INVALID, n + " pitch, chroma_pitch, offsets and frame_stride must be multiples of " + std::to_string(S) + " bytes (one sample)");
+    return PB_OK;
+}
+static bool pb_planar_sub_ok(int sub) { return sub == PB_PLANAR_444 || sub == PB_PLANAR_422 || sub == PB_PLANAR_420; }
+static int pb_planar_dims(const pb_plan* plan, int sub) {
+    const PbParams& P = plan->P;
+    const int cx = pb_planar_cx(sub), cy = pb_planar_cy(sub);
+    if (((P.src.width | P.dst.width) & cx) || ((P.src.height | P.dst.height) & cy))
+        return pb_fail(PB_ERR_INVALID, sub == PB_PLANAR_420 ? "4:2:0 frames need even source and destination dimensions" : "4:2:2 frames need even source and destination widths");
+    return PB_OK;
+}
+// The arguments of the two planar entry points (pb_remap_planar, pb_remap_track_planar), in this order: null plan / frames, the frame
+// count, the sample size, the subsampling, the dimension rule, the two layouts, the pointers' alignment.  Resolves the layouts and fills.
+struct PbPlanarCall {
+    PbPlanarFrame fs, fd;
+    PbPlanar L;
+};
+static int pb_planar_check(const pb_plan* plan, const void* src_dev, const void* dst_dev, int n_frames, const pb_planar_layout* src_layout,
+                           const pb_planar_layout* dst_layout, int sub, int bytes_per_sample, const uint16_t fill[3], PbPlanarCall& c) {
+    if (!plan || !src_dev || !dst_dev) return pb_fail(PB_ERR_INVALID, "null argument");
+    if (n_frames < 0) return pb_fail(PB_ERR_INVALID, "negative frame count");
+    if (bytes_per_sample != 1 && bytes_per_sample != 2) return pb_fail(PB_ERR_INVALID, "bytes_per_sample outside {1, 2}");
+    if (!pb_planar_sub_ok(sub)) return pb_fail(PB_ERR_INVALID, "subsampling outside {PB_PLANAR_444, PB_PLANAR_422, PB_PLANAR_420}");
+    int rc = pb_planar_dims(plan, sub);
+    if (rc != PB_OK) return rc;
+    const PbParams& P = plan->P;
+    const unsigned long long S = (unsigned long long)bytes_per_sample;
+    const int cx = pb_planar_cx(sub), cy = pb_planar_cy(sub);
+    rc = pb_planar_resolve("source", src_layout, S, (unsigned long long)P.src.height, (unsigned long long)P.src.width, cx, cy, c.fs);
+    if (rc == PB_OK) rc = pb_planar_resolve("destination", dst_layout, S, (unsigned long long)P.dst.height, (unsigned long long)P.dst.width, cx, cy, c.fd);
+    if (rc != PB_OK) return rc;
+    if (((uintptr_t)src_dev | (uintptr_t)dst_dev) % S) return pb_fail(PB_ERR_INVALID, "frame pointers must be multiples of " + std::to_string(S) + " bytes (one sample)");
+    const unsigned sh = 8u * ((unsigned)S - 1u), smask = S == 1 ? 0xFFu : 0xFFFFu;
+    // (pitches and offsets are below 2^31: pb_planar_resolve; they are used only when the span is, too)
+    c.L = {(unsigned)c.fs.pitch, (unsigned)c.fs.cpitch, (unsigned)c.fs.o1, (unsigned)c.fs.o2, (unsigned)c.fd.pitch, (unsigned)c.fd.cpitch, (unsigned)c.fd.o1, (unsigned)c.fd.o2,
+           {fill ? fill[0] & smask : 16u << sh, fill ? fill[1] & smask : 128u << sh, fill ? fill[2] & smask : 128u << sh}};
+    return PB_OK;
+}
+static bool pb_planar_span_fits(const PbPlanarCall& c) { return c.fs.span < (1ull << 31) && c.fd.span < (1ull << 31); }
+int pb_remap_planar(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout,
+                    int subsampling, int bytes_per_sample, const uint16_t fill[3], void* stream) {
+    PbPlanarCall c;
+    int rc = pb_planar_check(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, subsampling, bytes_per_sample, fill, c);
+    if (rc != PB_OK || n_frames == 0) return rc;
+    rc = pb_check_device(plan);
+    if (rc != PB_OK) return rc;
+    const PbRoute r = pb_route(plan, PB_INTERP_NEAREST, 1, 0, false, bytes_per_sample, false, subsampling);
+    if (r.kind == PbRoute::PLANAR && !pb_planar_span_fits(c))
+        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_planar takes frames whose planes span less than 2^31 bytes: use pb_index_map_i32 and gather the three planes");
+    return pb_launch(plan, r, static_cast<const uint8_t*>(src_dev), static_cast<uint8_t*>(dst_dev), n_frames, c.fs.stride, c.fd.stride, (hipStream_t)stream, nullptr, &c.L);
+}
+int pb_remap_planar_supported(const pb_plan* plan, int subsampling, int bytes_per_sample) {
+    if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
+    if (bytes_per_sample != 1 && bytes_per_sample != 2) return pb_fail(PB_ERR_INVALID, "bytes_per_sample outside {1, 2}");
+    if (!pb_planar_sub_ok(subsampling)) return pb_fail(PB_ERR_INVALID, "subsampling outside {PB_PLANAR_444, PB_PLANAR_422, PB_PLANAR_420}");
+    if (int rc = pb_planar_dims(plan, subsampling)) return rc;
+    // (packed frames; a pitched layout's span is pb_remap_planar's to check)
+    PbPlanarFrame fs, fd;
+    const PbParams& P = plan->P;
+    const unsigned long long S = (unsigned long long)bytes_per_sample;
+    const int cx = pb_planar_cx(subsampling), cy = pb_planar_cy(subsampling);
+    if (pb_planar_resolve("source", nullptr, S, (unsigned long long)P.src.height, (unsigned long long)P.src.width, cx, cy, fs) != PB_OK ||
+        pb_planar_resolve("destination", nullptr, S, (unsigned long long)P.dst.height, (unsigned long long)P.dst.width, cx, cy, fd) != PB_OK)
+        return 0;
+    return pb_route(plan, PB_INTERP_NEAREST, 1, 0, false, bytes_per_sample, false, subsampling).kind == PbRoute::PLANAR && fs.span < (1ull << 31) && fd.span < (1ull << 31);
+}
+
 int pb_remap_u8v(const pb_plan* plan, const uint8_t* const* src_dev, uint8_t* const* dst_dev, int n_frames, void* stream) {
     size_t ss = 0, ds = 0;
     const int rc = pb_check_frames(plan, src_dev, dst_dev, n_frames, 1, ss, ds, true);
@@ -2243,6 +2373,45 @@ int pb_remap_track_nv12(const pb_plan* plan, const double* rot3x3_dev, int n_rot
         pb_pick_exact_kind(P, [&](auto K) {
             pb_pick<1, 2>(bytes_per_sample == 1, [&](auto S) {
                 hipLaunchKernelGGL((pb_track_nv12_kernel<S.value, K.value>), grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride, c.fd.stride, c.L);
+            });
+        });
+    }
+    PB_HIP(hipGetLastError());
+    return PB_OK;
+}
+
+// A rotation track of planar frames: pb_remap_planar's argument checks, then pb_remap_track_u8's table checks; the launches
+// are pb_remap_track_nv12's.
+int pb_remap_track_planar(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                          const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample, const uint16_t fill[3],
+                          void* stream) {
+    PbPlanarCall c;
+    int rc = pb_planar_check(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, subsampling, bytes_per_sample, fill, c);
+    if (rc == PB_OK) rc = pb_track_table_check(plan, rot3x3_dev, n_rot_per_frame);
+    if (rc != PB_OK || n_frames == 0) return rc;
+    rc = pb_check_device(plan);
+    if (rc != PB_OK) return rc;
+    const PbParams& P = plan->P;
+    if (P.src.kind == PB_KIND_DOUBLE)
+        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_track_planar takes single sources (a double fisheye's blend is sample-typed): convert to RGB8 and use pb_remap_track_u8");
+    if (!pb_planar_span_fits(c) || P.src.height >= 32768 || P.src.width >= 32768)
+        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_track_planar takes frames whose planes span less than 2^31 bytes and sources below 32768 px a side: use a plan per "
+                                           "frame with pb_index_map_i32 and gather the three planes");
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned long long quads = (unsigned long long)P.dst.height * (((unsigned)P.dst.width + PB_PX - 1) / PB_PX);
+    const int fpc = pb_track_fpc();
+    const int per_launch = 65535 * fpc;
+    const int cx = pb_planar_cx(subsampling), cy = pb_planar_cy(subsampling);
+    for (int f0 = 0; f0 < n_frames; f0 += per_launch) {
+        const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
+        const double* rot = rot3x3_dev + 9ull * (unsigned)n_rot_per_frame * (unsigned)f0;
+        const uint8_t* s = static_cast<const uint8_t*>(src_dev) + (unsigned long long)f0 * c.fs.stride;
+        uint8_t* d = static_cast<uint8_t*>(dst_dev) + (unsigned long long)f0 * c.fd.stride;
+        const dim3 grid(pb_blocks(quads), (unsigned)((nf + fpc - 1) / fpc));
+        pb_pick_exact_kind(P, [&](auto K) {
+            pb_pick<1, 2>(bytes_per_sample == 1, [&](auto S) {
+                hipLaunchKernelGGL((pb_track_planar_kernel<S.value, K.value>), grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride, c.fd.stride, c.L, cx,
+                                   cy);
             });
         });
     }

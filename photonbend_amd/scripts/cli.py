@@ -413,6 +413,63 @@ def _read_exact(stream, nbytes: int) -> bytes:
     return b"".join(parts)
 
 
+def _video_chain(width, height, otype, lens, fov, size, rotation, lens_coefficients, lens_max_theta):
+    """The coordinate map of a raw-video command (remap-nv12, remap-yuv): by default a panorama of the input's size (--size H: H x 2H), with
+    --type, --lens and --fov the photo make-photo would make; every -r applied in order."""
+    if otype is None:
+        if lens is not None or fov is not None or lens_coefficients or lens_max_theta is not None:
+            raise click.UsageError("--lens / --fov and the lens parameters belong to a photo: give --type too")
+        h_out = height if size is None else size
+        destiny = PanoramaImage(np.zeros((h_out, width if size is None else 2 * h_out, 3), np.uint8))
+    else:
+        if lens is None or fov is None:
+            raise click.UsageError("a photo needs --type, --lens and --fov")
+        shape = camera_shape(otype, np.zeros((height, width, 3), np.uint8), size)
+        destiny = camera_object(otype, np.zeros(shape, np.uint8), radians_fov(fov, otype), lens_object(lens, lens_coefficients, lens_max_theta), magnitude_for(otype, shape))
+    cmap = destiny.get_coordinate_map()
+    for rot in rotation:
+        cmap = Rotation(*map(to_radians, rot)).rotate_coordinate_map(cmap)
+    return cmap
+
+
+def _stream_frames(input_frames, output_frames, frame_in: int, dt, chunk: int, mats, remap) -> None:
+    """The frame loop of a raw-video command: `chunk` packed frames of frame_in bytes at a time from a file or stdin through
+    remap(host (n, samples of a frame), index of the first frame) -> device frames, written to a file or stdout.  A truncated frame and a
+    rotation track (`mats`, or None) shorter than the input are usage errors - for a file, before anything is written."""
+    piped = str(input_frames) == "-"
+    if not piped:  # a file's length is known: refuse before anything is written
+        if not input_frames.is_file():
+            _fail(f"{input_frames}: no such file")
+        total = input_frames.stat().st_size
+        if total % frame_in:
+            _fail(f"{input_frames}: {total} bytes are {total // frame_in} frames of {frame_in} bytes and a truncated one of {total % frame_in}")
+        if mats is not None and total // frame_in > len(mats):
+            _fail(f"{input_frames} holds {total // frame_in} frames, the rotation track {len(mats)} lines")
+    fin = sys.stdin.buffer if piped else open(input_frames, "rb")
+    fout = sys.stdout.buffer if str(output_frames) == "-" else open(output_frames, "wb")
+    done = 0
+    try:
+        while True:
+            data = _read_exact(fin, chunk * frame_in)
+            n, rest = divmod(len(data), frame_in)
+            if mats is not None and done + n + (1 if rest else 0) > len(mats):
+                _fail(f"the input holds more than {len(mats)} frames, the rotation track {len(mats)} lines")
+            if n:
+                host = np.frombuffer(data, dt, n * frame_in // dt.itemsize).reshape(n, frame_in // dt.itemsize)
+                fout.write(nat.to_host(remap(host, done)).tobytes())
+                done += n
+            if rest:
+                _fail(f"the input ends with a truncated frame: {rest} of {frame_in} bytes after {done} whole frames")
+            if len(data) < chunk * frame_in:
+                break
+        fout.flush()
+    finally:
+        if fin is not sys.stdin.buffer:
+            fin.close()
+        if fout is not sys.stdout.buffer:
+            fout.close()
+
+
 @main.command("remap-nv12")
 @click.argument("input_frames", metavar="INPUT", type=click.Path(path_type=Path, allow_dash=True))
 @click.argument("output_frames", metavar="OUTPUT", type=click.Path(path_type=Path, allow_dash=True))
@@ -444,60 +501,76 @@ def remap_nv12(input_frames, output_frames, width, height, pix_fmt, otype, lens,
         _fail(f"4:2:0 frames have even dimensions, got --size {size}")
     if chunk < TRACK_FRAMES or chunk % TRACK_FRAMES:
         _fail(f"--chunk is a multiple of {TRACK_FRAMES}, got {chunk}")
-    if otype is None:
-        if lens is not None or fov is not None or lens_coefficients or lens_max_theta is not None:
-            raise click.UsageError("--lens / --fov and the lens parameters belong to a photo: give --type too")
-        h_out = height if size is None else size
-        destiny = PanoramaImage(np.zeros((h_out, width if size is None else 2 * h_out, 3), np.uint8))
-    else:
-        if lens is None or fov is None:
-            raise click.UsageError("a photo needs --type, --lens and --fov")
-        shape = camera_shape(otype, np.zeros((height, width, 3), np.uint8), size)
-        destiny = camera_object(otype, np.zeros(shape, np.uint8), radians_fov(fov, otype), lens_object(lens, lens_coefficients, lens_max_theta), magnitude_for(otype, shape))
-    cmap = destiny.get_coordinate_map()
-    for rot in rotation:
-        cmap = Rotation(*map(to_radians, rot)).rotate_coordinate_map(cmap)
+    cmap = _video_chain(width, height, otype, lens, fov, size, rotation, lens_coefficients, lens_max_theta)
     dstp, srcp = cmap.dst_proj, PanoramaImage(np.zeros((height, width, 3), np.uint8))._proj("src")
     if dstp.width & 1:
         _fail(f"4:2:0 frames have even dimensions: the output would be {dstp.height} x {dstp.width}")
     mats = None if track is None else core.rotation_track(_read_track(track))
     frame_in, frame_out = 3 * height * width // 2 * dt.itemsize, 3 * dstp.height * dstp.width // 2 * dt.itemsize
-    piped = str(input_frames) == "-"
-    if not piped:  # a file's length is known: refuse before anything is written
-        if not input_frames.is_file():
-            _fail(f"{input_frames}: no such file")
-        total = input_frames.stat().st_size
-        if total % frame_in:
-            _fail(f"{input_frames}: {total} bytes are {total // frame_in} frames of {frame_in} bytes and a truncated one of {total % frame_in}")
-        if mats is not None and total // frame_in > len(mats):
-            _fail(f"{input_frames} holds {total // frame_in} frames, the rotation track {len(mats)} lines")
     # without a track: a prepared plan and the tile kernel; with one: a deferred plan (its tables are never read) and the track kernel
-    plan = nat.Plan(dstp, list(cmap.rotations), srcp, bilinear=False) if mats is None else nat.Plan(dstp, list(cmap.rotations), srcp, defer=True)
-    fin = sys.stdin.buffer if piped else open(input_frames, "rb")
-    fout = sys.stdout.buffer if str(output_frames) == "-" else open(output_frames, "wb")
-    done = 0
-    try:
-        while True:
-            data = _read_exact(fin, chunk * frame_in)
-            n, rest = divmod(len(data), frame_in)
-            if mats is not None and done + n + (1 if rest else 0) > len(mats):
-                _fail(f"the input holds more than {len(mats)} frames, the rotation track {len(mats)} lines")
-            if n:  # upload, ONE launch, download
-                host = np.frombuffer(data, dt, n * frame_in // dt.itemsize).reshape(n, 3 * height // 2, width)
-                s = nat.to_device(host)
-                o = plan.remap_nv12(s) if mats is None else plan.remap_track_nv12(s, mats[done : done + n])
-                fout.write(nat.to_host(o).tobytes())
-                done += n
-            if rest:
-                _fail(f"the input ends with a truncated frame: {rest} of {frame_in} bytes after {done} whole frames")
-            if len(data) < chunk * frame_in:
-                break
-        fout.flush()
-    finally:
-        if fin is not sys.stdin.buffer:
-            fin.close()
-        if fout is not sys.stdout.buffer:
-            fout.close()
+    plan = None
+
+    def remap(host, first):  # upload, ONE launch, download
+        nonlocal plan
+        if plan is None:  # (made with the first frames: the usage errors of the input come before any plan is prepared)
+            plan = nat.Plan(dstp, list(cmap.rotations), srcp, bilinear=False) if mats is None else nat.Plan(dstp, list(cmap.rotations), srcp, defer=True)
+        s = nat.to_device(host.reshape(len(host), 3 * height // 2, width))
+        return plan.remap_nv12(s) if mats is None else plan.remap_track_nv12(s, mats[first : first + len(host)])
+
+    _stream_frames(input_frames, output_frames, frame_in, dt, chunk, mats, remap)
+
+
+@main.command("remap-yuv")
+@click.argument("input_frames", metavar="INPUT", type=click.Path(path_type=Path, allow_dash=True))
+@click.argument("output_frames", metavar="OUTPUT", type=click.Path(path_type=Path, allow_dash=True))
+@click.option("--width", required=True, type=click.INT, help="The width of an input frame in pixels.")
+@click.option("--height", required=True, type=click.INT, help="The height of an input frame in pixels.")
+@click.option("--pix-fmt", type=click.Choice(list(nat.PLANAR_FORMATS)), default="yuv420p", show_default=True, help="The frames' planar layout, as ffmpeg names it.")
+@click.option("--type", "otype", type=click.Choice([t for t in TYPES if t != "double"]), default=None,
+              help="Make a photo: the type of the output image (with --lens and --fov). " + TYPE_HELP)
+@click.option("--lens", type=_lens_choice, default=None, help="With --type: the lens type of the output photo.")
+@_lens_parameters("--lens", "lens")
+@click.option("--fov", type=click.FLOAT, default=None, help="With --type: the lens field of view of the output photo in degrees.")
+@click.option("-s", "--size", type=click.INT, default=None, help="The vertical size of an output frame. [default: the input's]")
+@click.option("-r", "--rotation", type=click.FLOAT, nargs=3, multiple=True, default=[], help=ROTATION_HELP)
+@click.option("--rotations", "track", type=click.Path(exists=True, dir_okay=False, path_type=Path), default=None,
+              help="A rotation track: a text file of one `pitch yaw roll` line in degrees per frame, applied after every -r.")
+@click.option("--chunk", type=click.INT, default=8, show_default=True, help=f"Frames per launch, a multiple of {TRACK_FRAMES}.")
+def remap_yuv(input_frames, output_frames, width, height, pix_fmt, otype, lens, fov, size, rotation, track, chunk, lens_coefficients, lens_max_theta):
+    """Remap raw PLANAR video frames of an equirectangular panorama - yuv420p, yuv422p, yuv444p, their 10- and 16-bit forms, gbrp - e.g.
+    between two `ffmpeg -f rawvideo -pix_fmt yuv420p` pipes.
+
+    \b
+    INPUT is a file of packed frames, three planes each: HEIGHT x WIDTH, then two of the format's chroma size; - is stdin.
+    OUTPUT receives the packed output frames; - is stdout.
+    By default the output is a panorama of the same size (--size H: H x 2H); with --type, --lens and --fov it is the photo make-photo would make.
+    4:2:0 formats have even widths and heights, 4:2:2 formats even widths, 4:4:4 formats (gbrp among them) take any size.
+    """
+    dt, sub, fill = nat.PLANAR_FORMATS[pix_fmt]
+    rule = nat.planar_dims_rule(sub, pix_fmt)
+    if width < 1 or height < 1 or not nat.planar_dims_ok(sub, (height, width)):
+        _fail(f"{rule}, got --width {width} --height {height}")
+    if size is not None and (size < 1 or not nat.planar_dims_ok(sub, (size, 2))):
+        _fail(f"{rule}, got --size {size}")
+    if chunk < TRACK_FRAMES or chunk % TRACK_FRAMES:
+        _fail(f"--chunk is a multiple of {TRACK_FRAMES}, got {chunk}")
+    cmap = _video_chain(width, height, otype, lens, fov, size, rotation, lens_coefficients, lens_max_theta)
+    dstp, srcp = cmap.dst_proj, PanoramaImage(np.zeros((height, width, 3), np.uint8))._proj("src")
+    if not nat.planar_dims_ok(sub, (dstp.height, dstp.width)):
+        _fail(f"{rule}: the output would be {dstp.height} x {dstp.width}")
+    mats = None if track is None else core.rotation_track(_read_track(track))
+    frame_in = nat.planar_frame_samples(height, width, sub) * dt.itemsize
+    # without a track: a prepared plan and the tile kernel; with one: a deferred plan (its tables are never read) and the track kernel
+    plan = None
+
+    def remap(host, first):  # upload, ONE launch, download
+        nonlocal plan
+        if plan is None:  # (made with the first frames: the usage errors of the input come before any plan is prepared)
+            plan = nat.Plan(dstp, list(cmap.rotations), srcp, bilinear=False) if mats is None else nat.Plan(dstp, list(cmap.rotations), srcp, defer=True)
+        s = nat.to_device(host)
+        return plan.remap_planar(s, sub, fill=fill) if mats is None else plan.remap_track_planar(s, mats[first : first + len(host)], sub, fill=fill)
+
+    _stream_frames(input_frames, output_frames, frame_in, dt, chunk, mats, remap)
 
 
 if __name__ == "__main__":

@@ -6,7 +6,7 @@ import math
 from typing import Callable, Dict, Tuple
 
 __all__ = ["to_radians", "to_degrees", "calculate_size_panorama_to_photo", "CUBEMAP_FACES", "cubemap_faces", "cubemap_from_faces",
-           "cubemap_face_rotation", "nv12_planes", "nv12_frame"]
+           "cubemap_face_rotation", "nv12_planes", "nv12_frame", "planar_planes", "planar_frame"]
 
 # the six faces of a cube map in frame order: face k occupies rows (k // 3) N ... and columns (k % 3) N ... of the (2N, 3N) image
 CUBEMAP_FACES = ("left", "front", "right", "up", "back", "down")
@@ -82,6 +82,41 @@ def nv12_frame(y, uv):
     if y.ndim != 2 or y.shape[0] % 2 or y.shape[1] % 2 or uv.shape != (y.shape[0] // 2, y.shape[1] // 2, 2) or uv.dtype != y.dtype:
         raise ValueError(f"a luma plane (h, w) with h and w even and a chroma plane (h/2, w/2, 2) of its sample type, got {y.shape} {y.dtype} and {uv.shape} {uv.dtype}")
     return np.concatenate([y, uv.reshape(y.shape[0] // 2, y.shape[1])], axis=0)
+
+
+def planar_planes(frame, h: int, w: int, subsampling):
+    """(p0, p1, p2) VIEWS of one packed planar frame - a flat array of h * w + 2 * (h >> cy) * (w >> cx) samples, an ndarray or anything
+    sliceable and reshapeable the same way: p0 is (h, w), p1 and p2 are (h >> cy, w >> cx).  ``subsampling``: "444", "422", "420" or the
+    PLANAR_* ids of ``Plan.remap_planar`` ((cx, cy) = (0, 0), (1, 0), (1, 1)).  A 4:4:4 frame may also come as (3, h, w)."""
+    from .. import _native as nat
+
+    sub = nat.planar_subsampling(subsampling)
+    cx, cy = nat.PLANAR_SHIFTS[sub]
+    h, w = int(h), int(w)
+    if h < 1 or w < 1 or not nat.planar_dims_ok(sub, (h, w)):
+        raise ValueError(f"{nat.planar_dims_rule(sub)}, got {h} x {w}")
+    shape = tuple(int(v) for v in frame.shape)
+    if sub == nat.PLANAR_444 and shape == (3, h, w):
+        return frame[0], frame[1], frame[2]
+    n0, nc = h * w, (h >> cy) * (w >> cx)
+    if shape != (n0 + 2 * nc,):
+        raise ValueError(f"a packed planar frame of {h} x {w} is a flat array of {n0 + 2 * nc} samples, got {shape}")
+    return frame[:n0].reshape(h, w), frame[n0 : n0 + nc].reshape(h >> cy, w >> cx), frame[n0 + nc :].reshape(h >> cy, w >> cx)
+
+
+def planar_frame(p0, p1, p2):
+    """The packed flat frame of three planes of one sample type, p1 and p2 of one shape (h >> cy, w >> cx) for one of the three
+    subsamplings: planar_planes' inverse, in NumPy."""
+    import numpy as np
+
+    p0, p1, p2 = np.asarray(p0), np.asarray(p1), np.asarray(p2)
+    ok = p0.ndim == 2 and p1.shape == p2.shape and p1.dtype == p0.dtype and p2.dtype == p0.dtype
+    if ok:
+        h, w = p0.shape
+        ok = p1.shape in ((h, w), (h, w >> 1), (h >> 1, w >> 1)) and (p1.shape == (h, w) or not w & 1) and (p1.shape[0] == h or not h & 1)
+    if not ok:
+        raise ValueError(f"a plane (h, w) and two planes (h >> cy, w >> cx) of its sample type, got {p0.shape} {p0.dtype}, {p1.shape} {p1.dtype} and {p2.shape} {p2.dtype}")
+    return np.concatenate([p0.ravel(), p1.ravel(), p2.ravel()])
 
 
 def to_radians(degrees: float) -> float:
