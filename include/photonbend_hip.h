@@ -350,6 +350,41 @@ int pb_remap_track_planar(const pb_plan* plan, const double* rot3x3_dev, int n_r
                           const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample,
                           const uint16_t fill[3], void* stream);
 
+/* OPT-IN: BILINEAR sampling of the same video frames in ONE launch of the tile kernel pb_planar_bilinear_kernel whatever n_frames
+ * (ABI 5, additive).  No reference counterpart: the definition is written down in tests/video_bilinear_ref.py.  With f the
+ * reference's pre-truncation source coordinate of an output pixel and "live" as for pb_remap_bilinear_u8:
+ *   plane 0       pb_remap_bilinear_u8's definition on a grey plane: s = f - 0.5, taps floor(s), floor(s) + 1 per axis, rows clamped, a
+ *                 panorama's columns wrapped, a camera's clamped, round half to even; fill[0] where the pixel is not live.
+ *   planes 1, 2   sample (i, j) is decided by its ANCHOR (i << cy, j << cx) as in the nearest calls.  Chroma is co-sited with the top-left
+ *                 luma pixel of its block (source and destination alike): the anchor's coordinate in chroma samples is s / (1 << c) per
+ *                 axis, and the same bilinear expression runs on the (height >> cy) x (width >> cx) plane - rows clamped to it, a
+ *                 panorama's columns wrapped modulo width >> cx; fill[k] where the anchor is not live.
+ * Precision: the tile models' coordinates are certified to 1/1024 px per axis, so a sample is within T(R) = 1 + floor(R / 512) of the
+ * definition, R the largest sample value of the source frame and the fills: 1 LSB for 8-bit samples, 2 for 10-bit samples stored low,
+ * 128 for full 16-bit or high-aligned (P010) samples.  At the rim of a camera source a pixel within 1/512 px of the liveness edge may
+ * be fill where the definition samples, or the reverse.
+ * Arguments, layouts, defaults, PB_ERR_INVALID (checks, order and messages) and n_frames == 0: exactly pb_remap_planar's / pb_remap_nv12's.
+ *   PB_ERR_UNSUPPORTED   nothing is written: whatever the nearest call refuses; plans without the bilinear mode's tables (created with
+ *                        PB_PLAN_NO_BILINEAR and not given pb_plan_prepare(plan, PB_PLAN_BILINEAR) since, or whose coordinate table did
+ *                        not fit); cube and equi-angular-cube sources (no interpolating tile kernel).
+ * Asynchronous on `stream`, never allocates or synchronises (graph-capture safe).  The _supported calls: 1 / 0 / negative as above.
+ * (The return type stands on a line of its own: tools that read the nearest calls' declarations as `int pb_remap_planar...(` and
+ * `int pb_remap_nv12...(` keep finding exactly those.) */
+int
+pb_remap_planar_bilinear(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_planar_layout* src_layout,
+                             const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample, const uint16_t fill[3], void* stream);
+int
+pb_remap_nv12_bilinear(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout,
+                           const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3], void* stream);
+int
+pb_remap_planar_bilinear_supported(const pb_plan* plan, int subsampling, int bytes_per_sample);
+int
+pb_remap_nv12_bilinear_supported(const pb_plan* plan, int bytes_per_sample);
+/* Diagnostic, synchronous: what the fix-pixel path of pb_planar_bilinear_kernel meets in `plan`.  mix[0] = modelled tiles with fix pixels,
+ * mix[1] = their fix pixels, mix[2] = of those the chroma anchors at PB_PLANAR_422 (an even column), mix[3] = at PB_PLANAR_420 (an even
+ * row too).  All zero for a plan without the bilinear mode's tables. */
+int pb_plan_video_bilinear_mix(const pb_plan* plan, long long mix[4]);
+
 /* OPT-IN extension with no reference counterpart (the reference samples nearest-by-truncation only):
  * bilinear interpolation at the reference's pre-truncation coordinate (pixel k covers [k, k+1), centre
  * k + 0.5; taps clamped to the image, panorama columns wrap; round half to even).  Pixels the nearest mode

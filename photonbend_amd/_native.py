@@ -109,6 +109,7 @@ SIGNATURES = {
     "pb_plan_bilinear_float64_tiles": (C.c_int, [_VP]),
     "pb_plan_bilinear_tile_mix": (C.c_int, [_VP, C.POINTER(C.c_longlong)]),
     "pb_plan_bilinear_launch_shape": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "pb_plan_video_bilinear_mix": (C.c_int, [_VP, C.POINTER(C.c_longlong)]),
     "pb_plan_matches": (C.c_int, [_VP, C.POINTER(pb_proj), C.POINTER(C.c_double), C.c_int, C.POINTER(pb_proj)]),
     "pb_remap_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_u8v": (C.c_int, [_VP, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, _VP]),
@@ -118,6 +119,10 @@ SIGNATURES = {
     "pb_remap_nv12_supported": (C.c_int, [_VP, C.c_int]),
     "pb_remap_planar": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, _VP]),
     "pb_remap_planar_supported": (C.c_int, [_VP, C.c_int, C.c_int]),
+    "pb_remap_planar_bilinear": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, _VP]),
+    "pb_remap_nv12_bilinear": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP]),
+    "pb_remap_planar_bilinear_supported": (C.c_int, [_VP, C.c_int, C.c_int]),
+    "pb_remap_nv12_bilinear_supported": (C.c_int, [_VP, C.c_int]),
     "pb_remap_bilinear_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_catmull_rom_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_track_u8": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
@@ -215,6 +220,18 @@ def check_interpolation(interpolation: str, supersample: int = 1) -> int:
     if n > 1 and interpolation not in INTERP_IDS:
         raise ValueError(f"{interpolation} sampling is not supersampled: pass supersample=1")
     return n
+
+
+VIDEO_INTERPOLATIONS = ("nearest", "bilinear")  # what remap_nv12 / remap_planar sample with
+
+
+def check_video_interpolation(interpolation: str) -> bool:
+    """The interpolation name of a video call (``remap_nv12``, ``remap_planar`` and their ``_supported``): ``check_interpolation``'s
+    ValueError for an unknown name, and one for a mode video frames do not have.  -> whether it is "bilinear"."""
+    check_interpolation(interpolation)
+    if interpolation not in VIDEO_INTERPOLATIONS:
+        raise ValueError(f"video frames are sampled with one of {', '.join(map(repr, VIDEO_INTERPOLATIONS))}, got {interpolation!r}")
+    return interpolation == "bilinear"
 
 
 TRACK_INTERP_IDS = {"nearest": 0, "bilinear": 1, "catmull-rom": 2}  # pb_remap_track_u8's PB_INTERP_* ids
@@ -689,7 +706,13 @@ class Plan:
         self.ensure_bilinear()
         m = (C.c_longlong * 8)()
         check(load().pb_plan_bilinear_tile_mix(self._h, m))
-        return dict(zip(("window", "direct", "table", "black", "td3", "entries", "half_windows", "table_plain"), (int(x) for x in m)))
+        mix = dict(zip(("window", "direct", "table", "black", "td3", "entries", "half_windows", "table_plain"), (int(x) for x in m)))
+        # what the video kernel's fix-pixel path meets (pb_plan_video_bilinear_mix): modelled tiles with fix pixels, their fix pixels, and
+        # of those the chroma anchors at 4:2:2 and at 4:2:0
+        v = (C.c_longlong * 4)()
+        check(load().pb_plan_video_bilinear_mix(self._h, v))
+        mix.update(zip(("fix_tiles", "fix_pixels", "fix_anchors_422", "fix_anchors_420"), (int(x) for x in v)))
+        return mix
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -908,34 +931,40 @@ class Plan:
             self.launch(s.data_ptr(), o.data_ptr(), n, None, bytes_per_px=bpp)
         return o
 
-    def nv12_supported(self, bytes_per_sample: int = 1) -> bool:
+    def nv12_supported(self, bytes_per_sample: int = 1, *, interpolation: str = "nearest") -> bool:
         """Whether ``remap_nv12`` takes this plan with samples of this size (pb_remap_nv12_supported): the plans ``px_supported`` takes,
-        with even dimensions.  A size outside (1, 2) or an odd dimension is a PbError.  Needs no GPU."""
-        r = load().pb_remap_nv12_supported(self._h, int(bytes_per_sample))
+        with even dimensions.  A size outside (1, 2) or an odd dimension is a PbError.  ``interpolation="bilinear"``: whether the
+        bilinear call does (pb_remap_nv12_bilinear_supported): of those plans, the ones with the bilinear mode's tables.  Needs no GPU."""
+        fn = load().pb_remap_nv12_bilinear_supported if check_video_interpolation(interpolation) else load().pb_remap_nv12_supported
+        r = fn(self._h, int(bytes_per_sample))
         if r < 0:
             check(r)
         return r == 1
 
     def launch_nv12(self, src_ptr: int, dst_ptr: int, n_frames: int = 1, stream: int | None = None, bytes_per_sample: int = 1, fill=None,
-                    src_layout=None, dst_layout=None) -> None:
-        """The raw call (pb_remap_nv12): n_frames 4:2:0 semi-planar frames at src_ptr / dst_ptr on `stream`, layouts in bytes (None: packed),
-        ``fill`` the (Y, U, V) samples of black pixels (None: video black)."""
+                    src_layout=None, dst_layout=None, *, interpolation: str = "nearest") -> None:
+        """The raw call (pb_remap_nv12; ``interpolation="bilinear"``: pb_remap_nv12_bilinear): n_frames 4:2:0 semi-planar frames at src_ptr /
+        dst_ptr on `stream`, layouts in bytes (None: packed), ``fill`` the (Y, U, V) samples of black pixels (None: video black)."""
+        fn = load().pb_remap_nv12_bilinear if check_video_interpolation(interpolation) else load().pb_remap_nv12
         f = None if fill is None else (C.c_uint16 * 3)(*[int(v) for v in fill])
         sl, dl = nv12_layout(src_layout), nv12_layout(dst_layout)
-        self._gated(load().pb_remap_nv12, self._h, src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl), None if dl is None else C.addressof(dl),
+        self._gated(fn, self._h, src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl), None if dl is None else C.addressof(dl),
                     int(bytes_per_sample), None if f is None else C.addressof(f), current_stream() if stream is None else stream)
 
-    def remap_nv12(self, src, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None):
+    def remap_nv12(self, src, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None, *, interpolation: str = "nearest"):
         """The nearest remap of NV12 (uint8) or P010 / P016 (uint16) video frames in ONE launch (pb_remap_nv12): luma moves
         like a grey image, and the (U, V) pair of an output 2 x 2 block is the source pair at the block's top-left pixel's source position.
         src: a device array (3h/2, w) or (N, 3h/2, w), packed - or, with ``src_layout``, any 1-D uint8 / uint16 device buffer that holds
         the frames at that layout (then ``out`` is required with ``dst_layout``, or the result is packed).  -> (3H/2, W) / (N, 3H/2, W) of
         src's kind and dtype.  ``fill``: (Y, U, V) for black pixels (None: 16, 128, 128 scaled to the sample size).  Layouts: a
         (pitch, uv_offset, frame_stride) tuple, dict or pb_nv12_layout, in bytes, 0 = default.  A plan ``nv12_supported`` refuses is a
-        PbError (no fallback)."""
+        PbError (no fallback).  ``interpolation="bilinear"`` (opt-in): luma is the bilinear mode's grey sample and a pair is
+        sampled bilinearly on the pair plane at half its block's top-left pixel's coordinate; within 1 + R // 512 of the written definition
+        (R the largest sample value), on plans prepared with ``bilinear=True``."""
+        check_video_interpolation(interpolation)
         s, o, n, S, sl, dl = self._nv12_out(*self._nv12_source(src, src_layout), out, dst_layout)
         with _on(s):
-            self.launch_nv12(s.data_ptr(), o.data_ptr(), n, stream, S, fill, sl, dl)
+            self.launch_nv12(s.data_ptr(), o.data_ptr(), n, stream, S, fill, sl, dl, interpolation=interpolation)
         return o
 
     def _nv12_source(self, src, src_layout):
@@ -1022,24 +1051,28 @@ class Plan:
             release()
         return o
 
-    def planar_supported(self, subsampling, bytes_per_sample: int = 1) -> bool:
+    def planar_supported(self, subsampling, bytes_per_sample: int = 1, *, interpolation: str = "nearest") -> bool:
         """Whether ``remap_planar`` takes this plan with this subsampling and sample size (pb_remap_planar_supported): the plans
-        ``px_supported`` takes.  A size outside (1, 2) or a dimension that breaks the subsampling's rule is a PbError.  Needs no GPU."""
-        r = load().pb_remap_planar_supported(self._h, planar_subsampling(subsampling), int(bytes_per_sample))
+        ``px_supported`` takes.  A size outside (1, 2) or a dimension that breaks the subsampling's rule is a PbError.
+        ``interpolation="bilinear"``: whether the bilinear call does (pb_remap_planar_bilinear_supported).  Needs no GPU."""
+        fn = load().pb_remap_planar_bilinear_supported if check_video_interpolation(interpolation) else load().pb_remap_planar_supported
+        r = fn(self._h, planar_subsampling(subsampling), int(bytes_per_sample))
         if r < 0:
             check(r)
         return r == 1
 
     def launch_planar(self, src_ptr: int, dst_ptr: int, subsampling, n_frames: int = 1, stream: int | None = None, bytes_per_sample: int = 1, fill=None,
-                      src_layout=None, dst_layout=None) -> None:
-        """The raw call (pb_remap_planar): n_frames planar frames at src_ptr / dst_ptr on `stream`, layouts in bytes (None: packed),
-        ``fill`` the samples of black pixels per plane (None: video black)."""
+                      src_layout=None, dst_layout=None, *, interpolation: str = "nearest") -> None:
+        """The raw call (pb_remap_planar; ``interpolation="bilinear"``: pb_remap_planar_bilinear): n_frames planar frames at src_ptr /
+        dst_ptr on `stream`, layouts in bytes (None: packed), ``fill`` the samples of black pixels per plane (None: video black)."""
+        fn = load().pb_remap_planar_bilinear if check_video_interpolation(interpolation) else load().pb_remap_planar
         f = None if fill is None else (C.c_uint16 * 3)(*[int(v) for v in fill])
         sl, dl = planar_layout(src_layout), planar_layout(dst_layout)
-        self._gated(load().pb_remap_planar, self._h, src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl), None if dl is None else C.addressof(dl),
+        self._gated(fn, self._h, src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl), None if dl is None else C.addressof(dl),
                     planar_subsampling(subsampling), int(bytes_per_sample), None if f is None else C.addressof(f), current_stream() if stream is None else stream)
 
-    def remap_planar(self, src, subsampling, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None):
+    def remap_planar(self, src, subsampling, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None, *,
+                     interpolation: str = "nearest"):
         """The nearest remap of PLANAR video frames - three planes of uint8 or uint16 samples at 4:4:4, 4:2:2 or 4:2:0 - in ONE launch
         (pb_remap_planar): plane 0 moves like a grey image, and a sample of planes 1 and 2 is the source sample at the source
         position of its block's top-left pixel.  src: a flat device array of one packed frame, or (N, frame_samples) - a 4:2:0 or 4:2:2
@@ -1047,11 +1080,15 @@ class Plan:
         at that layout (then ``out`` is required with ``dst_layout``, or the result is packed).  -> the same shape for the destination.
         ``subsampling``: PLANAR_444 / PLANAR_422 / PLANAR_420 or "444" / "422" / "420".  ``fill``: the samples of black per plane (None:
         16, 128, 128 scaled to the sample size).  Layouts: a (pitch, chroma_pitch, offset1, offset2, frame_stride) tuple, dict or
-        pb_planar_layout, in bytes, 0 = default.  A plan ``planar_supported`` refuses is a PbError (no fallback)."""
+        pb_planar_layout, in bytes, 0 = default.  A plan ``planar_supported`` refuses is a PbError (no fallback).
+        ``interpolation="bilinear"`` (opt-in): plane 0 is the bilinear mode's grey sample; a sample of planes 1 and 2 is sampled
+        bilinearly on its own plane at its block's top-left pixel's coordinate, halved where subsampled (chroma co-sited with that pixel);
+        within 1 + R // 512 of the written definition (R the largest sample value), on plans prepared with ``bilinear=True``."""
+        check_video_interpolation(interpolation)
         sub = planar_subsampling(subsampling)
         s, o, n, S, sl, dl = self._planar_out(*self._planar_source(src, sub, src_layout), out, dst_layout)
         with _on(s):
-            self.launch_planar(s.data_ptr(), o.data_ptr(), sub, n, stream, S, fill, sl, dl)
+            self.launch_planar(s.data_ptr(), o.data_ptr(), sub, n, stream, S, fill, sl, dl, interpolation=interpolation)
         return o
 
     def _planar_source(self, src, sub, src_layout):

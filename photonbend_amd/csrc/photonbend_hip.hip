@@ -43,6 +43,7 @@
 #include "pb_kernels_track_nv12.hpp"
 #include "pb_kernels_planar.hpp"
 #include "pb_kernels_track_planar.hpp"
+#include "pb_kernels_planar_bilinear.hpp"
 
 #define PB_DOUBLE_FRAMES_PER_WAVE 1  // frames a double-source wave loops over (the rest of a batch is a grid dimension)
 
@@ -999,11 +1000,15 @@ struct PbRoute {
         NV12_NONE,           // ... on a plan that kernel does not serve - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
         PLANAR,              // nearest, planar 4:4:4 / 4:2:2 / 4:2:0 frames (pb_remap_planar): pb_planar_hot_kernel
         PLANAR_NONE,         // ... on a plan that kernel does not serve - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
+        VIDEO_BIL,           // bilinear, planar or 4:2:0 semi-planar frames (pb_remap_planar_bilinear, pb_remap_nv12_bilinear): pb_planar_bilinear_kernel
+        VIDEO_BIL_NEAREST_NONE,  // ... on a plan the nearest call refuses too - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
+        VIDEO_BIL_NONE,      // ... on a plan without the bilinear mode's tile and coordinate tables (a cube source never has them): nothing is launched
     } kind;
     bool windows;                    // BIL_DOUBLE / bilinear INTERP_TILES: LEAN tiles gather from LDS windows
     int filter = PB_INTERP_NEAREST;  // the INTERP_* routes: PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM
     int bpp = 3;                     // PX: bytes per pixel; NV12, PLANAR: bytes per sample
-    int sub = 0;                     // PLANAR: the subsampling (PB_PLANAR_*)
+    int sub = 0;                     // PLANAR, VIDEO_BIL: the subsampling (PB_PLANAR_*)
+    bool pairs = false;              // VIDEO_BIL*: planes 1 and 2 are NV12's interleaved pairs
 };
 static bool pb_aligned16(const void* src, unsigned long long stride) { return ((((uintptr_t)src) | stride) & 15u) == 0; }
 // planar: the subsampling of a pb_remap_planar call (PB_PLANAR_*), -1 everywhere else
@@ -1012,8 +1017,15 @@ static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned fl
     if (bpp != 3 || nv12 || planar >= 0) {
         // the tile kernel of the nearest plan's launch-order table, or nothing: no window, so no alignment beyond the pixel's own
         // (pb_check_frames); fast_ready says single source, prepared, device state; generic tiles pack row and column in 16 bits each
-        const bool px = interpolation == PB_INTERP_NEAREST && n == 1 && pb_use_fast(pl) && pl->nearest.lt.entries && pl->nearest.P_dev &&
-                        P.src.width < 32768 && P.src.height < 32768;
+        const bool served = n == 1 && pb_use_fast(pl) && pl->nearest.lt.entries && pl->nearest.P_dev && P.src.width < 32768 && P.src.height < 32768;
+        const bool px = interpolation == PB_INTERP_NEAREST && served;
+        if (interpolation == PB_INTERP_BILINEAR) {
+            // the nearest call's plans, and of those the ones with the bilinear mode's launch-order, tile and exact coordinate tables (no
+            // second kernel picks up what a plan without coordinate tables leaves; a cube source never has bil.tiles: pb_bilinear_tiles_allowed)
+            const bool tabs = pl->bil.lt.entries && pl->bil.tiles && pl->bil.xy && pl->bil.fix_xy && !pb_is_cube(P.src.kind);
+            return {!served ? PbRoute::VIDEO_BIL_NEAREST_NONE : tabs ? PbRoute::VIDEO_BIL : PbRoute::VIDEO_BIL_NONE, false, PB_INTERP_BILINEAR, bpp,
+                    nv12 ? PB_PLANAR_420 : planar, nv12};
+        }
         if (nv12) return {px ? PbRoute::NV12 : PbRoute::NV12_NONE, false, PB_INTERP_NEAREST, bpp};  // (bpp: bytes per sample)
         if (planar >= 0) return {px ? PbRoute::PLANAR : PbRoute::PLANAR_NONE, false, PB_INTERP_NEAREST, bpp, planar};
         return {px ? PbRoute::PX : PbRoute::PX_NONE, false, PB_INTERP_NEAREST, bpp};
@@ -1076,7 +1088,8 @@ static void pb_launch_direct(const pb_plan* pl, const uint8_t* src, uint8_t* dst
 }
 
 // Launches a nearest or bilinear route (n = 1) for n_frames frames at strides ss / ds (pb_check_frames has filled them in).
-// nv12 / planar: the plane layouts and fills of the NV12 route (pb_remap_nv12) / the PLANAR route (pb_remap_planar), null everywhere else.
+// nv12 / planar: the plane layouts and fills of the NV12 route (pb_remap_nv12) / the PLANAR and VIDEO_BIL routes (pb_remap_planar, the two
+// bilinear video calls: an NV12 layout travels as a PbPlanar there), null everywhere else.
 static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* dst, int n_frames, unsigned long long ss, unsigned long long ds,
                      hipStream_t st, const PbNv12* nv12 = nullptr, const PbPlanar* planar = nullptr) {
     const PbParams& P = pl->P;
@@ -1181,6 +1194,34 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
         case PbRoute::PLANAR_NONE:
             return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_planar takes prepared plans of a single source in a tile mode (not deferred, not PB_MODE_FAITHFUL, not "
                                                "double-fisheye, sources below 32768 px a side): use pb_index_map_i32 and gather the three planes");
+        case PbRoute::VIDEO_BIL: {
+            // launched like the Catmull-Rom tile kernel: the bilinear mode's launch-order table read with four waves per workgroup
+            const unsigned gpf = pl->bil.lt.groups;
+            pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
+                pb_pick_kind(P, [&](auto K) {
+                    pb_pick<1, 2>(r.bpp == 1, [&](auto S) {
+                        auto go = [&](auto SUB, auto PAIRS) {
+                            hipLaunchKernelGGL((pb_planar_bilinear_kernel<K.value, S.value, SUB.value, PAIRS.value != 0>), dim3(gpf * (unsigned)nf), dim3(64 * PB_VBIL_WAVES),
+                                               0, st, pb_hot_of_host(P), pl->bil.lt.entries, sf, df, gpf, ss, ds, pl->bil.xy, pl->cert.fix_px, pl->bil.fix_xy, *planar);
+                        };
+                        if (r.pairs) go(PbInt<PB_SUB_420>(), PbInt<1>());
+                        else pb_pick_subsampling(r.sub, [&](auto SUB) { go(SUB, PbInt<0>()); });
+                    });
+                });
+            });
+            break;
+        }
+        case PbRoute::VIDEO_BIL_NEAREST_NONE:
+        case PbRoute::VIDEO_BIL_NONE: {
+            const std::string name = r.pairs ? "pb_remap_nv12_bilinear" : "pb_remap_planar_bilinear";
+            if (r.kind == PbRoute::VIDEO_BIL_NEAREST_NONE)
+                return pb_fail(PB_ERR_UNSUPPORTED, name + " takes prepared plans of a single source in a tile mode (not deferred, not PB_MODE_FAITHFUL, not "
+                                                          "double-fisheye, sources below 32768 px a side): convert to RGB and use pb_remap_bilinear_u8");
+            if (pb_is_cube(P.src.kind))
+                return pb_fail(PB_ERR_UNSUPPORTED, name + " takes camera and panorama sources (a cube source has no interpolating tile kernel): convert to RGB and use "
+                                                          "pb_remap_bilinear_u8");
+            return pb_fail(PB_ERR_UNSUPPORTED, name + " needs the bilinear mode's tile and coordinate tables: call pb_plan_prepare(plan, PB_PLAN_BILINEAR) first");
+        }
         case PbRoute::BIL_DOUBLE: {
             // the per-eye tile models of the nearest mode's plan + the exact coordinate tables: one wave per tile
             const unsigned gpf = pb_bil_groups(pl);
@@ -2012,6 +2053,26 @@ int pb_plan_bilinear_tile_mix(const pb_plan* plan, long long mix[8]) {
     PB_HIP(e);
     return PB_OK;
 }
+int pb_plan_video_bilinear_mix(const pb_plan* plan, long long mix[4]) {
+    if (!plan || !mix) return pb_fail(PB_ERR_INVALID, "null argument");
+    for (int k = 0; k < 4; ++k) mix[k] = 0;
+    if (!plan->cert.fast_ready || !plan->bil.lt.entries || plan->bil.lt.groups == 0 || !plan->cert.n_fix_px) return PB_OK;
+    if (int rc = pb_check_device(plan)) return rc;
+    PbBlock<unsigned> counters;
+    PB_HIP(counters.alloc(4));
+    hipError_t e = hipMemsetAsync(counters, 0, 4 * sizeof(unsigned), 0);
+    if (e == hipSuccess) {
+        const unsigned n_slots = 4u * plan->bil.lt.groups;
+        hipLaunchKernelGGL(pb_video_bilinear_mix_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, 0, plan->bil.lt.entries, n_slots, plan->cert.fix_px, plan->P.dst.width,
+                           counters);
+        unsigned res[4] = {0, 0, 0, 0};
+        e = hipMemcpy(res, counters, sizeof(res), hipMemcpyDeviceToHost);
+        for (int k = 0; k < 4; ++k) mix[k] = res[k];
+    }
+    if (e != hipSuccess) (void)hipDeviceSynchronize();
+    PB_HIP(e);
+    return PB_OK;
+}
 int pb_plan_bilinear_launch_shape(const pb_plan* plan, int* lds_bytes, int* workgroups_per_frame) {
     if (!plan || !lds_bytes || !workgroups_per_frame) return pb_fail(PB_ERR_INVALID, "null argument");
     const bool tiles = (plan->cert.fast_ready || plan->cert.dbl_ready) && plan->bil.lt.entries && plan->bil.lt.groups > 0;
@@ -2086,7 +2147,6 @@ static bool pb_nv12_dims_even(const pb_plan* plan) {
     const PbParams& P = plan->P;
     return !((P.src.height | P.src.width | P.dst.height | P.dst.width) & 1);
 }
-static bool pb_nv12_served(const pb_plan* plan, int S) { return pb_route(plan, PB_INTERP_NEAREST, 1, 0, false, S, true).kind == PbRoute::NV12; }
 // The arguments of the two 4:2:0 entry points (pb_remap_nv12, pb_remap_track_nv12), in this order: null plan / frames, the frame count,
 // the sample size, even dimensions, the two layouts, the pointers' alignment.  Resolves the layouts, and the fills in stored form.
 struct PbNv12Call {
@@ -2112,26 +2172,41 @@ static int pb_nv12_check(const pb_plan* plan, const void* src_dev, const void* d
     c.L = {(unsigned)c.fs.pitch, (unsigned)c.fs.uv, (unsigned)c.fd.pitch, (unsigned)c.fd.uv, fy, fu | (fv << (8u * (unsigned)S))};
     return PB_OK;
 }
-int pb_remap_nv12(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout,
-                  int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
+// the two 4:2:0 semi-planar calls: nearest (pb_nv12_hot_kernel) and bilinear (pb_planar_bilinear_kernel with pairs; the layout as a PbPlanar)
+static int pb_nv12_call(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout,
+                        int bytes_per_sample, const uint16_t fill_yuv[3], void* stream, int interpolation, const char* name) {
     PbNv12Call c;
     int rc = pb_nv12_check(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, bytes_per_sample, fill_yuv, c);
     if (rc != PB_OK || n_frames == 0) return rc;
     rc = pb_check_device(plan);
     if (rc != PB_OK) return rc;
-    const PbRoute r = pb_route(plan, PB_INTERP_NEAREST, 1, 0, false, bytes_per_sample, true);
-    if (r.kind == PbRoute::NV12 && (c.fs.span >= (1ull << 31) || c.fd.span >= (1ull << 31)))
-        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_nv12 takes frames whose planes span less than 2^31 bytes: use pb_index_map_i32 and gather the two planes");
-    return pb_launch(plan, r, static_cast<const uint8_t*>(src_dev), static_cast<uint8_t*>(dst_dev), n_frames, c.fs.stride, c.fd.stride, (hipStream_t)stream, &c.L);
+    const PbRoute r = pb_route(plan, interpolation, 1, 0, false, bytes_per_sample, true);
+    if ((r.kind == PbRoute::NV12 || r.kind == PbRoute::VIDEO_BIL) && (c.fs.span >= (1ull << 31) || c.fd.span >= (1ull << 31)))
+        return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes frames whose planes span less than 2^31 bytes: use pb_index_map_i32 and gather the two planes");
+    const unsigned sbits = 8u * (unsigned)bytes_per_sample, smask = (1u << sbits) - 1u;
+    const PbPlanar Lp = {c.L.src_pitch, c.L.src_pitch, c.L.src_uv, 0u, c.L.dst_pitch, c.L.dst_pitch, c.L.dst_uv, 0u, {c.L.fill_y, c.L.fill_uv & smask, c.L.fill_uv >> sbits}};
+    return pb_launch(plan, r, static_cast<const uint8_t*>(src_dev), static_cast<uint8_t*>(dst_dev), n_frames, c.fs.stride, c.fd.stride, (hipStream_t)stream, &c.L, &Lp);
 }
-int pb_remap_nv12_supported(const pb_plan* plan, int bytes_per_sample) {
+int pb_remap_nv12_bilinear(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout,
+                           int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
+    return pb_nv12_call(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, bytes_per_sample, fill_yuv, stream, PB_INTERP_BILINEAR, "pb_remap_nv12_bilinear");
+}
+int pb_remap_nv12(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout,
+                  int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
+    return pb_nv12_call(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, bytes_per_sample, fill_yuv, stream, PB_INTERP_NEAREST, "pb_remap_nv12");
+}
+static int pb_nv12_supported(const pb_plan* plan, int bytes_per_sample, int interpolation);
+int pb_remap_nv12_supported(const pb_plan* plan, int bytes_per_sample) { return pb_nv12_supported(plan, bytes_per_sample, PB_INTERP_NEAREST); }
+int pb_remap_nv12_bilinear_supported(const pb_plan* plan, int bytes_per_sample) { return pb_nv12_supported(plan, bytes_per_sample, PB_INTERP_BILINEAR); }
+static int pb_nv12_supported(const pb_plan* plan, int bytes_per_sample, int interpolation) {
     if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
     if (bytes_per_sample != 1 && bytes_per_sample != 2) return pb_fail(PB_ERR_INVALID, "bytes_per_sample outside {1, 2}");
     if (!pb_nv12_dims_even(plan)) return pb_fail(PB_ERR_INVALID, "4:2:0 frames need even source and destination dimensions");
     // (packed frames: 3/2 S h w bytes; a pitched layout's span is pb_remap_nv12's to check)
     const PbParams& P = plan->P;
     const unsigned long long S = (unsigned long long)bytes_per_sample;
-    return pb_nv12_served(plan, bytes_per_sample) && 3 * S * P.src.height * P.src.width / 2 < (1ull << 31) && 3 * S * P.dst.height * P.dst.width / 2 < (1ull << 31);
+    const PbRoute::Kind k = pb_route(plan, interpolation, 1, 0, false, bytes_per_sample, true).kind;
+    return (k == PbRoute::NV12 || k == PbRoute::VIDEO_BIL) && 3 * S * P.src.height * P.src.width / 2 < (1ull << 31) && 3 * S * P.dst.height * P.dst.width / 2 < (1ull << 31);
 }
 
 // Planar frames.  Every check comes before the device is looked at and before any launch.
@@ -2200,19 +2275,33 @@ static int pb_planar_check(const pb_plan* plan, const void* src_dev, const void*
     return PB_OK;
 }
 static bool pb_planar_span_fits(const PbPlanarCall& c) { return c.fs.span < (1ull << 31) && c.fd.span < (1ull << 31); }
-int pb_remap_planar(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout,
-                    int subsampling, int bytes_per_sample, const uint16_t fill[3], void* stream) {
+// the two planar calls: nearest (pb_planar_hot_kernel) and bilinear (pb_planar_bilinear_kernel)
+static int pb_planar_call(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout,
+                          int subsampling, int bytes_per_sample, const uint16_t fill[3], void* stream, int interpolation, const char* name) {
     PbPlanarCall c;
     int rc = pb_planar_check(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, subsampling, bytes_per_sample, fill, c);
     if (rc != PB_OK || n_frames == 0) return rc;
     rc = pb_check_device(plan);
     if (rc != PB_OK) return rc;
-    const PbRoute r = pb_route(plan, PB_INTERP_NEAREST, 1, 0, false, bytes_per_sample, false, subsampling);
-    if (r.kind == PbRoute::PLANAR && !pb_planar_span_fits(c))
-        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_planar takes frames whose planes span less than 2^31 bytes: use pb_index_map_i32 and gather the three planes");
+    const PbRoute r = pb_route(plan, interpolation, 1, 0, false, bytes_per_sample, false, subsampling);
+    if ((r.kind == PbRoute::PLANAR || r.kind == PbRoute::VIDEO_BIL) && !pb_planar_span_fits(c))
+        return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes frames whose planes span less than 2^31 bytes: use pb_index_map_i32 and gather the three planes");
     return pb_launch(plan, r, static_cast<const uint8_t*>(src_dev), static_cast<uint8_t*>(dst_dev), n_frames, c.fs.stride, c.fd.stride, (hipStream_t)stream, nullptr, &c.L);
 }
-int pb_remap_planar_supported(const pb_plan* plan, int subsampling, int bytes_per_sample) {
+int pb_remap_planar(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout,
+                    int subsampling, int bytes_per_sample, const uint16_t fill[3], void* stream) {
+    return pb_planar_call(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, subsampling, bytes_per_sample, fill, stream, PB_INTERP_NEAREST, "pb_remap_planar");
+}
+int pb_remap_planar_bilinear(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout,
+                             int subsampling, int bytes_per_sample, const uint16_t fill[3], void* stream) {
+    return pb_planar_call(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, subsampling, bytes_per_sample, fill, stream, PB_INTERP_BILINEAR, "pb_remap_planar_bilinear");
+}
+static int pb_planar_supported(const pb_plan* plan, int subsampling, int bytes_per_sample, int interpolation);
+int pb_remap_planar_supported(const pb_plan* plan, int subsampling, int bytes_per_sample) { return pb_planar_supported(plan, subsampling, bytes_per_sample, PB_INTERP_NEAREST); }
+int pb_remap_planar_bilinear_supported(const pb_plan* plan, int subsampling, int bytes_per_sample) {
+    return pb_planar_supported(plan, subsampling, bytes_per_sample, PB_INTERP_BILINEAR);
+}
+static int pb_planar_supported(const pb_plan* plan, int subsampling, int bytes_per_sample, int interpolation) {
     if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
     if (bytes_per_sample != 1 && bytes_per_sample != 2) return pb_fail(PB_ERR_INVALID, "bytes_per_sample outside {1, 2}");
     if (!pb_planar_sub_ok(subsampling)) return pb_fail(PB_ERR_INVALID, "subsampling outside {PB_PLANAR_444, PB_PLANAR_422, PB_PLANAR_420}");
@@ -2225,7 +2314,8 @@ int pb_remap_planar_supported(const pb_plan* plan, int subsampling, int bytes_pe
     if (pb_planar_resolve("source", nullptr, S, (unsigned long long)P.src.height, (unsigned long long)P.src.width, cx, cy, fs) != PB_OK ||
         pb_planar_resolve("destination", nullptr, S, (unsigned long long)P.dst.height, (unsigned long long)P.dst.width, cx, cy, fd) != PB_OK)
         return 0;
-    return pb_route(plan, PB_INTERP_NEAREST, 1, 0, false, bytes_per_sample, false, subsampling).kind == PbRoute::PLANAR && fs.span < (1ull << 31) && fd.span < (1ull << 31);
+    const PbRoute::Kind k = pb_route(plan, interpolation, 1, 0, false, bytes_per_sample, false, subsampling).kind;
+    return (k == PbRoute::PLANAR || k == PbRoute::VIDEO_BIL) && fs.span < (1ull << 31) && fd.span < (1ull << 31);
 }
 
 int pb_remap_u8v(const pb_plan* plan, const uint8_t* const* src_dev, uint8_t* const* dst_dev, int n_frames, void* stream) {

@@ -432,6 +432,14 @@ def _video_chain(width, height, otype, lens, fov, size, rotation, lens_coefficie
     return cmap
 
 
+def _video_sampler(interpolation: str, track) -> bool:
+    """--interpolation of a raw-video command -> whether the plan carries the bilinear mode's tables.  With a rotation track it is a usage
+    error, raised before any input is read: the track kernels sample nearest."""
+    if interpolation != "nearest" and track is not None:
+        _fail(f"--interpolation {interpolation} does not go with --rotations: a rotation track is sampled nearest")
+    return interpolation == "bilinear"
+
+
 def _stream_frames(input_frames, output_frames, frame_in: int, dt, chunk: int, mats, remap) -> None:
     """The frame loop of a raw-video command: `chunk` packed frames of frame_in bytes at a time from a file or stdin through
     remap(host (n, samples of a frame), index of the first frame) -> device frames, written to a file or stdout.  A truncated frame and a
@@ -486,7 +494,9 @@ def _stream_frames(input_frames, output_frames, frame_in: int, dt, chunk: int, m
 @click.option("--rotations", "track", type=click.Path(exists=True, dir_okay=False, path_type=Path), default=None,
               help="A rotation track: a text file of one `pitch yaw roll` line in degrees per frame, applied after every -r.")
 @click.option("--chunk", type=click.INT, default=8, show_default=True, help=f"Frames per launch, a multiple of {TRACK_FRAMES}.")
-def remap_nv12(input_frames, output_frames, width, height, pix_fmt, otype, lens, fov, size, rotation, track, chunk, lens_coefficients, lens_max_theta):
+@click.option("--interpolation", type=click.Choice(list(nat.VIDEO_INTERPOLATIONS)), default="nearest", show_default=True,
+              help="The sampler: nearest (the reference's) or bilinear (chroma co-sited with its block's top-left pixel; not with --rotations).")
+def remap_nv12(input_frames, output_frames, width, height, pix_fmt, otype, lens, fov, size, rotation, track, chunk, interpolation, lens_coefficients, lens_max_theta):
     """Remap raw NV12 / P010 video frames of an equirectangular panorama, e.g. between two `ffmpeg -f rawvideo -pix_fmt nv12` pipes.
 
     \b
@@ -494,6 +504,7 @@ def remap_nv12(input_frames, output_frames, width, height, pix_fmt, otype, lens,
     OUTPUT receives the packed output frames; - is stdout.
     By default the output is a panorama of the same size (--size H: H x 2H); with --type, --lens and --fov it is the photo make-photo would make.
     """
+    bilinear = _video_sampler(interpolation, track)
     dt = np.dtype(PIX_FMTS[pix_fmt])
     if width < 2 or height < 2 or (width | height) & 1:
         _fail(f"4:2:0 frames have even dimensions, got --width {width} --height {height}")
@@ -513,9 +524,9 @@ def remap_nv12(input_frames, output_frames, width, height, pix_fmt, otype, lens,
     def remap(host, first):  # upload, ONE launch, download
         nonlocal plan
         if plan is None:  # (made with the first frames: the usage errors of the input come before any plan is prepared)
-            plan = nat.Plan(dstp, list(cmap.rotations), srcp, bilinear=False) if mats is None else nat.Plan(dstp, list(cmap.rotations), srcp, defer=True)
+            plan = nat.Plan(dstp, list(cmap.rotations), srcp, bilinear=bilinear) if mats is None else nat.Plan(dstp, list(cmap.rotations), srcp, defer=True)
         s = nat.to_device(host.reshape(len(host), 3 * height // 2, width))
-        return plan.remap_nv12(s) if mats is None else plan.remap_track_nv12(s, mats[first : first + len(host)])
+        return plan.remap_nv12(s, **_sampler(interpolation)) if mats is None else plan.remap_track_nv12(s, mats[first : first + len(host)])
 
     _stream_frames(input_frames, output_frames, frame_in, dt, chunk, mats, remap)
 
@@ -536,7 +547,9 @@ def remap_nv12(input_frames, output_frames, width, height, pix_fmt, otype, lens,
 @click.option("--rotations", "track", type=click.Path(exists=True, dir_okay=False, path_type=Path), default=None,
               help="A rotation track: a text file of one `pitch yaw roll` line in degrees per frame, applied after every -r.")
 @click.option("--chunk", type=click.INT, default=8, show_default=True, help=f"Frames per launch, a multiple of {TRACK_FRAMES}.")
-def remap_yuv(input_frames, output_frames, width, height, pix_fmt, otype, lens, fov, size, rotation, track, chunk, lens_coefficients, lens_max_theta):
+@click.option("--interpolation", type=click.Choice(list(nat.VIDEO_INTERPOLATIONS)), default="nearest", show_default=True,
+              help="The sampler: nearest (the reference's) or bilinear (chroma co-sited with its block's top-left pixel; not with --rotations).")
+def remap_yuv(input_frames, output_frames, width, height, pix_fmt, otype, lens, fov, size, rotation, track, chunk, interpolation, lens_coefficients, lens_max_theta):
     """Remap raw PLANAR video frames of an equirectangular panorama - yuv420p, yuv422p, yuv444p, their 10- and 16-bit forms, gbrp - e.g.
     between two `ffmpeg -f rawvideo -pix_fmt yuv420p` pipes.
 
@@ -546,6 +559,7 @@ def remap_yuv(input_frames, output_frames, width, height, pix_fmt, otype, lens, 
     By default the output is a panorama of the same size (--size H: H x 2H); with --type, --lens and --fov it is the photo make-photo would make.
     4:2:0 formats have even widths and heights, 4:2:2 formats even widths, 4:4:4 formats (gbrp among them) take any size.
     """
+    bilinear = _video_sampler(interpolation, track)
     dt, sub, fill = nat.PLANAR_FORMATS[pix_fmt]
     rule = nat.planar_dims_rule(sub, pix_fmt)
     if width < 1 or height < 1 or not nat.planar_dims_ok(sub, (height, width)):
@@ -566,9 +580,9 @@ def remap_yuv(input_frames, output_frames, width, height, pix_fmt, otype, lens, 
     def remap(host, first):  # upload, ONE launch, download
         nonlocal plan
         if plan is None:  # (made with the first frames: the usage errors of the input come before any plan is prepared)
-            plan = nat.Plan(dstp, list(cmap.rotations), srcp, bilinear=False) if mats is None else nat.Plan(dstp, list(cmap.rotations), srcp, defer=True)
+            plan = nat.Plan(dstp, list(cmap.rotations), srcp, bilinear=bilinear) if mats is None else nat.Plan(dstp, list(cmap.rotations), srcp, defer=True)
         s = nat.to_device(host)
-        return plan.remap_planar(s, sub, fill=fill) if mats is None else plan.remap_track_planar(s, mats[first : first + len(host)], sub, fill=fill)
+        return plan.remap_planar(s, sub, fill=fill, **_sampler(interpolation)) if mats is None else plan.remap_track_planar(s, mats[first : first + len(host)], sub, fill=fill)
 
     _stream_frames(input_frames, output_frames, frame_in, dt, chunk, mats, remap)
 
