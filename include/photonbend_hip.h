@@ -448,6 +448,34 @@ int pb_remap_track_nv12(const pb_plan* plan, const double* rot3x3_dev, int n_rot
                         const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3],
                         void* stream);
 
+/* OPT-IN: BILINEAR ROTATION TRACKS FOR VIDEO FRAMES (ABI 5, additive): pb_remap_track_nv12's and pb_remap_track_planar's
+ * arguments and launches, sampled bilinearly - smooth stabilised, levelled or reframed video without a plan per frame.  Frame f receives
+ * the definition of pb_remap_planar_bilinear / pb_remap_nv12_bilinear above (tests/video_bilinear_ref.py: plane 0 the grey bilinear sample,
+ * planes 1 and 2 decided by their anchor, chroma co-sited top-left, the anchor's coordinate halved where the plane is subsampled) with f and
+ * "live" those of the float64 chain "this plan's own n_rot rotations followed by the n_rot_per_frame matrices of table entry f", applied
+ * one after another as for pb_remap_track_u8 (nothing folded).  A panorama source is live where the entry is not invalid and finite, a
+ * camera source additionally where 0 <= fy < height and 0 <= fx < width.
+ * Precision: the kernel (pb_track_video_bilinear_kernel) holds the chain's float64 coordinate itself, not a certified model, and evaluates
+ * the three lerps in float64 in the definition's order: every sample is the definition's bytes exactly, for 8-, 10- and 16-bit samples
+ * alike.  There is no tolerance and no edge band.
+ * The plan's tables are never read: a deferred plan, a prepared one, with or without the bilinear mode's tables, and any mode are served
+ * alike.
+ *   PB_ERR_INVALID       checks, order and messages are the nearest tracked calls': pb_remap_nv12's / pb_remap_planar's, then
+ *                        pb_remap_track_u8's table checks.  n_frames == 0: PB_OK, no launch, no device.
+ *   PB_ERR_UNSUPPORTED   nothing is written: a double-fisheye source; cube and equi-angular-cube sources (the definition covers panorama
+ *                        and camera sources, as for the untracked bilinear video calls); frames whose byte span reaches 2^31 or sources
+ *                        of 32768 px a side or more.
+ * Asynchronous on `stream`; never allocates, never synchronises, never copies the table (graph-capture safe); one launch per 65535 chunks
+ * of frames.  (The return type stands on a line of its own, as for the bilinear video calls above.) */
+int
+pb_remap_track_nv12_bilinear(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                                 const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3],
+                                 void* stream);
+int
+pb_remap_track_planar_bilinear(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                                   const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample,
+                                   const uint16_t fill[3], void* stream);
+
 /* SUPERSAMPLED REMAPPING (ABI 5, additive).  Output pixel (i, j) is, per channel, the round-half-to-even mean of the n x n block
  * S[n i : n i + n, n j : n j + n] of S = the remap of the n x destination: the same kind and lens with image (n H, n W) and, for a camera,
  * magnitude n x (a double fisheye's magnitude = height / 2 scales by itself); n in {2, 4}, a power of two, so its f_distance is exactly

@@ -128,6 +128,8 @@ SIGNATURES = {
     "pb_remap_track_u8": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_track_nv12": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP]),
     "pb_remap_track_planar": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, _VP]),
+    "pb_remap_track_nv12_bilinear": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP]),
+    "pb_remap_track_planar_bilinear": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, _VP]),
     "pb_remap_ss_workspace": (C.c_int, [_VP, C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_size_t)]),
     "pb_remap_ss_u8": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP, C.c_size_t, C.c_uint, _VP]),
     "pb_box_reduce": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
@@ -1024,20 +1026,26 @@ class Plan:
         return s, o, n, S, sl, dl
 
     def launch_track_nv12(self, table_ptr: int, n_rot_per_frame: int, src_ptr: int, dst_ptr: int, n_frames: int = 1, stream: int | None = None,
-                          bytes_per_sample: int = 1, fill=None, src_layout=None, dst_layout=None) -> None:
-        """The raw rotation-track call for video frames (pb_remap_track_nv12): ``launch_track``'s table, ``launch_nv12``'s frames, layouts
-        and fill.  The table must stay alive and unchanged until the stream has run the launch."""
+                          bytes_per_sample: int = 1, fill=None, src_layout=None, dst_layout=None, *, interpolation: str = "nearest") -> None:
+        """The raw rotation-track call for video frames (pb_remap_track_nv12; ``interpolation="bilinear"``: pb_remap_track_nv12_bilinear):
+        ``launch_track``'s table, ``launch_nv12``'s frames, layouts and fill.  The table must stay alive and unchanged until the stream
+        has run the launch."""
+        fn = load().pb_remap_track_nv12_bilinear if check_video_interpolation(interpolation) else load().pb_remap_track_nv12
         f = None if fill is None else (C.c_uint16 * 3)(*[int(v) for v in fill])
         sl, dl = nv12_layout(src_layout), nv12_layout(dst_layout)
-        self._gated(load().pb_remap_track_nv12, self._h, table_ptr, int(n_rot_per_frame), src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl),
+        self._gated(fn, self._h, table_ptr, int(n_rot_per_frame), src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl),
                     None if dl is None else C.addressof(dl), int(bytes_per_sample), None if f is None else C.addressof(f), current_stream() if stream is None else stream)
 
-    def remap_track_nv12(self, src, rotations, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None):
+    def remap_track_nv12(self, src, rotations, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None, *,
+                         interpolation: str = "nearest"):
         """NV12 (uint8) or P010 / P016 (uint16) video frames with a rotation per frame in ONE launch (pb_remap_track_nv12):
         frame f is ``remap_nv12``'s definition with the index map of this plan's rotations followed by ``rotations[f]``.  ``src``, ``out``,
         ``fill`` and the layouts follow ``remap_nv12``'s rules, ``rotations`` follows ``rotation_table``'s as for ``remap_track``; the frame
         count must equal the table's (ValueError).  Any plan of a single source is served alike, a deferred one included.  Shapes, dtypes
-        and counts are checked before any device work."""
+        and counts are checked before any device work.  ``interpolation="bilinear"`` (opt-in, pb_remap_track_nv12_bilinear):
+        frame f is ``remap_nv12``'s bilinear definition at the float64 coordinates of that chain - its bytes exactly, for either sample
+        size; panorama and camera sources."""
+        check_video_interpolation(interpolation)
         source = self._nv12_source(src, src_layout)
         n = source[-1]
         tab, n_tab, k = rotation_table(rotations, self.n_rot)
@@ -1047,7 +1055,7 @@ class Plan:
         with _on(s):
             st = current_stream() if stream is None else stream
             tab, release = self._track_table(tab, s, st)
-            self.launch_track_nv12(tab.data_ptr(), k, s.data_ptr(), o.data_ptr(), n, st, S, fill, sl, dl)
+            self.launch_track_nv12(tab.data_ptr(), k, s.data_ptr(), o.data_ptr(), n, st, S, fill, sl, dl, interpolation=interpolation)
             release()
         return o
 
@@ -1156,21 +1164,27 @@ class Plan:
         return s, o, n, S, sl, dl
 
     def launch_track_planar(self, table_ptr: int, n_rot_per_frame: int, src_ptr: int, dst_ptr: int, subsampling, n_frames: int = 1, stream: int | None = None,
-                            bytes_per_sample: int = 1, fill=None, src_layout=None, dst_layout=None) -> None:
-        """The raw rotation-track call for planar frames (pb_remap_track_planar): ``launch_track``'s table, ``launch_planar``'s frames,
-        layouts and fill.  The table must stay alive and unchanged until the stream has run the launch."""
+                            bytes_per_sample: int = 1, fill=None, src_layout=None, dst_layout=None, *, interpolation: str = "nearest") -> None:
+        """The raw rotation-track call for planar frames (pb_remap_track_planar; ``interpolation="bilinear"``:
+        pb_remap_track_planar_bilinear): ``launch_track``'s table, ``launch_planar``'s frames, layouts and fill.  The table must stay
+        alive and unchanged until the stream has run the launch."""
+        fn = load().pb_remap_track_planar_bilinear if check_video_interpolation(interpolation) else load().pb_remap_track_planar
         f = None if fill is None else (C.c_uint16 * 3)(*[int(v) for v in fill])
         sl, dl = planar_layout(src_layout), planar_layout(dst_layout)
-        self._gated(load().pb_remap_track_planar, self._h, table_ptr, int(n_rot_per_frame), src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl),
+        self._gated(fn, self._h, table_ptr, int(n_rot_per_frame), src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl),
                     None if dl is None else C.addressof(dl), planar_subsampling(subsampling), int(bytes_per_sample), None if f is None else C.addressof(f),
                     current_stream() if stream is None else stream)
 
-    def remap_track_planar(self, src, rotations, subsampling, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None):
+    def remap_track_planar(self, src, rotations, subsampling, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None, *,
+                           interpolation: str = "nearest"):
         """Planar video frames with a rotation per frame in ONE launch (pb_remap_track_planar): frame f is ``remap_planar``'s
         definition with the index map of this plan's rotations followed by ``rotations[f]``.  ``src``, ``subsampling``, ``out``, ``fill``
         and the layouts follow ``remap_planar``'s rules, ``rotations`` follows ``rotation_table``'s as for ``remap_track``; the frame count
         must equal the table's (ValueError).  Any plan of a single source is served alike, a deferred one included.  Shapes, dtypes and
-        counts are checked before any device work."""
+        counts are checked before any device work.  ``interpolation="bilinear"`` (opt-in, pb_remap_track_planar_bilinear):
+        frame f is ``remap_planar``'s bilinear definition at the float64 coordinates of that chain - its bytes exactly, for either sample
+        size; panorama and camera sources."""
+        check_video_interpolation(interpolation)
         source = self._planar_source(src, planar_subsampling(subsampling), src_layout)
         n = source[-1]
         tab, n_tab, k = rotation_table(rotations, self.n_rot)
@@ -1180,7 +1194,7 @@ class Plan:
         with _on(s):
             st = current_stream() if stream is None else stream
             tab, release = self._track_table(tab, s, st)
-            self.launch_track_planar(tab.data_ptr(), k, s.data_ptr(), o.data_ptr(), source[1], n, st, S, fill, sl, dl)
+            self.launch_track_planar(tab.data_ptr(), k, s.data_ptr(), o.data_ptr(), source[1], n, st, S, fill, sl, dl, interpolation=interpolation)
             release()
         return o
 

@@ -7,6 +7,7 @@
 //   pb_kernels_sep.hpp       separable tables for the unrotated stitch (row factors; unaligned-frame fallback)
 //   pb_kernels_bilinear.hpp  opt-in bilinear sampling
 //   pb_kernels_track.hpp     rotation tracks: a rotation per frame in one launch of the float64 chain
+//   pb_kernels_track_video_bilinear.hpp  ... of video frames, sampled bilinearly
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared ...
 // (-ffp-contract=off is REQUIRED: the reference rounds every multiply and add
@@ -44,6 +45,7 @@
 #include "pb_kernels_planar.hpp"
 #include "pb_kernels_track_planar.hpp"
 #include "pb_kernels_planar_bilinear.hpp"
+#include "pb_kernels_track_video_bilinear.hpp"
 
 #define PB_DOUBLE_FRAMES_PER_WAVE 1  // frames a double-source wave loops over (the rest of a batch is a grid dimension)
 
@@ -2434,10 +2436,12 @@ int pb_remap_track_u8(const pb_plan* plan, const double* rot3x3_dev, int n_rot_p
     return PB_OK;
 }
 
-// A rotation track of 4:2:0 semi-planar frames: pb_remap_nv12's argument checks, then pb_remap_track_u8's table checks; the
-// launches are pb_remap_track_u8's, one per 65535 chunks of frames.
-int pb_remap_track_nv12(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
-                        const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
+// A rotation track of 4:2:0 semi-planar frames (bilinear: 3.19): pb_remap_nv12's argument checks, then pb_remap_track_u8's table
+// checks; the launches are pb_remap_track_u8's, one per 65535 chunks of frames.  Nearest: pb_track_nv12_kernel; bilinear:
+// pb_track_video_bilinear_kernel with pairs (the layout as a PbPlanar), a panorama or camera source.
+static int pb_track_nv12_call(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                              const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3], void* stream,
+                              int interpolation, const char* name) {
     PbNv12Call c;
     int rc = pb_nv12_check(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, bytes_per_sample, fill_yuv, c);
     if (rc == PB_OK) rc = pb_track_table_check(plan, rot3x3_dev, n_rot_per_frame);
@@ -2446,35 +2450,58 @@ int pb_remap_track_nv12(const pb_plan* plan, const double* rot3x3_dev, int n_rot
     if (rc != PB_OK) return rc;
     const PbParams& P = plan->P;
     if (P.src.kind == PB_KIND_DOUBLE)
-        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_track_nv12 takes single sources (a double fisheye's blend is sample-typed): convert to RGB8 and use pb_remap_track_u8");
+        return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes single sources (a double fisheye's blend is sample-typed): convert to RGB8 and use pb_remap_track_u8");
+    if (interpolation == PB_INTERP_BILINEAR && pb_is_cube(P.src.kind))
+        return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes panorama and camera sources (the bilinear definition of video frames covers no cube map): convert to "
+                                                               "RGB8 and use pb_remap_track_u8");
     if (c.fs.span >= (1ull << 31) || c.fd.span >= (1ull << 31) || P.src.height >= 32768 || P.src.width >= 32768)
-        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_track_nv12 takes frames whose planes span less than 2^31 bytes and sources below 32768 px a side: use a plan per "
-                                           "frame with pb_index_map_i32 and gather the two planes");
+        return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes frames whose planes span less than 2^31 bytes and sources below 32768 px a side: use a plan per "
+                                                               "frame with pb_index_map_i32 and gather the two planes");
     hipStream_t st = (hipStream_t)stream;
     const unsigned long long quads = (unsigned long long)P.dst.height * (((unsigned)P.dst.width + PB_PX - 1) / PB_PX);
     const int fpc = pb_track_fpc();
     const int per_launch = 65535 * fpc;
+    const unsigned sbits = 8u * (unsigned)bytes_per_sample, smask = (1u << sbits) - 1u;
+    const PbPlanar Lp = {c.L.src_pitch, c.L.src_pitch, c.L.src_uv, 0u, c.L.dst_pitch, c.L.dst_pitch, c.L.dst_uv, 0u, {c.L.fill_y, c.L.fill_uv & smask, c.L.fill_uv >> sbits}};
     for (int f0 = 0; f0 < n_frames; f0 += per_launch) {
         const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
         const double* rot = rot3x3_dev + 9ull * (unsigned)n_rot_per_frame * (unsigned)f0;
         const uint8_t* s = static_cast<const uint8_t*>(src_dev) + (unsigned long long)f0 * c.fs.stride;
         uint8_t* d = static_cast<uint8_t*>(dst_dev) + (unsigned long long)f0 * c.fd.stride;
         const dim3 grid(pb_blocks(quads), (unsigned)((nf + fpc - 1) / fpc));
-        pb_pick_exact_kind(P, [&](auto K) {
-            pb_pick<1, 2>(bytes_per_sample == 1, [&](auto S) {
-                hipLaunchKernelGGL((pb_track_nv12_kernel<S.value, K.value>), grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride, c.fd.stride, c.L);
+        if (interpolation == PB_INTERP_BILINEAR)
+            pb_pick_kind(P, [&](auto K) {
+                pb_pick<1, 2>(bytes_per_sample == 1, [&](auto S) {
+                    hipLaunchKernelGGL((pb_track_video_bilinear_kernel<S.value, K.value, true>), grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride,
+                                       c.fd.stride, Lp, 1, 1);
+                });
             });
-        });
+        else
+            pb_pick_exact_kind(P, [&](auto K) {
+                pb_pick<1, 2>(bytes_per_sample == 1, [&](auto S) {
+                    hipLaunchKernelGGL((pb_track_nv12_kernel<S.value, K.value>), grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride, c.fd.stride, c.L);
+                });
+            });
     }
     PB_HIP(hipGetLastError());
     return PB_OK;
 }
+int pb_remap_track_nv12(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                        const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
+    return pb_track_nv12_call(plan, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, n_frames, src_layout, dst_layout, bytes_per_sample, fill_yuv, stream, PB_INTERP_NEAREST,
+                              "pb_remap_track_nv12");
+}
+int pb_remap_track_nv12_bilinear(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                                 const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
+    return pb_track_nv12_call(plan, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, n_frames, src_layout, dst_layout, bytes_per_sample, fill_yuv, stream, PB_INTERP_BILINEAR,
+                              "pb_remap_track_nv12_bilinear");
+}
 
-// A rotation track of planar frames: pb_remap_planar's argument checks, then pb_remap_track_u8's table checks; the launches
-// are pb_remap_track_nv12's.
-int pb_remap_track_planar(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
-                          const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample, const uint16_t fill[3],
-                          void* stream) {
+// A rotation track of planar frames (bilinear: 3.19): pb_remap_planar's argument checks, then pb_remap_track_u8's table checks;
+// the launches are pb_remap_track_nv12's.  Nearest: pb_track_planar_kernel; bilinear: pb_track_video_bilinear_kernel, a panorama or camera source.
+static int pb_track_planar_call(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                                const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample, const uint16_t fill[3],
+                                void* stream, int interpolation, const char* name) {
     PbPlanarCall c;
     int rc = pb_planar_check(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, subsampling, bytes_per_sample, fill, c);
     if (rc == PB_OK) rc = pb_track_table_check(plan, rot3x3_dev, n_rot_per_frame);
@@ -2483,10 +2510,13 @@ int pb_remap_track_planar(const pb_plan* plan, const double* rot3x3_dev, int n_r
     if (rc != PB_OK) return rc;
     const PbParams& P = plan->P;
     if (P.src.kind == PB_KIND_DOUBLE)
-        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_track_planar takes single sources (a double fisheye's blend is sample-typed): convert to RGB8 and use pb_remap_track_u8");
+        return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes single sources (a double fisheye's blend is sample-typed): convert to RGB8 and use pb_remap_track_u8");
+    if (interpolation == PB_INTERP_BILINEAR && pb_is_cube(P.src.kind))
+        return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes panorama and camera sources (the bilinear definition of video frames covers no cube map): convert to "
+                                                               "RGB8 and use pb_remap_track_u8");
     if (!pb_planar_span_fits(c) || P.src.height >= 32768 || P.src.width >= 32768)
-        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_track_planar takes frames whose planes span less than 2^31 bytes and sources below 32768 px a side: use a plan per "
-                                           "frame with pb_index_map_i32 and gather the three planes");
+        return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes frames whose planes span less than 2^31 bytes and sources below 32768 px a side: use a plan per "
+                                                               "frame with pb_index_map_i32 and gather the three planes");
     hipStream_t st = (hipStream_t)stream;
     const unsigned long long quads = (unsigned long long)P.dst.height * (((unsigned)P.dst.width + PB_PX - 1) / PB_PX);
     const int fpc = pb_track_fpc();
@@ -2498,15 +2528,35 @@ int pb_remap_track_planar(const pb_plan* plan, const double* rot3x3_dev, int n_r
         const uint8_t* s = static_cast<const uint8_t*>(src_dev) + (unsigned long long)f0 * c.fs.stride;
         uint8_t* d = static_cast<uint8_t*>(dst_dev) + (unsigned long long)f0 * c.fd.stride;
         const dim3 grid(pb_blocks(quads), (unsigned)((nf + fpc - 1) / fpc));
-        pb_pick_exact_kind(P, [&](auto K) {
-            pb_pick<1, 2>(bytes_per_sample == 1, [&](auto S) {
-                hipLaunchKernelGGL((pb_track_planar_kernel<S.value, K.value>), grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride, c.fd.stride, c.L, cx,
-                                   cy);
+        if (interpolation == PB_INTERP_BILINEAR)
+            pb_pick_kind(P, [&](auto K) {
+                pb_pick<1, 2>(bytes_per_sample == 1, [&](auto S) {
+                    hipLaunchKernelGGL((pb_track_video_bilinear_kernel<S.value, K.value, false>), grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride,
+                                       c.fd.stride, c.L, cx, cy);
+                });
             });
-        });
+        else
+            pb_pick_exact_kind(P, [&](auto K) {
+                pb_pick<1, 2>(bytes_per_sample == 1, [&](auto S) {
+                    hipLaunchKernelGGL((pb_track_planar_kernel<S.value, K.value>), grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride, c.fd.stride, c.L, cx,
+                                       cy);
+                });
+            });
     }
     PB_HIP(hipGetLastError());
     return PB_OK;
+}
+int pb_remap_track_planar(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                          const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample, const uint16_t fill[3],
+                          void* stream) {
+    return pb_track_planar_call(plan, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, n_frames, src_layout, dst_layout, subsampling, bytes_per_sample, fill, stream,
+                                PB_INTERP_NEAREST, "pb_remap_track_planar");
+}
+int pb_remap_track_planar_bilinear(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                                   const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample, const uint16_t fill[3],
+                                   void* stream) {
+    return pb_track_planar_call(plan, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, n_frames, src_layout, dst_layout, subsampling, bytes_per_sample, fill, stream,
+                                PB_INTERP_BILINEAR, "pb_remap_track_planar_bilinear");
 }
 
 int pb_index_map_i32(const pb_plan* plan, int32_t* idx_dev, double* weights_dev, void* stream) {
