@@ -178,51 +178,42 @@ def _px_kw(bpp: int) -> dict:
     return {} if bpp == 3 else {"bytes_per_px": bpp}
 
 
-VIDEO_FORMATS = {"nv12": np.dtype(np.uint8), "p010": np.dtype(np.uint16)}  # 4:2:0 semi-planar frames (3h/2, w): Plan.launch_nv12
+VIDEO_FORMATS = {name: dt for name, (dt, fam, _) in nat.VIDEO_FORMATS.items() if fam.pairs}  # 4:2:0 semi-planar frames (3h/2, w): Plan.launch_nv12
 
 
 def check_video_call(pixel_format: str, interpolation: str, supersample: int, track=None) -> np.dtype:
     """The sample type of a video pixel format, for a call it can be part of: nearest, not supersampled, no rotation track (pb_remap_nv12).
     ValueError otherwise.  THE place that says so: ``_video_format`` and ``batch.remap_frames`` (before its first frame) ask here."""
-    dt = VIDEO_FORMATS.get(pixel_format)
-    if dt is None and pixel_format in nat.PLANAR_FORMATS:
-        dt = nat.PLANAR_FORMATS[pixel_format][0]
-    if dt is None:
+    if pixel_format not in nat.VIDEO_FORMATS:
         raise ValueError(f"pixel_format must be None or one of {sorted(VIDEO_FORMATS) + sorted(nat.PLANAR_FORMATS)}, got {pixel_format!r}")
     if interpolation != "nearest" or supersample != 1 or track is not None:
         raise ValueError(f"{pixel_format} frames take nearest sampling without supersampling or a rotation track")
-    return dt
+    return nat.VIDEO_FORMATS[pixel_format][0]
 
 
 def _video_format(plan, a: np.ndarray, pixel_format: str, interpolation: str, supersample: int, track=None) -> tuple:
-    """(result shape, dtype, bytes per sample) of a 4:2:0 semi-planar frame (3h/2, w) for `plan`.  The keyword is needed: such an array is
-    indistinguishable from a grey image.  ValueError otherwise."""
+    """(result shape, dtype, bytes per sample) of a packed video frame for `plan`: (3h/2, w) for the semi-planar formats; a flat array of the
+    three planes' samples - at 4:4:4 also (3, h, w) - for the planar ones.  The keyword is needed: such an array is indistinguishable from a
+    grey image.  ValueError otherwise."""
     dt = check_video_call(pixel_format, interpolation, supersample, track)
+    fam = nat.VIDEO_FORMATS[pixel_format][1]
     h, w, H, W = plan.src.height, plan.src.width, plan.dst.height, plan.dst.width
-    if pixel_format in nat.PLANAR_FORMATS:
-        # a planar frame (nat.PLANAR_FORMATS): a flat array of the three planes' samples - at 4:4:4 also (3, h, w)
-        sub = nat.PLANAR_FORMATS[pixel_format][1]
-        if not nat.planar_dims_ok(sub, (h, w), (H, W)):
-            raise ValueError(f"{nat.planar_dims_rule(sub, pixel_format)}, the plan maps {h} x {w} to {H} x {W}")
-        flat = (nat.planar_frame_samples(h, w, sub),)
-        cube = sub == nat.PLANAR_444 and tuple(a.shape) == (3, h, w)
-        if a.dtype != dt or not (cube or tuple(a.shape) == flat):
-            raise ValueError(f"{pixel_format} frames must be {dt} {flat}" + (f" or {(3, h, w)}" if sub == nat.PLANAR_444 else "") + f", got {a.dtype} {tuple(a.shape)}")
-        return ((3, H, W) if cube else (nat.planar_frame_samples(H, W, sub),)), dt, dt.itemsize
-    if (h | w | H | W) & 1:
-        raise ValueError(f"{pixel_format} frames need even dimensions, the plan maps {h} x {w} to {H} x {W}")
-    if a.dtype != dt or tuple(a.shape) != (3 * h // 2, w):
-        raise ValueError(f"{pixel_format} frames must be {dt} {(3 * h // 2, w)}, got {a.dtype} {tuple(a.shape)}")
-    return (3 * H // 2, W), dt, dt.itemsize
+    if not nat.planar_dims_ok(fam.sub, (h, w), (H, W)):
+        rule = f"{pixel_format} frames need even dimensions" if fam.pairs else nat.planar_dims_rule(fam.sub, pixel_format)
+        raise ValueError(f"{rule}, the plan maps {h} x {w} to {H} x {W}")
+    frames = fam.packed(h, w)
+    if a.dtype != dt or tuple(a.shape) not in frames:
+        raise ValueError(f"{pixel_format} frames must be {dt} {' or '.join(map(str, frames))}, got {a.dtype} {tuple(a.shape)}")
+    return fam.packed(H, W)[frames.index(tuple(a.shape))], dt, dt.itemsize
 
 
 def _launch_video(plan, pixel_format: str, src_ptr: int, dst_ptr: int, stream: int, bps: int) -> None:
     """One packed video frame: pb_remap_nv12 for the semi-planar formats, pb_remap_planar with the format's black for the planar ones."""
-    if pixel_format in VIDEO_FORMATS:
+    _, fam, fill = nat.VIDEO_FORMATS[pixel_format]
+    if fam.pairs:
         plan.launch_nv12(src_ptr, dst_ptr, 1, stream, bps)
     else:
-        _, sub, fill = nat.PLANAR_FORMATS[pixel_format]
-        plan.launch_planar(src_ptr, dst_ptr, sub, 1, stream, bps, fill)
+        plan.launch_planar(src_ptr, dst_ptr, fam.sub, 1, stream, bps, fill)
 
 
 def remap_ndarray(plan: nat.Plan, image: np.ndarray, interpolation: str = "nearest", device: int | None = None, supersample: int = 1,

@@ -16,6 +16,7 @@ import contextlib
 import ctypes as C
 import os
 import threading
+import typing
 
 import numpy as np
 
@@ -230,6 +231,8 @@ VIDEO_INTERPOLATIONS = ("nearest", "bilinear")  # what remap_nv12 / remap_planar
 def check_video_interpolation(interpolation: str) -> bool:
     """The interpolation name of a video call (``remap_nv12``, ``remap_planar`` and their ``_supported``): ``check_interpolation``'s
     ValueError for an unknown name, and one for a mode video frames do not have.  -> whether it is "bilinear"."""
+    if interpolation == "nearest" or interpolation == "bilinear":  # (every launch asks: the two good answers first)
+        return interpolation == "bilinear"
     check_interpolation(interpolation)
     if interpolation not in VIDEO_INTERPOLATIONS:
         raise ValueError(f"video frames are sampled with one of {', '.join(map(repr, VIDEO_INTERPOLATIONS))}, got {interpolation!r}")
@@ -305,20 +308,6 @@ PLANAR_444, PLANAR_422, PLANAR_420 = 0, 1, 2  # include/photonbend_hip.h: PB_PLA
 PLANAR_SHIFTS = {PLANAR_444: (0, 0), PLANAR_422: (1, 0), PLANAR_420: (1, 1)}  # (cx, cy): planes 1 and 2 are (h >> cy, w >> cx)
 _PLANAR_NAMES = {"444": PLANAR_444, "4:4:4": PLANAR_444, "422": PLANAR_422, "4:2:2": PLANAR_422, "420": PLANAR_420, "4:2:0": PLANAR_420}
 _U8, _U16 = np.dtype(np.uint8), np.dtype(np.uint16)
-# THE table of planar pixel formats, by ffmpeg's -pix_fmt names: name -> (sample type, subsampling, the samples of black).  10-bit formats
-# carry their value in the low bits of a 16-bit sample; gbrp is planar RGB in the order G, B, R, black (0, 0, 0)
-PLANAR_FORMATS = {
-    "yuv420p": (_U8, PLANAR_420, (16, 128, 128)),
-    "yuv422p": (_U8, PLANAR_422, (16, 128, 128)),
-    "yuv444p": (_U8, PLANAR_444, (16, 128, 128)),
-    "yuv420p10le": (_U16, PLANAR_420, (64, 512, 512)),
-    "yuv422p10le": (_U16, PLANAR_422, (64, 512, 512)),
-    "yuv444p10le": (_U16, PLANAR_444, (64, 512, 512)),
-    "yuv420p16le": (_U16, PLANAR_420, (16 << 8, 128 << 8, 128 << 8)),
-    "yuv444p16le": (_U16, PLANAR_444, (16 << 8, 128 << 8, 128 << 8)),
-    "gbrp": (_U8, PLANAR_444, (0, 0, 0)),
-    "gbrp16le": (_U16, PLANAR_444, (0, 0, 0)),
-}
 
 
 def planar_subsampling(subsampling) -> int:
@@ -395,6 +384,79 @@ def planar_frame_bytes(layout, height: int, width: int, bytes_per_sample: int, s
     if any(v % S for v in (pitch, cpitch, o1, o2, stride)):
         raise PbError(f"pitch, chroma_pitch, offsets and frame_stride must be multiples of {S} bytes (one sample)")
     return pitch, cpitch, o1, o2, span, stride
+
+
+# (semi-planar?, rotation track?, bilinear?, the _supported question?) -> pb_remap[_track]_{nv12,planar}[_bilinear][_supported]
+_VIDEO_FUNCTIONS = {(pairs, tracked, bilinear, question): f"pb_remap_{'track_' if tracked else ''}{'nv12' if pairs else 'planar'}{'_bilinear' if bilinear else ''}"
+                                                          f"{'_supported' if question else ''}"
+                    for pairs in (False, True) for tracked in (False, True) for bilinear in (False, True) for question in (False, True) if not (tracked and question)}
+_FILL = C.c_uint16 * 3  # the samples of black pixels, as the video calls take them
+
+
+class VideoFamily(typing.NamedTuple):
+    """What distinguishes the families of video frames (the library's PbVideoFmt): 4:2:0 semi-planar frames - NV12 / P010, planes 1 and 2
+    as one plane of interleaved pairs (``NV12``) - or planar frames at a subsampling (``video_family``).  What ``Plan``'s video
+    methods check differently for the two is said here; the library's functions are ``_VIDEO_FUNCTIONS``."""
+
+    pairs: bool
+    sub: int  # PLANAR_* (pairs: PLANAR_420)
+
+    def layout(self, layout):
+        return nv12_layout(layout) if self.pairs else planar_layout(layout)
+
+    def frame_bytes(self, layout, height: int, width: int, bytes_per_sample: int) -> tuple:
+        """(bytes one frame spans, frame stride) of a layout (None: packed); a planar layout is checked (``planar_frame_bytes``)."""
+        if self.pairs:
+            return nv12_frame_bytes(layout, height, width, bytes_per_sample)
+        return planar_frame_bytes(layout, height, width, bytes_per_sample, self.sub)[4:]
+
+    def check(self, h: int, w: int, Hd: int, Wd: int, dt) -> None:
+        """The dimension rule for a plan's source and destination, and the sample type.  PbError."""
+        if not planar_dims_ok(self.sub, (h, w), (Hd, Wd)):
+            raise PbError("4:2:0 frames need even source and destination dimensions" if self.pairs
+                          else f"{planar_dims_rule(self.sub)}, source and destination: the plan maps {h} x {w} to {Hd} x {Wd}")
+        if dt not in (_U8, _U16):
+            raise PbError(f"NV12 frames are uint8 and P010 / P016 frames uint16, got {dt}" if self.pairs else f"planar frames hold uint8 or uint16 samples, got {dt}")
+
+    def packed(self, h: int, w: int) -> tuple:
+        """The shapes of one packed (h, w) frame: (3h/2, w), or flat - a 4:2:0 or 4:2:2 frame is no rectangle - and at 4:4:4 also (3, h, w)."""
+        if self.pairs:
+            return ((3 * h // 2, w),)
+        return ((planar_frame_samples(h, w, self.sub),),) + (((3, h, w),) if self.sub == PLANAR_444 else ())
+
+    def packed_error(self, h: int, w: int, shp: tuple) -> str:
+        if self.pairs:
+            return f"packed source frames must be ({3 * h // 2}, {w}) or (N, {3 * h // 2}, {w}), got {shp}"
+        ns = planar_frame_samples(h, w, self.sub)
+        return f"packed source frames must be ({ns},) or (N, {ns})" + (f", or (3, {h}, {w}) / (N, 3, {h}, {w})" if self.sub == PLANAR_444 else "") + f", got {shp}"
+
+
+NV12 = VideoFamily(True, PLANAR_420)
+
+
+def video_family(subsampling) -> VideoFamily:
+    """The planar family of a subsampling (``planar_subsampling``'s names and ValueError)."""
+    return VideoFamily(False, planar_subsampling(subsampling))
+
+
+# THE table of video pixel formats, by ffmpeg's -pix_fmt names: name -> (sample type, family, the samples of black; None: video black
+# scaled to the sample size).  10-bit formats carry their value in the low bits of a 16-bit sample; gbrp is planar RGB in the order G, B, R
+VIDEO_FORMATS = {
+    "nv12": (_U8, NV12, None),
+    "p010": (_U16, NV12, None),
+    "yuv420p": (_U8, video_family(PLANAR_420), (16, 128, 128)),
+    "yuv422p": (_U8, video_family(PLANAR_422), (16, 128, 128)),
+    "yuv444p": (_U8, video_family(PLANAR_444), (16, 128, 128)),
+    "yuv420p10le": (_U16, video_family(PLANAR_420), (64, 512, 512)),
+    "yuv422p10le": (_U16, video_family(PLANAR_422), (64, 512, 512)),
+    "yuv444p10le": (_U16, video_family(PLANAR_444), (64, 512, 512)),
+    "yuv420p16le": (_U16, video_family(PLANAR_420), (16 << 8, 128 << 8, 128 << 8)),
+    "yuv444p16le": (_U16, video_family(PLANAR_444), (16 << 8, 128 << 8, 128 << 8)),
+    "gbrp": (_U8, video_family(PLANAR_444), (0, 0, 0)),
+    "gbrp16le": (_U16, video_family(PLANAR_444), (0, 0, 0)),
+}
+# ... and its planar part as name -> (sample type, subsampling, the samples of black)
+PLANAR_FORMATS = {name: (dt, fam.sub, fill) for name, (dt, fam, fill) in VIDEO_FORMATS.items() if not fam.pairs}
 
 
 def px_align(bytes_per_px: int) -> int:
@@ -937,21 +999,13 @@ class Plan:
         """Whether ``remap_nv12`` takes this plan with samples of this size (pb_remap_nv12_supported): the plans ``px_supported`` takes,
         with even dimensions.  A size outside (1, 2) or an odd dimension is a PbError.  ``interpolation="bilinear"``: whether the
         bilinear call does (pb_remap_nv12_bilinear_supported): of those plans, the ones with the bilinear mode's tables.  Needs no GPU."""
-        fn = load().pb_remap_nv12_bilinear_supported if check_video_interpolation(interpolation) else load().pb_remap_nv12_supported
-        r = fn(self._h, int(bytes_per_sample))
-        if r < 0:
-            check(r)
-        return r == 1
+        return self._video_supported(True, None, bytes_per_sample, interpolation)
 
     def launch_nv12(self, src_ptr: int, dst_ptr: int, n_frames: int = 1, stream: int | None = None, bytes_per_sample: int = 1, fill=None,
                     src_layout=None, dst_layout=None, *, interpolation: str = "nearest") -> None:
         """The raw call (pb_remap_nv12; ``interpolation="bilinear"``: pb_remap_nv12_bilinear): n_frames 4:2:0 semi-planar frames at src_ptr /
         dst_ptr on `stream`, layouts in bytes (None: packed), ``fill`` the (Y, U, V) samples of black pixels (None: video black)."""
-        fn = load().pb_remap_nv12_bilinear if check_video_interpolation(interpolation) else load().pb_remap_nv12
-        f = None if fill is None else (C.c_uint16 * 3)(*[int(v) for v in fill])
-        sl, dl = nv12_layout(src_layout), nv12_layout(dst_layout)
-        self._gated(fn, self._h, src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl), None if dl is None else C.addressof(dl),
-                    int(bytes_per_sample), None if f is None else C.addressof(f), current_stream() if stream is None else stream)
+        self._launch_video(True, None, None, src_ptr, dst_ptr, n_frames, stream, bytes_per_sample, fill, src_layout, dst_layout, interpolation)
 
     def remap_nv12(self, src, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None, *, interpolation: str = "nearest"):
         """The nearest remap of NV12 (uint8) or P010 / P016 (uint16) video frames in ONE launch (pb_remap_nv12): luma moves
@@ -964,77 +1018,14 @@ class Plan:
         sampled bilinearly on the pair plane at half its block's top-left pixel's coordinate; within 1 + R // 512 of the written definition
         (R the largest sample value), on plans prepared with ``bilinear=True``."""
         check_video_interpolation(interpolation)
-        s, o, n, S, sl, dl = self._nv12_out(*self._nv12_source(src, src_layout), out, dst_layout)
-        with _on(s):
-            self.launch_nv12(s.data_ptr(), o.data_ptr(), n, stream, S, fill, sl, dl, interpolation=interpolation)
-        return o
-
-    def _nv12_source(self, src, src_layout):
-        """The source checks of ``remap_nv12`` and ``remap_track_nv12`` -> (src, its shape, dtype, layout, frame count).  Needs no GPU."""
-        h, w, Hd, Wd = self.src.height, self.src.width, self.dst.height, self.dst.width
-        if not is_device_array(src):
-            raise PbError(f"source frames must be device arrays (CUDA tensors or DeviceArrays), got {type(src).__name__}")
-        if (h | w | Hd | Wd) & 1:
-            raise PbError("4:2:0 frames need even source and destination dimensions")
-        shp = tuple(int(v) for v in src.shape)
-        dt = torch_dtype_np(src.dtype) if is_tensor(src) else np.dtype(src.dtype)
-        if dt not in (np.dtype(np.uint8), np.dtype(np.uint16)):
-            raise PbError(f"NV12 frames are uint8 and P010 / P016 frames uint16, got {dt}")
-        S = dt.itemsize
-        sl = nv12_layout(src_layout)
-        if sl is None:
-            if len(shp) not in (2, 3) or shp[-2:] != (3 * h // 2, w):
-                raise PbError(f"packed source frames must be ({3 * h // 2}, {w}) or (N, {3 * h // 2}, {w}), got {shp}")
-            n = shp[0] if len(shp) == 3 else 1
-        else:
-            if len(shp) != 1:
-                raise PbError(f"frames at a layout come as a 1-D buffer, got {shp}")
-            span, stride = nv12_frame_bytes(sl, h, w, S)
-            n = 0 if shp[0] * S < span else (shp[0] * S - span) // stride + 1
-            if n < 1:
-                raise PbError(f"the source buffer holds {shp[0] * S} bytes, a frame at this layout spans {span}")
-        return src, shp, dt, sl, n
-
-    def _nv12_out(self, src, shp, dt, sl, n, out, dst_layout):
-        """... and their ``out`` checks (allocating it when None) -> (source, out, frame count, sample size, the two layouts)."""
-        Hd, Wd, S = self.dst.height, self.dst.width, dt.itemsize
-        tens = is_tensor(src)
-        dl = nv12_layout(dst_layout)
-        require_gpu()
-        s = src.contiguous() if tens else src
-        packed_out = ((n,) if len(shp) == 3 else ()) + (3 * Hd // 2, Wd)
-        if out is None:
-            if dl is not None:
-                raise PbError("a destination layout needs the `out` buffer it describes")
-            o = empty(packed_out if sl is None else (n, 3 * Hd // 2, Wd), dt, like=s)
-        else:
-            o = out
-            odt = (torch_dtype_np(o.dtype) if is_tensor(o) else np.dtype(o.dtype)) if is_device_array(o) else None
-            if odt != dt or is_tensor(o) != tens or (tens and not o.is_contiguous()):
-                raise PbError(f"out must be a contiguous {dt} device array of the source's kind")
-            oshp = tuple(int(v) for v in o.shape)
-            if dl is None:
-                if oshp not in (packed_out, (n, 3 * Hd // 2, Wd)):
-                    raise PbError(f"out must be {packed_out}, got {oshp}")
-            else:
-                span, stride = nv12_frame_bytes(dl, Hd, Wd, S)
-                have = int(np.prod(oshp)) * S
-                if have < (n - 1) * stride + span:
-                    raise PbError(f"out holds {have} bytes, {n} frames at this layout span {(n - 1) * stride + span}")
-            if tens and (not o.is_cuda or o.device != s.device):
-                raise PbError(f"out must live on the source's device ({s.device}), got {o.device}")
-        return s, o, n, S, sl, dl
+        return self._remap_video(NV12, src, out, fill, src_layout, dst_layout, stream, interpolation)
 
     def launch_track_nv12(self, table_ptr: int, n_rot_per_frame: int, src_ptr: int, dst_ptr: int, n_frames: int = 1, stream: int | None = None,
                           bytes_per_sample: int = 1, fill=None, src_layout=None, dst_layout=None, *, interpolation: str = "nearest") -> None:
         """The raw rotation-track call for video frames (pb_remap_track_nv12; ``interpolation="bilinear"``: pb_remap_track_nv12_bilinear):
         ``launch_track``'s table, ``launch_nv12``'s frames, layouts and fill.  The table must stay alive and unchanged until the stream
         has run the launch."""
-        fn = load().pb_remap_track_nv12_bilinear if check_video_interpolation(interpolation) else load().pb_remap_track_nv12
-        f = None if fill is None else (C.c_uint16 * 3)(*[int(v) for v in fill])
-        sl, dl = nv12_layout(src_layout), nv12_layout(dst_layout)
-        self._gated(fn, self._h, table_ptr, int(n_rot_per_frame), src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl),
-                    None if dl is None else C.addressof(dl), int(bytes_per_sample), None if f is None else C.addressof(f), current_stream() if stream is None else stream)
+        self._launch_video(True, None, (table_ptr, n_rot_per_frame), src_ptr, dst_ptr, n_frames, stream, bytes_per_sample, fill, src_layout, dst_layout, interpolation)
 
     def remap_track_nv12(self, src, rotations, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None, *,
                          interpolation: str = "nearest"):
@@ -1046,38 +1037,19 @@ class Plan:
         frame f is ``remap_nv12``'s bilinear definition at the float64 coordinates of that chain - its bytes exactly, for either sample
         size; panorama and camera sources."""
         check_video_interpolation(interpolation)
-        source = self._nv12_source(src, src_layout)
-        n = source[-1]
-        tab, n_tab, k = rotation_table(rotations, self.n_rot)
-        if n_tab != n:
-            raise ValueError(f"{n} frames need {n} rotations, the table holds {n_tab}")
-        s, o, n, S, sl, dl = self._nv12_out(*source, out, dst_layout)
-        with _on(s):
-            st = current_stream() if stream is None else stream
-            tab, release = self._track_table(tab, s, st)
-            self.launch_track_nv12(tab.data_ptr(), k, s.data_ptr(), o.data_ptr(), n, st, S, fill, sl, dl, interpolation=interpolation)
-            release()
-        return o
+        return self._remap_video(NV12, src, out, fill, src_layout, dst_layout, stream, interpolation, track=(rotations,))
 
     def planar_supported(self, subsampling, bytes_per_sample: int = 1, *, interpolation: str = "nearest") -> bool:
         """Whether ``remap_planar`` takes this plan with this subsampling and sample size (pb_remap_planar_supported): the plans
         ``px_supported`` takes.  A size outside (1, 2) or a dimension that breaks the subsampling's rule is a PbError.
         ``interpolation="bilinear"``: whether the bilinear call does (pb_remap_planar_bilinear_supported).  Needs no GPU."""
-        fn = load().pb_remap_planar_bilinear_supported if check_video_interpolation(interpolation) else load().pb_remap_planar_supported
-        r = fn(self._h, planar_subsampling(subsampling), int(bytes_per_sample))
-        if r < 0:
-            check(r)
-        return r == 1
+        return self._video_supported(False, subsampling, bytes_per_sample, interpolation)
 
     def launch_planar(self, src_ptr: int, dst_ptr: int, subsampling, n_frames: int = 1, stream: int | None = None, bytes_per_sample: int = 1, fill=None,
                       src_layout=None, dst_layout=None, *, interpolation: str = "nearest") -> None:
         """The raw call (pb_remap_planar; ``interpolation="bilinear"``: pb_remap_planar_bilinear): n_frames planar frames at src_ptr /
         dst_ptr on `stream`, layouts in bytes (None: packed), ``fill`` the samples of black pixels per plane (None: video black)."""
-        fn = load().pb_remap_planar_bilinear if check_video_interpolation(interpolation) else load().pb_remap_planar
-        f = None if fill is None else (C.c_uint16 * 3)(*[int(v) for v in fill])
-        sl, dl = planar_layout(src_layout), planar_layout(dst_layout)
-        self._gated(fn, self._h, src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl), None if dl is None else C.addressof(dl),
-                    planar_subsampling(subsampling), int(bytes_per_sample), None if f is None else C.addressof(f), current_stream() if stream is None else stream)
+        self._launch_video(False, subsampling, None, src_ptr, dst_ptr, n_frames, stream, bytes_per_sample, fill, src_layout, dst_layout, interpolation)
 
     def remap_planar(self, src, subsampling, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None, *,
                      interpolation: str = "nearest"):
@@ -1093,87 +1065,15 @@ class Plan:
         bilinearly on its own plane at its block's top-left pixel's coordinate, halved where subsampled (chroma co-sited with that pixel);
         within 1 + R // 512 of the written definition (R the largest sample value), on plans prepared with ``bilinear=True``."""
         check_video_interpolation(interpolation)
-        sub = planar_subsampling(subsampling)
-        s, o, n, S, sl, dl = self._planar_out(*self._planar_source(src, sub, src_layout), out, dst_layout)
-        with _on(s):
-            self.launch_planar(s.data_ptr(), o.data_ptr(), sub, n, stream, S, fill, sl, dl, interpolation=interpolation)
-        return o
-
-    def _planar_source(self, src, sub, src_layout):
-        """The source checks of ``remap_planar`` and ``remap_track_planar`` -> (src, subsampling, its shape, dtype, layout, frame count).
-        Needs no GPU."""
-        h, w, Hd, Wd = self.src.height, self.src.width, self.dst.height, self.dst.width
-        if not is_device_array(src):
-            raise PbError(f"source frames must be device arrays (CUDA tensors or DeviceArrays), got {type(src).__name__}")
-        if not planar_dims_ok(sub, (h, w), (Hd, Wd)):
-            raise PbError(f"{planar_dims_rule(sub)}, source and destination: the plan maps {h} x {w} to {Hd} x {Wd}")
-        shp = tuple(int(v) for v in src.shape)
-        dt = torch_dtype_np(src.dtype) if is_tensor(src) else np.dtype(src.dtype)
-        if dt not in (_U8, _U16):
-            raise PbError(f"planar frames hold uint8 or uint16 samples, got {dt}")
-        S = dt.itemsize
-        sl = planar_layout(src_layout)
-        ns = planar_frame_samples(h, w, sub)
-        if sl is None:
-            ok = (len(shp) in (1, 2) and shp[-1] == ns) or (sub == PLANAR_444 and len(shp) in (3, 4) and shp[-3:] == (3, h, w))
-            if not ok:
-                raise PbError(f"packed source frames must be ({ns},) or (N, {ns})" + (f", or (3, {h}, {w}) / (N, 3, {h}, {w})" if sub == PLANAR_444 else "") + f", got {shp}")
-            n = shp[0] if len(shp) in (2, 4) else 1
-        else:
-            if len(shp) != 1:
-                raise PbError(f"frames at a layout come as a 1-D buffer, got {shp}")
-            span, stride = planar_frame_bytes(sl, h, w, S, sub)[4:]
-            n = 0 if shp[0] * S < span else (shp[0] * S - span) // stride + 1
-            if n < 1:
-                raise PbError(f"the source buffer holds {shp[0] * S} bytes, a frame at this layout spans {span}")
-        return src, sub, shp, dt, sl, n
-
-    def _planar_out(self, src, sub, shp, dt, sl, n, out, dst_layout):
-        """... and their ``out`` checks (allocating it when None) -> (source, out, frame count, sample size, the two layouts)."""
-        Hd, Wd, S = self.dst.height, self.dst.width, dt.itemsize
-        tens = is_tensor(src)
-        dl = planar_layout(dst_layout)
-        if dl is not None:
-            planar_frame_bytes(dl, Hd, Wd, S, sub)
-        require_gpu()
-        s = src.contiguous() if tens else src
-        nd = planar_frame_samples(Hd, Wd, sub)
-        batched = len(shp) in (2, 4)
-        cube = sl is None and len(shp) >= 3  # (4:4:4 as (3, h, w))
-        packed_out = ((n,) if batched else ()) + ((3, Hd, Wd) if cube else (nd,))
-        if out is None:
-            if dl is not None:
-                raise PbError("a destination layout needs the `out` buffer it describes")
-            o = empty(packed_out if sl is None else (n, nd), dt, like=s)
-        else:
-            o = out
-            odt = (torch_dtype_np(o.dtype) if is_tensor(o) else np.dtype(o.dtype)) if is_device_array(o) else None
-            if odt != dt or is_tensor(o) != tens or (tens and not o.is_contiguous()):
-                raise PbError(f"out must be a contiguous {dt} device array of the source's kind")
-            oshp = tuple(int(v) for v in o.shape)
-            if dl is None:
-                if oshp not in (packed_out, (n, nd)):
-                    raise PbError(f"out must be {packed_out}, got {oshp}")
-            else:
-                span, stride = planar_frame_bytes(dl, Hd, Wd, S, sub)[4:]
-                have = int(np.prod(oshp)) * S
-                if have < (n - 1) * stride + span:
-                    raise PbError(f"out holds {have} bytes, {n} frames at this layout span {(n - 1) * stride + span}")
-            if tens and (not o.is_cuda or o.device != s.device):
-                raise PbError(f"out must live on the source's device ({s.device}), got {o.device}")
-        return s, o, n, S, sl, dl
+        return self._remap_video(video_family(subsampling), src, out, fill, src_layout, dst_layout, stream, interpolation)
 
     def launch_track_planar(self, table_ptr: int, n_rot_per_frame: int, src_ptr: int, dst_ptr: int, subsampling, n_frames: int = 1, stream: int | None = None,
                             bytes_per_sample: int = 1, fill=None, src_layout=None, dst_layout=None, *, interpolation: str = "nearest") -> None:
         """The raw rotation-track call for planar frames (pb_remap_track_planar; ``interpolation="bilinear"``:
         pb_remap_track_planar_bilinear): ``launch_track``'s table, ``launch_planar``'s frames, layouts and fill.  The table must stay
         alive and unchanged until the stream has run the launch."""
-        fn = load().pb_remap_track_planar_bilinear if check_video_interpolation(interpolation) else load().pb_remap_track_planar
-        f = None if fill is None else (C.c_uint16 * 3)(*[int(v) for v in fill])
-        sl, dl = planar_layout(src_layout), planar_layout(dst_layout)
-        self._gated(fn, self._h, table_ptr, int(n_rot_per_frame), src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl),
-                    None if dl is None else C.addressof(dl), planar_subsampling(subsampling), int(bytes_per_sample), None if f is None else C.addressof(f),
-                    current_stream() if stream is None else stream)
+        self._launch_video(False, subsampling, (table_ptr, n_rot_per_frame), src_ptr, dst_ptr, n_frames, stream, bytes_per_sample, fill, src_layout,
+                           dst_layout, interpolation)
 
     def remap_track_planar(self, src, rotations, subsampling, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None, *,
                            interpolation: str = "nearest"):
@@ -1185,18 +1085,106 @@ class Plan:
         frame f is ``remap_planar``'s bilinear definition at the float64 coordinates of that chain - its bytes exactly, for either sample
         size; panorama and camera sources."""
         check_video_interpolation(interpolation)
-        source = self._planar_source(src, planar_subsampling(subsampling), src_layout)
-        n = source[-1]
-        tab, n_tab, k = rotation_table(rotations, self.n_rot)
-        if n_tab != n:
-            raise ValueError(f"{n} frames need {n} rotations, the table holds {n_tab}")
-        s, o, n, S, sl, dl = self._planar_out(*source, out, dst_layout)
+        return self._remap_video(video_family(subsampling), src, out, fill, src_layout, dst_layout, stream, interpolation, track=(rotations,))
+
+    # the one path behind the ten video methods above; `pairs`, `sub`: a VideoFamily's members - in the raw calls the subsampling as the caller
+    # gave it, checked where the library's argument stands
+    def _video_supported(self, pairs, sub, bytes_per_sample, interpolation) -> bool:
+        fn = getattr(load(), _VIDEO_FUNCTIONS[pairs, False, check_video_interpolation(interpolation), True])
+        r = fn(self._h, int(bytes_per_sample)) if pairs else fn(self._h, planar_subsampling(sub), int(bytes_per_sample))
+        if r < 0:
+            check(r)
+        return r == 1
+
+    def _launch_video(self, pairs, sub, table, src_ptr, dst_ptr, n_frames, stream, bytes_per_sample, fill, src_layout, dst_layout, interpolation) -> None:
+        """The raw call; table: None, or the (pointer, rotations per frame) of a rotation track's table."""
+        fn = getattr(load(), _VIDEO_FUNCTIONS[pairs, table is not None, check_video_interpolation(interpolation), False])
+        f = None if fill is None else _FILL(*[int(v) for v in fill])
+        to_layout = nv12_layout if pairs else planar_layout
+        sl, dl = to_layout(src_layout), to_layout(dst_layout)
+        self._gated(fn, self._h, *(() if table is None else (table[0], int(table[1]))), src_ptr, dst_ptr, int(n_frames), None if sl is None else C.addressof(sl),
+                    None if dl is None else C.addressof(dl), *(() if pairs else (planar_subsampling(sub),)), int(bytes_per_sample), None if f is None else C.addressof(f),
+                    current_stream() if stream is None else stream)
+
+    def _remap_video(self, fam, src, out, fill, src_layout, dst_layout, stream, interpolation, track=None):
+        """``remap_nv12`` / ``remap_planar`` and, with track = (rotations,), their rotation tracks: the source checks, the table's, the
+        ``out`` checks, one launch."""
+        source = self._video_source(fam, src, src_layout)
+        if track is not None:
+            n = source[-1]
+            tab, n_tab, k = rotation_table(track[0], self.n_rot)
+            if n_tab != n:
+                raise ValueError(f"{n} frames need {n} rotations, the table holds {n_tab}")
+        s, o, n, S, sl, dl = self._video_out(*source, out, dst_layout)
         with _on(s):
-            st = current_stream() if stream is None else stream
-            tab, release = self._track_table(tab, s, st)
-            self.launch_track_planar(tab.data_ptr(), k, s.data_ptr(), o.data_ptr(), source[1], n, st, S, fill, sl, dl, interpolation=interpolation)
-            release()
+            if track is None:
+                self._launch_video(*fam, None, s.data_ptr(), o.data_ptr(), n, stream, S, fill, sl, dl, interpolation)
+            else:
+                st = current_stream() if stream is None else stream
+                tab, release = self._track_table(tab, s, st)
+                self._launch_video(*fam, (tab.data_ptr(), k), s.data_ptr(), o.data_ptr(), n, st, S, fill, sl, dl, interpolation)
+                release()
         return o
+
+    def _video_source(self, fam, src, src_layout):
+        """The source checks of the video methods -> (src, family, its shape, dtype, layout, frame count).  Needs no GPU."""
+        h, w = self.src.height, self.src.width
+        if not is_device_array(src):
+            raise PbError(f"source frames must be device arrays (CUDA tensors or DeviceArrays), got {type(src).__name__}")
+        dt = torch_dtype_np(src.dtype) if is_tensor(src) else np.dtype(src.dtype)
+        fam.check(h, w, self.dst.height, self.dst.width, dt)
+        shp = tuple(int(v) for v in src.shape)
+        S = dt.itemsize
+        sl = fam.layout(src_layout)
+        if sl is None:
+            frames = fam.packed(h, w)
+            if shp not in frames and shp[1:] not in frames:
+                raise PbError(fam.packed_error(h, w, shp))
+            n = 1 if shp in frames else shp[0]
+        else:
+            if len(shp) != 1:
+                raise PbError(f"frames at a layout come as a 1-D buffer, got {shp}")
+            span, stride = fam.frame_bytes(sl, h, w, S)
+            n = 0 if shp[0] * S < span else (shp[0] * S - span) // stride + 1
+            if n < 1:
+                raise PbError(f"the source buffer holds {shp[0] * S} bytes, a frame at this layout spans {span}")
+        return src, fam, shp, dt, sl, n
+
+    def _video_out(self, src, fam, shp, dt, sl, n, out, dst_layout):
+        """... and their ``out`` checks (allocating it when None) -> (source, out, frame count, sample size, the two layouts)."""
+        h, w, Hd, Wd, S = self.src.height, self.src.width, self.dst.height, self.dst.width, dt.itemsize
+        tens = is_tensor(src)
+        dl = fam.layout(dst_layout)
+        if dl is not None:
+            fam.frame_bytes(dl, Hd, Wd, S)
+        require_gpu()
+        s = src.contiguous() if tens else src
+        # the destination in the source's form: one frame or a batch of the same one of the family's packed shapes (frames at a layout: the first)
+        frames, frames_out = fam.packed(h, w), fam.packed(Hd, Wd)
+        batched = sl is None and shp not in frames
+        form = 0 if sl is not None else frames.index(shp[1:] if batched else shp)
+        packed_out = ((n,) if batched else ()) + frames_out[form]
+        if out is None:
+            if dl is not None:
+                raise PbError("a destination layout needs the `out` buffer it describes")
+            o = empty(packed_out if sl is None else (n,) + frames_out[0], dt, like=s)
+        else:
+            o = out
+            odt = (torch_dtype_np(o.dtype) if is_tensor(o) else np.dtype(o.dtype)) if is_device_array(o) else None
+            if odt != dt or is_tensor(o) != tens or (tens and not o.is_contiguous()):
+                raise PbError(f"out must be a contiguous {dt} device array of the source's kind")
+            oshp = tuple(int(v) for v in o.shape)
+            if dl is None:
+                if oshp not in (packed_out, (n,) + frames_out[0]):
+                    raise PbError(f"out must be {packed_out}, got {oshp}")
+            else:
+                span, stride = fam.frame_bytes(dl, Hd, Wd, S)
+                have = int(np.prod(oshp)) * S
+                if have < (n - 1) * stride + span:
+                    raise PbError(f"out holds {have} bytes, {n} frames at this layout span {(n - 1) * stride + span}")
+            if tens and (not o.is_cuda or o.device != s.device):
+                raise PbError(f"out must live on the source's device ({s.device}), got {o.device}")
+        return s, o, n, S, sl, dl
 
     def remap_each(self, srcs, outs=None, stream: int | None = None):
         """A batch of SEPARATELY ALLOCATED frames (a ring of buffers) in one launch (``pb_remap_u8v``): srcs / outs are

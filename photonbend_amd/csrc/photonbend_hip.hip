@@ -632,7 +632,7 @@ static void pb_pick_px_size(int bpp, F&& f) {
         default: f(PbInt<8>()); break;
     }
 }
-// pb_planar_hot_kernel's SUB (PB_PLANAR_444 / _422 / _420; pb_planar_check has refused everything else)
+// pb_planar_hot_kernel's SUB (PB_PLANAR_444 / _422 / _420; pb_video_fmt_check has refused everything else)
 template <class F>
 static void pb_pick_subsampling(int sub, F&& f) {
     static_assert(PB_PLANAR_444 == PB_SUB_444 && PB_PLANAR_422 == PB_SUB_422 && PB_PLANAR_420 == PB_SUB_420, "the kernel's SUB is the header's constant");
@@ -982,6 +982,19 @@ static int pb_check_frames(const pb_plan* plan, const void* src, const void* dst
 // What the plan builders guarantee, and the conditions below rely on: fast_ready is set for single sources only (pb_fast_possible),
 // dbl_ready and sep_ready for double-fisheye sources only, dbl_ready for sources below 32768 px a side only (pb_fast_possible_dims);
 // a launch table (nearest.lt / bil.lt) that holds its entries comes with groups >= 8 (PbLaunchTable: pb_build_launch_table moves both in together).
+// What distinguishes the families of video entry points: NV12 / P010 frames - 4:2:0, planes 1 and 2 as one plane of
+// interleaved pairs, laid out by a pb_nv12_layout - and planar frames at a subsampling (pb_planar_layout).  The words are the messages'.
+struct PbVideoFmt {
+    bool pairs = false;       // planes 1 and 2 are interleaved pairs
+    int sub = PB_PLANAR_420;  // PB_PLANAR_* (pairs: 4:2:0)
+    int S = 1;                // bytes per sample
+    int cx() const { return pb_planar_cx(sub); }  // planes 1 and 2 are (h >> cy, w >> cx)
+    int cy() const { return pb_planar_cy(sub); }
+    unsigned long long unit() const { return (unsigned long long)(pairs ? 2 * S : S); }  // what pointers, pitches and offsets are multiples of
+    const char* unit_name() const { return pairs ? "one chroma pair" : "one sample"; }
+    const char* planes() const { return pairs ? "two" : "three"; }                       // "... and gather the two planes"
+    std::string nearest() const { return pairs ? "pb_remap_nv12" : "pb_remap_planar"; }  // the nearest call, which the layout messages cite
+};
 struct PbRoute {
     enum Kind {
         DOUBLE,              // nearest: pb_hot_double_kernel
@@ -998,38 +1011,34 @@ struct PbRoute {
         SS_GENERIC,          // supersampled: frame by frame the route of n = 1 into a workspace, then pb_box_reduce_kernel
         PX,                  // nearest, pixels of bpp != 3 bytes (pb_remap_px): pb_px_hot_kernel
         PX_NONE,             // ... on a plan that kernel does not serve: nothing is launched (PB_ERR_UNSUPPORTED)
-        NV12,                // nearest, 4:2:0 semi-planar frames (pb_remap_nv12): pb_nv12_hot_kernel
-        NV12_NONE,           // ... on a plan that kernel does not serve - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
-        PLANAR,              // nearest, planar 4:4:4 / 4:2:2 / 4:2:0 frames (pb_remap_planar): pb_planar_hot_kernel
-        PLANAR_NONE,         // ... on a plan that kernel does not serve - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
+        VIDEO,               // nearest, video frames: 4:2:0 semi-planar (pb_remap_nv12): pb_nv12_hot_kernel; planar 4:4:4 / 4:2:2 / 4:2:0
+                             // (pb_remap_planar): pb_planar_hot_kernel
+        VIDEO_NONE,          // ... on a plan those kernels do not serve - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
         VIDEO_BIL,           // bilinear, planar or 4:2:0 semi-planar frames (pb_remap_planar_bilinear, pb_remap_nv12_bilinear): pb_planar_bilinear_kernel
         VIDEO_BIL_NEAREST_NONE,  // ... on a plan the nearest call refuses too - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
         VIDEO_BIL_NONE,      // ... on a plan without the bilinear mode's tile and coordinate tables (a cube source never has them): nothing is launched
     } kind;
     bool windows;                    // BIL_DOUBLE / bilinear INTERP_TILES: LEAN tiles gather from LDS windows
     int filter = PB_INTERP_NEAREST;  // the INTERP_* routes: PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM
-    int bpp = 3;                     // PX: bytes per pixel; NV12, PLANAR: bytes per sample
-    int sub = 0;                     // PLANAR, VIDEO_BIL: the subsampling (PB_PLANAR_*)
-    bool pairs = false;              // VIDEO_BIL*: planes 1 and 2 are NV12's interleaved pairs
+    int bpp = 3;                     // PX: bytes per pixel
+    PbVideoFmt video = {};           // VIDEO*: the frames' format
 };
 static bool pb_aligned16(const void* src, unsigned long long stride) { return ((((uintptr_t)src) | stride) & 15u) == 0; }
-// planar: the subsampling of a pb_remap_planar call (PB_PLANAR_*), -1 everywhere else
-static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned flags, bool aligned, int bpp = 3, bool nv12 = false, int planar = -1) {
+// video: the format of a video call's frames, null everywhere else
+static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned flags, bool aligned, int bpp = 3, const PbVideoFmt* video = nullptr) {
     const PbParams& P = pl->P;
-    if (bpp != 3 || nv12 || planar >= 0) {
+    if (bpp != 3 || video) {
         // the tile kernel of the nearest plan's launch-order table, or nothing: no window, so no alignment beyond the pixel's own
         // (pb_check_frames); fast_ready says single source, prepared, device state; generic tiles pack row and column in 16 bits each
         const bool served = n == 1 && pb_use_fast(pl) && pl->nearest.lt.entries && pl->nearest.P_dev && P.src.width < 32768 && P.src.height < 32768;
         const bool px = interpolation == PB_INTERP_NEAREST && served;
-        if (interpolation == PB_INTERP_BILINEAR) {
+        if (video && interpolation == PB_INTERP_BILINEAR) {
             // the nearest call's plans, and of those the ones with the bilinear mode's launch-order, tile and exact coordinate tables (no
             // second kernel picks up what a plan without coordinate tables leaves; a cube source never has bil.tiles: pb_bilinear_tiles_allowed)
             const bool tabs = pl->bil.lt.entries && pl->bil.tiles && pl->bil.xy && pl->bil.fix_xy && !pb_is_cube(P.src.kind);
-            return {!served ? PbRoute::VIDEO_BIL_NEAREST_NONE : tabs ? PbRoute::VIDEO_BIL : PbRoute::VIDEO_BIL_NONE, false, PB_INTERP_BILINEAR, bpp,
-                    nv12 ? PB_PLANAR_420 : planar, nv12};
+            return {!served ? PbRoute::VIDEO_BIL_NEAREST_NONE : tabs ? PbRoute::VIDEO_BIL : PbRoute::VIDEO_BIL_NONE, false, PB_INTERP_BILINEAR, 3, *video};
         }
-        if (nv12) return {px ? PbRoute::NV12 : PbRoute::NV12_NONE, false, PB_INTERP_NEAREST, bpp};  // (bpp: bytes per sample)
-        if (planar >= 0) return {px ? PbRoute::PLANAR : PbRoute::PLANAR_NONE, false, PB_INTERP_NEAREST, bpp, planar};
+        if (video) return {px ? PbRoute::VIDEO : PbRoute::VIDEO_NONE, false, PB_INTERP_NEAREST, 3, *video};
         return {px ? PbRoute::PX : PbRoute::PX_NONE, false, PB_INTERP_NEAREST, bpp};
     }
     if (n > 1) {
@@ -1089,11 +1098,15 @@ static void pb_launch_direct(const pb_plan* pl, const uint8_t* src, uint8_t* dst
                            (int)pl->cert.n_fix_px, pl->cert.idx_tab, pl->cert.fix_idx, src, dst, n_frames, ss, ds, idx_out);
 }
 
+// the layout and fills pb_nv12_hot_kernel and pb_track_nv12_kernel take, of a semi-planar call's resolved layout (S: bytes per sample)
+static PbNv12 pb_nv12_of(const PbPlanar& L, int S) {
+    return {L.src_pitch, L.src_o1, L.dst_pitch, L.dst_o1, L.fill[0], L.fill[1] | (L.fill[2] << (8u * (unsigned)S))};
+}
+
 // Launches a nearest or bilinear route (n = 1) for n_frames frames at strides ss / ds (pb_check_frames has filled them in).
-// nv12 / planar: the plane layouts and fills of the NV12 route (pb_remap_nv12) / the PLANAR and VIDEO_BIL routes (pb_remap_planar, the two
-// bilinear video calls: an NV12 layout travels as a PbPlanar there), null everywhere else.
+// video: the plane layouts and fills of the VIDEO and VIDEO_BIL routes (an NV12 layout travels as a PbPlanar: pb_nv12_of), null everywhere else.
 static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* dst, int n_frames, unsigned long long ss, unsigned long long ds,
-                     hipStream_t st, const PbNv12* nv12 = nullptr, const PbPlanar* planar = nullptr) {
+                     hipStream_t st, const PbPlanar* video = nullptr) {
     const PbParams& P = pl->P;
     const unsigned long long npx = (unsigned long long)P.dst.height * P.dst.width;
     switch (r.kind) {
@@ -1160,54 +1173,42 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
         case PbRoute::PX_NONE:
             return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_px takes prepared plans of a single source in a tile mode (not deferred, not PB_MODE_FAITHFUL, not "
                                                "double-fisheye, sources below 32768 px a side): use pb_index_map_i32 + pb_gather_px");
-        case PbRoute::NV12: {
-            // launched like PX: both planes of a tile by the tile's wave
+        case PbRoute::VIDEO: {
+            // launched like PX: every plane of a tile by the tile's wave
             const unsigned gpf = pl->nearest.lt.groups;
             pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
-                pb_pick_kind(P, [&](auto K) {
-                    pb_pick<1, 2>(r.bpp == 1, [&](auto S) {
-                        hipLaunchKernelGGL((pb_nv12_hot_kernel<K.value, S.value>), dim3(gpf * (unsigned)nf), dim3(64 * PB_TILE_WAVES), 0, st,
-                                           (const PbParams*)pl->nearest.P_dev, pb_hot_of_host(P), pl->nearest.lt.entries, sf, df, gpf, ss, ds, pl->cert.idx_tab,
-                                           pl->cert.fix_px, pl->cert.fix_idx, *nv12);
+                auto go = [&](auto kernel, auto layout) {
+                    hipLaunchKernelGGL(kernel, dim3(gpf * (unsigned)nf), dim3(64 * PB_TILE_WAVES), 0, st, (const PbParams*)pl->nearest.P_dev, pb_hot_of_host(P),
+                                       pl->nearest.lt.entries, sf, df, gpf, ss, ds, pl->cert.idx_tab, pl->cert.fix_px, pl->cert.fix_idx, layout);
+                };
+                if (r.video.pairs)
+                    pb_pick_kind(P, [&](auto K) {
+                        pb_pick<1, 2>(r.video.S == 1, [&](auto S) { go(pb_nv12_hot_kernel<K.value, S.value>, pb_nv12_of(*video, S.value)); });
                     });
-                });
-            });
-            break;
-        }
-        case PbRoute::NV12_NONE:
-            return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_nv12 takes prepared plans of a single source in a tile mode (not deferred, not PB_MODE_FAITHFUL, not "
-                                               "double-fisheye, sources below 32768 px a side): use pb_index_map_i32 and gather the two planes");
-        case PbRoute::PLANAR: {
-            // launched like NV12: the three planes of a tile by the tile's wave
-            const unsigned gpf = pl->nearest.lt.groups;
-            pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
-                pb_pick_kind(P, [&](auto K) {
-                    pb_pick<1, 2>(r.bpp == 1, [&](auto S) {
-                        pb_pick_subsampling(r.sub, [&](auto SUB) {
-                            hipLaunchKernelGGL((pb_planar_hot_kernel<K.value, S.value, SUB.value>), dim3(gpf * (unsigned)nf), dim3(64 * PB_TILE_WAVES), 0, st,
-                                               (const PbParams*)pl->nearest.P_dev, pb_hot_of_host(P), pl->nearest.lt.entries, sf, df, gpf, ss, ds, pl->cert.idx_tab,
-                                               pl->cert.fix_px, pl->cert.fix_idx, *planar);
+                else
+                    pb_pick_kind(P, [&](auto K) {
+                        pb_pick<1, 2>(r.video.S == 1, [&](auto S) {
+                            pb_pick_subsampling(r.video.sub, [&](auto SUB) { go(pb_planar_hot_kernel<K.value, S.value, SUB.value>, *video); });
                         });
                     });
-                });
             });
             break;
         }
-        case PbRoute::PLANAR_NONE:
-            return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_planar takes prepared plans of a single source in a tile mode (not deferred, not PB_MODE_FAITHFUL, not "
-                                               "double-fisheye, sources below 32768 px a side): use pb_index_map_i32 and gather the three planes");
+        case PbRoute::VIDEO_NONE:
+            return pb_fail(PB_ERR_UNSUPPORTED, r.video.nearest() + " takes prepared plans of a single source in a tile mode (not deferred, not PB_MODE_FAITHFUL, not "
+                                               "double-fisheye, sources below 32768 px a side): use pb_index_map_i32 and gather the " + r.video.planes() + " planes");
         case PbRoute::VIDEO_BIL: {
             // launched like the Catmull-Rom tile kernel: the bilinear mode's launch-order table read with four waves per workgroup
             const unsigned gpf = pl->bil.lt.groups;
             pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
                 pb_pick_kind(P, [&](auto K) {
-                    pb_pick<1, 2>(r.bpp == 1, [&](auto S) {
+                    pb_pick<1, 2>(r.video.S == 1, [&](auto S) {
                         auto go = [&](auto SUB, auto PAIRS) {
                             hipLaunchKernelGGL((pb_planar_bilinear_kernel<K.value, S.value, SUB.value, PAIRS.value != 0>), dim3(gpf * (unsigned)nf), dim3(64 * PB_VBIL_WAVES),
-                                               0, st, pb_hot_of_host(P), pl->bil.lt.entries, sf, df, gpf, ss, ds, pl->bil.xy, pl->cert.fix_px, pl->bil.fix_xy, *planar);
+                                               0, st, pb_hot_of_host(P), pl->bil.lt.entries, sf, df, gpf, ss, ds, pl->bil.xy, pl->cert.fix_px, pl->bil.fix_xy, *video);
                         };
-                        if (r.pairs) go(PbInt<PB_SUB_420>(), PbInt<1>());
-                        else pb_pick_subsampling(r.sub, [&](auto SUB) { go(SUB, PbInt<0>()); });
+                        if (r.video.pairs) go(PbInt<PB_SUB_420>(), PbInt<1>());
+                        else pb_pick_subsampling(r.video.sub, [&](auto SUB) { go(SUB, PbInt<0>()); });
                     });
                 });
             });
@@ -1215,7 +1216,7 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
         }
         case PbRoute::VIDEO_BIL_NEAREST_NONE:
         case PbRoute::VIDEO_BIL_NONE: {
-            const std::string name = r.pairs ? "pb_remap_nv12_bilinear" : "pb_remap_planar_bilinear";
+            const std::string name = r.video.nearest() + "_bilinear";
             if (r.kind == PbRoute::VIDEO_BIL_NEAREST_NONE)
                 return pb_fail(PB_ERR_UNSUPPORTED, name + " takes prepared plans of a single source in a tile mode (not deferred, not PB_MODE_FAITHFUL, not "
                                                           "double-fisheye, sources below 32768 px a side): convert to RGB and use pb_remap_bilinear_u8");
@@ -2124,99 +2125,31 @@ int pb_remap_px_supported(const pb_plan* plan, int bytes_per_px) {
     return pb_route(plan, PB_INTERP_NEAREST, 1, 0, false, bytes_per_px).kind == PbRoute::PX && pb_px_frames_fit(plan, bytes_per_px);
 }
 
-// 4:2:0 semi-planar frames.  Every check comes before the device is looked at and before any launch.
-struct PbNv12Frame {  // a resolved layout, in bytes
-    unsigned long long pitch, uv, span, stride;
+// Video frames: one path through the checks, the route and the launch for every family (PbVideoFmt).  Every check comes
+// before the device is looked at and before any launch.
+struct PbVideoFrame {  // a resolved layout, in bytes (semi-planar: cpitch = pitch, o1 = uv_offset, o2 = 0)
+    unsigned long long pitch, cpitch, o1, o2, span, stride;
 };
-static int pb_nv12_resolve(const char* what, const pb_nv12_layout* l, unsigned long long S, unsigned long long h, unsigned long long w, PbNv12Frame& f) {
+static int pb_nv12_resolve(const char* what, const pb_nv12_layout* l, unsigned long long S, unsigned long long h, unsigned long long w, PbVideoFrame& f) {
     const std::string n(what);
     // (a frame must span less than 2^31 bytes to be served: a pitch or an offset at or beyond that is refused here, before anything is
     //  multiplied - no product below can wrap, whatever the caller passes)
     if (l && (l->pitch >= (1ull << 31) || l->uv_offset >= (1ull << 31)))
         return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_nv12 takes frames whose planes span less than 2^31 bytes (" + n + " pitch or uv_offset): use pb_index_map_i32 and gather the two planes");
-    f.pitch = (l && l->pitch) ? l->pitch : S * w;
+    f.pitch = f.cpitch = (l && l->pitch) ? l->pitch : S * w;
     if (f.pitch < S * w) return pb_fail(PB_ERR_INVALID, n + " pitch smaller than a row");
-    f.uv = (l && l->uv_offset) ? l->uv_offset : f.pitch * h;
-    if (f.uv < f.pitch * h) return pb_fail(PB_ERR_INVALID, n + " uv_offset smaller than the luma plane");
-    f.span = f.uv + f.pitch * (h / 2);
+    f.o1 = (l && l->uv_offset) ? l->uv_offset : f.pitch * h;
+    f.o2 = 0;
+    if (f.o1 < f.pitch * h) return pb_fail(PB_ERR_INVALID, n + " uv_offset smaller than the luma plane");
+    f.span = f.o1 + f.pitch * (h / 2);  // (whole pitches: the pair plane's last row counts to its pitch)
     f.stride = (l && l->frame_stride) ? l->frame_stride : f.span;
     if (f.stride < f.span) return pb_fail(PB_ERR_INVALID, n + " frame_stride smaller than a frame");
-    if ((f.pitch | f.uv | f.stride) % (2 * S))
+    if ((f.pitch | f.o1 | f.stride) % (2 * S))
         return pb_fail(PB_ERR_INVALID, n + " pitch, uv_offset and frame_stride must be multiples of " + std::to_string(2 * S) + " bytes (one chroma pair)");
     return PB_OK;
 }
-static bool pb_nv12_dims_even(const pb_plan* plan) {
-    const PbParams& P = plan->P;
-    return !((P.src.height | P.src.width | P.dst.height | P.dst.width) & 1);
-}
-// The arguments of the two 4:2:0 entry points (pb_remap_nv12, pb_remap_track_nv12), in this order: null plan / frames, the frame count,
-// the sample size, even dimensions, the two layouts, the pointers' alignment.  Resolves the layouts, and the fills in stored form.
-struct PbNv12Call {
-    PbNv12Frame fs, fd;
-    PbNv12 L;
-};
-static int pb_nv12_check(const pb_plan* plan, const void* src_dev, const void* dst_dev, int n_frames, const pb_nv12_layout* src_layout,
-                         const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3], PbNv12Call& c) {
-    if (!plan || !src_dev || !dst_dev) return pb_fail(PB_ERR_INVALID, "null argument");
-    if (n_frames < 0) return pb_fail(PB_ERR_INVALID, "negative frame count");
-    if (bytes_per_sample != 1 && bytes_per_sample != 2) return pb_fail(PB_ERR_INVALID, "bytes_per_sample outside {1, 2}");
-    if (!pb_nv12_dims_even(plan)) return pb_fail(PB_ERR_INVALID, "4:2:0 frames need even source and destination dimensions");
-    const PbParams& P = plan->P;
-    const unsigned long long S = (unsigned long long)bytes_per_sample;
-    int rc = pb_nv12_resolve("source", src_layout, S, (unsigned long long)P.src.height, (unsigned long long)P.src.width, c.fs);
-    if (rc == PB_OK) rc = pb_nv12_resolve("destination", dst_layout, S, (unsigned long long)P.dst.height, (unsigned long long)P.dst.width, c.fd);
-    if (rc != PB_OK) return rc;
-    if (((uintptr_t)src_dev | (uintptr_t)dst_dev) % (2 * S))
-        return pb_fail(PB_ERR_INVALID, "frame pointers must be multiples of " + std::to_string(2 * S) + " bytes (one chroma pair)");
-    const unsigned sh = 8u * ((unsigned)S - 1u), smask = S == 1 ? 0xFFu : 0xFFFFu;
-    const unsigned fy = fill_yuv ? fill_yuv[0] & smask : 16u << sh, fu = fill_yuv ? fill_yuv[1] & smask : 128u << sh, fv = fill_yuv ? fill_yuv[2] & smask : 128u << sh;
-    // (pitches and offsets are below 2^31: pb_nv12_resolve)
-    c.L = {(unsigned)c.fs.pitch, (unsigned)c.fs.uv, (unsigned)c.fd.pitch, (unsigned)c.fd.uv, fy, fu | (fv << (8u * (unsigned)S))};
-    return PB_OK;
-}
-// the two 4:2:0 semi-planar calls: nearest (pb_nv12_hot_kernel) and bilinear (pb_planar_bilinear_kernel with pairs; the layout as a PbPlanar)
-static int pb_nv12_call(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout,
-                        int bytes_per_sample, const uint16_t fill_yuv[3], void* stream, int interpolation, const char* name) {
-    PbNv12Call c;
-    int rc = pb_nv12_check(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, bytes_per_sample, fill_yuv, c);
-    if (rc != PB_OK || n_frames == 0) return rc;
-    rc = pb_check_device(plan);
-    if (rc != PB_OK) return rc;
-    const PbRoute r = pb_route(plan, interpolation, 1, 0, false, bytes_per_sample, true);
-    if ((r.kind == PbRoute::NV12 || r.kind == PbRoute::VIDEO_BIL) && (c.fs.span >= (1ull << 31) || c.fd.span >= (1ull << 31)))
-        return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes frames whose planes span less than 2^31 bytes: use pb_index_map_i32 and gather the two planes");
-    const unsigned sbits = 8u * (unsigned)bytes_per_sample, smask = (1u << sbits) - 1u;
-    const PbPlanar Lp = {c.L.src_pitch, c.L.src_pitch, c.L.src_uv, 0u, c.L.dst_pitch, c.L.dst_pitch, c.L.dst_uv, 0u, {c.L.fill_y, c.L.fill_uv & smask, c.L.fill_uv >> sbits}};
-    return pb_launch(plan, r, static_cast<const uint8_t*>(src_dev), static_cast<uint8_t*>(dst_dev), n_frames, c.fs.stride, c.fd.stride, (hipStream_t)stream, &c.L, &Lp);
-}
-int pb_remap_nv12_bilinear(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout,
-                           int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
-    return pb_nv12_call(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, bytes_per_sample, fill_yuv, stream, PB_INTERP_BILINEAR, "pb_remap_nv12_bilinear");
-}
-int pb_remap_nv12(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout,
-                  int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
-    return pb_nv12_call(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, bytes_per_sample, fill_yuv, stream, PB_INTERP_NEAREST, "pb_remap_nv12");
-}
-static int pb_nv12_supported(const pb_plan* plan, int bytes_per_sample, int interpolation);
-int pb_remap_nv12_supported(const pb_plan* plan, int bytes_per_sample) { return pb_nv12_supported(plan, bytes_per_sample, PB_INTERP_NEAREST); }
-int pb_remap_nv12_bilinear_supported(const pb_plan* plan, int bytes_per_sample) { return pb_nv12_supported(plan, bytes_per_sample, PB_INTERP_BILINEAR); }
-static int pb_nv12_supported(const pb_plan* plan, int bytes_per_sample, int interpolation) {
-    if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
-    if (bytes_per_sample != 1 && bytes_per_sample != 2) return pb_fail(PB_ERR_INVALID, "bytes_per_sample outside {1, 2}");
-    if (!pb_nv12_dims_even(plan)) return pb_fail(PB_ERR_INVALID, "4:2:0 frames need even source and destination dimensions");
-    // (packed frames: 3/2 S h w bytes; a pitched layout's span is pb_remap_nv12's to check)
-    const PbParams& P = plan->P;
-    const unsigned long long S = (unsigned long long)bytes_per_sample;
-    const PbRoute::Kind k = pb_route(plan, interpolation, 1, 0, false, bytes_per_sample, true).kind;
-    return (k == PbRoute::NV12 || k == PbRoute::VIDEO_BIL) && 3 * S * P.src.height * P.src.width / 2 < (1ull << 31) && 3 * S * P.dst.height * P.dst.width / 2 < (1ull << 31);
-}
-
-// Planar frames.  Every check comes before the device is looked at and before any launch.
-struct PbPlanarFrame {  // a resolved layout, in bytes
-    unsigned long long pitch, cpitch, o1, o2, span, stride;
-};
 static int pb_planar_resolve(const char* what, const pb_planar_layout* l, unsigned long long S, unsigned long long h, unsigned long long w, int cx, int cy,
-                             PbPlanarFrame& f) {
+                             PbVideoFrame& f) {
     const std::string n(what);
     // (a frame must span less than 2^31 bytes to be served: a member at or beyond that is refused here, before anything is multiplied -
     //  no product below can wrap, whatever the caller passes)
@@ -2241,83 +2174,95 @@ static int pb_planar_resolve(const char* what, const pb_planar_layout* l, unsign
         return pb_fail(PB_ERR_INVALID, n + " pitch, chroma_pitch, offsets and frame_stride must be multiples of " + std::to_string(S) + " bytes (one sample)");
     return PB_OK;
 }
-static bool pb_planar_sub_ok(int sub) { return sub == PB_PLANAR_444 || sub == PB_PLANAR_422 || sub == PB_PLANAR_420; }
-static int pb_planar_dims(const pb_plan* plan, int sub) {
+// layout: a pb_nv12_layout (pairs) or a pb_planar_layout, null for the packed defaults
+static int pb_video_resolve(const PbVideoFmt& v, const char* what, const void* layout, const PbEnd& p, PbVideoFrame& f) {
+    const unsigned long long S = (unsigned long long)v.S, h = (unsigned long long)p.height, w = (unsigned long long)p.width;
+    return v.pairs ? pb_nv12_resolve(what, static_cast<const pb_nv12_layout*>(layout), S, h, w, f)
+                   : pb_planar_resolve(what, static_cast<const pb_planar_layout*>(layout), S, h, w, v.cx(), v.cy(), f);
+}
+// the sample size, the subsampling and the dimension rule of a format: what the calls and the _supported questions check alike
+static int pb_video_fmt_check(const pb_plan* plan, const PbVideoFmt& v) {
+    if (v.S != 1 && v.S != 2) return pb_fail(PB_ERR_INVALID, "bytes_per_sample outside {1, 2}");
+    if (v.sub != PB_PLANAR_444 && v.sub != PB_PLANAR_422 && v.sub != PB_PLANAR_420)
+        return pb_fail(PB_ERR_INVALID, "subsampling outside {PB_PLANAR_444, PB_PLANAR_422, PB_PLANAR_420}");
     const PbParams& P = plan->P;
-    const int cx = pb_planar_cx(sub), cy = pb_planar_cy(sub);
-    if (((P.src.width | P.dst.width) & cx) || ((P.src.height | P.dst.height) & cy))
-        return pb_fail(PB_ERR_INVALID, sub == PB_PLANAR_420 ? "4:2:0 frames need even source and destination dimensions" : "4:2:2 frames need even source and destination widths");
+    if (((P.src.width | P.dst.width) & v.cx()) || ((P.src.height | P.dst.height) & v.cy()))
+        return pb_fail(PB_ERR_INVALID, v.sub == PB_PLANAR_420 ? "4:2:0 frames need even source and destination dimensions" : "4:2:2 frames need even source and destination widths");
     return PB_OK;
 }
-// The arguments of the two planar entry points (pb_remap_planar, pb_remap_track_planar), in this order: null plan / frames, the frame
-// count, the sample size, the subsampling, the dimension rule, the two layouts, the pointers' alignment.  Resolves the layouts and fills.
-struct PbPlanarCall {
-    PbPlanarFrame fs, fd;
+// The arguments of every video entry point, in this order: null plan / frames, the frame count, the sample size, the subsampling, the
+// dimension rule, the two layouts (source first), the pointers' alignment.  Resolves the layouts, and the fills in stored form.
+struct PbVideoCall {
+    PbVideoFmt fmt;
+    PbVideoFrame fs, fd;
     PbPlanar L;
+    bool span_fits() const { return fs.span < (1ull << 31) && fd.span < (1ull << 31); }
 };
-static int pb_planar_check(const pb_plan* plan, const void* src_dev, const void* dst_dev, int n_frames, const pb_planar_layout* src_layout,
-                           const pb_planar_layout* dst_layout, int sub, int bytes_per_sample, const uint16_t fill[3], PbPlanarCall& c) {
+static int pb_video_check(const pb_plan* plan, const void* src_dev, const void* dst_dev, int n_frames, const void* src_layout, const void* dst_layout,
+                          const PbVideoFmt& v, const uint16_t fill[3], PbVideoCall& c) {
     if (!plan || !src_dev || !dst_dev) return pb_fail(PB_ERR_INVALID, "null argument");
     if (n_frames < 0) return pb_fail(PB_ERR_INVALID, "negative frame count");
-    if (bytes_per_sample != 1 && bytes_per_sample != 2) return pb_fail(PB_ERR_INVALID, "bytes_per_sample outside {1, 2}");
-    if (!pb_planar_sub_ok(sub)) return pb_fail(PB_ERR_INVALID, "subsampling outside {PB_PLANAR_444, PB_PLANAR_422, PB_PLANAR_420}");
-    int rc = pb_planar_dims(plan, sub);
+    int rc = pb_video_fmt_check(plan, v);
+    if (rc == PB_OK) rc = pb_video_resolve(v, "source", src_layout, plan->P.src, c.fs);
+    if (rc == PB_OK) rc = pb_video_resolve(v, "destination", dst_layout, plan->P.dst, c.fd);
     if (rc != PB_OK) return rc;
-    const PbParams& P = plan->P;
-    const unsigned long long S = (unsigned long long)bytes_per_sample;
-    const int cx = pb_planar_cx(sub), cy = pb_planar_cy(sub);
-    rc = pb_planar_resolve("source", src_layout, S, (unsigned long long)P.src.height, (unsigned long long)P.src.width, cx, cy, c.fs);
-    if (rc == PB_OK) rc = pb_planar_resolve("destination", dst_layout, S, (unsigned long long)P.dst.height, (unsigned long long)P.dst.width, cx, cy, c.fd);
-    if (rc != PB_OK) return rc;
-    if (((uintptr_t)src_dev | (uintptr_t)dst_dev) % S) return pb_fail(PB_ERR_INVALID, "frame pointers must be multiples of " + std::to_string(S) + " bytes (one sample)");
-    const unsigned sh = 8u * ((unsigned)S - 1u), smask = S == 1 ? 0xFFu : 0xFFFFu;
-    // (pitches and offsets are below 2^31: pb_planar_resolve; they are used only when the span is, too)
+    if (((uintptr_t)src_dev | (uintptr_t)dst_dev) % v.unit())
+        return pb_fail(PB_ERR_INVALID, "frame pointers must be multiples of " + std::to_string(v.unit()) + " bytes (" + v.unit_name() + ")");
+    const unsigned sh = 8u * ((unsigned)v.S - 1u), smask = v.S == 1 ? 0xFFu : 0xFFFFu;
+    // (pitches and offsets are below 2^31: the resolvers; they are used only when the span is, too)
+    c.fmt = v;
     c.L = {(unsigned)c.fs.pitch, (unsigned)c.fs.cpitch, (unsigned)c.fs.o1, (unsigned)c.fs.o2, (unsigned)c.fd.pitch, (unsigned)c.fd.cpitch, (unsigned)c.fd.o1, (unsigned)c.fd.o2,
            {fill ? fill[0] & smask : 16u << sh, fill ? fill[1] & smask : 128u << sh, fill ? fill[2] & smask : 128u << sh}};
     return PB_OK;
 }
-static bool pb_planar_span_fits(const PbPlanarCall& c) { return c.fs.span < (1ull << 31) && c.fd.span < (1ull << 31); }
-// the two planar calls: nearest (pb_planar_hot_kernel) and bilinear (pb_planar_bilinear_kernel)
-static int pb_planar_call(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout,
-                          int subsampling, int bytes_per_sample, const uint16_t fill[3], void* stream, int interpolation, const char* name) {
-    PbPlanarCall c;
-    int rc = pb_planar_check(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, subsampling, bytes_per_sample, fill, c);
+// the plain calls: nearest (pb_nv12_hot_kernel / pb_planar_hot_kernel) and bilinear (pb_planar_bilinear_kernel, with pairs for NV12)
+static int pb_video_call(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const void* src_layout, const void* dst_layout, const PbVideoFmt& v,
+                         const uint16_t fill[3], void* stream, int interpolation, const char* name) {
+    PbVideoCall c;
+    int rc = pb_video_check(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, v, fill, c);
     if (rc != PB_OK || n_frames == 0) return rc;
     rc = pb_check_device(plan);
     if (rc != PB_OK) return rc;
-    const PbRoute r = pb_route(plan, interpolation, 1, 0, false, bytes_per_sample, false, subsampling);
-    if ((r.kind == PbRoute::PLANAR || r.kind == PbRoute::VIDEO_BIL) && !pb_planar_span_fits(c))
-        return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes frames whose planes span less than 2^31 bytes: use pb_index_map_i32 and gather the three planes");
-    return pb_launch(plan, r, static_cast<const uint8_t*>(src_dev), static_cast<uint8_t*>(dst_dev), n_frames, c.fs.stride, c.fd.stride, (hipStream_t)stream, nullptr, &c.L);
+    const PbRoute r = pb_route(plan, interpolation, 1, 0, false, 3, &v);
+    if ((r.kind == PbRoute::VIDEO || r.kind == PbRoute::VIDEO_BIL) && !c.span_fits())
+        return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes frames whose planes span less than 2^31 bytes: use pb_index_map_i32 and gather the " + v.planes() + " planes");
+    return pb_launch(plan, r, static_cast<const uint8_t*>(src_dev), static_cast<uint8_t*>(dst_dev), n_frames, c.fs.stride, c.fd.stride, (hipStream_t)stream, &c.L);
 }
+// (packed frames; a pitched layout's span is the call's to check)
+static int pb_video_supported(const pb_plan* plan, const PbVideoFmt& v, int interpolation) {
+    if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
+    if (int rc = pb_video_fmt_check(plan, v)) return rc;
+    PbVideoCall c;
+    if (pb_video_resolve(v, "source", nullptr, plan->P.src, c.fs) != PB_OK || pb_video_resolve(v, "destination", nullptr, plan->P.dst, c.fd) != PB_OK) return 0;
+    const PbRoute::Kind k = pb_route(plan, interpolation, 1, 0, false, 3, &v).kind;
+    return (k == PbRoute::VIDEO || k == PbRoute::VIDEO_BIL) && c.span_fits();
+}
+static PbVideoFmt pb_fmt_nv12(int bytes_per_sample) { return {true, PB_PLANAR_420, bytes_per_sample}; }
+static PbVideoFmt pb_fmt_planar(int subsampling, int bytes_per_sample) { return {false, subsampling, bytes_per_sample}; }
+int pb_remap_nv12_bilinear(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout,
+                           int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
+    return pb_video_call(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, pb_fmt_nv12(bytes_per_sample), fill_yuv, stream, PB_INTERP_BILINEAR, "pb_remap_nv12_bilinear");
+}
+int pb_remap_nv12(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout,
+                  int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
+    return pb_video_call(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, pb_fmt_nv12(bytes_per_sample), fill_yuv, stream, PB_INTERP_NEAREST, "pb_remap_nv12");
+}
+int pb_remap_nv12_supported(const pb_plan* plan, int bytes_per_sample) { return pb_video_supported(plan, pb_fmt_nv12(bytes_per_sample), PB_INTERP_NEAREST); }
+int pb_remap_nv12_bilinear_supported(const pb_plan* plan, int bytes_per_sample) { return pb_video_supported(plan, pb_fmt_nv12(bytes_per_sample), PB_INTERP_BILINEAR); }
 int pb_remap_planar(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout,
                     int subsampling, int bytes_per_sample, const uint16_t fill[3], void* stream) {
-    return pb_planar_call(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, subsampling, bytes_per_sample, fill, stream, PB_INTERP_NEAREST, "pb_remap_planar");
+    return pb_video_call(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, pb_fmt_planar(subsampling, bytes_per_sample), fill, stream, PB_INTERP_NEAREST, "pb_remap_planar");
 }
 int pb_remap_planar_bilinear(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout,
                              int subsampling, int bytes_per_sample, const uint16_t fill[3], void* stream) {
-    return pb_planar_call(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, subsampling, bytes_per_sample, fill, stream, PB_INTERP_BILINEAR, "pb_remap_planar_bilinear");
+    return pb_video_call(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, pb_fmt_planar(subsampling, bytes_per_sample), fill, stream, PB_INTERP_BILINEAR,
+                         "pb_remap_planar_bilinear");
 }
-static int pb_planar_supported(const pb_plan* plan, int subsampling, int bytes_per_sample, int interpolation);
-int pb_remap_planar_supported(const pb_plan* plan, int subsampling, int bytes_per_sample) { return pb_planar_supported(plan, subsampling, bytes_per_sample, PB_INTERP_NEAREST); }
+int pb_remap_planar_supported(const pb_plan* plan, int subsampling, int bytes_per_sample) {
+    return pb_video_supported(plan, pb_fmt_planar(subsampling, bytes_per_sample), PB_INTERP_NEAREST);
+}
 int pb_remap_planar_bilinear_supported(const pb_plan* plan, int subsampling, int bytes_per_sample) {
-    return pb_planar_supported(plan, subsampling, bytes_per_sample, PB_INTERP_BILINEAR);
-}
-static int pb_planar_supported(const pb_plan* plan, int subsampling, int bytes_per_sample, int interpolation) {
-    if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
-    if (bytes_per_sample != 1 && bytes_per_sample != 2) return pb_fail(PB_ERR_INVALID, "bytes_per_sample outside {1, 2}");
-    if (!pb_planar_sub_ok(subsampling)) return pb_fail(PB_ERR_INVALID, "subsampling outside {PB_PLANAR_444, PB_PLANAR_422, PB_PLANAR_420}");
-    if (int rc = pb_planar_dims(plan, subsampling)) return rc;
-    // (packed frames; a pitched layout's span is pb_remap_planar's to check)
-    PbPlanarFrame fs, fd;
-    const PbParams& P = plan->P;
-    const unsigned long long S = (unsigned long long)bytes_per_sample;
-    const int cx = pb_planar_cx(subsampling), cy = pb_planar_cy(subsampling);
-    if (pb_planar_resolve("source", nullptr, S, (unsigned long long)P.src.height, (unsigned long long)P.src.width, cx, cy, fs) != PB_OK ||
-        pb_planar_resolve("destination", nullptr, S, (unsigned long long)P.dst.height, (unsigned long long)P.dst.width, cx, cy, fd) != PB_OK)
-        return 0;
-    const PbRoute::Kind k = pb_route(plan, interpolation, 1, 0, false, bytes_per_sample, false, subsampling).kind;
-    return (k == PbRoute::PLANAR || k == PbRoute::VIDEO_BIL) && fs.span < (1ull << 31) && fd.span < (1ull << 31);
+    return pb_video_supported(plan, pb_fmt_planar(subsampling, bytes_per_sample), PB_INTERP_BILINEAR);
 }
 
 int pb_remap_u8v(const pb_plan* plan, const uint8_t* const* src_dev, uint8_t* const* dst_dev, int n_frames, void* stream) {
@@ -2436,14 +2381,14 @@ int pb_remap_track_u8(const pb_plan* plan, const double* rot3x3_dev, int n_rot_p
     return PB_OK;
 }
 
-// A rotation track of 4:2:0 semi-planar frames (bilinear: 3.19): pb_remap_nv12's argument checks, then pb_remap_track_u8's table
-// checks; the launches are pb_remap_track_u8's, one per 65535 chunks of frames.  Nearest: pb_track_nv12_kernel; bilinear:
-// pb_track_video_bilinear_kernel with pairs (the layout as a PbPlanar), a panorama or camera source.
-static int pb_track_nv12_call(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
-                              const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3], void* stream,
-                              int interpolation, const char* name) {
-    PbNv12Call c;
-    int rc = pb_nv12_check(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, bytes_per_sample, fill_yuv, c);
+// A rotation track of video frames (bilinear: 3.19): the plain video calls' argument checks, then pb_remap_track_u8's
+// table checks; the launches are pb_remap_track_u8's, one per 65535 chunks of frames.  Nearest: pb_track_nv12_kernel / pb_track_planar_kernel;
+// bilinear: pb_track_video_bilinear_kernel (with pairs for NV12), a panorama or camera source.
+static int pb_track_video_call(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                               const void* src_layout, const void* dst_layout, const PbVideoFmt& v, const uint16_t fill[3], void* stream, int interpolation,
+                               const char* name) {
+    PbVideoCall c;
+    int rc = pb_video_check(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, v, fill, c);
     if (rc == PB_OK) rc = pb_track_table_check(plan, rot3x3_dev, n_rot_per_frame);
     if (rc != PB_OK || n_frames == 0) return rc;
     rc = pb_check_device(plan);
@@ -2454,33 +2399,39 @@ static int pb_track_nv12_call(const pb_plan* plan, const double* rot3x3_dev, int
     if (interpolation == PB_INTERP_BILINEAR && pb_is_cube(P.src.kind))
         return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes panorama and camera sources (the bilinear definition of video frames covers no cube map): convert to "
                                                                "RGB8 and use pb_remap_track_u8");
-    if (c.fs.span >= (1ull << 31) || c.fd.span >= (1ull << 31) || P.src.height >= 32768 || P.src.width >= 32768)
+    if (!c.span_fits() || P.src.height >= 32768 || P.src.width >= 32768)
         return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes frames whose planes span less than 2^31 bytes and sources below 32768 px a side: use a plan per "
-                                                               "frame with pb_index_map_i32 and gather the two planes");
+                                                               "frame with pb_index_map_i32 and gather the " + v.planes() + " planes");
     hipStream_t st = (hipStream_t)stream;
     const unsigned long long quads = (unsigned long long)P.dst.height * (((unsigned)P.dst.width + PB_PX - 1) / PB_PX);
     const int fpc = pb_track_fpc();
     const int per_launch = 65535 * fpc;
-    const unsigned sbits = 8u * (unsigned)bytes_per_sample, smask = (1u << sbits) - 1u;
-    const PbPlanar Lp = {c.L.src_pitch, c.L.src_pitch, c.L.src_uv, 0u, c.L.dst_pitch, c.L.dst_pitch, c.L.dst_uv, 0u, {c.L.fill_y, c.L.fill_uv & smask, c.L.fill_uv >> sbits}};
+    const int cx = v.cx(), cy = v.cy();
     for (int f0 = 0; f0 < n_frames; f0 += per_launch) {
         const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
         const double* rot = rot3x3_dev + 9ull * (unsigned)n_rot_per_frame * (unsigned)f0;
         const uint8_t* s = static_cast<const uint8_t*>(src_dev) + (unsigned long long)f0 * c.fs.stride;
         uint8_t* d = static_cast<uint8_t*>(dst_dev) + (unsigned long long)f0 * c.fd.stride;
         const dim3 grid(pb_blocks(quads), (unsigned)((nf + fpc - 1) / fpc));
-        if (interpolation == PB_INTERP_BILINEAR)
+        auto launch = [&](auto kernel, auto... layout) {
+            hipLaunchKernelGGL(kernel, grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride, c.fd.stride, layout...);
+        };
+        const bool bilinear = interpolation == PB_INTERP_BILINEAR;
+        if (v.pairs && bilinear)
             pb_pick_kind(P, [&](auto K) {
-                pb_pick<1, 2>(bytes_per_sample == 1, [&](auto S) {
-                    hipLaunchKernelGGL((pb_track_video_bilinear_kernel<S.value, K.value, true>), grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride,
-                                       c.fd.stride, Lp, 1, 1);
-                });
+                pb_pick<1, 2>(v.S == 1, [&](auto S) { launch(pb_track_video_bilinear_kernel<S.value, K.value, true>, c.L, cx, cy); });
+            });
+        else if (v.pairs)
+            pb_pick_exact_kind(P, [&](auto K) {
+                pb_pick<1, 2>(v.S == 1, [&](auto S) { launch(pb_track_nv12_kernel<S.value, K.value>, pb_nv12_of(c.L, S.value)); });
+            });
+        else if (bilinear)
+            pb_pick_kind(P, [&](auto K) {
+                pb_pick<1, 2>(v.S == 1, [&](auto S) { launch(pb_track_video_bilinear_kernel<S.value, K.value, false>, c.L, cx, cy); });
             });
         else
             pb_pick_exact_kind(P, [&](auto K) {
-                pb_pick<1, 2>(bytes_per_sample == 1, [&](auto S) {
-                    hipLaunchKernelGGL((pb_track_nv12_kernel<S.value, K.value>), grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride, c.fd.stride, c.L);
-                });
+                pb_pick<1, 2>(v.S == 1, [&](auto S) { launch(pb_track_planar_kernel<S.value, K.value>, c.L, cx, cy); });
             });
     }
     PB_HIP(hipGetLastError());
@@ -2488,75 +2439,25 @@ static int pb_track_nv12_call(const pb_plan* plan, const double* rot3x3_dev, int
 }
 int pb_remap_track_nv12(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
                         const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
-    return pb_track_nv12_call(plan, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, n_frames, src_layout, dst_layout, bytes_per_sample, fill_yuv, stream, PB_INTERP_NEAREST,
-                              "pb_remap_track_nv12");
+    return pb_track_video_call(plan, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, n_frames, src_layout, dst_layout, pb_fmt_nv12(bytes_per_sample), fill_yuv, stream,
+                               PB_INTERP_NEAREST, "pb_remap_track_nv12");
 }
 int pb_remap_track_nv12_bilinear(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
                                  const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
-    return pb_track_nv12_call(plan, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, n_frames, src_layout, dst_layout, bytes_per_sample, fill_yuv, stream, PB_INTERP_BILINEAR,
-                              "pb_remap_track_nv12_bilinear");
-}
-
-// A rotation track of planar frames (bilinear: 3.19): pb_remap_planar's argument checks, then pb_remap_track_u8's table checks;
-// the launches are pb_remap_track_nv12's.  Nearest: pb_track_planar_kernel; bilinear: pb_track_video_bilinear_kernel, a panorama or camera source.
-static int pb_track_planar_call(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
-                                const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample, const uint16_t fill[3],
-                                void* stream, int interpolation, const char* name) {
-    PbPlanarCall c;
-    int rc = pb_planar_check(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, subsampling, bytes_per_sample, fill, c);
-    if (rc == PB_OK) rc = pb_track_table_check(plan, rot3x3_dev, n_rot_per_frame);
-    if (rc != PB_OK || n_frames == 0) return rc;
-    rc = pb_check_device(plan);
-    if (rc != PB_OK) return rc;
-    const PbParams& P = plan->P;
-    if (P.src.kind == PB_KIND_DOUBLE)
-        return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes single sources (a double fisheye's blend is sample-typed): convert to RGB8 and use pb_remap_track_u8");
-    if (interpolation == PB_INTERP_BILINEAR && pb_is_cube(P.src.kind))
-        return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes panorama and camera sources (the bilinear definition of video frames covers no cube map): convert to "
-                                                               "RGB8 and use pb_remap_track_u8");
-    if (!pb_planar_span_fits(c) || P.src.height >= 32768 || P.src.width >= 32768)
-        return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes frames whose planes span less than 2^31 bytes and sources below 32768 px a side: use a plan per "
-                                                               "frame with pb_index_map_i32 and gather the three planes");
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned long long quads = (unsigned long long)P.dst.height * (((unsigned)P.dst.width + PB_PX - 1) / PB_PX);
-    const int fpc = pb_track_fpc();
-    const int per_launch = 65535 * fpc;
-    const int cx = pb_planar_cx(subsampling), cy = pb_planar_cy(subsampling);
-    for (int f0 = 0; f0 < n_frames; f0 += per_launch) {
-        const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
-        const double* rot = rot3x3_dev + 9ull * (unsigned)n_rot_per_frame * (unsigned)f0;
-        const uint8_t* s = static_cast<const uint8_t*>(src_dev) + (unsigned long long)f0 * c.fs.stride;
-        uint8_t* d = static_cast<uint8_t*>(dst_dev) + (unsigned long long)f0 * c.fd.stride;
-        const dim3 grid(pb_blocks(quads), (unsigned)((nf + fpc - 1) / fpc));
-        if (interpolation == PB_INTERP_BILINEAR)
-            pb_pick_kind(P, [&](auto K) {
-                pb_pick<1, 2>(bytes_per_sample == 1, [&](auto S) {
-                    hipLaunchKernelGGL((pb_track_video_bilinear_kernel<S.value, K.value, false>), grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride,
-                                       c.fd.stride, c.L, cx, cy);
-                });
-            });
-        else
-            pb_pick_exact_kind(P, [&](auto K) {
-                pb_pick<1, 2>(bytes_per_sample == 1, [&](auto S) {
-                    hipLaunchKernelGGL((pb_track_planar_kernel<S.value, K.value>), grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride, c.fd.stride, c.L, cx,
-                                       cy);
-                });
-            });
-    }
-    PB_HIP(hipGetLastError());
-    return PB_OK;
+    return pb_track_video_call(plan, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, n_frames, src_layout, dst_layout, pb_fmt_nv12(bytes_per_sample), fill_yuv, stream,
+                               PB_INTERP_BILINEAR, "pb_remap_track_nv12_bilinear");
 }
 int pb_remap_track_planar(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
                           const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample, const uint16_t fill[3],
                           void* stream) {
-    return pb_track_planar_call(plan, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, n_frames, src_layout, dst_layout, subsampling, bytes_per_sample, fill, stream,
-                                PB_INTERP_NEAREST, "pb_remap_track_planar");
+    return pb_track_video_call(plan, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, n_frames, src_layout, dst_layout, pb_fmt_planar(subsampling, bytes_per_sample), fill,
+                               stream, PB_INTERP_NEAREST, "pb_remap_track_planar");
 }
 int pb_remap_track_planar_bilinear(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
                                    const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample, const uint16_t fill[3],
                                    void* stream) {
-    return pb_track_planar_call(plan, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, n_frames, src_layout, dst_layout, subsampling, bytes_per_sample, fill, stream,
-                                PB_INTERP_BILINEAR, "pb_remap_track_planar_bilinear");
+    return pb_track_video_call(plan, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, n_frames, src_layout, dst_layout, pb_fmt_planar(subsampling, bytes_per_sample), fill,
+                               stream, PB_INTERP_BILINEAR, "pb_remap_track_planar_bilinear");
 }
 
 int pb_index_map_i32(const pb_plan* plan, int32_t* idx_dev, double* weights_dev, void* stream) {

@@ -374,7 +374,7 @@ def cubemap_to_cubemap(input_image, input_mapping, output_mapping, face_size, ou
 
 
 # ---- raw video frames ---------------------------------------------------------------------------
-PIX_FMTS = {"nv12": np.uint8, "p010": np.uint16}  # ffmpeg's -pix_fmt names of the two 4:2:0 semi-planar layouts
+PIX_FMTS = {name: dt.type for name, (dt, fam, _) in nat.VIDEO_FORMATS.items() if fam.pairs}  # ffmpeg's -pix_fmt names of the two 4:2:0 semi-planar layouts
 TRACK_FRAMES = 4  # PB_TRACK_FRAMES (csrc/pb_kernels_track.hpp): --chunk is a multiple of it
 
 
@@ -478,6 +478,38 @@ def _stream_frames(input_frames, output_frames, frame_in: int, dt, chunk: int, m
             fout.close()
 
 
+def _remap_video(pix_fmt, input_frames, output_frames, width, height, otype, lens, fov, size, rotation, track, chunk, interpolation, lens_coefficients, lens_max_theta):
+    """The body of remap-nv12 and remap-yuv: frames of the pixel format `pix_fmt` (``nat.VIDEO_FORMATS``)."""
+    bilinear = _video_sampler(interpolation, track)
+    dt, fam, fill = nat.VIDEO_FORMATS[pix_fmt]
+    rule, least = ("4:2:0 frames have even dimensions", 2) if fam.pairs else (nat.planar_dims_rule(fam.sub, pix_fmt), 1)
+    if width < least or height < least or not nat.planar_dims_ok(fam.sub, (height, width)):
+        _fail(f"{rule}, got --width {width} --height {height}")
+    if size is not None and (size < least or not nat.planar_dims_ok(fam.sub, (size, 2))):
+        _fail(f"{rule}, got --size {size}")
+    if chunk < TRACK_FRAMES or chunk % TRACK_FRAMES:
+        _fail(f"--chunk is a multiple of {TRACK_FRAMES}, got {chunk}")
+    cmap = _video_chain(width, height, otype, lens, fov, size, rotation, lens_coefficients, lens_max_theta)
+    dstp, srcp = cmap.dst_proj, PanoramaImage(np.zeros((height, width, 3), np.uint8))._proj("src")
+    if dstp.width & 1 if fam.pairs else not nat.planar_dims_ok(fam.sub, (dstp.height, dstp.width)):  # (a semi-planar output's height is --size or the input's)
+        _fail(f"{rule}: the output would be {dstp.height} x {dstp.width}")
+    mats = None if track is None else core.rotation_track(_read_track(track))
+    frame = fam.packed(height, width)[0]  # a packed frame as the plan's methods take it: (3h/2, w), or flat
+    # without a track: a prepared plan and the tile kernel; with one: a deferred plan (its tables are never read) and the track kernel
+    plan = None
+
+    def remap(host, first):  # upload, ONE launch, download
+        nonlocal plan
+        if plan is None:  # (made with the first frames: the usage errors of the input come before any plan is prepared)
+            plan = nat.Plan(dstp, list(cmap.rotations), srcp, bilinear=bilinear) if mats is None else nat.Plan(dstp, list(cmap.rotations), srcp, defer=True)
+        s = nat.to_device(host.reshape((len(host),) + frame))
+        if fam.pairs:
+            return plan.remap_nv12(s, **_sampler(interpolation)) if mats is None else plan.remap_track_nv12(s, mats[first : first + len(host)])
+        return plan.remap_planar(s, fam.sub, fill=fill, **_sampler(interpolation)) if mats is None else plan.remap_track_planar(s, mats[first : first + len(host)], fam.sub, fill=fill)
+
+    _stream_frames(input_frames, output_frames, int(np.prod(frame)) * dt.itemsize, dt, chunk, mats, remap)
+
+
 @main.command("remap-nv12")
 @click.argument("input_frames", metavar="INPUT", type=click.Path(path_type=Path, allow_dash=True))
 @click.argument("output_frames", metavar="OUTPUT", type=click.Path(path_type=Path, allow_dash=True))
@@ -504,31 +536,7 @@ def remap_nv12(input_frames, output_frames, width, height, pix_fmt, otype, lens,
     OUTPUT receives the packed output frames; - is stdout.
     By default the output is a panorama of the same size (--size H: H x 2H); with --type, --lens and --fov it is the photo make-photo would make.
     """
-    bilinear = _video_sampler(interpolation, track)
-    dt = np.dtype(PIX_FMTS[pix_fmt])
-    if width < 2 or height < 2 or (width | height) & 1:
-        _fail(f"4:2:0 frames have even dimensions, got --width {width} --height {height}")
-    if size is not None and (size < 2 or size & 1):
-        _fail(f"4:2:0 frames have even dimensions, got --size {size}")
-    if chunk < TRACK_FRAMES or chunk % TRACK_FRAMES:
-        _fail(f"--chunk is a multiple of {TRACK_FRAMES}, got {chunk}")
-    cmap = _video_chain(width, height, otype, lens, fov, size, rotation, lens_coefficients, lens_max_theta)
-    dstp, srcp = cmap.dst_proj, PanoramaImage(np.zeros((height, width, 3), np.uint8))._proj("src")
-    if dstp.width & 1:
-        _fail(f"4:2:0 frames have even dimensions: the output would be {dstp.height} x {dstp.width}")
-    mats = None if track is None else core.rotation_track(_read_track(track))
-    frame_in, frame_out = 3 * height * width // 2 * dt.itemsize, 3 * dstp.height * dstp.width // 2 * dt.itemsize
-    # without a track: a prepared plan and the tile kernel; with one: a deferred plan (its tables are never read) and the track kernel
-    plan = None
-
-    def remap(host, first):  # upload, ONE launch, download
-        nonlocal plan
-        if plan is None:  # (made with the first frames: the usage errors of the input come before any plan is prepared)
-            plan = nat.Plan(dstp, list(cmap.rotations), srcp, bilinear=bilinear) if mats is None else nat.Plan(dstp, list(cmap.rotations), srcp, defer=True)
-        s = nat.to_device(host.reshape(len(host), 3 * height // 2, width))
-        return plan.remap_nv12(s, **_sampler(interpolation)) if mats is None else plan.remap_track_nv12(s, mats[first : first + len(host)])
-
-    _stream_frames(input_frames, output_frames, frame_in, dt, chunk, mats, remap)
+    _remap_video(pix_fmt, input_frames, output_frames, width, height, otype, lens, fov, size, rotation, track, chunk, interpolation, lens_coefficients, lens_max_theta)
 
 
 @main.command("remap-yuv")
@@ -559,32 +567,7 @@ def remap_yuv(input_frames, output_frames, width, height, pix_fmt, otype, lens, 
     By default the output is a panorama of the same size (--size H: H x 2H); with --type, --lens and --fov it is the photo make-photo would make.
     4:2:0 formats have even widths and heights, 4:2:2 formats even widths, 4:4:4 formats (gbrp among them) take any size.
     """
-    bilinear = _video_sampler(interpolation, track)
-    dt, sub, fill = nat.PLANAR_FORMATS[pix_fmt]
-    rule = nat.planar_dims_rule(sub, pix_fmt)
-    if width < 1 or height < 1 or not nat.planar_dims_ok(sub, (height, width)):
-        _fail(f"{rule}, got --width {width} --height {height}")
-    if size is not None and (size < 1 or not nat.planar_dims_ok(sub, (size, 2))):
-        _fail(f"{rule}, got --size {size}")
-    if chunk < TRACK_FRAMES or chunk % TRACK_FRAMES:
-        _fail(f"--chunk is a multiple of {TRACK_FRAMES}, got {chunk}")
-    cmap = _video_chain(width, height, otype, lens, fov, size, rotation, lens_coefficients, lens_max_theta)
-    dstp, srcp = cmap.dst_proj, PanoramaImage(np.zeros((height, width, 3), np.uint8))._proj("src")
-    if not nat.planar_dims_ok(sub, (dstp.height, dstp.width)):
-        _fail(f"{rule}: the output would be {dstp.height} x {dstp.width}")
-    mats = None if track is None else core.rotation_track(_read_track(track))
-    frame_in = nat.planar_frame_samples(height, width, sub) * dt.itemsize
-    # without a track: a prepared plan and the tile kernel; with one: a deferred plan (its tables are never read) and the track kernel
-    plan = None
-
-    def remap(host, first):  # upload, ONE launch, download
-        nonlocal plan
-        if plan is None:  # (made with the first frames: the usage errors of the input come before any plan is prepared)
-            plan = nat.Plan(dstp, list(cmap.rotations), srcp, bilinear=bilinear) if mats is None else nat.Plan(dstp, list(cmap.rotations), srcp, defer=True)
-        s = nat.to_device(host)
-        return plan.remap_planar(s, sub, fill=fill, **_sampler(interpolation)) if mats is None else plan.remap_track_planar(s, mats[first : first + len(host)], sub, fill=fill)
-
-    _stream_frames(input_frames, output_frames, frame_in, dt, chunk, mats, remap)
+    _remap_video(pix_fmt, input_frames, output_frames, width, height, otype, lens, fov, size, rotation, track, chunk, interpolation, lens_coefficients, lens_max_theta)
 
 
 if __name__ == "__main__":

@@ -195,24 +195,24 @@ def test_plan_remap_planar_checks_its_arguments_without_a_gpu(monkeypatch):
     with pytest.raises(nat.PbError, match="pb_index_map_i32"):  # (the raw calls: refused by the library, a deferred plan)
         plan.launch_planar(FAKE, FAKE, "422", 1, 0)
     with pytest.raises(nat.PbError, match="uint8 or uint16"):
-        plan._planar_source(FakeDevice((48,), np.float32), nat.PLANAR_420, None)
+        plan._video_source(nat.video_family(nat.PLANAR_420), FakeDevice((48,), np.float32), None)
     # shapes: flat or (N, flat); 4:4:4 also (3, h, w) / (N, 3, h, w); nothing else
     for sub, good, bad in (("420", [(48,), (3, 48)], [(6, 8), (47,), (3, 4, 8), (96,)]), ("422", [(64,), (2, 64)], [(8, 8), (48,), (3, 4, 8)]),
                            ("444", [(96,), (5, 96), (3, 4, 8), (2, 3, 4, 8)], [(12, 8), (4, 8, 3), (3, 8, 4), (64,)])):
         sid = SUBS[sub]
         for shp in good:
-            src, s, got, dt, sl, n = plan._planar_source(FakeDevice(shp, np.uint16), sid, None)
-            assert (s, got, dt, sl) == (sid, shp, np.dtype(np.uint16), None) and n == (shp[0] if len(shp) in (2, 4) else 1)
+            src, fam, got, dt, sl, n = plan._video_source(nat.video_family(sid), FakeDevice(shp, np.uint16), None)
+            assert (fam.sub, got, dt, sl) == (sid, shp, np.dtype(np.uint16), None) and n == (shp[0] if len(shp) in (2, 4) else 1)
         for shp in bad:
             with pytest.raises(nat.PbError, match="packed source frames"):
-                plan._planar_source(FakeDevice(shp, np.uint8), sid, None)
+                plan._video_source(nat.video_family(sid), FakeDevice(shp, np.uint8), None)
     # frames at a layout: a 1-D buffer, counted by the stride
     l = (16, 8, 80, 128, 256)
-    assert plan._planar_source(FakeDevice((256 * 2 + 140,), np.uint8), nat.PLANAR_420, l)[-1] == 3  # (a frame ends with plane 2's last sample: 128 + 8 + 4)
+    assert plan._video_source(nat.video_family(nat.PLANAR_420), FakeDevice((256 * 2 + 140,), np.uint8), l)[-1] == 3  # (a frame ends with plane 2's last sample: 128 + 8 + 4)
     with pytest.raises(nat.PbError, match="1-D"):
-        plan._planar_source(FakeDevice((3, 256), np.uint8), nat.PLANAR_420, l)
+        plan._video_source(nat.video_family(nat.PLANAR_420), FakeDevice((3, 256), np.uint8), l)
     with pytest.raises(nat.PbError, match="spans 140"):
-        plan._planar_source(FakeDevice((139,), np.uint8), nat.PLANAR_420, l)
+        plan._video_source(nat.video_family(nat.PLANAR_420), FakeDevice((139,), np.uint8), l)
     # the dimension rule per subsampling
     for dims, refused in (((3, 8), ("420",)), ((4, 7), ("422", "420")), ((3, 7), ("422", "420"))):
         odd = nat.Plan(nat.make_proj(nat.KIND_PANO, *dims), [], p, defer=True)
@@ -220,7 +220,7 @@ def test_plan_remap_planar_checks_its_arguments_without_a_gpu(monkeypatch):
             n = planar_ref.frame_samples(4, 8, sub)
             if sub in refused:
                 with pytest.raises(nat.PbError, match="even"):
-                    odd._planar_source(FakeDevice((n,), np.uint8), sid, None)
+                    odd._video_source(nat.video_family(sid), FakeDevice((n,), np.uint8), None)
                 with pytest.raises(nat.PbError, match="even"):
                     odd.planar_supported(sub)
             else:
