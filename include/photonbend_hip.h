@@ -385,6 +385,43 @@ pb_remap_nv12_bilinear_supported(const pb_plan* plan, int bytes_per_sample);
  * row too).  All zero for a plan without the bilinear mode's tables. */
 int pb_plan_video_bilinear_mix(const pb_plan* plan, long long mix[4]);
 
+/* STITCHING video frames of a DOUBLE-FISHEYE source in ONE launch of the tile kernel pb_stitch_video_kernel whatever n_frames (ABI 5,
+ * additive): the side-by-side double fisheye as NV12 / P010 (pb_stitch_nv12) or planar frames (pb_stitch_planar), the
+ * destination in the same format.  The definition is written down in tests/stitch_video_ref.py.  With (il, ir, fl, fr) the reference's
+ * taps and factors of an output pixel (DoubleCameraImage.process_coordinate_map; pb_index_map_i32 with weights: indices r * width + c
+ * into the full frame, the right eye's already mirrored, -1 = that eye is black there) and
+ *   blend(a_l, a_r) = cast((il < 0 ? 0.0 : a_l) * fl + (ir < 0 ? 0.0 : a_r) * fr) in float64, the cast NumPy's astype widened to the
+ *                     sample: non-finite or |v| >= 2^31 gives 0, else truncate toward zero and keep the low 8 * S bits,
+ *   plane 0       out[y][x] = blend(P0[r_l][c_l], P0[r_r][c_r]); fill[0] where both taps are -1.
+ *   planes 1, 2   sample (i, j) (or the two members of a pair) is decided by its ANCHOR, output pixel (i << cy, j << cx), as in the nearest
+ *                 calls: blend(Pk[r_l >> cy][c_l >> cx], Pk[r_r >> cy][c_r >> cx]) with the anchor's taps and factors; fill[k] where both
+ *                 of the anchor's taps are -1.
+ * Exact: with S = 1, 4:4:4 and fill (0, 0, 0) the three planes are the three channels of pb_remap_u8's output for the RGB image whose
+ * channels are the source planes.  An eye that is black where the other is live contributes 0.0, as in the reference; the fill is used
+ * only where nothing is live.  In the reference's half-degree safety zone beside the merge band a factor slightly exceeds 1: a bright
+ * sample may wrap modulo 2^(8 * S) there (a 10-bit sample stored low wraps at 2^16) - the reference's quirk, reproduced.
+ * Arguments, layouts, defaults, PB_ERR_INVALID (checks, order and messages) and n_frames == 0: exactly pb_remap_planar's / pb_remap_nv12's.
+ * Frames need no alignment beyond one sample (one chroma pair for pb_stitch_nv12).
+ *   PB_ERR_UNSUPPORTED   nothing is written: a source that is not a double fisheye (use pb_remap_planar / pb_remap_nv12); deferred plans,
+ *                        PB_MODE_FAITHFUL, plans without both eyes' tile tables and a launch-order table (a geometry whose plan got
+ *                        none), sources of 32768 px a side or more; frames whose byte span reaches 2^31.
+ * Asynchronous on `stream`, never allocates or synchronises (graph-capture safe).  The _supported calls: 1 / 0 / negative as above. */
+int
+pb_stitch_planar(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_planar_layout* src_layout,
+                 const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample, const uint16_t fill[3], void* stream);
+int
+pb_stitch_nv12(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout,
+               const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3], void* stream);
+int
+pb_stitch_planar_supported(const pb_plan* plan, int subsampling, int bytes_per_sample);
+int
+pb_stitch_nv12_supported(const pb_plan* plan, int bytes_per_sample);
+/* Diagnostic, synchronous: what the waves of a stitch launch meet in `plan`, slot by slot of its launch-order table.  mix[0] = one-eye
+ * (SOLO) slots, mix[1] / mix[2] / mix[3] = two-eye tiles of weight class UNIT / ROW / LAT, mix[4] = failed tiles, mix[5] = two-eye
+ * tiles with fix pixels, mix[6] = their fix pixels, mix[7] = of those the chroma anchors at PB_PLANAR_422 (an even column), mix[8] = at
+ * PB_PLANAR_420 (an even row too).  All zero for a plan without the double-fisheye tile tables. */
+int pb_plan_stitch_tile_mix(const pb_plan* plan, long long mix[9]);
+
 /* OPT-IN extension with no reference counterpart (the reference samples nearest-by-truncation only):
  * bilinear interpolation at the reference's pre-truncation coordinate (pixel k covers [k, k+1), centre
  * k + 0.5; taps clamped to the image, panorama columns wrap; round half to even).  Pixels the nearest mode

@@ -111,6 +111,11 @@ SIGNATURES = {
     "pb_plan_bilinear_tile_mix": (C.c_int, [_VP, C.POINTER(C.c_longlong)]),
     "pb_plan_bilinear_launch_shape": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pb_plan_video_bilinear_mix": (C.c_int, [_VP, C.POINTER(C.c_longlong)]),
+    "pb_plan_stitch_tile_mix": (C.c_int, [_VP, C.POINTER(C.c_longlong)]),
+    "pb_stitch_nv12": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP]),
+    "pb_stitch_nv12_supported": (C.c_int, [_VP, C.c_int]),
+    "pb_stitch_planar": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, _VP]),
+    "pb_stitch_planar_supported": (C.c_int, [_VP, C.c_int, C.c_int]),
     "pb_plan_matches": (C.c_int, [_VP, C.POINTER(pb_proj), C.POINTER(C.c_double), C.c_int, C.POINTER(pb_proj)]),
     "pb_remap_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_u8v": (C.c_int, [_VP, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, _VP]),
@@ -390,6 +395,8 @@ def planar_frame_bytes(layout, height: int, width: int, bytes_per_sample: int, s
 _VIDEO_FUNCTIONS = {(pairs, tracked, bilinear, question): f"pb_remap_{'track_' if tracked else ''}{'nv12' if pairs else 'planar'}{'_bilinear' if bilinear else ''}"
                                                           f"{'_supported' if question else ''}"
                     for pairs in (False, True) for tracked in (False, True) for bilinear in (False, True) for question in (False, True) if not (tracked and question)}
+# ... and the stitch calls of a double-fisheye source: (semi-planar?, the _supported question?)
+_STITCH_FUNCTIONS = {(pairs, question): f"pb_stitch_{'nv12' if pairs else 'planar'}{'_supported' if question else ''}" for pairs in (False, True) for question in (False, True)}
 _FILL = C.c_uint16 * 3  # the samples of black pixels, as the video calls take them
 
 
@@ -778,6 +785,14 @@ class Plan:
         mix.update(zip(("fix_tiles", "fix_pixels", "fix_anchors_422", "fix_anchors_420"), (int(x) for x in v)))
         return mix
 
+    def stitch_tile_mix(self) -> dict:
+        """What the waves of a stitch launch (``stitch_planar`` / ``stitch_nv12``) meet in this plan, slot by slot of its launch-order table
+        (pb_plan_stitch_tile_mix; diagnostic, synchronous): one-eye slots, two-eye tiles by weight class, failed tiles, two-eye tiles with
+        fix pixels, those pixels, and of them the chroma anchors at 4:2:2 and at 4:2:0.  All zero without double-fisheye tile tables."""
+        m = (C.c_longlong * 9)()
+        check(load().pb_plan_stitch_tile_mix(self._h, m))
+        return dict(zip(("solo", "unit", "row", "lat", "failed", "fix_tiles", "fix_pixels", "fix_anchors_422", "fix_anchors_420"), (int(x) for x in m)))
+
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h and _lib is not None:
@@ -1087,18 +1102,53 @@ class Plan:
         check_video_interpolation(interpolation)
         return self._remap_video(video_family(subsampling), src, out, fill, src_layout, dst_layout, stream, interpolation, track=(rotations,))
 
-    # the one path behind the ten video methods above; `pairs`, `sub`: a VideoFamily's members - in the raw calls the subsampling as the caller
+    def stitch_nv12_supported(self, bytes_per_sample: int = 1) -> bool:
+        """Whether ``stitch_nv12`` takes this plan with samples of this size (pb_stitch_nv12_supported): prepared plans of a double-fisheye
+        source in a tile mode, with even dimensions.  A size outside (1, 2) or an odd dimension is a PbError.  Needs no GPU."""
+        return self._video_supported(True, None, bytes_per_sample, "nearest", stitch=True)
+
+    def launch_stitch_nv12(self, src_ptr: int, dst_ptr: int, n_frames: int = 1, stream: int | None = None, bytes_per_sample: int = 1, fill=None,
+                           src_layout=None, dst_layout=None) -> None:
+        """The raw call (pb_stitch_nv12): ``launch_nv12``'s arguments, the source a side-by-side double fisheye."""
+        self._launch_video(True, None, None, src_ptr, dst_ptr, n_frames, stream, bytes_per_sample, fill, src_layout, dst_layout, "nearest", stitch=True)
+
+    def stitch_nv12(self, src, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None):
+        """Stitches NV12 (uint8) or P010 / P016 (uint16) frames of a side-by-side DOUBLE FISHEYE in ONE launch (pb_stitch_nv12):
+        every sample is the reference's blend of the two eyes' samples - luma at the pixel's two taps, the (U, V) pair of an output 2 x 2
+        block at the taps of the block's top-left pixel, with that pixel's factors - exactly; ``fill`` only where neither eye is live.
+        ``src``, ``out``, ``fill`` and the layouts follow ``remap_nv12``'s rules.  A plan ``stitch_nv12_supported`` refuses is a PbError
+        (no fallback); a single source goes to ``remap_nv12``."""
+        return self._remap_video(NV12, src, out, fill, src_layout, dst_layout, stream, "nearest", stitch=True)
+
+    def stitch_planar_supported(self, subsampling, bytes_per_sample: int = 1) -> bool:
+        """Whether ``stitch_planar`` takes this plan with this subsampling and sample size (pb_stitch_planar_supported).  Needs no GPU."""
+        return self._video_supported(False, subsampling, bytes_per_sample, "nearest", stitch=True)
+
+    def launch_stitch_planar(self, src_ptr: int, dst_ptr: int, subsampling, n_frames: int = 1, stream: int | None = None, bytes_per_sample: int = 1, fill=None,
+                             src_layout=None, dst_layout=None) -> None:
+        """The raw call (pb_stitch_planar): ``launch_planar``'s arguments, the source a side-by-side double fisheye."""
+        self._launch_video(False, subsampling, None, src_ptr, dst_ptr, n_frames, stream, bytes_per_sample, fill, src_layout, dst_layout, "nearest", stitch=True)
+
+    def stitch_planar(self, src, subsampling, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None):
+        """Stitches PLANAR frames (4:4:4, 4:2:2 or 4:2:0; uint8 or uint16) of a side-by-side DOUBLE FISHEYE in ONE launch (pb_stitch_planar,
+        DESIGN 3.20): plane 0 is the reference's stitch of a grey image, and a sample of planes 1 and 2 is the blend of the two eyes' samples
+        at the taps of its block's top-left pixel, with that pixel's factors - exactly; at 4:4:4 with fill (0, 0, 0) the planes are the
+        channels of ``remap`` of the RGB image built from the source planes.  ``src``, ``subsampling``, ``out``, ``fill`` and the layouts
+        follow ``remap_planar``'s rules.  A plan ``stitch_planar_supported`` refuses is a PbError (no fallback)."""
+        return self._remap_video(video_family(subsampling), src, out, fill, src_layout, dst_layout, stream, "nearest", stitch=True)
+
+    # the one path behind the video methods above (the stitch methods of a double-fisheye source included: `stitch`); `pairs`, `sub`: a VideoFamily's members - in the raw calls the subsampling as the caller
     # gave it, checked where the library's argument stands
-    def _video_supported(self, pairs, sub, bytes_per_sample, interpolation) -> bool:
-        fn = getattr(load(), _VIDEO_FUNCTIONS[pairs, False, check_video_interpolation(interpolation), True])
+    def _video_supported(self, pairs, sub, bytes_per_sample, interpolation, stitch=False) -> bool:
+        fn = getattr(load(), _STITCH_FUNCTIONS[pairs, True] if stitch else _VIDEO_FUNCTIONS[pairs, False, check_video_interpolation(interpolation), True])
         r = fn(self._h, int(bytes_per_sample)) if pairs else fn(self._h, planar_subsampling(sub), int(bytes_per_sample))
         if r < 0:
             check(r)
         return r == 1
 
-    def _launch_video(self, pairs, sub, table, src_ptr, dst_ptr, n_frames, stream, bytes_per_sample, fill, src_layout, dst_layout, interpolation) -> None:
-        """The raw call; table: None, or the (pointer, rotations per frame) of a rotation track's table."""
-        fn = getattr(load(), _VIDEO_FUNCTIONS[pairs, table is not None, check_video_interpolation(interpolation), False])
+    def _launch_video(self, pairs, sub, table, src_ptr, dst_ptr, n_frames, stream, bytes_per_sample, fill, src_layout, dst_layout, interpolation, stitch=False) -> None:
+        """The raw call; table: None, or the (pointer, rotations per frame) of a rotation track's table; stitch: the stitch calls' twin."""
+        fn = getattr(load(), _STITCH_FUNCTIONS[pairs, False] if stitch else _VIDEO_FUNCTIONS[pairs, table is not None, check_video_interpolation(interpolation), False])
         f = None if fill is None else _FILL(*[int(v) for v in fill])
         to_layout = nv12_layout if pairs else planar_layout
         sl, dl = to_layout(src_layout), to_layout(dst_layout)
@@ -1106,7 +1156,7 @@ class Plan:
                     None if dl is None else C.addressof(dl), *(() if pairs else (planar_subsampling(sub),)), int(bytes_per_sample), None if f is None else C.addressof(f),
                     current_stream() if stream is None else stream)
 
-    def _remap_video(self, fam, src, out, fill, src_layout, dst_layout, stream, interpolation, track=None):
+    def _remap_video(self, fam, src, out, fill, src_layout, dst_layout, stream, interpolation, track=None, stitch=False):
         """``remap_nv12`` / ``remap_planar`` and, with track = (rotations,), their rotation tracks: the source checks, the table's, the
         ``out`` checks, one launch."""
         source = self._video_source(fam, src, src_layout)
@@ -1118,7 +1168,7 @@ class Plan:
         s, o, n, S, sl, dl = self._video_out(*source, out, dst_layout)
         with _on(s):
             if track is None:
-                self._launch_video(*fam, None, s.data_ptr(), o.data_ptr(), n, stream, S, fill, sl, dl, interpolation)
+                self._launch_video(*fam, None, s.data_ptr(), o.data_ptr(), n, stream, S, fill, sl, dl, interpolation, stitch=stitch)
             else:
                 st = current_stream() if stream is None else stream
                 tab, release = self._track_table(tab, s, st)

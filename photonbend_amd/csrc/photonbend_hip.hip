@@ -46,6 +46,7 @@
 #include "pb_kernels_track_planar.hpp"
 #include "pb_kernels_planar_bilinear.hpp"
 #include "pb_kernels_track_video_bilinear.hpp"
+#include "pb_kernels_stitch_video.hpp"
 
 #define PB_DOUBLE_FRAMES_PER_WAVE 1  // frames a double-source wave loops over (the rest of a batch is a grid dimension)
 
@@ -988,12 +989,14 @@ struct PbVideoFmt {
     bool pairs = false;       // planes 1 and 2 are interleaved pairs
     int sub = PB_PLANAR_420;  // PB_PLANAR_* (pairs: 4:2:0)
     int S = 1;                // bytes per sample
+    bool stitch = false;      // the stitch calls (pb_stitch_nv12 / pb_stitch_planar): a double-fisheye source, blended
     int cx() const { return pb_planar_cx(sub); }  // planes 1 and 2 are (h >> cy, w >> cx)
     int cy() const { return pb_planar_cy(sub); }
     unsigned long long unit() const { return (unsigned long long)(pairs ? 2 * S : S); }  // what pointers, pitches and offsets are multiples of
     const char* unit_name() const { return pairs ? "one chroma pair" : "one sample"; }
     const char* planes() const { return pairs ? "two" : "three"; }                       // "... and gather the two planes"
     std::string nearest() const { return pairs ? "pb_remap_nv12" : "pb_remap_planar"; }  // the nearest call, which the layout messages cite
+    std::string stitch_name() const { return pairs ? "pb_stitch_nv12" : "pb_stitch_planar"; }
 };
 struct PbRoute {
     enum Kind {
@@ -1014,6 +1017,8 @@ struct PbRoute {
         VIDEO,               // nearest, video frames: 4:2:0 semi-planar (pb_remap_nv12): pb_nv12_hot_kernel; planar 4:4:4 / 4:2:2 / 4:2:0
                              // (pb_remap_planar): pb_planar_hot_kernel
         VIDEO_NONE,          // ... on a plan those kernels do not serve - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
+        VIDEO_STITCH,        // nearest, video frames of a double-fisheye source (pb_stitch_nv12, pb_stitch_planar): pb_stitch_video_kernel
+        VIDEO_STITCH_NONE,   // ... on a plan that kernel does not serve: nothing is launched (PB_ERR_UNSUPPORTED)
         VIDEO_BIL,           // bilinear, planar or 4:2:0 semi-planar frames (pb_remap_planar_bilinear, pb_remap_nv12_bilinear): pb_planar_bilinear_kernel
         VIDEO_BIL_NEAREST_NONE,  // ... on a plan the nearest call refuses too - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
         VIDEO_BIL_NONE,      // ... on a plan without the bilinear mode's tile and coordinate tables (a cube source never has them): nothing is launched
@@ -1032,6 +1037,12 @@ static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned fl
         // (pb_check_frames); fast_ready says single source, prepared, device state; generic tiles pack row and column in 16 bits each
         const bool served = n == 1 && pb_use_fast(pl) && pl->nearest.lt.entries && pl->nearest.P_dev && P.src.width < 32768 && P.src.height < 32768;
         const bool px = interpolation == PB_INTERP_NEAREST && served;
+        if (video && video->stitch) {
+            // the double plan's own state, as pb_hot_double_kernel takes it - without the LDS windows, so no alignment and no window mode
+            const bool stitched = n == 1 && interpolation == PB_INTERP_NEAREST && P.src.kind == PB_KIND_DOUBLE && pl->mode != PB_MODE_FAITHFUL && pl->cert.dbl_ready &&
+                                  pl->nearest.lt.entries && P.src.width < 32768 && P.src.height < 32768;
+            return {stitched ? PbRoute::VIDEO_STITCH : PbRoute::VIDEO_STITCH_NONE, false, PB_INTERP_NEAREST, 3, *video};
+        }
         if (video && interpolation == PB_INTERP_BILINEAR) {
             // the nearest call's plans, and of those the ones with the bilinear mode's launch-order, tile and exact coordinate tables (no
             // second kernel picks up what a plan without coordinate tables leaves; a cube source never has bil.tiles: pb_bilinear_tiles_allowed)
@@ -1197,6 +1208,28 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
         case PbRoute::VIDEO_NONE:
             return pb_fail(PB_ERR_UNSUPPORTED, r.video.nearest() + " takes prepared plans of a single source in a tile mode (not deferred, not PB_MODE_FAITHFUL, not "
                                                "double-fisheye, sources below 32768 px a side): use pb_index_map_i32 and gather the " + r.video.planes() + " planes");
+        case PbRoute::VIDEO_STITCH: {
+            // launched like DOUBLE's single-frame form, frames of a batch as a grid dimension; static LDS (the regrouping buffer)
+            const unsigned gpf = pl->nearest.lt.groups;
+            pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
+                pb_pick<1, 2>(r.video.S == 1, [&](auto S) {
+                    auto go = [&](auto SUB, auto PAIRS) {
+                        hipLaunchKernelGGL((pb_stitch_video_kernel<S.value, SUB.value, PAIRS.value != 0>), dim3(gpf * (unsigned)nf), dim3(64 * PB_TILE_WAVES), 0, st, P,
+                                           pl->cert.table, pl->cert.table_r, pl->nearest.lt.entries, pb_sep_rows(pl), pl->cert.lat_tab, pl->cert.fix_px, pl->cert.dbl_px_fix,
+                                           pl->cert.dbl_tile_fix, sf, df, gpf, ss, ds, *video);
+                    };
+                    if (r.video.pairs) go(PbInt<PB_SUB_420>(), PbInt<1>());
+                    else pb_pick_subsampling(r.video.sub, [&](auto SUB) { go(SUB, PbInt<0>()); });
+                });
+            });
+            break;
+        }
+        case PbRoute::VIDEO_STITCH_NONE:
+            if (P.src.kind != PB_KIND_DOUBLE)
+                return pb_fail(PB_ERR_UNSUPPORTED, r.video.stitch_name() + " takes double-fisheye sources: use " + r.video.nearest() + " for a single source");
+            return pb_fail(PB_ERR_UNSUPPORTED, r.video.stitch_name() + " takes prepared double-fisheye plans in a tile mode (not deferred, not PB_MODE_FAITHFUL, with both eyes' "
+                                               "tile tables and a launch-order table, sources below 32768 px a side): use pb_index_map_i32 with weights and "
+                                               "pb_gather_blend_u8 per plane");
         case PbRoute::VIDEO_BIL: {
             // launched like the Catmull-Rom tile kernel: the bilinear mode's launch-order table read with four waves per workgroup
             const unsigned gpf = pl->bil.lt.groups;
@@ -2076,6 +2109,27 @@ int pb_plan_video_bilinear_mix(const pb_plan* plan, long long mix[4]) {
     PB_HIP(e);
     return PB_OK;
 }
+int pb_plan_stitch_tile_mix(const pb_plan* plan, long long mix[9]) {
+    if (!plan || !mix) return pb_fail(PB_ERR_INVALID, "null argument");
+    for (int k = 0; k < 9; ++k) mix[k] = 0;
+    if (!plan->cert.dbl_ready || !plan->nearest.lt.entries || plan->nearest.lt.groups == 0) return PB_OK;
+    if (int rc = pb_check_device(plan)) return rc;
+    // the slots a stitch launch's waves read, classified as pb_stitch_video_kernel takes them (pb_stitch_mix_kernel)
+    PbBlock<unsigned> counters;
+    PB_HIP(counters.alloc(9));
+    hipError_t e = hipMemsetAsync(counters, 0, 9 * sizeof(unsigned), 0);
+    if (e == hipSuccess) {
+        const unsigned n_slots = 4u * plan->nearest.lt.groups;
+        hipLaunchKernelGGL(pb_stitch_mix_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, 0, plan->nearest.lt.entries, n_slots, plan->cert.table, plan->cert.table_r,
+                           (plan->P.dst.width + PB_TILE - 1) / PB_TILE, plan->cert.fix_px, plan->P.dst.width, counters);
+        unsigned res[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        e = hipMemcpy(res, counters, sizeof(res), hipMemcpyDeviceToHost);
+        for (int k = 0; k < 9; ++k) mix[k] = res[k];
+    }
+    if (e != hipSuccess) (void)hipDeviceSynchronize();
+    PB_HIP(e);
+    return PB_OK;
+}
 int pb_plan_bilinear_launch_shape(const pb_plan* plan, int* lds_bytes, int* workgroups_per_frame) {
     if (!plan || !lds_bytes || !workgroups_per_frame) return pb_fail(PB_ERR_INVALID, "null argument");
     const bool tiles = (plan->cert.fast_ready || plan->cert.dbl_ready) && plan->bil.lt.entries && plan->bil.lt.groups > 0;
@@ -2224,7 +2278,7 @@ static int pb_video_call(const pb_plan* plan, const void* src_dev, void* dst_dev
     rc = pb_check_device(plan);
     if (rc != PB_OK) return rc;
     const PbRoute r = pb_route(plan, interpolation, 1, 0, false, 3, &v);
-    if ((r.kind == PbRoute::VIDEO || r.kind == PbRoute::VIDEO_BIL) && !c.span_fits())
+    if ((r.kind == PbRoute::VIDEO || r.kind == PbRoute::VIDEO_BIL || r.kind == PbRoute::VIDEO_STITCH) && !c.span_fits())
         return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes frames whose planes span less than 2^31 bytes: use pb_index_map_i32 and gather the " + v.planes() + " planes");
     return pb_launch(plan, r, static_cast<const uint8_t*>(src_dev), static_cast<uint8_t*>(dst_dev), n_frames, c.fs.stride, c.fd.stride, (hipStream_t)stream, &c.L);
 }
@@ -2235,10 +2289,27 @@ static int pb_video_supported(const pb_plan* plan, const PbVideoFmt& v, int inte
     PbVideoCall c;
     if (pb_video_resolve(v, "source", nullptr, plan->P.src, c.fs) != PB_OK || pb_video_resolve(v, "destination", nullptr, plan->P.dst, c.fd) != PB_OK) return 0;
     const PbRoute::Kind k = pb_route(plan, interpolation, 1, 0, false, 3, &v).kind;
-    return (k == PbRoute::VIDEO || k == PbRoute::VIDEO_BIL) && c.span_fits();
+    return (k == PbRoute::VIDEO || k == PbRoute::VIDEO_BIL || k == PbRoute::VIDEO_STITCH) && c.span_fits();
 }
 static PbVideoFmt pb_fmt_nv12(int bytes_per_sample) { return {true, PB_PLANAR_420, bytes_per_sample}; }
 static PbVideoFmt pb_fmt_planar(int subsampling, int bytes_per_sample) { return {false, subsampling, bytes_per_sample}; }
+static PbVideoFmt pb_fmt_stitch(PbVideoFmt v) {
+    v.stitch = true;
+    return v;
+}
+int pb_stitch_nv12(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout,
+                   int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
+    return pb_video_call(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, pb_fmt_stitch(pb_fmt_nv12(bytes_per_sample)), fill_yuv, stream, PB_INTERP_NEAREST, "pb_stitch_nv12");
+}
+int pb_stitch_planar(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout,
+                     int subsampling, int bytes_per_sample, const uint16_t fill[3], void* stream) {
+    return pb_video_call(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, pb_fmt_stitch(pb_fmt_planar(subsampling, bytes_per_sample)), fill, stream, PB_INTERP_NEAREST,
+                         "pb_stitch_planar");
+}
+int pb_stitch_nv12_supported(const pb_plan* plan, int bytes_per_sample) { return pb_video_supported(plan, pb_fmt_stitch(pb_fmt_nv12(bytes_per_sample)), PB_INTERP_NEAREST); }
+int pb_stitch_planar_supported(const pb_plan* plan, int subsampling, int bytes_per_sample) {
+    return pb_video_supported(plan, pb_fmt_stitch(pb_fmt_planar(subsampling, bytes_per_sample)), PB_INTERP_NEAREST);
+}
 int pb_remap_nv12_bilinear(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout,
                            int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
     return pb_video_call(plan, src_dev, dst_dev, n_frames, src_layout, dst_layout, pb_fmt_nv12(bytes_per_sample), fill_yuv, stream, PB_INTERP_BILINEAR, "pb_remap_nv12_bilinear");
