@@ -513,6 +513,29 @@ pb_remap_track_planar_bilinear(const pb_plan* plan, const double* rot3x3_dev, in
                                    const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample,
                                    const uint16_t fill[3], void* stream);
 
+/* ROTATION TRACKS FOR DOUBLE-FISHEYE VIDEO FRAMES (ABI 5, additive): a batch of NV12 / P010 (pb_track_stitch_nv12) or planar
+ * frames (pb_track_stitch_planar) of a side-by-side double fisheye, every frame with rotations of its own, stitched in ONE launch of
+ * pb_track_stitch_kernel per 65535 chunks of frames, every plane written - a stabilised, horizon-levelled panorama straight from a
+ * decoder's surfaces.  The argument lists are pb_remap_track_planar's and pb_remap_track_nv12's.  Frame f receives the definition of
+ * pb_stitch_planar / pb_stitch_nv12 above (tests/stitch_video_ref.py), unchanged, with (il, ir, fl, fr) the taps and factors of the float64
+ * chain "this plan's own n_rot rotations followed by the n_rot_per_frame matrices of table entry f", applied one after another as for
+ * pb_remap_track_u8 (nothing folded).  Equivalently: what pb_stitch_planar / pb_stitch_nv12 write for frame f alone from a prepared plan of
+ * that whole chain, byte for byte; and with S = 1, 4:4:4 and fill (0, 0, 0) the three planes are the three channels of pb_remap_track_u8's
+ * frame f.  There is no tolerance.  An invalid destination pixel has both taps -1 and takes the fill; a black eye contributes 0.0; only
+ * the anchor decides a chroma sample, with the anchor's factors.
+ * The plan's tables are never read: a deferred plan, a prepared one and any mode are served alike.
+ *   PB_ERR_INVALID       before any launch, in this order: pb_remap_planar's / pb_remap_nv12's checks, then pb_remap_track_u8's table
+ *                        checks, with their messages.  n_frames == 0: PB_OK, no launch, no device.
+ *   PB_ERR_UNSUPPORTED   nothing is written: a source that is not a double fisheye (use pb_remap_track_planar / pb_remap_track_nv12);
+ *                        frames whose byte span reaches 2^31; sources of 32768 px a side or more.
+ * Asynchronous on `stream`; never allocates, never synchronises, never copies the table (graph-capture safe). */
+int pb_track_stitch_planar(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                           const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample,
+                           const uint16_t fill[3], void* stream);
+int pb_track_stitch_nv12(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                         const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3],
+                         void* stream);
+
 /* SUPERSAMPLED REMAPPING (ABI 5, additive).  Output pixel (i, j) is, per channel, the round-half-to-even mean of the n x n block
  * S[n i : n i + n, n j : n j + n] of S = the remap of the n x destination: the same kind and lens with image (n H, n W) and, for a camera,
  * magnitude n x (a double fisheye's magnitude = height / 2 scales by itself); n in {2, 4}, a power of two, so its f_distance is exactly

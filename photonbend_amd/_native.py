@@ -136,6 +136,8 @@ SIGNATURES = {
     "pb_remap_track_planar": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, _VP]),
     "pb_remap_track_nv12_bilinear": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP]),
     "pb_remap_track_planar_bilinear": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, _VP]),
+    "pb_track_stitch_nv12": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP]),
+    "pb_track_stitch_planar": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, _VP]),
     "pb_remap_ss_workspace": (C.c_int, [_VP, C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_size_t)]),
     "pb_remap_ss_u8": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP, C.c_size_t, C.c_uint, _VP]),
     "pb_box_reduce": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
@@ -397,6 +399,8 @@ _VIDEO_FUNCTIONS = {(pairs, tracked, bilinear, question): f"pb_remap_{'track_' i
                     for pairs in (False, True) for tracked in (False, True) for bilinear in (False, True) for question in (False, True) if not (tracked and question)}
 # ... and the stitch calls of a double-fisheye source: (semi-planar?, the _supported question?)
 _STITCH_FUNCTIONS = {(pairs, question): f"pb_stitch_{'nv12' if pairs else 'planar'}{'_supported' if question else ''}" for pairs in (False, True) for question in (False, True)}
+# ... and their rotation tracks: semi-planar?
+_TRACK_STITCH_FUNCTIONS = {False: "pb_track_stitch_planar", True: "pb_track_stitch_nv12"}
 _FILL = C.c_uint16 * 3  # the samples of black pixels, as the video calls take them
 
 
@@ -1137,6 +1141,38 @@ class Plan:
         follow ``remap_planar``'s rules.  A plan ``stitch_planar_supported`` refuses is a PbError (no fallback)."""
         return self._remap_video(video_family(subsampling), src, out, fill, src_layout, dst_layout, stream, "nearest", stitch=True)
 
+    def launch_stitch_track_nv12(self, table_ptr: int, n_rot_per_frame: int, src_ptr: int, dst_ptr: int, n_frames: int = 1, stream: int | None = None,
+                                 bytes_per_sample: int = 1, fill=None, src_layout=None, dst_layout=None) -> None:
+        """The raw rotation-track call for frames of a side-by-side double fisheye (pb_track_stitch_nv12): ``launch_track_nv12``'s
+        arguments.  The table must stay alive and unchanged until the stream has run the launch."""
+        self._launch_video(True, None, (table_ptr, n_rot_per_frame), src_ptr, dst_ptr, n_frames, stream, bytes_per_sample, fill, src_layout, dst_layout, "nearest",
+                           stitch=True)
+
+    def stitch_track_nv12(self, src, rotations, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None):
+        """Stitches NV12 (uint8) or P010 / P016 (uint16) frames of a side-by-side DOUBLE FISHEYE with a rotation per frame in ONE launch
+        (pb_track_stitch_nv12): frame f is ``stitch_nv12``'s definition with the taps and factors of this plan's rotations
+        followed by ``rotations[f]`` - exactly what ``stitch_nv12`` writes from a prepared plan of that whole chain.  ``src``, ``out``,
+        ``fill`` and the layouts follow ``remap_nv12``'s rules, ``rotations`` follows ``rotation_table``'s as for ``remap_track``; the frame
+        count must equal the table's (ValueError).  Any plan of a double fisheye is served alike, a deferred one included; a single
+        source goes to ``remap_track_nv12``."""
+        return self._remap_video(NV12, src, out, fill, src_layout, dst_layout, stream, "nearest", track=(rotations,), stitch=True)
+
+    def launch_stitch_track_planar(self, table_ptr: int, n_rot_per_frame: int, src_ptr: int, dst_ptr: int, subsampling, n_frames: int = 1,
+                                   stream: int | None = None, bytes_per_sample: int = 1, fill=None, src_layout=None, dst_layout=None) -> None:
+        """The raw rotation-track call for planar frames of a side-by-side double fisheye (pb_track_stitch_planar):
+        ``launch_track_planar``'s arguments.  The table must stay alive and unchanged until the stream has run the launch."""
+        self._launch_video(False, subsampling, (table_ptr, n_rot_per_frame), src_ptr, dst_ptr, n_frames, stream, bytes_per_sample, fill, src_layout, dst_layout,
+                           "nearest", stitch=True)
+
+    def stitch_track_planar(self, src, rotations, subsampling, out=None, fill=None, src_layout=None, dst_layout=None, stream: int | None = None):
+        """Stitches PLANAR frames (4:4:4, 4:2:2 or 4:2:0; uint8 or uint16) of a side-by-side DOUBLE FISHEYE with a rotation per frame in
+        ONE launch (pb_track_stitch_planar): frame f is ``stitch_planar``'s definition with the taps and factors of this
+        plan's rotations followed by ``rotations[f]`` - exactly; at 4:4:4 uint8 with fill (0, 0, 0) the planes are the channels of
+        ``remap_track``'s frame f.  ``src``, ``subsampling``, ``out``, ``fill`` and the layouts follow ``remap_planar``'s rules,
+        ``rotations`` follows ``rotation_table``'s; the frame count must equal the table's (ValueError).  Any plan of a double fisheye
+        is served alike, a deferred one included; a single source goes to ``remap_track_planar``."""
+        return self._remap_video(video_family(subsampling), src, out, fill, src_layout, dst_layout, stream, "nearest", track=(rotations,), stitch=True)
+
     # the one path behind the video methods above (the stitch methods of a double-fisheye source included: `stitch`); `pairs`, `sub`: a VideoFamily's members - in the raw calls the subsampling as the caller
     # gave it, checked where the library's argument stands
     def _video_supported(self, pairs, sub, bytes_per_sample, interpolation, stitch=False) -> bool:
@@ -1148,7 +1184,10 @@ class Plan:
 
     def _launch_video(self, pairs, sub, table, src_ptr, dst_ptr, n_frames, stream, bytes_per_sample, fill, src_layout, dst_layout, interpolation, stitch=False) -> None:
         """The raw call; table: None, or the (pointer, rotations per frame) of a rotation track's table; stitch: the stitch calls' twin."""
-        fn = getattr(load(), _STITCH_FUNCTIONS[pairs, False] if stitch else _VIDEO_FUNCTIONS[pairs, table is not None, check_video_interpolation(interpolation), False])
+        name = _VIDEO_FUNCTIONS[pairs, table is not None, check_video_interpolation(interpolation), False]
+        if stitch:
+            name = _STITCH_FUNCTIONS[pairs, False] if table is None else _TRACK_STITCH_FUNCTIONS[pairs]
+        fn = getattr(load(), name)
         f = None if fill is None else _FILL(*[int(v) for v in fill])
         to_layout = nv12_layout if pairs else planar_layout
         sl, dl = to_layout(src_layout), to_layout(dst_layout)
@@ -1172,7 +1211,7 @@ class Plan:
             else:
                 st = current_stream() if stream is None else stream
                 tab, release = self._track_table(tab, s, st)
-                self._launch_video(*fam, (tab.data_ptr(), k), s.data_ptr(), o.data_ptr(), n, st, S, fill, sl, dl, interpolation)
+                self._launch_video(*fam, (tab.data_ptr(), k), s.data_ptr(), o.data_ptr(), n, st, S, fill, sl, dl, interpolation, stitch=stitch)
                 release()
         return o
 

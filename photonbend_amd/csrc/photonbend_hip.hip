@@ -8,6 +8,7 @@
 //   pb_kernels_bilinear.hpp  opt-in bilinear sampling
 //   pb_kernels_track.hpp     rotation tracks: a rotation per frame in one launch of the float64 chain
 //   pb_kernels_track_video_bilinear.hpp  ... of video frames, sampled bilinearly
+//   pb_kernels_track_stitch.hpp          ... of double-fisheye video frames, stitched
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared ...
 // (-ffp-contract=off is REQUIRED: the reference rounds every multiply and add
@@ -47,6 +48,7 @@
 #include "pb_kernels_planar_bilinear.hpp"
 #include "pb_kernels_track_video_bilinear.hpp"
 #include "pb_kernels_stitch_video.hpp"
+#include "pb_kernels_track_stitch.hpp"
 
 #define PB_DOUBLE_FRAMES_PER_WAVE 1  // frames a double-source wave loops over (the rest of a batch is a grid dimension)
 
@@ -2455,6 +2457,7 @@ int pb_remap_track_u8(const pb_plan* plan, const double* rot3x3_dev, int n_rot_p
 // A rotation track of video frames (bilinear: 3.19): the plain video calls' argument checks, then pb_remap_track_u8's
 // table checks; the launches are pb_remap_track_u8's, one per 65535 chunks of frames.  Nearest: pb_track_nv12_kernel / pb_track_planar_kernel;
 // bilinear: pb_track_video_bilinear_kernel (with pairs for NV12), a panorama or camera source.
+// A format with `stitch` (pb_track_stitch_nv12 / _planar) takes a double-fisheye source and no other: pb_track_stitch_kernel.
 static int pb_track_video_call(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
                                const void* src_layout, const void* dst_layout, const PbVideoFmt& v, const uint16_t fill[3], void* stream, int interpolation,
                                const char* name) {
@@ -2465,7 +2468,10 @@ static int pb_track_video_call(const pb_plan* plan, const double* rot3x3_dev, in
     rc = pb_check_device(plan);
     if (rc != PB_OK) return rc;
     const PbParams& P = plan->P;
-    if (P.src.kind == PB_KIND_DOUBLE)
+    if (v.stitch && P.src.kind != PB_KIND_DOUBLE)
+        return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes double-fisheye sources: use " + (v.pairs ? "pb_remap_track_nv12" : "pb_remap_track_planar") +
+                                               " for a single source");
+    if (!v.stitch && P.src.kind == PB_KIND_DOUBLE)
         return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes single sources (a double fisheye's blend is sample-typed): convert to RGB8 and use pb_remap_track_u8");
     if (interpolation == PB_INTERP_BILINEAR && pb_is_cube(P.src.kind))
         return pb_fail(PB_ERR_UNSUPPORTED, std::string(name) + " takes panorama and camera sources (the bilinear definition of video frames covers no cube map): convert to "
@@ -2488,7 +2494,11 @@ static int pb_track_video_call(const pb_plan* plan, const double* rot3x3_dev, in
             hipLaunchKernelGGL(kernel, grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride, c.fd.stride, layout...);
         };
         const bool bilinear = interpolation == PB_INTERP_BILINEAR;
-        if (v.pairs && bilinear)
+        if (v.stitch)
+            pb_pick<1, 0>(v.pairs, [&](auto PAIRS) {
+                pb_pick<1, 2>(v.S == 1, [&](auto S) { launch(pb_track_stitch_kernel<S.value, PAIRS.value != 0>, c.L, cx, cy); });
+            });
+        else if (v.pairs && bilinear)
             pb_pick_kind(P, [&](auto K) {
                 pb_pick<1, 2>(v.S == 1, [&](auto S) { launch(pb_track_video_bilinear_kernel<S.value, K.value, true>, c.L, cx, cy); });
             });
@@ -2529,6 +2539,19 @@ int pb_remap_track_planar_bilinear(const pb_plan* plan, const double* rot3x3_dev
                                    void* stream) {
     return pb_track_video_call(plan, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, n_frames, src_layout, dst_layout, pb_fmt_planar(subsampling, bytes_per_sample), fill,
                                stream, PB_INTERP_BILINEAR, "pb_remap_track_planar_bilinear");
+}
+
+// ... of a double fisheye: the same checks and launches around pb_track_stitch_kernel
+int pb_track_stitch_nv12(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                         const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {
+    return pb_track_video_call(plan, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, n_frames, src_layout, dst_layout, pb_fmt_stitch(pb_fmt_nv12(bytes_per_sample)), fill_yuv,
+                               stream, PB_INTERP_NEAREST, "pb_track_stitch_nv12");
+}
+int pb_track_stitch_planar(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
+                           const pb_planar_layout* src_layout, const pb_planar_layout* dst_layout, int subsampling, int bytes_per_sample, const uint16_t fill[3],
+                           void* stream) {
+    return pb_track_video_call(plan, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, n_frames, src_layout, dst_layout,
+                               pb_fmt_stitch(pb_fmt_planar(subsampling, bytes_per_sample)), fill, stream, PB_INTERP_NEAREST, "pb_track_stitch_planar");
 }
 
 int pb_index_map_i32(const pb_plan* plan, int32_t* idx_dev, double* weights_dev, void* stream) {

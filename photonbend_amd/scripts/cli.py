@@ -570,29 +570,8 @@ def remap_yuv(input_frames, output_frames, width, height, pix_fmt, otype, lens, 
     _remap_video(pix_fmt, input_frames, output_frames, width, height, otype, lens, fov, size, rotation, track, chunk, interpolation, lens_coefficients, lens_max_theta)
 
 
-@main.command("stitch-yuv")
-@click.argument("input_frames", metavar="INPUT", type=click.Path(path_type=Path, allow_dash=True))
-@click.argument("output_frames", metavar="OUTPUT", type=click.Path(path_type=Path, allow_dash=True))
-@click.option("--width", required=True, type=click.INT, help="The width of an input frame in pixels: both fisheye circles side by side.")
-@click.option("--height", required=True, type=click.INT, help="The height of an input frame in pixels.")
-@click.option("--pix-fmt", type=click.Choice(list(nat.VIDEO_FORMATS)), default="nv12", show_default=True, help="The frames' layout, as ffmpeg names it.")
-@click.option("--lens", type=_lens_choice, required=True, help="The lens type of the two fisheye cameras.")
-@_lens_parameters("--lens", "lens")
-@click.option("--fov", type=click.FLOAT, required=True, help="The field of view of each fisheye camera in degrees (180 to 360).")
-@click.option("--out-width", type=click.INT, default=None, help="The width of an output frame. [default: twice the output height]")
-@click.option("--out-height", type=click.INT, default=None, help="The height of an output frame. [default: the input's]")
-@click.option("-r", "--rotation", type=click.FLOAT, nargs=3, multiple=True, default=[], help=ROTATION_HELP)
-@click.option("--chunk", type=click.INT, default=8, show_default=True, help=f"Frames per launch, a multiple of {TRACK_FRAMES}.")
-def stitch_yuv(input_frames, output_frames, width, height, pix_fmt, lens, fov, out_width, out_height, rotation, chunk, lens_coefficients, lens_max_theta):
-    """Stitch raw video frames of a side-by-side DOUBLE FISHEYE - NV12, P010, yuv420p, yuv422p, yuv444p, their 10- and 16-bit forms, gbrp -
-    into an equirectangular panorama of the same pixel format, e.g. between two `ffmpeg -f rawvideo` pipes.  One launch per chunk, both
-    planes, no RGB detour; every sample is the reference's blend of the two eyes' samples.
-
-    \b
-    INPUT is a file of packed frames, HEIGHT x WIDTH each; - is stdin.
-    OUTPUT receives the packed panorama frames, OUT-HEIGHT x OUT-WIDTH each; - is stdout.
-    4:2:0 formats have even widths and heights, 4:2:2 formats even widths, 4:4:4 formats (gbrp among them) take any size.
-    """
+def _stitch_video(input_frames, output_frames, width, height, pix_fmt, lens, fov, out_width, out_height, rotation, track, chunk, lens_coefficients, lens_max_theta):
+    """The body of stitch-yuv and stitch-track-yuv (`track`: the file of a rotation track, or None)."""
     dt, fam, fill = nat.VIDEO_FORMATS[pix_fmt]
     rule, least = ("4:2:0 frames have even dimensions", 2) if fam.pairs else (nat.planar_dims_rule(fam.sub, pix_fmt), 1)
     if width < max(least, 2) or height < least or not nat.planar_dims_ok(fam.sub, (height, width)):
@@ -612,17 +591,74 @@ def stitch_yuv(input_frames, output_frames, width, height, pix_fmt, lens, fov, o
     for rot in rotation:
         cmap = Rotation(*map(to_radians, rot)).rotate_coordinate_map(cmap)
     dstp, srcp = cmap.dst_proj, source._proj()
+    mats = None if track is None else core.rotation_track(_read_track(track))
     frame = fam.packed(height, width)[0]
+    # without a track: a prepared plan and the tile kernel; with one: a deferred plan (its tables are never read) and the track kernel
     plan = None
 
     def remap(host, first):  # upload, ONE launch, download
         nonlocal plan
         if plan is None:  # (made with the first frames: the usage errors of the input come before any plan is prepared)
-            plan = nat.Plan(dstp, list(cmap.rotations), srcp, bilinear=False)
+            plan = nat.Plan(dstp, list(cmap.rotations), srcp, bilinear=False) if mats is None else nat.Plan(dstp, list(cmap.rotations), srcp, defer=True)
         s = nat.to_device(host.reshape((len(host),) + frame))
-        return plan.stitch_nv12(s) if fam.pairs else plan.stitch_planar(s, fam.sub, fill=fill)
+        if mats is None:
+            return plan.stitch_nv12(s) if fam.pairs else plan.stitch_planar(s, fam.sub, fill=fill)
+        rots = mats[first : first + len(host)]
+        return plan.stitch_track_nv12(s, rots) if fam.pairs else plan.stitch_track_planar(s, rots, fam.sub, fill=fill)
 
-    _stream_frames(input_frames, output_frames, int(np.prod(frame)) * dt.itemsize, dt, chunk, None, remap)
+    _stream_frames(input_frames, output_frames, int(np.prod(frame)) * dt.itemsize, dt, chunk, mats, remap)
+
+
+def _stitch_options(command):
+    """The arguments and options the two stitch commands share."""
+    for decorate in reversed([
+        click.argument("input_frames", metavar="INPUT", type=click.Path(path_type=Path, allow_dash=True)),
+        click.argument("output_frames", metavar="OUTPUT", type=click.Path(path_type=Path, allow_dash=True)),
+        click.option("--width", required=True, type=click.INT, help="The width of an input frame in pixels: both fisheye circles side by side."),
+        click.option("--height", required=True, type=click.INT, help="The height of an input frame in pixels."),
+        click.option("--pix-fmt", type=click.Choice(list(nat.VIDEO_FORMATS)), default="nv12", show_default=True, help="The frames' layout, as ffmpeg names it."),
+        click.option("--lens", type=_lens_choice, required=True, help="The lens type of the two fisheye cameras."),
+        _lens_parameters("--lens", "lens"),
+        click.option("--fov", type=click.FLOAT, required=True, help="The field of view of each fisheye camera in degrees (180 to 360)."),
+        click.option("--out-width", type=click.INT, default=None, help="The width of an output frame. [default: twice the output height]"),
+        click.option("--out-height", type=click.INT, default=None, help="The height of an output frame. [default: the input's]"),
+        click.option("-r", "--rotation", type=click.FLOAT, nargs=3, multiple=True, default=[], help=ROTATION_HELP),
+        click.option("--chunk", type=click.INT, default=8, show_default=True, help=f"Frames per launch, a multiple of {TRACK_FRAMES}."),
+    ]):
+        command = decorate(command)
+    return command
+
+
+@main.command("stitch-yuv")
+@_stitch_options
+def stitch_yuv(input_frames, output_frames, width, height, pix_fmt, lens, fov, out_width, out_height, rotation, chunk, lens_coefficients, lens_max_theta):
+    """Stitch raw video frames of a side-by-side DOUBLE FISHEYE - NV12, P010, yuv420p, yuv422p, yuv444p, their 10- and 16-bit forms, gbrp -
+    into an equirectangular panorama of the same pixel format, e.g. between two `ffmpeg -f rawvideo` pipes.  One launch per chunk, both
+    planes, no RGB detour; every sample is the reference's blend of the two eyes' samples.
+
+    \b
+    INPUT is a file of packed frames, HEIGHT x WIDTH each; - is stdin.
+    OUTPUT receives the packed panorama frames, OUT-HEIGHT x OUT-WIDTH each; - is stdout.
+    4:2:0 formats have even widths and heights, 4:2:2 formats even widths, 4:4:4 formats (gbrp among them) take any size.
+    """
+    _stitch_video(input_frames, output_frames, width, height, pix_fmt, lens, fov, out_width, out_height, rotation, None, chunk, lens_coefficients, lens_max_theta)
+
+
+@main.command("stitch-track-yuv")
+@_stitch_options
+@click.option("--rotations", "track", type=click.Path(exists=True, dir_okay=False, path_type=Path), required=True,
+              help="A rotation track: a text file of one `pitch yaw roll` line in degrees per frame, applied after every -r.")
+def stitch_track_yuv(input_frames, output_frames, width, height, pix_fmt, lens, fov, out_width, out_height, rotation, track, chunk, lens_coefficients, lens_max_theta):
+    """Stitch raw video frames of a side-by-side DOUBLE FISHEYE with a ROTATION PER FRAME - a gyro track: a stabilised, horizon-levelled
+    panorama of the same pixel format.  stitch-yuv's formats, sizes and options; one launch per chunk, every plane, no RGB detour and no
+    plan per frame; every sample is the reference's blend of the two eyes' samples for that frame's rotations.
+
+    \b
+    INPUT is a file of packed frames, HEIGHT x WIDTH each; - is stdin.
+    OUTPUT receives the packed panorama frames, OUT-HEIGHT x OUT-WIDTH each; - is stdout.
+    --rotations holds at least one line per input frame.
+    """
+    _stitch_video(input_frames, output_frames, width, height, pix_fmt, lens, fov, out_width, out_height, rotation, track, chunk, lens_coefficients, lens_max_theta)
 
 
 if __name__ == "__main__":
