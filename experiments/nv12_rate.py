@@ -3,7 +3,7 @@
 between two HIP events, after a warm-up launch (the method of experiments/pixel_format_rate.py).
     python experiments/nv12_rate.py [--reps 5] [--iters 20] [--cases c2,c1] [--out file.json]
 On each case's geometry, for NV12 (S = 1) and P010 (S = 2), time per frame of
-  (a)   pb_remap_nv12: one launch of pb_nv12_hot_kernel, both planes;
+  (a)   pb_remap_nv12: one launch of pb_video_hot_kernel (PAIRS), both planes;
   (b)   what a caller could do for the same frame before, on the same build and with the same bytes: pb_remap_px of the luma plane, plus
         pb_index_map_i32 into a preallocated buffer, the chroma index of the anchors from it (tensor arithmetic on the device) and
         pb_gather_px of the pairs - measured twice (A / A) for that figure's own spread;

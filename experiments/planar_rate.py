@@ -3,7 +3,7 @@
 between two HIP events, after a warm-up launch (the method of experiments/nv12_rate.py).
     python experiments/planar_rate.py [--reps 5] [--iters 20] [--cases c2,c1] [--formats yuv420p,yuv444p,yuv420p16le] [--out file.json]
 On each case's geometry and for each pixel format, time per frame of
-  (a)   pb_remap_planar: one launch of pb_planar_hot_kernel, the three planes;
+  (a)   pb_remap_planar: one launch of pb_video_hot_kernel, the three planes;
   (b)   what a caller could do for the same frame before, on the same build and with the same bytes: pb_remap_px of plane 0, plus
         pb_index_map_i32 into a preallocated buffer, the chroma index of the anchors from it (tensor arithmetic on the device) and
         two pb_gather_px, one per chroma plane - measured twice (A / A) for that figure's own spread;

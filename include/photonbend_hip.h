@@ -276,7 +276,7 @@ int pb_remap_px(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_f
                 size_t dst_frame_stride, int bytes_per_px, void* stream);
 int pb_remap_px_supported(const pb_plan* plan, int bytes_per_px);
 
-/* 4:2:0 semi-planar video frames - NV12 (bytes_per_sample 1) and P010 / P016 (2) - in ONE launch of the tile kernel pb_nv12_hot_kernel
+/* 4:2:0 semi-planar video frames - NV12 (bytes_per_sample 1) and P010 / P016 (2) - in ONE launch of the tile kernel pb_video_hot_kernel
  * whatever n_frames (ABI 5, additive).  A frame is a plane of height x width luma samples and, uv_offset bytes after its
  * start, a plane of height/2 x width/2 interleaved (U, V) pairs; the rows of both planes are `pitch` bytes apart - the surface a hardware
  * video decoder writes.  With idx the plan's index map (pb_index_map_i32):
@@ -305,7 +305,7 @@ int pb_remap_nv12(const pb_plan* plan, const void* src_dev, void* dst_dev, int n
 int pb_remap_nv12_supported(const pb_plan* plan, int bytes_per_sample);
 
 /* PLANAR video frames - yuv420p / yuv422p / yuv444p, their 10- and 16-bit forms, gbrp - in ONE launch of the tile kernel
- * pb_planar_hot_kernel whatever n_frames (ABI 5, additive).  A frame is three planes of S-byte samples, S = bytes_per_sample:
+ * pb_video_hot_kernel whatever n_frames (ABI 5, additive).  A frame is three planes of S-byte samples, S = bytes_per_sample:
  * plane 0 of height x width samples at the frame's start, rows `pitch` bytes apart; planes 1 and 2 of (height >> cy) x (width >> cx)
  * samples each, offset1 and offset2 bytes after the frame's start, rows `chroma_pitch` bytes apart.  (cx, cy) is (0, 0) for PB_PLANAR_444,
  * (1, 0) for PB_PLANAR_422 and (1, 1) for PB_PLANAR_420.  With idx the plan's index map (pb_index_map_i32):

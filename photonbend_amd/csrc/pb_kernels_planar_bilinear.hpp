@@ -31,11 +31,11 @@
 // samples as U | V << 16 at the anchor's place of the second; the lanes read them back in the store shape (four pixels of a row) and
 // they leave through pb_nv12_store_y, pb_planar_store_c and pb_nv12_store_uv, clipped to their planes.  Padding is never read or written.
 //
-// Scalar registers: pb_kernels_nv12.hpp's rule - the layouts and fills live in vector registers, the tile entry stays in SGPRs.
+// Scalar registers: pb_video.hpp's rule - the layouts and fills live in vector registers, the tile entry stays in SGPRs.
 // Limits: pb_remap_planar's (32-bit byte offsets inside a frame, sources below 32768 px a side).  LDS: 8448 bytes per wave.
 #pragma once
 #include "pb_kernels_catmull_rom.hpp"
-#include "pb_kernels_planar.hpp"
+#include "pb_video.hpp"
 
 #define PB_VBIL_WAVES 4
 #define PB_VBIL_WPE 4  // waves per SIMD the kernel is compiled for (128 VGPRs)
@@ -81,17 +81,7 @@ __device__ __forceinline__ void pb_vbil_px(const uint8_t* __restrict__ s, const 
         unsigned rc[2], cc[2];
         pb_vbil_rc<WRAP>(i0 >> CY, j0 >> CX, h >> CY, w >> CX, rc, cc);  // (arithmetic shifts: floor)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if constexpr (PAIRS) {
-                const unsigned t = pb_nv12_load_uv<S>(s, L.src_o1 + rc[k >> 1] * L.src_cpitch + cc[k & 1] * (unsigned)(2 * S));
-                u[k] = t & (S == 1 ? 0xFFu : 0xFFFFu);
-                v[k] = t >> (8 * S);
-            } else {
-                const unsigned off = rc[k >> 1] * L.src_cpitch + cc[k & 1] * (unsigned)S;
-                u[k] = pb_nv12_load_y<S>(s, L.src_o1 + off);
-                v[k] = pb_nv12_load_y<S>(s, L.src_o2 + off);
-            }
-        }
+        for (int k = 0; k < 4; ++k) pb_video_load_c<S, PAIRS>(s, L, rc[k >> 1] * L.src_cpitch + cc[k & 1] * (unsigned)(PAIRS ? 2 * S : S), u[k], v[k]);
     }
     const unsigned vy = pb_vbil_mix(a0, a1, a2, a3, tx, ty);
     y = dead ? L.fill[0] : vy;
@@ -125,19 +115,7 @@ __global__ __launch_bounds__(64 * PB_VBIL_WAVES, PB_VBIL_WPE) void pb_planar_bil
     constexpr int NC = 4 >> CX;
     constexpr bool WRAP = SRC_KIND == PB_KIND_PANO;
     constexpr bool NT = PB_NT_DEFAULT(SRC_KIND);
-    // the layouts and fills live in VECTOR registers (pb_kernels_nv12.hpp, "Scalar registers")
-    PbPlanar L;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.src_pitch) : "s"(Ls.src_pitch));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.src_cpitch) : "s"(Ls.src_cpitch));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.src_o1) : "s"(Ls.src_o1));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.src_o2) : "s"(Ls.src_o2));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.dst_pitch) : "s"(Ls.dst_pitch));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.dst_cpitch) : "s"(Ls.dst_cpitch));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.dst_o1) : "s"(Ls.dst_o1));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.dst_o2) : "s"(Ls.dst_o2));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.fill[0]) : "s"(Ls.fill[0]));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.fill[1]) : "s"(Ls.fill[1]));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.fill[2]) : "s"(Ls.fill[2]));
+    const PbPlanar L = pb_video_in_vgprs(Ls);  // (pb_video.hpp, "Scalar registers")
     __shared__ unsigned park[PB_VBIL_WAVES][2][PB_PX_PLANE];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -164,19 +142,11 @@ __global__ __launch_bounds__(64 * PB_VBIL_WAVES, PB_VBIL_WPE) void pb_planar_bil
     if (e->bil_off < 0 && !(flags & (PB_TILE_LEAN | PB_TILE_DIRECT))) {  // BLACK (every other class has a table slot)
         const unsigned z0[4] = {L.fill[0], L.fill[0], L.fill[0], L.fill[0]}, z1[4] = {L.fill[1], L.fill[1], L.fill[1], L.fill[1]},
                        z2[4] = {L.fill[2], L.fill[2], L.fill[2], L.fill[2]};
-        const unsigned zuv[2] = {pb_vbil_pair<S>(L.fill[1] | (L.fill[2] << 16)), pb_vbil_pair<S>(L.fill[1] | (L.fill[2] << 16))};
 #pragma unroll
         for (int jr = 0; jr < 4; ++jr) {
             const int y = Y0 + yb + 8 * jr;
             pb_nv12_store_y<S, false>(dst, L.dst_pitch, W, H, x, y, z0);
-            if (!CY || pb_nv12_even(yb)) {
-                if constexpr (PAIRS) {
-                    pb_nv12_store_uv<S, false>(dst + L.dst_o1, L.dst_cpitch, W, H, x, y, zuv);
-                } else {
-                    pb_planar_store_c<S, SUB, false>(dst + L.dst_o1, L.dst_cpitch, W, H, x, y, z1);
-                    pb_planar_store_c<S, SUB, false>(dst + L.dst_o2, L.dst_cpitch, W, H, x, y, z2);
-                }
-            }
+            if (!CY || pb_nv12_even(yb)) pb_video_store_c<S, SUB, PAIRS>(dst, L, W, H, x, y, z1, z2);
         }
     } else if (e->bil_off >= 0) {
         // a table tile: the slot's exact coordinates, walked as pb_cr_vals walks them
@@ -255,12 +225,7 @@ __global__ __launch_bounds__(64 * PB_VBIL_WAVES, PB_VBIL_WPE) void pb_planar_bil
                     c1[j] = PAIRS ? pb_vbil_pair<S>(uv) : (uv & 0xFFFFu);
                     c2[j] = uv >> 16;
                 }
-                if constexpr (PAIRS) {
-                    pb_nv12_store_uv<S, NT>(dst + L.dst_o1, L.dst_cpitch, W, H, x, y, c1);
-                } else {
-                    pb_planar_store_c<S, SUB, NT>(dst + L.dst_o1, L.dst_cpitch, W, H, x, y, c1);
-                    pb_planar_store_c<S, SUB, NT>(dst + L.dst_o2, L.dst_cpitch, W, H, x, y, c2);
-                }
+                pb_video_store_stored<S, SUB, PAIRS, NT>(dst, L, W, H, x, y, c1, c2);  // (PAIRS: c1 holds the pairs)
             }
         }
     }
@@ -282,15 +247,7 @@ __global__ __launch_bounds__(64 * PB_VBIL_WAVES, PB_VBIL_WPE) void pb_planar_bil
             unsigned vy, vuv = 0u;
             pb_vbil_px<S, SUB, PAIRS, WRAP>(src, L, h, w, i0, j0, fty, ftx, dead, anchor, vy, vuv);
             pb_nv12_store_y1<S>(dst + (y * L.dst_pitch + xx * (unsigned)S), vy);
-            if (anchor) {
-                if constexpr (PAIRS) {
-                    pb_nv12_store_uv1<S>(dst + (L.dst_o1 + (y >> 1) * L.dst_cpitch + xx * (unsigned)S), pb_vbil_pair<S>(vuv));
-                } else {
-                    const unsigned doff = (y >> CY) * L.dst_cpitch + (xx >> CX) * (unsigned)S;
-                    pb_nv12_store_y1<S>(dst + (L.dst_o1 + doff), vuv & 0xFFFFu);
-                    pb_nv12_store_y1<S>(dst + (L.dst_o2 + doff), vuv >> 16);
-                }
-            }
+            if (anchor) pb_video_store_c1<S, SUB, PAIRS>(dst, L, y, xx, vuv & 0xFFFFu, vuv >> 16);
         }
     }
 }

@@ -135,6 +135,66 @@ __device__ __forceinline__ void pb_px_store_row(uint8_t* __restrict__ d, const i
     }
 }
 
+// The front end of the direct-gather path of a LEAN / DIRECT tile (pb_win_tile's, its comments hold): which sixteen pixels of the tile a
+// lane gathers, and where they come from.  Lanes lie along the line of constant source row: lane (p, hh) holds the pixels n = 0 .. 15 at
+// q = (2 n + hh + shift) & 31 of line p - pixel (y, x) = (q, p) with along_x, else (p, q) -, `shift` the line's shear.
+struct PbGather {
+    bool along_x;  // |d row / du| <= |d row / dv|
+    int p, hh, shift;
+    __device__ __forceinline__ int q(const int n) const { return (2 * n + hh + shift) & 31; }
+    __device__ __forceinline__ int at(const int n) const { return along_x ? q(n) * 33 + p : p * 33 + q(n); }  // pixel n's dword of a [y][x] regrouping plane
+};
+__device__ __forceinline__ PbGather pb_gather_lanes(const PbTileEntry* __restrict__ e, const int lane) {
+    PbGather g;
+    g.along_x = fabsf(e->c[1][0]) <= fabsf(e->c[5][0]);
+    g.p = lane & 31;
+    g.hh = lane >> 5;
+    const float num = g.along_x ? e->c[1][0] : e->c[5][0], den = g.along_x ? e->c[5][0] : e->c[1][0];
+    const float slope = (den != 0.0f) ? -num / den : 0.0f;
+    g.shift = (int)rintf(slope * ((float)g.p - 15.5f));
+    return g;
+}
+// rc[n] = pixel n's certified source pixel, row << 16 | column (both below 32768): the model from the SGPR-resident entry, evaluated in the
+// two certified orders only (pb_collapse_col / pb_collapse_row + pb_eval_row)
+__device__ __forceinline__ PbGather pb_gather_front(const PbTileEntry* __restrict__ e, const int lane, unsigned rc[16]) {
+    const PbGather g = pb_gather_lanes(e, lane);
+    const int ar = e->anchor_r, ac = e->anchor_c;
+    if (g.along_x) {
+        pb_f2 bcol[5];
+        pb_collapse_col(e, g.p, bcol);
+#pragma unroll
+        for (int n = 0; n < 16; ++n) {
+            const pb_f2 fv = pb_eval_row(bcol, pb_tile_coord(g.q(n)));
+            rc[n] = ((unsigned)(ar + (int)fv.x) << 16) | (unsigned)(ac + (int)fv.y);
+        }
+    } else {
+        pb_f2 a[5];
+        pb_collapse_row(e, g.p, a);
+#pragma unroll
+        for (int n = 0; n < 16; ++n) {
+            const pb_f2 fv = pb_eval_row(a, pb_tile_coord(g.q(n)));
+            rc[n] = ((unsigned)(ar + (int)fv.x) << 16) | (unsigned)(ac + (int)fv.y);
+        }
+    }
+    return g;
+}
+// the `dead` bits of a MASKED tile at (X0, Y0): bit n is set where the lane's pixel n is black by the destination's mask
+__device__ __forceinline__ unsigned pb_gather_dead(const PbParams& P, const PbGather& g, const int X0, const int Y0) {
+    const int side = (P.dst.kind == PB_KIND_DOUBLE) && (X0 >= P.dst_half_w);
+    const int wc = (P.dst.kind == PB_KIND_DOUBLE) ? P.dst_half_w : P.dst.width;
+    const long long lo = P.inv_lo[side], hi = P.inv_hi[side];
+    unsigned dead = 0u;
+#pragma unroll
+    for (int n = 0; n < 16; ++n) {
+        const int q = g.q(n);
+        const int px = g.along_x ? g.p : q, py = g.along_x ? q : g.p;
+        const long long x2 = 2ll * (X0 + px - (side ? P.dst_half_w : 0)) - (wc - 1), y2 = (long long)(P.dst.height - 1) - 2ll * (Y0 + py);
+        const long long n4 = x2 * x2 + y2 * y2;
+        dead |= (unsigned)(n4 >= lo && n4 < hi) << n;
+    }
+    return dead;
+}
+
 template <int SRC_KIND, int BPP>
 __global__ __launch_bounds__(64 * PB_TILE_WAVES) void pb_px_hot_kernel(const PbParams* __restrict__ Pp, const PbHot Hd, const PbTileEntry* __restrict__ table,
                                                                         const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
@@ -197,11 +257,11 @@ __global__ __launch_bounds__(64 * PB_TILE_WAVES) void pb_px_hot_kernel(const PbP
         unsigned* win = lds[wave];
         const unsigned rowbytes = (unsigned)BPP * (unsigned)Hd.src_w;
         const unsigned gbase = (unsigned)e->anchor_r * rowbytes + (unsigned)BPP * (unsigned)e->anchor_c;
-        const bool along_x = fabsf(e->c[1][0]) <= fabsf(e->c[5][0]);  // |d row / du| <= |d row / dv|
-        const int p = lane & 31, hh = lane >> 5;
-        const float num = along_x ? e->c[1][0] : e->c[5][0], den = along_x ? e->c[5][0] : e->c[1][0];
-        const float slope = (den != 0.0f) ? -num / den : 0.0f;
-        const int shift = (int)rintf(slope * ((float)p - 15.5f));
+        // (of the shared front end this kernel takes the lanes' geometry alone: its source offsets are bytes of BPP-byte pixels, and with
+        //  the `dead` loop behind pb_gather_dead the compiler allocates its registers differently - tests/test_isa_pixel_formats.py pins them)
+        const PbGather g = pb_gather_lanes(e, lane);
+        const bool along_x = g.along_x;
+        const int p = g.p, hh = g.hh, shift = g.shift;
         unsigned dead = 0u;
         if (flags & PB_TILE_MASKED) {
             const int side = (P.dst.kind == PB_KIND_DOUBLE) && (X0 >= P.dst_half_w);
@@ -253,10 +313,7 @@ __global__ __launch_bounds__(64 * PB_TILE_WAVES) void pb_px_hot_kernel(const PbP
         for (int i = 0; i < NW; ++i) {
             if (i) pb_wave_sync();  // (the plane's previous contents have been read)
 #pragma unroll
-            for (int n = 0; n < 16; ++n) {
-                const int q = (2 * n + hh + shift) & 31;
-                win[along_x ? q * 33 + p : p * 33 + q] = t[n].w[i];
-            }
+            for (int n = 0; n < 16; ++n) win[g.at(n)] = t[n].w[i];
             pb_wave_sync();
 #pragma unroll
             for (int jr = 0; jr < 4; ++jr)

@@ -1,8 +1,8 @@
 // pb_kernels_stitch_video.hpp - the nearest tile kernel for DOUBLE-fisheye video frames: NV12 / P010 and planar 4:4:4 / 4:2:2 / 4:2:0
 // (pb_stitch_nv12, pb_stitch_planar).
 //
-// The frame is pb_kernels_planar.hpp's (three planes of S-byte samples) or pb_kernels_nv12.hpp's (PAIRS: planes 1 and 2 as one plane of
-// interleaved pairs, 4:2:0); the plan is pb_kernels_double.hpp's, unchanged: two certified tile tables, the weight class of every tile
+// The frame is pb_video.hpp's: three planes of S-byte samples or, with PAIRS, planes 1 and 2 as one plane of interleaved pairs at
+// 4:2:0; the plan is pb_kernels_double.hpp's, unchanged: two certified tile tables, the weight class of every tile
 // (UNIT / ROW / LAT), the latitude table, the faithful taps and factors of failed tiles and fix pixels (PbDoubleFix), the launch-order
 // table with its SOLO entries.  With (il, ir, fl, fr) the reference's taps and factors of an output pixel
 //   blend(a_l, a_r) = cast((il < 0 ? 0.0 : a_l) * fl + (ir < 0 ? 0.0 : a_r) * fr), the cast pb_cvt_u8's widened to the sample: non-finite
@@ -12,9 +12,9 @@
 //                     anchor's taps and factors, fillk where both of the anchor's taps are black.  Only the anchor decides.
 //
 // pb_stitch_video_kernel<S, SUB, PAIRS> has pb_hot_double_kernel's single-frame launch shape: one wave per slot of the double plan's
-// launch-order table, frames of a batch as a grid dimension, the layouts and fills in vector registers (pb_kernels_nv12.hpp's rule).
+// launch-order table, frames of a batch as a grid dimension, the layouts and fills in vector registers (pb_video.hpp's rule).
 //   SOLO slot       one eye at weight exactly 1, nothing on a fix list: the slot's entry is that eye's, in scalar registers, and the tile
-//                   is a camera-source tile - pb_planar_hot_kernel's BLACK and LEAN / DIRECT paths (an eye's tile is never MASKED), with
+//                   is a camera-source tile - pb_video_hot_kernel's BLACK and LEAN / DIRECT paths (an eye's tile is never MASKED), with
 //                   the regrouping through LDS and the anchor lanes, the pair gathered whole with PAIRS.
 //   two-eye tile    both entries lane-held (pb_desc_of_lanes, pb_coefs_of_lanes).  Per eye the certified source pixel of the lane's
 //                   sixteen pixels (store shape: four pixels of four rows): pb_collapse_row_lanes + pb_eval_row + the entry's anchor for
@@ -31,7 +31,7 @@
 // refuse frames that span 2^31 bytes or more and sources of 32768 px a side or more.  LDS: the regrouping buffer, 4224 bytes per wave.
 #pragma once
 #include "pb_kernels_double.hpp"
-#include "pb_kernels_planar.hpp"
+#include "pb_video.hpp"
 
 template <int S>
 __device__ __forceinline__ unsigned pb_sv_cvt(double v) {  // pb_cvt_u8, keeping the low 8 * S bits
@@ -42,47 +42,6 @@ template <int S>
 __device__ __forceinline__ unsigned pb_sv_blend(unsigned l, unsigned r, double fl, double fr) {  // pb_blend_u8 on a sample
     return pb_sv_cvt<S>((double)l * fl + (double)r * fr);
 }
-// the byte offset of the chroma sample (PAIRS: the pair) of source pixel (r, c) inside its plane
-template <int S, int SUB, bool PAIRS>
-__device__ __forceinline__ unsigned pb_sv_coff(const unsigned cpitch, const unsigned r, const unsigned c) {
-    return (r >> pb_planar_cy(SUB)) * cpitch + (c >> pb_planar_cx(SUB)) * (unsigned)(PAIRS ? 2 * S : S);
-}
-// the two chroma samples at byte offset `off` of their planes (PAIRS: one load of the pair)
-template <int S, bool PAIRS>
-__device__ __forceinline__ void pb_sv_load_c(const uint8_t* __restrict__ s, const PbPlanar& L, const unsigned off, unsigned& c1, unsigned& c2) {
-    if constexpr (PAIRS) {
-        const unsigned v = pb_nv12_load_uv<S>(s, L.src_o1 + off);
-        c1 = v & (S == 1 ? 0xFFu : 0xFFFFu);
-        c2 = v >> (8 * S);
-    } else {
-        c1 = pb_nv12_load_y<S>(s, L.src_o1 + off);
-        c2 = pb_nv12_load_y<S>(s, L.src_o2 + off);
-    }
-}
-// one chroma sample pair of the destination, at the block of the anchor pixel (y, x)
-template <int S, int SUB, bool PAIRS>
-__device__ __forceinline__ void pb_sv_store_c1(uint8_t* __restrict__ d, const PbPlanar& L, const unsigned y, const unsigned x, const unsigned c1, const unsigned c2) {
-    const unsigned off = (y >> pb_planar_cy(SUB)) * L.dst_cpitch + (x >> pb_planar_cx(SUB)) * (unsigned)(PAIRS ? 2 * S : S);
-    if constexpr (PAIRS) {
-        pb_nv12_store_uv1<S>(d + (L.dst_o1 + off), c1 | (c2 << (8 * S)));
-    } else {
-        pb_nv12_store_y1<S>(d + (L.dst_o1 + off), c1);
-        pb_nv12_store_y1<S>(d + (L.dst_o2 + off), c2);
-    }
-}
-// the lane's chroma samples of output row y, columns x .. x + 3 (the caller has established that row y holds anchors)
-template <int S, int SUB, bool PAIRS>
-__device__ __forceinline__ void pb_sv_store_c(uint8_t* __restrict__ d, const PbPlanar& L, const int W, const int H, const int x, const int y, const unsigned c1[4],
-                                              const unsigned c2[4]) {
-    if constexpr (PAIRS) {
-        const unsigned uv[2] = {c1[0] | (c2[0] << (8 * S)), c1[1] | (c2[1] << (8 * S))};
-        pb_nv12_store_uv<S, false>(d + L.dst_o1, L.dst_cpitch, W, H, x, y, uv);
-    } else {
-        pb_planar_store_c<S, SUB, false>(d + L.dst_o1, L.dst_cpitch, W, H, x, y, c1);
-        pb_planar_store_c<S, SUB, false>(d + L.dst_o2, L.dst_cpitch, W, H, x, y, c2);
-    }
-}
-
 // One output pixel through its stored faithful taps and factors: the plane-0 sample and, with CHROMA, the two chroma samples of the
 // block it anchors.  Every load is issued before the first blend.
 template <int S, int SUB, bool PAIRS, bool CHROMA>
@@ -95,8 +54,8 @@ __device__ __forceinline__ void pb_sv_tap(const uint8_t* __restrict__ src, const
     unsigned yl = pb_nv12_load_y<S>(src, rl * L.src_pitch + cl * (unsigned)S), yr = pb_nv12_load_y<S>(src, rr * L.src_pitch + cr * (unsigned)S);
     unsigned c1l = 0u, c2l = 0u, c1r = 0u, c2r = 0u;
     if constexpr (CHROMA) {
-        pb_sv_load_c<S, PAIRS>(src, L, pb_sv_coff<S, SUB, PAIRS>(L.src_cpitch, rl, cl), c1l, c2l);
-        pb_sv_load_c<S, PAIRS>(src, L, pb_sv_coff<S, SUB, PAIRS>(L.src_cpitch, rr, cr), c1r, c2r);
+        pb_video_load_c<S, PAIRS>(src, L, pb_video_coff<S, SUB, PAIRS>(L.src_cpitch, rl, cl), c1l, c2l);
+        pb_video_load_c<S, PAIRS>(src, L, pb_video_coff<S, SUB, PAIRS>(L.src_cpitch, rr, cr), c1r, c2r);
     }
     yl = bl ? 0u : yl;
     yr = br ? 0u : yr;
@@ -137,7 +96,7 @@ __device__ __forceinline__ void pb_sv_eye_rc(const PbParams& P, const PbDesc& D,
     }
 }
 
-// A SOLO slot: a camera-source tile of the live eye (entry in scalar registers) - pb_planar_hot_kernel's BLACK and LEAN / DIRECT paths
+// A SOLO slot: a camera-source tile of the live eye (entry in scalar registers) - pb_video_hot_kernel's BLACK and LEAN / DIRECT paths
 template <int S, int SUB, bool PAIRS>
 __device__ __forceinline__ void pb_sv_solo(const PbTileEntry* __restrict__ e, const int flags, const int X0, const int Y0, const int lane, unsigned* win,
                                            const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const PbPlanar& L, const int W, const int H) {
@@ -151,61 +110,28 @@ __device__ __forceinline__ void pb_sv_solo(const PbTileEntry* __restrict__ e, co
 #pragma unroll
         for (int jr = 0; jr < 4; ++jr) {
             pb_nv12_store_y<S, false>(dst, L.dst_pitch, W, H, x, Y0 + yb + 8 * jr, z0);
-            if (!CY || pb_nv12_even(yb)) pb_sv_store_c<S, SUB, PAIRS>(dst, L, W, H, x, Y0 + yb + 8 * jr, z1, z2);
+            if (!CY || pb_nv12_even(yb)) pb_video_store_c<S, SUB, PAIRS>(dst, L, W, H, x, Y0 + yb + 8 * jr, z1, z2);
         }
         return;
     }
-    // the direct-gather path in the two certified evaluation orders (pb_planar_hot_kernel's comments hold): every pixel lies inside the
+    // the direct-gather path in the two certified evaluation orders (pb_video_hot_kernel's comments hold): every pixel lies inside the
     // image and samples inside the tile's source box
-    const int ar = e->anchor_r, ac = e->anchor_c;
-    const bool along_x = fabsf(e->c[1][0]) <= fabsf(e->c[5][0]);
-    const int p = lane & 31, hh = lane >> 5;
-    const float num = along_x ? e->c[1][0] : e->c[5][0], den = along_x ? e->c[5][0] : e->c[1][0];
-    const float slope = (den != 0.0f) ? -num / den : 0.0f;
-    const int shift = (int)rintf(slope * ((float)p - 15.5f));
-    const int colpar = along_x ? p : hh + shift, rowpar = along_x ? hh + shift : p;
+    unsigned rc[16];  // the certified source pixel: row << 16 | column (both below 32768)
+    const PbGather g = pb_gather_front(e, lane, rc);
+    const int colpar = g.along_x ? g.p : g.hh + g.shift, rowpar = g.along_x ? g.hh + g.shift : g.p;
     const bool anchors = !(((colpar & CX) | (rowpar & CY)) & 1);  // this lane's 16 pixels are all anchors (else none is)
-    unsigned rc[16];
-    if (along_x) {
-        pb_f2 bcol[5];
-        pb_collapse_col(e, p, bcol);
-#pragma unroll
-        for (int n = 0; n < 16; ++n) {
-            const pb_f2 fv = pb_eval_row(bcol, pb_tile_coord((2 * n + hh + shift) & 31));
-            rc[n] = ((unsigned)(ar + (int)fv.x) << 16) | (unsigned)(ac + (int)fv.y);
-        }
-    } else {
-        pb_f2 a[5];
-        pb_collapse_row(e, p, a);
-#pragma unroll
-        for (int n = 0; n < 16; ++n) {
-            const pb_f2 fv = pb_eval_row(a, pb_tile_coord((2 * n + hh + shift) & 31));
-            rc[n] = ((unsigned)(ar + (int)fv.x) << 16) | (unsigned)(ac + (int)fv.y);
-        }
-    }
-    unsigned t0[16], t1[16], t2[16];  // (PAIRS: t1 holds the pair, t2 nothing)
+    unsigned t0[16], t1[16], t2[16];  // (PAIRS: t1 holds the pair as stored, t2 nothing)
 #pragma unroll
     for (int n = 0; n < 16; ++n) t0[n] = pb_nv12_load_y<S>(src, (rc[n] >> 16) * L.src_pitch + (rc[n] & 0xFFFFu) * (unsigned)S);
     if (anchors) {
 #pragma unroll
-        for (int n = 0; n < 16; ++n) {
-            const unsigned off = pb_sv_coff<S, SUB, PAIRS>(L.src_cpitch, rc[n] >> 16, rc[n] & 0xFFFFu);
-            if constexpr (PAIRS) {
-                t1[n] = pb_nv12_load_uv<S>(src, L.src_o1 + off);
-            } else {
-                t1[n] = pb_nv12_load_y<S>(src, L.src_o1 + off);
-                t2[n] = pb_nv12_load_y<S>(src, L.src_o2 + off);
-            }
-        }
+        for (int n = 0; n < 16; ++n) pb_video_load_stored<S, PAIRS>(src, L, pb_video_coff<S, SUB, PAIRS>(L.src_cpitch, rc[n] >> 16, rc[n] & 0xFFFFu), t1[n], t2[n]);
     }
     // park as [y][x], read back in the store shape and store: plane 0, then - through the same buffer - the chroma at its anchors
     {
         unsigned a[4][4];
 #pragma unroll
-        for (int n = 0; n < 16; ++n) {
-            const int q = (2 * n + hh + shift) & 31;
-            win[along_x ? q * 33 + p : p * 33 + q] = t0[n];
-        }
+        for (int n = 0; n < 16; ++n) win[g.at(n)] = t0[n];
         pb_wave_sync();
 #pragma unroll
         for (int jr = 0; jr < 4; ++jr)
@@ -220,10 +146,7 @@ __device__ __forceinline__ void pb_sv_solo(const PbTileEntry* __restrict__ e, co
         unsigned c[4][4];
         if (anchors) {
 #pragma unroll
-            for (int n = 0; n < 16; ++n) {
-                const int q = (2 * n + hh + shift) & 31;
-                win[along_x ? q * 33 + p : p * 33 + q] = (pl == 1) ? t1[n] : t2[n];
-            }
+            for (int n = 0; n < 16; ++n) win[g.at(n)] = (pl == 1) ? t1[n] : t2[n];
         }
         pb_wave_sync();
         if (!CY || pb_nv12_even(yb)) {
@@ -255,19 +178,7 @@ __global__ __launch_bounds__(64 * PB_TILE_WAVES) void pb_stitch_video_kernel(con
     static_assert(SUB == PB_SUB_444 || SUB == PB_SUB_422 || SUB == PB_SUB_420, "the subsamplings of pb_stitch_planar");
     static_assert(!PAIRS || SUB == PB_SUB_420, "interleaved pairs are 4:2:0");
     constexpr int CX = pb_planar_cx(SUB), CY = pb_planar_cy(SUB);
-    // the layouts and fills live in VECTOR registers (pb_kernels_nv12.hpp, "Scalar registers")
-    PbPlanar L;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.src_pitch) : "s"(Ls.src_pitch));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.src_cpitch) : "s"(Ls.src_cpitch));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.src_o1) : "s"(Ls.src_o1));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.src_o2) : "s"(Ls.src_o2));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.dst_pitch) : "s"(Ls.dst_pitch));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.dst_cpitch) : "s"(Ls.dst_cpitch));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.dst_o1) : "s"(Ls.dst_o1));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.dst_o2) : "s"(Ls.dst_o2));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.fill[0]) : "s"(Ls.fill[0]));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.fill[1]) : "s"(Ls.fill[1]));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(L.fill[2]) : "s"(Ls.fill[2]));
+    const PbPlanar L = pb_video_in_vgprs(Ls);  // (pb_video.hpp, "Scalar registers")
     __shared__ unsigned lds[PB_TILE_WAVES][PB_PX_PLANE];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -321,7 +232,7 @@ __global__ __launch_bounds__(64 * PB_TILE_WAVES) void pb_stitch_video_kernel(con
                 }
             }
             pb_nv12_store_y<S, false>(dst, L.dst_pitch, W, H, x, Y0 + yb + 8 * jr, a);
-            if (!CY || pb_nv12_even(yb)) pb_sv_store_c<S, SUB, PAIRS>(dst, L, W, H, x, Y0 + yb + 8 * jr, c1, c2);
+            if (!CY || pb_nv12_even(yb)) pb_video_store_c<S, SUB, PAIRS>(dst, L, W, H, x, Y0 + yb + 8 * jr, c1, c2);
         }
         return;  // (a failed tile has no fix pixels: its slot holds them all)
     }
@@ -341,8 +252,8 @@ __global__ __launch_bounds__(64 * PB_TILE_WAVES) void pb_stitch_video_kernel(con
             yl[k] = pb_nv12_load_y<S>(src, vL < 0 ? 0u : rl * L.src_pitch + cl * (unsigned)S);
             yr[k] = pb_nv12_load_y<S>(src, vR < 0 ? 0u : rr * L.src_pitch + cr * (unsigned)S);
             if (!(k & CX)) {  // (every lane gathers its anchors' chroma - no load inside a branch; at 4:2:0 the lanes of even rows store it)
-                pb_sv_load_c<S, PAIRS>(src, L, vL < 0 ? 0u : pb_sv_coff<S, SUB, PAIRS>(L.src_cpitch, rl, cl), c1l[k >> CX], c2l[k >> CX]);
-                pb_sv_load_c<S, PAIRS>(src, L, vR < 0 ? 0u : pb_sv_coff<S, SUB, PAIRS>(L.src_cpitch, rr, cr), c1r[k >> CX], c2r[k >> CX]);
+                pb_video_load_c<S, PAIRS>(src, L, vL < 0 ? 0u : pb_video_coff<S, SUB, PAIRS>(L.src_cpitch, rl, cl), c1l[k >> CX], c2l[k >> CX]);
+                pb_video_load_c<S, PAIRS>(src, L, vR < 0 ? 0u : pb_video_coff<S, SUB, PAIRS>(L.src_cpitch, rr, cr), c1r[k >> CX], c2r[k >> CX]);
             }
         }
         double wl[4], wr[4];
@@ -365,7 +276,7 @@ __global__ __launch_bounds__(64 * PB_TILE_WAVES) void pb_stitch_video_kernel(con
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             int vL = ql[jr * 4 + k], vR = qr[jr * 4 + k];
-            asm volatile("" : "+v"(vL));  // (the blacks after the loads, from values the compiler cannot trace: pb_kernels_nv12.hpp)
+            asm volatile("" : "+v"(vL));  // (the blacks after the loads, from values the compiler cannot trace: pb_video.hpp)
             asm volatile("" : "+v"(vR));
             const bool bl = vL < 0, br = vR < 0, none = bl && br;
             constexpr unsigned mask = S == 1 ? 0xFFu : 0xFFFFu;
@@ -388,7 +299,7 @@ __global__ __launch_bounds__(64 * PB_TILE_WAVES) void pb_stitch_video_kernel(con
             }
         }
         pb_nv12_store_y<S, false>(dst, L.dst_pitch, W, H, x, Y0 + yb + 8 * jr, a);
-        if (!CY || pb_nv12_even(yb)) pb_sv_store_c<S, SUB, PAIRS>(dst, L, W, H, x, Y0 + yb + 8 * jr, c1, c2);
+        if (!CY || pb_nv12_even(yb)) pb_video_store_c<S, SUB, PAIRS>(dst, L, W, H, x, Y0 + yb + 8 * jr, c1, c2);
     }
     // the tile's fix pixels (either eye's list; a pixel listed by both is written twice): through their stored taps, after the wave's own
     // stores have completed; an anchor among them redoes its two chroma samples
@@ -405,7 +316,7 @@ __global__ __launch_bounds__(64 * PB_TILE_WAVES) void pb_stitch_video_kernel(con
                 pb_nv12_divmod(p, (unsigned)W, __builtin_amdgcn_rcpf((float)W), y, xx);
                 if (!(((xx & CX) | (y & CY)) & 1u)) {
                     pb_sv_tap<S, SUB, PAIRS, true>(src, L, sw, inv_sw, t, v0, v1, v2);
-                    pb_sv_store_c1<S, SUB, PAIRS>(dst, L, y, xx, v1, v2);
+                    pb_video_store_c1<S, SUB, PAIRS>(dst, L, y, xx, v1, v2);
                 } else {
                     pb_sv_tap<S, SUB, PAIRS, false>(src, L, sw, inv_sw, t, v0, v1, v2);
                 }

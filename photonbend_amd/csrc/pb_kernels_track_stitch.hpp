@@ -5,11 +5,11 @@
 // is new: the chain is pb_track_body's, the taps are pb_src_double_taps' (one pb_expi_np for both eyes, as in pb_track_px), the blend is
 // pb_sv_blend, the loads and stores are the stitch kernel's.  The plan's tables are never read.
 //
-// pb_track_stitch_kernel<S, PAIRS> has pb_track_planar_kernel's structure: pb_chain<PB_ROT_ANY> once per pixel, two float64 and a flag per
+// pb_track_stitch_kernel<S, PAIRS> has pb_track_video_kernel's structure: pb_chain<PB_ROT_ANY> once per pixel, two float64 and a flag per
 // pixel live across the frame loop, frames chunked over blockIdx.y (`fpc` per chunk, a short last chunk), the frame's matrices through
 // pb_track_rotate (scalar loads), a work-item owns PB_PX = 4 consecutive pixels of ONE row (a row's last quad holds 1 to 4 pixels).
 //   PAIRS         planes 1 and 2 as one plane of interleaved pairs (NV12 / P010), 4:2:0.  Otherwise three planes, the subsampling a
-//                 RUN-TIME, wave-uniform (cx, cy) for pb_track_planar_kernel's reason.
+//                 RUN-TIME, wave-uniform (cx, cy) for pb_track_video_kernel's reason.
 //   taps          each tap comes apart through pb_nv12_divmod; each eye's plane-0 sample is loaded with exactly S bytes and, on anchors,
 //                 its two chroma samples (PAIRS: one 2 * S-byte pair) at (r >> cy, c >> cx).  A black tap reads its plane's first sample
 //                 and is zeroed after the load: branch-free, never out of bounds.  The anchor's factors serve its chroma.
@@ -17,7 +17,7 @@
 //   stores        pb_nv12_store_y, pb_planar_store2 and pb_nv12_store_uv, clipped to their planes.  Padding between rows, planes and
 //                 frames is neither read nor written.
 //   registers     a pixel's three samples are packed two to a register while the other pixels' chains run; the row and column are asked
-//                 anew in every frame behind an empty asm (pb_track_planar_kernel's reason).
+//                 anew in every frame behind an empty asm (pb_track_video_kernel's reason).
 //
 // Limits.  Byte offsets inside a frame are 32-bit: the calls refuse frames whose span reaches 2^31 bytes and sources of 32768 px a side
 // or more before any launch.  grid: (quads of a frame / PB_BLOCK, chunks of fpc frames).
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(PB_BLOCK, PB_TRACK_WPE(PB_KIND_DOUBLE)) void pb_tra
     for (int f = f0; f < f1; ++f) {
         const uint8_t* __restrict__ s = src + (unsigned long long)f * src_stride;
         uint8_t* __restrict__ d = dst + (unsigned long long)f * dst_stride;
-        // (the row and column are asked anew in every frame, in place: pb_track_planar_kernel's reason)
+        // (the row and column are asked anew in every frame, in place: pb_track_video_kernel's reason)
         asm volatile("" : "+v"(y), "+v"(x0));
         const unsigned yy = y;
         const int xx = x0;
@@ -86,8 +86,8 @@ __global__ __launch_bounds__(PB_BLOCK, PB_TRACK_WPE(PB_KIND_DOUBLE)) void pb_tra
                 if (anchor_row && !(k & cx)) {  // (an anchor: its taps and factors serve the two chroma samples)
                     constexpr unsigned CS = PAIRS ? 2 * S : S;
                     unsigned c1l, c2l, c1r, c2r;
-                    pb_sv_load_c<S, PAIRS>(s, L, (rl >> cy) * L.src_cpitch + (cl >> cx) * CS, c1l, c2l);
-                    pb_sv_load_c<S, PAIRS>(s, L, (rr >> cy) * L.src_cpitch + (cr >> cx) * CS, c1r, c2r);
+                    pb_video_load_c<S, PAIRS>(s, L, (rl >> cy) * L.src_cpitch + (cl >> cx) * CS, c1l, c2l);
+                    pb_video_load_c<S, PAIRS>(s, L, (rr >> cy) * L.src_cpitch + (cr >> cx) * CS, c1r, c2r);
                     const unsigned v1 = none ? L.fill[1] : pb_sv_blend<S>(bl ? 0u : c1l, br ? 0u : c1r, t.fl, t.fr);
                     const unsigned v2 = none ? L.fill[2] : pb_sv_blend<S>(bl ? 0u : c2l, br ? 0u : c2r, t.fl, t.fr);
                     p1[k >> 1] |= v1 << (16 * (k & 1));

@@ -14,13 +14,13 @@
 // definition's order under the build's -ffp-contract=off: the result is the definition's bytes exactly, for 8-, 10- and 16-bit samples
 // alike (the uint8 routes' float32 taps are not exact for 16-bit samples and are not used).  The plan's tables are never read.
 //
-// pb_track_video_bilinear_kernel<S, SRC_KIND, PAIRS> has pb_track_planar_kernel's structure: pb_chain<PB_ROT_ANY> once per pixel, two
+// pb_track_video_bilinear_kernel<S, SRC_KIND, PAIRS> has pb_track_video_kernel's structure: pb_chain<PB_ROT_ANY> once per pixel, two
 // float64 and a flag per pixel live across the frame loop, frames chunked over blockIdx.y, the frame's matrices through pb_track_rotate
 // (scalar loads), a work-item owns PB_PX = 4 consecutive pixels of ONE row.
 //   coordinate    a panorama's through pb_src_pretrunc; a camera's through pb_src_pretrunc_sc with the sine and cosine of pb_expi_np -
 //                 np.exp(lon * 1j), the definition's own (pb_sample_map_interp_px computes it so): pb_src_pretrunc's plain sincos is the
 //                 model builders' and differs from it in the last bit.
-//   PAIRS false   three planes; the subsampling is a RUN-TIME, wave-uniform (cx, cy), for pb_track_planar_kernel's reason.
+//   PAIRS false   three planes; the subsampling is a RUN-TIME, wave-uniform (cx, cy), for pb_track_video_kernel's reason.
 //   PAIRS true    NV12 / P010 at 4:2:0: planes 1 and 2 are the interleaved (U, V) plane, one 2 * S-byte load per chroma tap, pair stores.
 //                 The layout travels in the same PbPlanar: o1 = the pair plane's offset, cpitch = its pitch, o2 unused.
 //   taps          each loaded with exactly its S (or 2 * S) bytes.  Rows and columns are clamped for EVERY tap, a panorama's columns
@@ -36,7 +36,7 @@
 // grid: (quads of a frame / PB_BLOCK, chunks of fpc frames).
 #pragma once
 #include "pb_kernels_planar_bilinear.hpp"
-#include "pb_kernels_track_planar.hpp"
+#include "pb_kernels_track_video.hpp"
 
 // waves per SIMD the kernel is compiled for.  What the build gave at each bound tried, quads of four pixels throughout:
 //   8       panorama source 63 VGPRs, 78 scalar registers, no scratch, eight waves; camera source 63 VGPRs and 20 bytes of scratch
@@ -67,7 +67,7 @@ __device__ __forceinline__ unsigned pb_tvb_mix(const unsigned a, const unsigned 
     return (unsigned)rint(top + ty * (bot - top));
 }
 
-// (the sample size comes first, for the reason pb_kernels_track_nv12.hpp gives)
+// (the sample size comes first, for the reason pb_kernels_track_video.hpp gives)
 template <int S, int SRC_KIND, bool PAIRS>
 __global__ __launch_bounds__(PB_BLOCK, PB_TVB_WPE(SRC_KIND)) void pb_track_video_bilinear_kernel(const PbParams P, const double* __restrict__ rot, int k_rot, int fpc,
                                                                                      const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n_frames,
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(PB_BLOCK, PB_TVB_WPE(SRC_KIND)) void pb_track_video
     for (int f = f0; f < f1; ++f) {
         const uint8_t* __restrict__ s = src + (unsigned long long)f * src_stride;
         uint8_t* __restrict__ d = dst + (unsigned long long)f * dst_stride;
-        // (the row and column are asked anew in every frame, in place: pb_track_planar_kernel's reason)
+        // (the row and column are asked anew in every frame, in place: pb_track_video_kernel's reason)
         asm volatile("" : "+v"(y), "+v"(x0));
         const unsigned yy = y;
         const int xx = x0;
@@ -138,16 +138,7 @@ __global__ __launch_bounds__(PB_BLOCK, PB_TVB_WPE(SRC_KIND)) void pb_track_video
                     pb_tvb_taps<WRAP>(cy ? sy * 0.5 : sy, cx ? sx * 0.5 : sx, h >> cy, w >> cx, L.src_cpitch, (unsigned)(PAIRS ? 2 * S : S), o, ty, tx);
                     unsigned u[4], v[4];
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        if constexpr (PAIRS) {
-                            const unsigned uv = pb_nv12_load_uv<S>(s, L.src_o1 + o[t]);
-                            u[t] = uv & (S == 1 ? 0xFFu : 0xFFFFu);
-                            v[t] = uv >> (8 * S);
-                        } else {
-                            u[t] = pb_nv12_load_y<S>(s, L.src_o1 + o[t]);
-                            v[t] = pb_nv12_load_y<S>(s, L.src_o2 + o[t]);
-                        }
-                    }
+                    for (int t = 0; t < 4; ++t) pb_video_load_c<S, PAIRS>(s, L, o[t], u[t], v[t]);
                     const unsigned v1 = pb_tvb_mix(u[0], u[1], u[2], u[3], tx, ty), v2 = pb_tvb_mix(v[0], v[1], v[2], v[3], tx, ty);
                     p1[k >> 1] |= (live ? v1 : L.fill[1]) << (16 * (k & 1));
                     p2[k >> 1] |= (live ? v2 : L.fill[2]) << (16 * (k & 1));

@@ -40,11 +40,9 @@
 #include "pb_kernels_supersample.hpp"
 #include "pb_kernels_catmull_rom.hpp"
 #include "pb_kernels_px.hpp"
-#include "pb_kernels_nv12.hpp"
+#include "pb_kernels_video.hpp"
 #include "pb_kernels_track.hpp"
-#include "pb_kernels_track_nv12.hpp"
-#include "pb_kernels_planar.hpp"
-#include "pb_kernels_track_planar.hpp"
+#include "pb_kernels_track_video.hpp"
 #include "pb_kernels_planar_bilinear.hpp"
 #include "pb_kernels_track_video_bilinear.hpp"
 #include "pb_kernels_stitch_video.hpp"
@@ -635,7 +633,7 @@ static void pb_pick_px_size(int bpp, F&& f) {
         default: f(PbInt<8>()); break;
     }
 }
-// pb_planar_hot_kernel's SUB (PB_PLANAR_444 / _422 / _420; pb_video_fmt_check has refused everything else)
+// pb_video_hot_kernel's SUB (PB_PLANAR_444 / _422 / _420; pb_video_fmt_check has refused everything else)
 template <class F>
 static void pb_pick_subsampling(int sub, F&& f) {
     static_assert(PB_PLANAR_444 == PB_SUB_444 && PB_PLANAR_422 == PB_SUB_422 && PB_PLANAR_420 == PB_SUB_420, "the kernel's SUB is the header's constant");
@@ -1016,8 +1014,8 @@ struct PbRoute {
         SS_GENERIC,          // supersampled: frame by frame the route of n = 1 into a workspace, then pb_box_reduce_kernel
         PX,                  // nearest, pixels of bpp != 3 bytes (pb_remap_px): pb_px_hot_kernel
         PX_NONE,             // ... on a plan that kernel does not serve: nothing is launched (PB_ERR_UNSUPPORTED)
-        VIDEO,               // nearest, video frames: 4:2:0 semi-planar (pb_remap_nv12): pb_nv12_hot_kernel; planar 4:4:4 / 4:2:2 / 4:2:0
-                             // (pb_remap_planar): pb_planar_hot_kernel
+        VIDEO,               // nearest, video frames: planar 4:4:4 / 4:2:2 / 4:2:0 (pb_remap_planar) and, as PAIRS, 4:2:0 semi-planar
+                             // (pb_remap_nv12): pb_video_hot_kernel
         VIDEO_NONE,          // ... on a plan those kernels do not serve - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
         VIDEO_STITCH,        // nearest, video frames of a double-fisheye source (pb_stitch_nv12, pb_stitch_planar): pb_stitch_video_kernel
         VIDEO_STITCH_NONE,   // ... on a plan that kernel does not serve: nothing is launched (PB_ERR_UNSUPPORTED)
@@ -1111,13 +1109,8 @@ static void pb_launch_direct(const pb_plan* pl, const uint8_t* src, uint8_t* dst
                            (int)pl->cert.n_fix_px, pl->cert.idx_tab, pl->cert.fix_idx, src, dst, n_frames, ss, ds, idx_out);
 }
 
-// the layout and fills pb_nv12_hot_kernel and pb_track_nv12_kernel take, of a semi-planar call's resolved layout (S: bytes per sample)
-static PbNv12 pb_nv12_of(const PbPlanar& L, int S) {
-    return {L.src_pitch, L.src_o1, L.dst_pitch, L.dst_o1, L.fill[0], L.fill[1] | (L.fill[2] << (8u * (unsigned)S))};
-}
-
 // Launches a nearest or bilinear route (n = 1) for n_frames frames at strides ss / ds (pb_check_frames has filled them in).
-// video: the plane layouts and fills of the VIDEO and VIDEO_BIL routes (an NV12 layout travels as a PbPlanar: pb_nv12_of), null everywhere else.
+// video: the plane layouts and fills of the VIDEO and VIDEO_BIL routes (an NV12 layout travels as a PbPlanar: pb_video.hpp), null everywhere else.
 static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* dst, int n_frames, unsigned long long ss, unsigned long long ds,
                      hipStream_t st, const PbPlanar* video = nullptr) {
     const PbParams& P = pl->P;
@@ -1190,20 +1183,17 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
             // launched like PX: every plane of a tile by the tile's wave
             const unsigned gpf = pl->nearest.lt.groups;
             pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
-                auto go = [&](auto kernel, auto layout) {
-                    hipLaunchKernelGGL(kernel, dim3(gpf * (unsigned)nf), dim3(64 * PB_TILE_WAVES), 0, st, (const PbParams*)pl->nearest.P_dev, pb_hot_of_host(P),
-                                       pl->nearest.lt.entries, sf, df, gpf, ss, ds, pl->cert.idx_tab, pl->cert.fix_px, pl->cert.fix_idx, layout);
-                };
-                if (r.video.pairs)
-                    pb_pick_kind(P, [&](auto K) {
-                        pb_pick<1, 2>(r.video.S == 1, [&](auto S) { go(pb_nv12_hot_kernel<K.value, S.value>, pb_nv12_of(*video, S.value)); });
+                pb_pick_kind(P, [&](auto K) {
+                    pb_pick<1, 2>(r.video.S == 1, [&](auto S) {
+                        auto go = [&](auto SUB, auto PAIRS) {
+                            hipLaunchKernelGGL((pb_video_hot_kernel<K.value, S.value, SUB.value, PAIRS.value != 0>), dim3(gpf * (unsigned)nf), dim3(64 * PB_TILE_WAVES), 0, st,
+                                               (const PbParams*)pl->nearest.P_dev, pb_hot_of_host(P), pl->nearest.lt.entries, sf, df, gpf, ss, ds, pl->cert.idx_tab,
+                                               pl->cert.fix_px, pl->cert.fix_idx, *video);
+                        };
+                        if (r.video.pairs) go(PbInt<PB_SUB_420>(), PbInt<1>());
+                        else pb_pick_subsampling(r.video.sub, [&](auto SUB) { go(SUB, PbInt<0>()); });
                     });
-                else
-                    pb_pick_kind(P, [&](auto K) {
-                        pb_pick<1, 2>(r.video.S == 1, [&](auto S) {
-                            pb_pick_subsampling(r.video.sub, [&](auto SUB) { go(pb_planar_hot_kernel<K.value, S.value, SUB.value>, *video); });
-                        });
-                    });
+                });
             });
             break;
         }
@@ -2271,7 +2261,7 @@ static int pb_video_check(const pb_plan* plan, const void* src_dev, const void* 
            {fill ? fill[0] & smask : 16u << sh, fill ? fill[1] & smask : 128u << sh, fill ? fill[2] & smask : 128u << sh}};
     return PB_OK;
 }
-// the plain calls: nearest (pb_nv12_hot_kernel / pb_planar_hot_kernel) and bilinear (pb_planar_bilinear_kernel, with pairs for NV12)
+// the plain calls: nearest (pb_video_hot_kernel) and bilinear (pb_planar_bilinear_kernel, with pairs for NV12)
 static int pb_video_call(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, const void* src_layout, const void* dst_layout, const PbVideoFmt& v,
                          const uint16_t fill[3], void* stream, int interpolation, const char* name) {
     PbVideoCall c;
@@ -2455,8 +2445,8 @@ int pb_remap_track_u8(const pb_plan* plan, const double* rot3x3_dev, int n_rot_p
 }
 
 // A rotation track of video frames (bilinear: 3.19): the plain video calls' argument checks, then pb_remap_track_u8's
-// table checks; the launches are pb_remap_track_u8's, one per 65535 chunks of frames.  Nearest: pb_track_nv12_kernel / pb_track_planar_kernel;
-// bilinear: pb_track_video_bilinear_kernel (with pairs for NV12), a panorama or camera source.
+// table checks; the launches are pb_remap_track_u8's, one per 65535 chunks of frames.  Nearest: pb_track_video_kernel; bilinear:
+// pb_track_video_bilinear_kernel, a panorama or camera source (both with pairs for NV12).
 // A format with `stitch` (pb_track_stitch_nv12 / _planar) takes a double-fisheye source and no other: pb_track_stitch_kernel.
 static int pb_track_video_call(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
                                const void* src_layout, const void* dst_layout, const PbVideoFmt& v, const uint16_t fill[3], void* stream, int interpolation,
@@ -2490,30 +2480,16 @@ static int pb_track_video_call(const pb_plan* plan, const double* rot3x3_dev, in
         const uint8_t* s = static_cast<const uint8_t*>(src_dev) + (unsigned long long)f0 * c.fs.stride;
         uint8_t* d = static_cast<uint8_t*>(dst_dev) + (unsigned long long)f0 * c.fd.stride;
         const dim3 grid(pb_blocks(quads), (unsigned)((nf + fpc - 1) / fpc));
-        auto launch = [&](auto kernel, auto... layout) {
-            hipLaunchKernelGGL(kernel, grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride, c.fd.stride, layout...);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride, c.fd.stride, c.L, cx, cy);
         };
-        const bool bilinear = interpolation == PB_INTERP_BILINEAR;
-        if (v.stitch)
-            pb_pick<1, 0>(v.pairs, [&](auto PAIRS) {
-                pb_pick<1, 2>(v.S == 1, [&](auto S) { launch(pb_track_stitch_kernel<S.value, PAIRS.value != 0>, c.L, cx, cy); });
+        pb_pick<1, 0>(v.pairs, [&](auto PAIRS) {
+            pb_pick<1, 2>(v.S == 1, [&](auto S) {
+                if (v.stitch) launch(pb_track_stitch_kernel<S.value, PAIRS.value != 0>);
+                else if (interpolation == PB_INTERP_BILINEAR) pb_pick_kind(P, [&](auto K) { launch(pb_track_video_bilinear_kernel<S.value, K.value, PAIRS.value != 0>); });
+                else pb_pick_exact_kind(P, [&](auto K) { launch(pb_track_video_kernel<S.value, K.value, PAIRS.value != 0>); });
             });
-        else if (v.pairs && bilinear)
-            pb_pick_kind(P, [&](auto K) {
-                pb_pick<1, 2>(v.S == 1, [&](auto S) { launch(pb_track_video_bilinear_kernel<S.value, K.value, true>, c.L, cx, cy); });
-            });
-        else if (v.pairs)
-            pb_pick_exact_kind(P, [&](auto K) {
-                pb_pick<1, 2>(v.S == 1, [&](auto S) { launch(pb_track_nv12_kernel<S.value, K.value>, pb_nv12_of(c.L, S.value)); });
-            });
-        else if (bilinear)
-            pb_pick_kind(P, [&](auto K) {
-                pb_pick<1, 2>(v.S == 1, [&](auto S) { launch(pb_track_video_bilinear_kernel<S.value, K.value, false>, c.L, cx, cy); });
-            });
-        else
-            pb_pick_exact_kind(P, [&](auto K) {
-                pb_pick<1, 2>(v.S == 1, [&](auto S) { launch(pb_track_planar_kernel<S.value, K.value>, c.L, cx, cy); });
-            });
+        });
     }
     PB_HIP(hipGetLastError());
     return PB_OK;

@@ -1,4 +1,4 @@
-"""pb_remap_nv12: NV12 and P010 video frames through the tile kernel pb_nv12_hot_kernel - the bytes of the definition
+"""pb_remap_nv12: NV12 and P010 video frames through the tile kernel pb_video_hot_kernel (its PAIRS form) - the bytes of the definition
 (tests/nv12_ref.py) with the reference's index map, for both sample sizes, every tile class, edge, layout and launch shape.  Every
 comparison is exact equality; images are independent random bytes per plane (a wrong index shows), destinations sit between sentinel
 bytes that must survive, and so must the padding bytes inside pitched frames."""

@@ -1,5 +1,5 @@
 """pb_remap_planar: planar video frames - three planes at 4:4:4, 4:2:2 or 4:2:0, uint8 or uint16 samples - through the tile
-kernel pb_planar_hot_kernel: the bytes of the definition (tests/planar_ref.py) with the reference's index map, for both sample sizes and
+kernel pb_video_hot_kernel: the bytes of the definition (tests/planar_ref.py) with the reference's index map, for both sample sizes and
 the three subsamplings, every tile class, edge, layout and launch shape.  Every comparison is exact equality; frames are independent
 random bytes per plane (a wrong index or a wrong plane shows), destinations sit between sentinel bytes that must survive, and so must the
 padding bytes inside pitched frames."""
