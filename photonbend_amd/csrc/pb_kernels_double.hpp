@@ -543,7 +543,10 @@ __global__ __launch_bounds__(64 * PB_TILE_WAVES) void pb_double_pair_kernel(cons
         // kernel used to evaluate both eyes' whole source stage per pixel for the sake of two numbers)
         const double t_fl = pb_merge_factor(P, c.lat), t_fr = pb_merge_factor(P, (c.lat * -1.0) + PB_PI);
         unit = unit && t_fl == 1.0 && t_fr == 1.0;
-        if (row_ok) row_ok = rows[i].f_l == t_fl && rows[i].f_r == t_fr && !c.inv;
+        // (a NaN factor - fov 180 and a row ON the equator: 0 / 0 - is the row table's NaN, as in pb_sep_check_kernel: with == the tile
+        // became LAT, which the WMODE 1 launch of an unrotated plan blends as UNIT)
+        if (row_ok) row_ok = (rows[i].f_l == t_fl || (rows[i].f_l != rows[i].f_l && t_fl != t_fl)) &&
+                             (rows[i].f_r == t_fr || (rows[i].f_r != rows[i].f_r && t_fr != t_fr)) && !c.inv;
     }
     const bool all_unit = __builtin_amdgcn_ballot_w64(!unit) == 0;
     const bool all_row = rows != nullptr && __builtin_amdgcn_ballot_w64(!row_ok) == 0;

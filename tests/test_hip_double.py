@@ -1,7 +1,12 @@
 """Double-fisheye sources on the GPU (DoubleCameraImage.process_coordinate_map, projection.py:408-462):
 the per-eye tile plans + weight classes must reproduce the faithful float64 kernel byte for byte -
 unrotated (row-table weights), rotated (merge-band tiles fall back to the faithful chain), from fisheye and
-double-fisheye destinations, in batches, with strides, and with frames the LDS-DMA path cannot take."""
+double-fisheye destinations, in batches, with strides, and with frames the LDS-DMA path cannot take.
+
+These tests compare the fast kernels with the project's own float64 kernel, which shares pb_blend_u8, pb_merge_factor and the eye
+geometry with them, on frames that are black outside the circles.  The comparison with the CPU ORACLE's bytes - random unmasked frames,
+a constant frame that shows the blend factors' last bit, guarded destinations, edge shapes, every kernel path - lives in
+tests/test_hip_double_tiles.py (its inputs: tests/double_cases.py, shown sound on the CPU by tests/test_double_cases_host.py)."""
 
 import pytest
 import torch

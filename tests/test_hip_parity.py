@@ -47,9 +47,9 @@ def test_index_map_matches_golden(case):
         nb += assert_equal_outside_fragile(idx[1], SMALL[f"{n}/idx_r"], fragile, "right index")
         for k, key in enumerate(("w_l", "w_r")):
             want = SMALL[f"{n}/{key}"].view(np.float64)
-            with np.errstate(all="ignore"):
-                ok = (w[k] == want) | (np.isnan(w[k]) & np.isnan(want)) | (np.abs(w[k] - want) <= 1e-12 * np.abs(want))
-            assert ok.all(), f"blend weight {key} differs"
+            # the oracle's BITS (NaN with NaN counts as equal): tests/test_hip_double_tiles.py shows what a last bit moves
+            ok = (H.bits(w[k]) == H.bits(want)) | (np.isnan(w[k]) & np.isnan(want))
+            assert ok.all(), f"blend weight {key}: {int((~ok).sum())} factors are not the reference's bits"
     else:
         idx = plan.index_map().cpu().numpy()
         nb = assert_equal_outside_fragile(idx, SMALL[f"{n}/idx"], fragile, "index")
