@@ -465,6 +465,30 @@ int pb_remap_catmull_rom_u8(const pb_plan* plan, const uint8_t* src_dev, uint8_t
 int pb_remap_track_u8(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, int interpolation, const uint8_t* src_dev, uint8_t* dst_dev,
                       int n_frames, size_t src_frame_stride, size_t dst_frame_stride, void* stream);
 
+/* ROTATION TRACKS OF GREY, RGBA AND 16-BIT FRAMES (ABI 5, additive): pb_remap_track_u8 for frames of `channels` samples of
+ * `sample_bytes` bytes a pixel, channels in {1, 2, 3, 4}, sample_bytes in {1, 2} - a pixel of B = channels * sample_bytes bytes, B in
+ * {1, 2, 3, 4, 6, 8} like pb_remap_px's.  Frame f receives exactly the bytes the materialised-map calls write for that frame alone:
+ * pb_coordmap_f64, pb_rotate_f64 by this plan's own n_rot rotations and then by the n_rot_per_frame matrices of table entry f (one after
+ * another, nothing folded), then by `interpolation`
+ *   PB_INTERP_NEAREST       pb_index_from_map_i32 + pb_gather_px - for a single source the reference's own image[positions], whatever the
+ *                           pixel holds; a double fisheye: pb_gather_blend_u8, the reference's blend per byte;
+ *   PB_INTERP_BILINEAR      pb_sample_map_bilinear_px;
+ *   PB_INTERP_CATMULL_ROM   pb_sample_map_catmull_rom_px - the float64 definitions per channel, rounded half to even and clamped to the
+ *                           sample type's range; a double fisheye samples each eye on its half and blends to uint8.
+ * All single source kinds and all destination kinds; a double-fisheye source with sample_bytes == 1.  channels == 3 with sample_bytes == 1
+ * is exactly pb_remap_track_u8 (same kernels, same bytes).  Like every track call it reads nothing of the plan but its parameters: deferred,
+ * prepared, any mode are served alike.  pb_remap_track_u8's contract with the pixel size: pb_remap_px's frame checks and messages first
+ * (frame pointers and strides multiples of min(4, B & -B) bytes), then pb_remap_track_u8's table checks, then the interpolation's;
+ * then PB_ERR_INVALID for channels or sample_bytes outside their sets; then PB_ERR_UNSUPPORTED, nothing written, for a double-fisheye
+ * source with sample_bytes == 2 (the reference narrows that blend to uint8 modulo 256: use pb_sample_map_*_px / pb_gather_blend_u8 per
+ * frame).  n_frames == 0: PB_OK, no launch.  Asynchronous on `stream`; never allocates, never synchronises, never copies the table
+ * (graph-capture safe).  Byte offsets inside a frame are 64-bit: no frame size is refused.
+ * pb_remap_track_px_supported: 1 when pb_remap_track_px takes `plan` with this format, 0 when it would return PB_ERR_UNSUPPORTED, negative
+ * on bad arguments. */
+int pb_remap_track_px(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, int interpolation, const void* src_dev, void* dst_dev,
+                      int n_frames, size_t src_frame_stride, size_t dst_frame_stride, int channels, int sample_bytes, void* stream);
+int pb_remap_track_px_supported(const pb_plan* plan, int channels, int sample_bytes);
+
 /* ROTATION TRACKS FOR 4:2:0 SEMI-PLANAR VIDEO FRAMES (ABI 5, additive): NV12 / P010 / P016 frames, every frame with rotations
  * of its own, both planes of all frames in as many launches as pb_remap_track_u8 makes.  Frame f receives exactly pb_remap_nv12's
  * definition above with idx the index map of the chain "this plan's own n_rot rotations followed by the n_rot_per_frame matrices of table

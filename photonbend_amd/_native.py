@@ -132,6 +132,8 @@ SIGNATURES = {
     "pb_remap_bilinear_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_catmull_rom_u8": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_track_u8": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
+    "pb_remap_track_px": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _VP]),
+    "pb_remap_track_px_supported": (C.c_int, [_VP, C.c_int, C.c_int]),
     "pb_remap_track_nv12": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP]),
     "pb_remap_track_planar": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, _VP]),
     "pb_remap_track_nv12_bilinear": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP]),
@@ -955,6 +957,76 @@ class Plan:
             st = current_stream() if stream is None else stream
             tab, release = self._track_table(tab, s, st)
             self.launch_track(tab.data_ptr(), k, s.data_ptr(), o.data_ptr(), n, st, interpolation)
+            release()
+        return o
+
+    def launch_track_px(self, table_ptr: int, n_rot_per_frame: int, src_ptr: int, dst_ptr: int, n_frames: int, channels: int, sample_bytes: int,
+                        stream: int | None = None, interpolation: str = "nearest", src_stride: int = 0, dst_stride: int = 0) -> None:
+        """The raw rotation-track call for frames of ``channels`` samples of ``sample_bytes`` bytes a pixel (pb_remap_track_px):
+        ``launch_track``'s table and frames, a pixel of channels * sample_bytes bytes.  The table must stay alive and unchanged until the
+        stream has run the launch."""
+        if interpolation not in TRACK_INTERP_IDS:
+            raise ValueError(f"interpolation must be one of {', '.join(map(repr, TRACK_INTERP_IDS))}, got {interpolation!r}")
+        self._gated(load().pb_remap_track_px, self._h, table_ptr, int(n_rot_per_frame), TRACK_INTERP_IDS[interpolation], src_ptr, dst_ptr, int(n_frames),
+                    int(src_stride), int(dst_stride), int(channels), int(sample_bytes), current_stream() if stream is None else stream)
+
+    def track_px_supported(self, channels: int, sample_bytes: int) -> bool:
+        """Whether ``remap_track_px`` / ``launch_track_px`` takes this plan with this format (pb_remap_track_px_supported): every plan but a
+        double-fisheye source's with 16-bit samples.  channels outside 1..4 or sample_bytes outside (1, 2) is a PbError.  Needs no GPU."""
+        r = load().pb_remap_track_px_supported(self._h, int(channels), int(sample_bytes))
+        if r < 0:
+            check(r)
+        return r == 1
+
+    def remap_track_px(self, src, rotations, out=None, interpolation: str = "nearest", stream: int | None = None):
+        """``remap_track`` for grey, RGBA and 16-bit frames in ONE launch (pb_remap_track_px): src is a device array (N, h, w)
+        or (N, h, w, C) -> (N, H, W[, C]) of the same dtype and kind; frame f is what the materialised-map route gives for this plan's
+        rotations followed by ``rotations[f]``.  An interpolating mode or a double-fisheye source looks inside the pixel: uint8 or uint16
+        samples, 1 to 4 channels (uint8 for a double fisheye).  Nearest on a single source never does: any dtype whose pixel is 1, 2, 3, 4,
+        6 or 8 bytes.  ``rotations``, ``out`` and ``stream`` follow ``remap_track``'s rules; shapes, dtypes, table and counts are checked
+        before any device work."""
+        if interpolation not in TRACK_INTERP_IDS:
+            raise ValueError(f"interpolation must be one of {', '.join(map(repr, TRACK_INTERP_IDS))}, got {interpolation!r}")
+        if not is_device_array(src):
+            raise PbError(f"source frames must be device arrays (CUDA tensors or DeviceArrays), got {type(src).__name__}")
+        tens = is_tensor(src)
+        shp = tuple(int(v) for v in src.shape)
+        dt = torch_dtype_np(src.dtype) if tens else np.dtype(src.dtype)
+        sh = (self.src.height, self.src.width)
+        if len(shp) not in (3, 4) or shp[1:3] != sh:
+            raise PbError(f"source frames must be (N, {sh[0]}, {sh[1]}) or (N, {sh[0]}, {sh[1]}, C), got {shp} {dt}")
+        tail = shp[3:]
+        double = self.src.kind == KIND_DOUBLE
+        if interpolation != "nearest" or double:
+            fmt = (tail[0] if tail else 1, dt.itemsize)  # the sampler looks inside the pixel: (channels, sample bytes)
+            if dt not in ((np.dtype(np.uint8),) if double else (np.dtype(np.uint8), np.dtype(np.uint16))) or not 1 <= fmt[0] <= 4:
+                what = "a double-fisheye source takes uint8 frames" if double else f"{interpolation} sampling takes uint8 or uint16 frames"
+                raise PbError(f"{what} of 1 to 4 channels, got {shp} {dt}")
+        else:
+            bpp = tail_bytes(tail, dt)  # the sampler never looks inside a pixel: B bytes as (B, 1), or (B / 2, 2) above four
+            if bpp not in PX_SIZES:
+                raise PbError(f"source frames must have pixels of {PX_SIZES} bytes, got {shp} {dt}")
+            fmt = (bpp, 1) if bpp <= 4 else (bpp // 2, 2)
+        n = shp[0]
+        tab, n_tab, k = rotation_table(rotations, self.n_rot)
+        if n_tab != n:
+            raise ValueError(f"{n} frames need {n} rotations, the table holds {n_tab}")
+        oshape = (n, self.dst.height, self.dst.width) + tail
+        if out is not None:
+            odt = (torch_dtype_np(out.dtype) if is_tensor(out) else np.dtype(out.dtype)) if is_device_array(out) else None
+            if odt != dt or tuple(out.shape) != oshape or is_tensor(out) != tens or (tens and not out.is_contiguous()):
+                raise PbError(f"out must be a contiguous device array {oshape} {dt} of the source's kind")
+            if tens and out.device != src.device:
+                raise PbError(f"out must live on the source's device ({src.device}), got {out.device}")
+        require_gpu()
+        s = src.contiguous() if tens else src
+        o = empty(oshape, dt, like=s) if out is None else out
+        if n == 0:
+            return o
+        with _on(s):
+            st = current_stream() if stream is None else stream
+            tab, release = self._track_table(tab, s, st)
+            self.launch_track_px(tab.data_ptr(), k, s.data_ptr(), o.data_ptr(), n, fmt[0], fmt[1], st, interpolation)
             release()
         return o
 

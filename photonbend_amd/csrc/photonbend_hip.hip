@@ -47,6 +47,7 @@
 #include "pb_kernels_track_video_bilinear.hpp"
 #include "pb_kernels_stitch_video.hpp"
 #include "pb_kernels_track_stitch.hpp"
+#include "pb_kernels_track_px.hpp"
 
 #define PB_DOUBLE_FRAMES_PER_WAVE 1  // frames a double-source wave loops over (the rest of a batch is a grid dimension)
 
@@ -692,6 +693,16 @@ template <int KIND, class FILTER>
 static constexpr auto pb_track_interp_kernel_of() {
     if constexpr (KIND == PB_KIND_EAC) return &pb_track_interp_eac_kernel<FILTER>;
     else return &pb_track_interp_kernel<KIND, FILTER>;
+}
+template <int KIND>
+static constexpr auto pb_track_px_kernel_of() {
+    if constexpr (KIND == PB_KIND_EAC) return &pb_track_px_equiangular_kernel;
+    else return &pb_track_px_kernel<KIND>;
+}
+template <int KIND, class FILTER, typename SAMPLE>
+static constexpr auto pb_track_px_interp_kernel_of() {
+    if constexpr (KIND == PB_KIND_EAC) return &pb_track_px_interp_equiangular_kernel<FILTER, SAMPLE>;
+    else return &pb_track_px_interp_kernel<KIND, FILTER, SAMPLE>;
 }
 template <class F>
 static void pb_pick_filter(int filter, F&& f) {  // (the FILTER of the shared sampler kernels, pb_kernels_bilinear.hpp)
@@ -2442,6 +2453,65 @@ int pb_remap_track_u8(const pb_plan* plan, const double* rot3x3_dev, int n_rot_p
     }
     PB_HIP(hipGetLastError());
     return PB_OK;
+}
+
+// A rotation track of frames whose pixel is not three bytes: pb_remap_track_u8's checks with the pixel size, its launches
+// with pb_track_px_kernel / pb_track_px_interp_kernel.  channels 3 of one byte is pb_remap_track_u8 itself.
+static bool pb_track_px_format_ok(int channels, int sample_bytes) { return channels >= 1 && channels <= 4 && (sample_bytes == 1 || sample_bytes == 2); }
+static const char* const pb_track_px_format_msg = "channels must be 1, 2, 3 or 4 and sample_bytes 1 or 2";
+static const char* const pb_track_px_double_msg =
+    "pb_remap_track_px takes a double-fisheye source with 8-bit samples only (the reference narrows the blend of 16-bit samples to uint8): use "
+    "pb_sample_map_bilinear_px / pb_sample_map_catmull_rom_px or pb_index_from_map_i32 + pb_gather_blend_u8 per frame";
+int pb_remap_track_px(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, int interpolation, const void* src_dev, void* dst_dev, int n_frames,
+                      size_t src_frame_stride, size_t dst_frame_stride, int channels, int sample_bytes, void* stream) {
+    const bool fmt = pb_track_px_format_ok(channels, sample_bytes);
+    const int B = fmt ? channels * sample_bytes : 1;  // (a format outside the sets is refused below, in its place: the weakest alignment until then)
+    if (B == 3) return pb_remap_track_u8(plan, rot3x3_dev, n_rot_per_frame, interpolation, static_cast<const uint8_t*>(src_dev), static_cast<uint8_t*>(dst_dev),
+                                         n_frames, src_frame_stride, dst_frame_stride, stream);
+    const int rc = pb_check_frames(plan, src_dev, dst_dev, n_frames, 1, src_frame_stride, dst_frame_stride, false, B);
+    if (rc != PB_OK) return rc;
+    if (int rt = pb_track_table_check(plan, rot3x3_dev, n_rot_per_frame)) return rt;
+    const PbParams& P = plan->P;
+    if (interpolation != PB_INTERP_NEAREST && interpolation != PB_INTERP_BILINEAR && interpolation != PB_INTERP_CATMULL_ROM)
+        return pb_fail(PB_ERR_INVALID, "interpolation must be PB_INTERP_NEAREST, PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM");
+    if (!fmt) return pb_fail(PB_ERR_INVALID, pb_track_px_format_msg);
+    if (P.src.kind == PB_KIND_DOUBLE && sample_bytes != 1) return pb_fail(PB_ERR_UNSUPPORTED, pb_track_px_double_msg);
+    if (n_frames == 0) return PB_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned long long npx = (unsigned long long)P.dst.height * P.dst.width;
+    const int fpc = pb_track_fpc();
+    const int per_launch = 65535 * fpc;  // frames are chunked over the grid's y, which ends at 65535
+    for (int f0 = 0; f0 < n_frames; f0 += per_launch) {
+        const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
+        const double* rot = rot3x3_dev + 9ull * (unsigned)n_rot_per_frame * (unsigned)f0;
+        const uint8_t* s = static_cast<const uint8_t*>(src_dev) + (unsigned long long)f0 * src_frame_stride;
+        uint8_t* d = static_cast<uint8_t*>(dst_dev) + (unsigned long long)f0 * dst_frame_stride;
+        const unsigned chunks = (unsigned)((nf + fpc - 1) / fpc);
+        if (interpolation == PB_INTERP_NEAREST) {
+            pb_pick_any_kind(P, [&](auto K) {
+                hipLaunchKernelGGL(pb_track_px_kernel_of<K.value>(), dim3(pb_blocks((npx + PB_PX - 1) / PB_PX), chunks), dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc,
+                                   s, d, nf, (unsigned long long)src_frame_stride, (unsigned long long)dst_frame_stride, B);
+            });
+        } else {
+            const auto launch = [&](auto K, auto* sample) {  // (the sample type: uint8_t or uint16_t)
+                using SAMPLE = std::remove_pointer_t<decltype(sample)>;
+                pb_pick_filter(interpolation, [&](auto F) {
+                    hipLaunchKernelGGL((pb_track_px_interp_kernel_of<K.value, decltype(F), SAMPLE>()), dim3(pb_blocks(npx), chunks), dim3(PB_BLOCK), 0, st, P, rot,
+                                       n_rot_per_frame, fpc, s, d, nf, (unsigned long long)src_frame_stride, (unsigned long long)dst_frame_stride, channels);
+                });
+            };
+            if (P.src.kind == PB_KIND_DOUBLE) launch(PbInt<PB_KIND_DOUBLE>(), (uint8_t*)nullptr);
+            else if (sample_bytes == 1) pb_pick_exact_kind(P, [&](auto K) { launch(K, (uint8_t*)nullptr); });
+            else pb_pick_exact_kind(P, [&](auto K) { launch(K, (uint16_t*)nullptr); });
+        }
+    }
+    PB_HIP(hipGetLastError());
+    return PB_OK;
+}
+int pb_remap_track_px_supported(const pb_plan* plan, int channels, int sample_bytes) {
+    if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
+    if (!pb_track_px_format_ok(channels, sample_bytes)) return pb_fail(PB_ERR_INVALID, pb_track_px_format_msg);
+    return (plan->P.src.kind == PB_KIND_DOUBLE && sample_bytes != 1) ? 0 : 1;
 }
 
 // A rotation track of video frames (bilinear: 3.19): the plain video calls' argument checks, then pb_remap_track_u8's
