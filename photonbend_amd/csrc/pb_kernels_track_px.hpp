@@ -6,8 +6,8 @@
 //   nearest       pb_index_from_map_i32 + pb_gather_px (a double fisheye: pb_gather_blend_u8) - the sampler never looks inside a pixel;
 //   interpolating pb_sample_map_bilinear_px / pb_sample_map_catmull_rom_px - FILTER::sample64<SAMPLE, WRAP> per channel.
 //
-// pb_track_px_kernel<SRC_KIND>: pb_track_body's structure.  The pixel size is a RUN-TIME kernel argument, uniform across the launch: the
-// body is the float64 chain (some 19 000 instructions per source kind), which is what the kernel costs; a copy per pixel size would
+// pb_track_px_kernel<SRC_KIND>: pb_track_body's frame loop, on the skeleton of pb_kernels_track.hpp.  The pixel size is a RUN-TIME
+// kernel argument, uniform across the launch: the body is the float64 chain (some 19 000 instructions per source kind), which is what the kernel costs; a copy per pixel size would
 // multiply that by five and buy nothing.  A pixel is loaded with exactly its own bytes (pb_px_load of pb_kernels_px.hpp: u8, u16, dword,
 // dword + u16, 2 x dword; frames aligned to A = min(4, B & -B)) and held in two dwords, so no load touches a byte outside the frame; four
 // pixels leave as dwords where their first byte is 4-byte aligned, else in units of A, every store clipped to the image.  Byte offsets
@@ -100,7 +100,7 @@ __device__ __forceinline__ void pb_track_px_store4_lo(uint8_t* __restrict__ d, u
     else pb_track_px_store4_lo<4>(d, p0, v, count);
 }
 
-// grid: (quads of the image / PB_BLOCK, chunks of fpc frames) - pb_track_body's
+// grid: (quads of the image / PB_BLOCK, chunks of fpc frames) - pb_track_body's; what is carried per pixel differs from it (above)
 template <int SRC_KIND>
 __device__ __forceinline__ void pb_track_px_body(const PbParams& P, const double* __restrict__ rot, int k_rot, int fpc, const uint8_t* __restrict__ src,
                                                  uint8_t* __restrict__ dst, int n_frames, unsigned long long src_stride, unsigned long long dst_stride, int B) {
@@ -129,9 +129,8 @@ __device__ __forceinline__ void pb_track_px_body(const PbParams& P, const double
             }
         }
     }
-    const int f0 = (int)blockIdx.y * fpc;
-    const int f1 = (n_frames - f0 < fpc) ? n_frames : f0 + fpc;
-    for (int f = f0; f < f1; ++f) {
+    const PbTrackChunk ch = pb_track_chunk(fpc, n_frames);
+    for (int f = ch.f0; f < ch.f1; ++f) {
         const uint8_t* s = src + (unsigned long long)f * src_stride;
         uint8_t* d = dst + (unsigned long long)f * dst_stride;
         int a[PB_PX];  // a single source: the pixel's source index; a double fisheye: its blended bytes
@@ -139,12 +138,7 @@ __device__ __forceinline__ void pb_track_px_body(const PbParams& P, const double
         for (int k = 0; k < PB_PX; ++k) {
             a[k] = SRC_KIND == PB_KIND_DOUBLE ? 0 : -1;
             if (k < count) {
-                PbCoord c;
-                c.lat = lat[k];
-                c.lon = lon[k];
-                c.inv = inv[k];
-                c.face = 0;
-                c = pb_track_rotate(rot, k_rot, f, c);
+                const PbCoord c = pb_track_quad_coord(lat, lon, inv, k, rot, k_rot, f);
                 if constexpr (SRC_KIND == PB_KIND_DOUBLE) a[k] = (int)pb_track_px_blend(P, c, s, B);
                 else a[k] = pb_track_px_index<SRC_KIND>(P, c);
             }
@@ -224,9 +218,8 @@ __device__ __forceinline__ void pb_track_px_interp_body(const PbParams& P, const
     if (!pb_pick_pixel(P, true, nullptr, 0, nullptr, 0, nullptr, 0, k)) return;
     const PbCoord base = pb_chain<PB_ROT_ANY>(P, k.i, k.j);
     const unsigned long long off = (unsigned long long)k.p * (unsigned)channels * sizeof(SAMPLE);
-    const int f0 = (int)blockIdx.y * fpc;
-    const int f1 = (n_frames - f0 < fpc) ? n_frames : f0 + fpc;
-    for (int f = f0; f < f1; ++f) {
+    const PbTrackChunk ch = pb_track_chunk(fpc, n_frames);
+    for (int f = ch.f0; f < ch.f1; ++f) {
         const SAMPLE* img = reinterpret_cast<const SAMPLE*>(src + (unsigned long long)f * src_stride);
         SAMPLE* o = reinterpret_cast<SAMPLE*>(dst + (unsigned long long)f * dst_stride + off);
         pb_track_px_sample<SRC_KIND, FILTER, SAMPLE>(P, pb_track_rotate(rot, k_rot, f, base), img, o, channels);

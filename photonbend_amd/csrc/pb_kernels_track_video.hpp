@@ -4,9 +4,9 @@
 // frame f's" (pb_kernels_track.hpp).  No arithmetic is new: the chain is pb_track_body's, the loads, fills and stores are
 // pb_video_hot_kernel's.  The plan's tables are never read.
 //
-// pb_track_video_kernel<S, SRC_KIND, PAIRS> has pb_track_body's structure: pb_chain<PB_ROT_ANY> once per pixel, two float64 and a flag per
-// pixel live across the frame loop, frames chunked over blockIdx.y (`fpc` per chunk), the frame's matrices through pb_track_rotate (a
-// uniform address: scalar loads).  What differs:
+// pb_track_video_kernel<S, SRC_KIND, PAIRS> is built on the skeleton of pb_kernels_track.hpp (what is live across the frame loop, the
+// chunks, the matrices as scalar operands, the row and column asked anew per frame, the packed samples, the stores).  What differs from
+// pb_track_body:
 //   quads         rows are pitched, so a work-item owns PB_PX = 4 consecutive pixels of ONE row; quads are counted per row (a row's last
 //                 quad holds 1 to 4 pixels: 4:4:4 takes odd widths).
 //   subsampling   a RUN-TIME, wave-uniform argument (cx, cy - the shifts of the chroma planes), not a template parameter: the kernel is
@@ -19,9 +19,8 @@
 //                 along a row, so whether the row holds anchors is uniform across every wave that does not straddle a row's end.
 //   index         the chain's index r * w + c comes apart through pb_nv12_divmod - exact for the sources this call takes (below 32768 px a
 //                 side: a row number far below 2^22).
-//   stores        pb_nv12_store_y for four samples of a row, pb_planar_store2 for two, pb_nv12_store_uv for two pairs: one store where
-//                 the address allows, else one by one, clipped to the row.  Loads take exactly S or 2 * S bytes, branch-free, the fill
-//                 applied after the load.  Padding between rows, planes and frames is neither read nor written.
+//   loads         exactly S or 2 * S bytes, branch-free, the fill applied after the load; the stores are pb_track_video_store's, with
+//                 the samples as stored (AS_STORED).  Padding between rows, planes and frames is neither read nor written.
 //
 // Limits.  Byte offsets inside a frame are 32-bit: the calls refuse frames whose span reaches 2^31 bytes before any launch.
 // grid: (quads of a frame / PB_BLOCK, chunks of fpc frames).
@@ -51,69 +50,34 @@ __global__ __launch_bounds__(PB_BLOCK, PB_TRACK_WPE(SRC_KIND)) void pb_track_vid
     const int count = (W - x0 >= PB_PX) ? PB_PX : W - x0;
     double lat[PB_PX], lon[PB_PX];
     bool inv[PB_PX];
-    PB_UNROLL(PB_FAITHFUL_UNROLL)
-    for (int k = 0; k < PB_PX; ++k) {
-        lat[k] = lon[k] = 0.0;
-        inv[k] = true;
-        if (k < count) {
-            const PbCoord c = pb_chain<PB_ROT_ANY>(P, (int)y, x0 + k);
-            lat[k] = c.lat;
-            lon[k] = c.lon;
-            inv[k] = c.inv;
-        }
-    }
+    pb_track_fill_row(P, y, x0, count, lat, lon, inv);
     const unsigned sw = (unsigned)P.src.width;
     const float inv_sw = __builtin_amdgcn_rcpf((float)sw);
-    const int f0 = (int)blockIdx.y * fpc;
-    const int f1 = (n_frames - f0 < fpc) ? n_frames : f0 + fpc;
-    for (int f = f0; f < f1; ++f) {
+    const PbTrackChunk ch = pb_track_chunk(fpc, n_frames);
+    for (int f = ch.f0; f < ch.f1; ++f) {
         const uint8_t* __restrict__ s = src + (unsigned long long)f * src_stride;
         uint8_t* __restrict__ d = dst + (unsigned long long)f * dst_stride;
-        // (the row and column are asked anew in every frame, IN PLACE, from values the compiler cannot trace: what it would otherwise
-        //  compute once from them - three planes' store offsets, the anchor tests - stays live across the float64 chains of the whole
-        //  frame loop and puts the panorama and camera instantiations into scratch at their eight waves)
-        asm volatile("" : "+v"(y), "+v"(x0));
+        pb_track_reask(y, x0);
         const unsigned yy = y;
         const int xx = x0;
         const bool anchor_row = !(yy & (unsigned)cy);  // (cy is 0 or 1)
-        // (a pixel's three samples are 16 bits each at the most: packed two to a register while the other pixels' chains run; a pair
-        //  belongs to an even pixel and takes the register whole)
-        unsigned pa[PB_PX / 2] = {0u, 0u}, p1[PB_PX / 2] = {0u, 0u}, p2[PB_PX / 2] = {0u, 0u};
+        unsigned pa[PB_PX / 2] = {0u, 0u}, p1[PB_PX / 2] = {0u, 0u}, p2[PB_PX / 2] = {0u, 0u};  // (pb_track_pack)
         PB_UNROLL(PB_FAITHFUL_UNROLL)
         for (int k = 0; k < PB_PX; ++k) {
             if (k < count) {
-                PbCoord c;
-                c.lat = lat[k];
-                c.lon = lon[k];
-                c.inv = inv[k];
-                c.face = 0;
-                const int id = pb_exact_index_of<SRC_KIND>(P, pb_track_rotate(rot, k_rot, f, c));
+                const int id = pb_exact_index_of<SRC_KIND>(P, pb_track_quad_coord(lat, lon, inv, k, rot, k_rot, f));
                 unsigned r, col;
                 pb_nv12_divmod((unsigned)(id < 0 ? 0 : id), sw, inv_sw, r, col);
                 const unsigned v0 = pb_nv12_load_y<S>(s, id < 0 ? 0u : r * L.src_pitch + col * (unsigned)S);
-                pa[k >> 1] |= (id < 0 ? L.fill[0] : v0) << (16 * (k & 1));
+                pb_track_pack(pa, k, id < 0 ? L.fill[0] : v0);
                 if (anchor_row && !(k & cx)) {  // (an anchor; cx is 0 or 1)
                     unsigned v1, v2 = 0u;
                     pb_video_load_stored<S, PAIRS>(s, L, id < 0 ? 0u : (r >> cy) * src_cpitch + (col >> cx) * (unsigned)(PAIRS ? 2 * S : S), v1, v2);
-                    p1[k >> 1] |= (id < 0 ? fill1 : v1) << (16 * (k & 1));
-                    if constexpr (!PAIRS) p2[k >> 1] |= (id < 0 ? L.fill[2] : v2) << (16 * (k & 1));
+                    pb_track_pack(p1, k, id < 0 ? fill1 : v1);
+                    if constexpr (!PAIRS) pb_track_pack(p2, k, id < 0 ? L.fill[2] : v2);
                 }
             }
         }
-        const unsigned a[PB_PX] = {pa[0] & 0xFFFFu, pa[0] >> 16, pa[1] & 0xFFFFu, pa[1] >> 16};
-        pb_nv12_store_y<S, false>(d, L.dst_pitch, W, H, xx, (int)yy, a);
-        if (anchor_row) {
-            if constexpr (PAIRS) {
-                pb_nv12_store_uv<S, false>(d + L.dst_o1, dst_cpitch, W, H, xx, (int)yy, p1);
-            } else if (cx == 0) {
-                const unsigned c1[PB_PX] = {p1[0] & 0xFFFFu, p1[0] >> 16, p1[1] & 0xFFFFu, p1[1] >> 16};
-                const unsigned c2[PB_PX] = {p2[0] & 0xFFFFu, p2[0] >> 16, p2[1] & 0xFFFFu, p2[1] >> 16};
-                pb_nv12_store_y<S, false>(d + L.dst_o1, dst_cpitch, W, H, xx, (int)yy, c1);
-                pb_nv12_store_y<S, false>(d + L.dst_o2, dst_cpitch, W, H, xx, (int)yy, c2);
-            } else {  // (the anchors are the pixels k = 0, 2: the low halves)
-                pb_planar_store2<S, false>(d + L.dst_o1, dst_cpitch, W >> 1, H >> cy, xx >> 1, (int)(yy >> cy), p1);
-                pb_planar_store2<S, false>(d + L.dst_o2, dst_cpitch, W >> 1, H >> cy, xx >> 1, (int)(yy >> cy), p2);
-            }
-        }
+        pb_track_video_store<S, PAIRS, true>(d, L, W, H, xx, yy, cx, cy, anchor_row, dst_cpitch, pa, p1, p2);
     }
 }

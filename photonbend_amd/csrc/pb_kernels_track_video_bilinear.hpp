@@ -14,9 +14,8 @@
 // definition's order under the build's -ffp-contract=off: the result is the definition's bytes exactly, for 8-, 10- and 16-bit samples
 // alike (the uint8 routes' float32 taps are not exact for 16-bit samples and are not used).  The plan's tables are never read.
 //
-// pb_track_video_bilinear_kernel<S, SRC_KIND, PAIRS> has pb_track_video_kernel's structure: pb_chain<PB_ROT_ANY> once per pixel, two
-// float64 and a flag per pixel live across the frame loop, frames chunked over blockIdx.y, the frame's matrices through pb_track_rotate
-// (scalar loads), a work-item owns PB_PX = 4 consecutive pixels of ONE row.
+// pb_track_video_bilinear_kernel<S, SRC_KIND, PAIRS> has pb_track_video_kernel's structure - the skeleton of pb_kernels_track.hpp, a
+// work-item owns PB_PX = 4 consecutive pixels of ONE row.
 //   coordinate    a panorama's through pb_src_pretrunc; a camera's through pb_src_pretrunc_sc with the sine and cosine of pb_expi_np -
 //                 np.exp(lon * 1j), the definition's own (pb_sample_map_interp_px computes it so): pb_src_pretrunc's plain sincos is the
 //                 model builders' and differs from it in the last bit.
@@ -29,8 +28,7 @@
 //                 samples at s = (0, 0) and takes the fill after the loads.
 //   chroma        a quad starts at a multiple of four, so on a row with (y & cy) == 0 its pixels k with (k & cx) == 0 are anchors, and the
 //                 work-item already holds their coordinate: chroma costs no second chain.
-//   stores        pb_nv12_store_y, pb_planar_store2 and pb_nv12_store_uv, clipped to their planes.  Padding between rows, planes and
-//                 frames is neither read nor written.
+//   stores        pb_track_video_store's, U in p1 and V in p2.  Padding between rows, planes and frames is neither read nor written.
 //
 // Limits: the nearest track kernels' (32-bit byte offsets inside a frame, sources below 32768 px a side).
 // grid: (quads of a frame / PB_BLOCK, chunks of fpc frames).
@@ -86,39 +84,21 @@ __global__ __launch_bounds__(PB_BLOCK, PB_TVB_WPE(SRC_KIND)) void pb_track_video
     const int count = (W - x0 >= PB_PX) ? PB_PX : W - x0;
     double lat[PB_PX], lon[PB_PX];
     bool inv[PB_PX];
-    PB_UNROLL(PB_FAITHFUL_UNROLL)
-    for (int k = 0; k < PB_PX; ++k) {
-        lat[k] = lon[k] = 0.0;
-        inv[k] = true;
-        if (k < count) {
-            const PbCoord c = pb_chain<PB_ROT_ANY>(P, (int)y, x0 + k);
-            lat[k] = c.lat;
-            lon[k] = c.lon;
-            inv[k] = c.inv;
-        }
-    }
+    pb_track_fill_row(P, y, x0, count, lat, lon, inv);
     const int h = P.src.height, w = P.src.width;
-    const int f0 = (int)blockIdx.y * fpc;
-    const int f1 = (n_frames - f0 < fpc) ? n_frames : f0 + fpc;
-    for (int f = f0; f < f1; ++f) {
+    const PbTrackChunk ch = pb_track_chunk(fpc, n_frames);
+    for (int f = ch.f0; f < ch.f1; ++f) {
         const uint8_t* __restrict__ s = src + (unsigned long long)f * src_stride;
         uint8_t* __restrict__ d = dst + (unsigned long long)f * dst_stride;
-        // (the row and column are asked anew in every frame, in place: pb_track_video_kernel's reason)
-        asm volatile("" : "+v"(y), "+v"(x0));
+        pb_track_reask(y, x0);
         const unsigned yy = y;
         const int xx = x0;
         const bool anchor_row = !(yy & (unsigned)cy);
-        // (a pixel's three samples are 16 bits each at the most: packed two to a register while the other pixels' chains run)
-        unsigned pa[PB_PX / 2] = {0u, 0u}, p1[PB_PX / 2] = {0u, 0u}, p2[PB_PX / 2] = {0u, 0u};
+        unsigned pa[PB_PX / 2] = {0u, 0u}, p1[PB_PX / 2] = {0u, 0u}, p2[PB_PX / 2] = {0u, 0u};  // (pb_track_pack)
         PB_UNROLL(PB_FAITHFUL_UNROLL)
         for (int k = 0; k < PB_PX; ++k) {
             if (k < count) {
-                PbCoord c;
-                c.lat = lat[k];
-                c.lon = lon[k];
-                c.inv = inv[k];
-                c.face = 0;
-                c = pb_track_rotate(rot, k_rot, f, c);
+                const PbCoord c = pb_track_quad_coord(lat, lon, inv, k, rot, k_rot, f);
                 double fy, fx;
                 if (WRAP) {
                     pb_src_pretrunc<PB_KIND_PANO>(P, c, fy, fx);
@@ -133,34 +113,18 @@ __global__ __launch_bounds__(PB_BLOCK, PB_TVB_WPE(SRC_KIND)) void pb_track_video
                 double ty, tx;
                 pb_tvb_taps<WRAP>(sy, sx, h, w, L.src_pitch, (unsigned)S, o, ty, tx);
                 const unsigned v0 = pb_tvb_mix(pb_nv12_load_y<S>(s, o[0]), pb_nv12_load_y<S>(s, o[1]), pb_nv12_load_y<S>(s, o[2]), pb_nv12_load_y<S>(s, o[3]), tx, ty);
-                pa[k >> 1] |= (live ? v0 : L.fill[0]) << (16 * (k & 1));
+                pb_track_pack(pa, k, live ? v0 : L.fill[0]);
                 if (anchor_row && !(k & cx)) {  // an anchor: its coordinate in chroma sample units, s / 2 where subsampled (exact)
                     pb_tvb_taps<WRAP>(cy ? sy * 0.5 : sy, cx ? sx * 0.5 : sx, h >> cy, w >> cx, L.src_cpitch, (unsigned)(PAIRS ? 2 * S : S), o, ty, tx);
                     unsigned u[4], v[4];
 #pragma unroll
                     for (int t = 0; t < 4; ++t) pb_video_load_c<S, PAIRS>(s, L, o[t], u[t], v[t]);
                     const unsigned v1 = pb_tvb_mix(u[0], u[1], u[2], u[3], tx, ty), v2 = pb_tvb_mix(v[0], v[1], v[2], v[3], tx, ty);
-                    p1[k >> 1] |= (live ? v1 : L.fill[1]) << (16 * (k & 1));
-                    p2[k >> 1] |= (live ? v2 : L.fill[2]) << (16 * (k & 1));
+                    pb_track_pack(p1, k, live ? v1 : L.fill[1]);
+                    pb_track_pack(p2, k, live ? v2 : L.fill[2]);
                 }
             }
         }
-        const unsigned a[PB_PX] = {pa[0] & 0xFFFFu, pa[0] >> 16, pa[1] & 0xFFFFu, pa[1] >> 16};
-        pb_nv12_store_y<S, false>(d, L.dst_pitch, W, H, xx, (int)yy, a);
-        if (anchor_row) {
-            if constexpr (PAIRS) {  // (the anchors are the pixels k = 0, 2: the low halves; a pair lies U first)
-                const unsigned uv[2] = {(p1[0] & 0xFFFFu) | ((p2[0] & 0xFFFFu) << (8 * S)), (p1[1] & 0xFFFFu) | ((p2[1] & 0xFFFFu) << (8 * S))};
-                pb_nv12_store_uv<S, false>(d + L.dst_o1, L.dst_cpitch, W, H, xx, (int)yy, uv);
-            } else if (cx == 0) {
-                const unsigned c1[PB_PX] = {p1[0] & 0xFFFFu, p1[0] >> 16, p1[1] & 0xFFFFu, p1[1] >> 16};
-                const unsigned c2[PB_PX] = {p2[0] & 0xFFFFu, p2[0] >> 16, p2[1] & 0xFFFFu, p2[1] >> 16};
-                pb_nv12_store_y<S, false>(d + L.dst_o1, L.dst_cpitch, W, H, xx, (int)yy, c1);
-                pb_nv12_store_y<S, false>(d + L.dst_o2, L.dst_cpitch, W, H, xx, (int)yy, c2);
-            } else {
-                const unsigned h1[2] = {p1[0] & 0xFFFFu, p1[1] & 0xFFFFu}, h2[2] = {p2[0] & 0xFFFFu, p2[1] & 0xFFFFu};
-                pb_planar_store2<S, false>(d + L.dst_o1, L.dst_cpitch, W >> 1, H >> cy, xx >> 1, (int)(yy >> cy), h1);
-                pb_planar_store2<S, false>(d + L.dst_o2, L.dst_cpitch, W >> 1, H >> cy, xx >> 1, (int)(yy >> cy), h2);
-            }
-        }
+        pb_track_video_store<S, PAIRS, false>(d, L, W, H, xx, yy, cx, cy, anchor_row, L.dst_cpitch, pa, p1, p2);
     }
 }

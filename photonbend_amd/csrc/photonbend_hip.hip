@@ -2414,6 +2414,27 @@ static int pb_track_table_check(const pb_plan* plan, const double* rot3x3_dev, i
 }
 // the frames of one launch of a rotation-track kernel: chunks of `fpc` frames over the grid's y, which ends at 65535
 static int pb_track_fpc() { return std::max(1, pb_knob("PB_TRACK_FRAMES", PB_TRACK_FRAMES)); }  // (the knob: the diagnostic build's, for the measurement of DESIGN 3.13)
+// The launches of every rotation-track entry point: one per 65535 chunks, launch(rot, s, d, nf, chunks, fpc) for the nf frames from
+// `s` / `d` on with their matrices from `rot` on.  Callers have checked the plan's device: pb_remap_track_u8 and pb_remap_track_px in
+// pb_check_frames (which returns before it for no frames at all, as they do before any launch), pb_track_video_call by itself.
+extern "C++" template <class LAUNCH>
+static int pb_track_launch(int n_frames, const double* rot3x3_dev, int n_rot_per_frame, const void* src, void* dst, size_t src_stride, size_t dst_stride, LAUNCH launch) {
+    const int fpc = pb_track_fpc();
+    const int per_launch = 65535 * fpc;
+    for (int f0 = 0; f0 < n_frames; f0 += per_launch) {
+        const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
+        launch(rot3x3_dev + 9ull * (unsigned)n_rot_per_frame * (unsigned)f0, static_cast<const uint8_t*>(src) + (unsigned long long)f0 * src_stride,
+               static_cast<uint8_t*>(dst) + (unsigned long long)f0 * dst_stride, nf, (unsigned)((nf + fpc - 1) / fpc), fpc);
+    }
+    PB_HIP(hipGetLastError());
+    return PB_OK;
+}
+// the sampling modes of pb_remap_track_u8 and pb_remap_track_px
+static int pb_track_interp_check(int interpolation) {
+    if (interpolation != PB_INTERP_NEAREST && interpolation != PB_INTERP_BILINEAR && interpolation != PB_INTERP_CATMULL_ROM)
+        return pb_fail(PB_ERR_INVALID, "interpolation must be PB_INTERP_NEAREST, PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM");
+    return PB_OK;
+}
 
 // A rotation track: the float64 chain of the plan's parameter block with frame f's matrices behind the plan's own.  No route:
 // no table of the plan is certified for these chains, so every plan state takes the same kernels.
@@ -2423,21 +2444,14 @@ int pb_remap_track_u8(const pb_plan* plan, const double* rot3x3_dev, int n_rot_p
     if (rc != PB_OK) return rc;
     if (int rt = pb_track_table_check(plan, rot3x3_dev, n_rot_per_frame)) return rt;
     const PbParams& P = plan->P;
-    if (interpolation != PB_INTERP_NEAREST && interpolation != PB_INTERP_BILINEAR && interpolation != PB_INTERP_CATMULL_ROM)
-        return pb_fail(PB_ERR_INVALID, "interpolation must be PB_INTERP_NEAREST, PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM");
+    if (int ri = pb_track_interp_check(interpolation)) return ri;
     if (n_frames == 0) return PB_OK;
     hipStream_t st = (hipStream_t)stream;
     const unsigned long long npx = (unsigned long long)P.dst.height * P.dst.width;
-    const int fpc = pb_track_fpc();
-    const int per_launch = 65535 * fpc;  // frames are chunked over the grid's y, which ends at 65535
-    for (int f0 = 0; f0 < n_frames; f0 += per_launch) {
-        const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
-        const double* rot = rot3x3_dev + 9ull * (unsigned)n_rot_per_frame * (unsigned)f0;
-        const uint8_t* s = src_dev + (unsigned long long)f0 * src_frame_stride;
-        uint8_t* d = dst_dev + (unsigned long long)f0 * dst_frame_stride;
-        const unsigned chunks = (unsigned)((nf + fpc - 1) / fpc);
+    // (the stride is part of the test, so what holds for the batch holds for every launch's first frame)
+    const int dst_aligned = (((uintptr_t)dst_dev | dst_frame_stride) & 3u) == 0;
+    const auto some_frames = [&](const double* rot, const uint8_t* s, uint8_t* d, int nf, unsigned chunks, int fpc) {  // (one launch: nf frames, their matrices from rot on)
         if (interpolation == PB_INTERP_NEAREST) {
-            const int dst_aligned = (((uintptr_t)dst_dev | dst_frame_stride) & 3u) == 0;
             pb_pick_any_kind(P, [&](auto K) {
                 hipLaunchKernelGGL(pb_track_kernel_of<K.value>(), dim3(pb_blocks((npx + PB_PX - 1) / PB_PX), chunks), dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d,
                                    nf, (unsigned long long)src_frame_stride, (unsigned long long)dst_frame_stride, dst_aligned);
@@ -2450,9 +2464,8 @@ int pb_remap_track_u8(const pb_plan* plan, const double* rot3x3_dev, int n_rot_p
                 });
             });
         }
-    }
-    PB_HIP(hipGetLastError());
-    return PB_OK;
+    };
+    return pb_track_launch(n_frames, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, src_frame_stride, dst_frame_stride, some_frames);
 }
 
 // A rotation track of frames whose pixel is not three bytes: pb_remap_track_u8's checks with the pixel size, its launches
@@ -2472,21 +2485,13 @@ int pb_remap_track_px(const pb_plan* plan, const double* rot3x3_dev, int n_rot_p
     if (rc != PB_OK) return rc;
     if (int rt = pb_track_table_check(plan, rot3x3_dev, n_rot_per_frame)) return rt;
     const PbParams& P = plan->P;
-    if (interpolation != PB_INTERP_NEAREST && interpolation != PB_INTERP_BILINEAR && interpolation != PB_INTERP_CATMULL_ROM)
-        return pb_fail(PB_ERR_INVALID, "interpolation must be PB_INTERP_NEAREST, PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM");
+    if (int ri = pb_track_interp_check(interpolation)) return ri;
     if (!fmt) return pb_fail(PB_ERR_INVALID, pb_track_px_format_msg);
     if (P.src.kind == PB_KIND_DOUBLE && sample_bytes != 1) return pb_fail(PB_ERR_UNSUPPORTED, pb_track_px_double_msg);
     if (n_frames == 0) return PB_OK;
     hipStream_t st = (hipStream_t)stream;
     const unsigned long long npx = (unsigned long long)P.dst.height * P.dst.width;
-    const int fpc = pb_track_fpc();
-    const int per_launch = 65535 * fpc;  // frames are chunked over the grid's y, which ends at 65535
-    for (int f0 = 0; f0 < n_frames; f0 += per_launch) {
-        const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
-        const double* rot = rot3x3_dev + 9ull * (unsigned)n_rot_per_frame * (unsigned)f0;
-        const uint8_t* s = static_cast<const uint8_t*>(src_dev) + (unsigned long long)f0 * src_frame_stride;
-        uint8_t* d = static_cast<uint8_t*>(dst_dev) + (unsigned long long)f0 * dst_frame_stride;
-        const unsigned chunks = (unsigned)((nf + fpc - 1) / fpc);
+    const auto some_frames = [&](const double* rot, const uint8_t* s, uint8_t* d, int nf, unsigned chunks, int fpc) {  // (one launch: nf frames, their matrices from rot on)
         if (interpolation == PB_INTERP_NEAREST) {
             pb_pick_any_kind(P, [&](auto K) {
                 hipLaunchKernelGGL(pb_track_px_kernel_of<K.value>(), dim3(pb_blocks((npx + PB_PX - 1) / PB_PX), chunks), dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc,
@@ -2504,9 +2509,8 @@ int pb_remap_track_px(const pb_plan* plan, const double* rot3x3_dev, int n_rot_p
             else if (sample_bytes == 1) pb_pick_exact_kind(P, [&](auto K) { launch(K, (uint8_t*)nullptr); });
             else pb_pick_exact_kind(P, [&](auto K) { launch(K, (uint16_t*)nullptr); });
         }
-    }
-    PB_HIP(hipGetLastError());
-    return PB_OK;
+    };
+    return pb_track_launch(n_frames, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, src_frame_stride, dst_frame_stride, some_frames);
 }
 int pb_remap_track_px_supported(const pb_plan* plan, int channels, int sample_bytes) {
     if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
@@ -2515,7 +2519,7 @@ int pb_remap_track_px_supported(const pb_plan* plan, int channels, int sample_by
 }
 
 // A rotation track of video frames (bilinear: 3.19): the plain video calls' argument checks, then pb_remap_track_u8's
-// table checks; the launches are pb_remap_track_u8's, one per 65535 chunks of frames.  Nearest: pb_track_video_kernel; bilinear:
+// table checks; the launches are pb_track_launch's.  Nearest: pb_track_video_kernel; bilinear:
 // pb_track_video_bilinear_kernel, a panorama or camera source (both with pairs for NV12).
 // A format with `stitch` (pb_track_stitch_nv12 / _planar) takes a double-fisheye source and no other: pb_track_stitch_kernel.
 static int pb_track_video_call(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
@@ -2541,17 +2545,10 @@ static int pb_track_video_call(const pb_plan* plan, const double* rot3x3_dev, in
                                                                "frame with pb_index_map_i32 and gather the " + v.planes() + " planes");
     hipStream_t st = (hipStream_t)stream;
     const unsigned long long quads = (unsigned long long)P.dst.height * (((unsigned)P.dst.width + PB_PX - 1) / PB_PX);
-    const int fpc = pb_track_fpc();
-    const int per_launch = 65535 * fpc;
     const int cx = v.cx(), cy = v.cy();
-    for (int f0 = 0; f0 < n_frames; f0 += per_launch) {
-        const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
-        const double* rot = rot3x3_dev + 9ull * (unsigned)n_rot_per_frame * (unsigned)f0;
-        const uint8_t* s = static_cast<const uint8_t*>(src_dev) + (unsigned long long)f0 * c.fs.stride;
-        uint8_t* d = static_cast<uint8_t*>(dst_dev) + (unsigned long long)f0 * c.fd.stride;
-        const dim3 grid(pb_blocks(quads), (unsigned)((nf + fpc - 1) / fpc));
+    const auto some_frames = [&](const double* rot, const uint8_t* s, uint8_t* d, int nf, unsigned chunks, int fpc) {  // (one launch: nf frames, their matrices from rot on)
         auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride, c.fd.stride, c.L, cx, cy);
+            hipLaunchKernelGGL(kernel, dim3(pb_blocks(quads), chunks), dim3(PB_BLOCK), 0, st, P, rot, n_rot_per_frame, fpc, s, d, nf, c.fs.stride, c.fd.stride, c.L, cx, cy);
         };
         pb_pick<1, 0>(v.pairs, [&](auto PAIRS) {
             pb_pick<1, 2>(v.S == 1, [&](auto S) {
@@ -2560,9 +2557,8 @@ static int pb_track_video_call(const pb_plan* plan, const double* rot3x3_dev, in
                 else pb_pick_exact_kind(P, [&](auto K) { launch(pb_track_video_kernel<S.value, K.value, PAIRS.value != 0>); });
             });
         });
-    }
-    PB_HIP(hipGetLastError());
-    return PB_OK;
+    };
+    return pb_track_launch(n_frames, rot3x3_dev, n_rot_per_frame, src_dev, dst_dev, c.fs.stride, c.fd.stride, some_frames);
 }
 int pb_remap_track_nv12(const pb_plan* plan, const double* rot3x3_dev, int n_rot_per_frame, const void* src_dev, void* dst_dev, int n_frames,
                         const pb_nv12_layout* src_layout, const pb_nv12_layout* dst_layout, int bytes_per_sample, const uint16_t fill_yuv[3], void* stream) {

@@ -42,6 +42,7 @@ GEOMETRIES = {
     "odd_half_width_40x82": (pano(40, 80), dbl(40, 82, "equidistant", 195), []),  # w // 2 = 41: a chroma block straddles the seam between the eyes
     "odd_destination_33x67": (pano(33, 67), dbl(24, 48, "equidistant", 180), []),  # 4:4:4 only: a row's last quad holds 3 pixels; non-finite factors
     "stereographic_36x36": (cam(36, 36, "stereographic", 140, inscribed(36)), dbl(32, 64, "equidistant", 190), [PLAN_DEGREES[0]]),  # 9 quads a row: rows straddle waves
+    "half_quad_20x30": (pano(20, 30), dbl(24, 48, "equidistant", 195), []),  # every format: a row's last quad holds 2 pixels and, subsampled, one anchor
 }
 
 
@@ -228,6 +229,7 @@ def test_the_geometries_reach_every_class_of_pixel():
     assert formats_of(*GEOMETRIES["odd_destination_33x67"][:2]) == ["444"] and GEOMETRIES["odd_destination_33x67"][0][2] % 4 == 3
     assert all(formats_of(*g[:2]) == list(FORMATS) for n, g in GEOMETRIES.items() if n != "odd_destination_33x67")
     assert (GEOMETRIES["odd_half_width_40x82"][1][2] // 2) & 1 and -(-GEOMETRIES["stereographic_36x36"][0][2] // 4) == 9
+    assert GEOMETRIES["half_quad_20x30"][0][2] % 4 == 2  # a row's last quad holds two pixels, at every subsampling
 
 
 @pytest.mark.parametrize("k", (1, 2))
