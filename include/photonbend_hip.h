@@ -489,6 +489,39 @@ int pb_remap_track_px(const pb_plan* plan, const double* rot3x3_dev, int n_rot_p
                       int n_frames, size_t src_frame_stride, size_t dst_frame_stride, int channels, int sample_bytes, void* stream);
 int pb_remap_track_px_supported(const pb_plan* plan, int channels, int sample_bytes);
 
+/* BILINEAR AND CATMULL-ROM SAMPLING OF GREY, RGBA AND 16-BIT FRAMES (ABI 5, additive): the interpolating modes of
+ * pb_remap_bilinear_u8 / pb_remap_catmull_rom_u8 for frames of `channels` samples of `sample_bytes` bytes a pixel - channels in {1, 2, 3, 4},
+ * sample_bytes in {1, 2} (uint8 / uint16, native byte order), tightly packed rows - in ONE launch of the tile kernel pb_px_interp_kernel
+ * whatever n_frames, without a coordinate map.  The definitions are those modes' own on an image of that layout (per channel; the cubic
+ * clipped to the sample type's range; zeros where the pixel is not live); the tile kernel's coordinates are certified to 1/1024 px per
+ * axis, so with R the largest sample value of the source frame every sample is within 1 + R / 512 (bilinear) or
+ * 1 + floor(15 R / 4096 + R / 2^18) (Catmull-Rom) of the definition, as for uint8 RGB with R = 255.
+ * interpolation is PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM.  channels 3 of one byte is pb_remap_bilinear_u8 / pb_remap_catmull_rom_u8
+ * itself, on every plan those take.  The checks, in this order:
+ *   pb_remap_px's frame checks and messages with bytes_per_px = channels * sample_bytes (frame pointers and strides multiples of
+ *   min(4, B & -B) bytes; the weakest alignment while the format is not known to be valid);
+ *   PB_ERR_INVALID        an interpolation other than the two (PB_INTERP_NEAREST: the message names pb_remap_px);
+ *   PB_ERR_INVALID        channels or sample_bytes outside their sets;
+ *   PB_ERR_UNSUPPORTED    nothing is written and nothing launched - the plans pb_remap_px refuses (deferred plans, PB_MODE_FAITHFUL,
+ *                         double-fisheye sources, plans without device state, sources of 32768 px a side or more, frames of 2^31 bytes or
+ *                         more); plans without the bilinear mode's tables (call pb_plan_prepare(plan, PB_PLAN_BILINEAR)); cube and
+ *                         equi-angular-cube sources (use pb_sample_map_bilinear_px / pb_sample_map_catmull_rom_px).
+ * A plan that WAS prepared with PB_PLAN_BILINEAR and whose coordinate tables cannot exist (a source of one or two pixels, of 2^18 px a
+ * side or more, a GiB of coordinates) is served per pixel from the plan's float64 chain - the definition itself, in one launch.
+ * n_frames == 0 is PB_OK and launches nothing.  Asynchronous on `stream`; never allocates or synchronises, so it can be captured into a graph.
+ * pb_remap_interp_px_supported: 1 when pb_remap_interp_px takes `plan` with this format and interpolation, 0 when it would return
+ * PB_ERR_UNSUPPORTED, negative on bad arguments. */
+int
+pb_remap_interp_px(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, size_t src_frame_stride,
+                   size_t dst_frame_stride, int channels, int sample_bytes, int interpolation, void* stream);
+int
+pb_remap_interp_px_supported(const pb_plan* plan, int channels, int sample_bytes, int interpolation);
+/* Diagnostic: what a pb_remap_interp_px call with these arguments launches on `plan` - 1 the tile kernel pb_px_interp_kernel, 2 the float64
+ * chain per pixel (a prepared plan whose coordinate tables cannot exist), 3 the uint8 RGB call it delegates to, 0 nothing
+ * (PB_ERR_UNSUPPORTED); negative on bad arguments, as pb_remap_interp_px_supported. */
+int
+pb_plan_px_interp_route(const pb_plan* plan, int channels, int sample_bytes, int interpolation);
+
 /* ROTATION TRACKS FOR 4:2:0 SEMI-PLANAR VIDEO FRAMES (ABI 5, additive): NV12 / P010 / P016 frames, every frame with rotations
  * of its own, both planes of all frames in as many launches as pb_remap_track_u8 makes.  Frame f receives exactly pb_remap_nv12's
  * definition above with idx the index map of the chain "this plan's own n_rot rotations followed by the n_rot_per_frame matrices of table

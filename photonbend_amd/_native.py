@@ -134,6 +134,9 @@ SIGNATURES = {
     "pb_remap_track_u8": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, _VP]),
     "pb_remap_track_px": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _VP]),
     "pb_remap_track_px_supported": (C.c_int, [_VP, C.c_int, C.c_int]),
+    "pb_remap_interp_px": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, _VP]),
+    "pb_remap_interp_px_supported": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int]),
+    "pb_plan_px_interp_route": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int]),
     "pb_remap_track_nv12": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP]),
     "pb_remap_track_planar": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, _VP]),
     "pb_remap_track_nv12_bilinear": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP]),
@@ -1054,10 +1057,81 @@ class Plan:
             check(r)
         return r == 1
 
-    def remap_px(self, src, out=None):
-        """The nearest remap of frames of any pixel layout (pb_remap_px): src is a device array (h, w, *tail) or (N, h, w, *tail) of any
+    def launch_px_interp(self, src_ptr: int, dst_ptr: int, n_frames: int, channels: int, sample_bytes: int, interpolation: str, stream: int | None = None,
+                         src_stride: int = 0, dst_stride: int = 0) -> None:
+        """The raw interpolating call for frames of ``channels`` samples of ``sample_bytes`` bytes a pixel (pb_remap_interp_px):
+        ``interpolation`` is "bilinear" or "catmull-rom" ("nearest" is ``launch(bytes_per_px=...)``).  The plan needs the bilinear mode's
+        tables (``Plan(..., bilinear=True)`` or ``ensure_bilinear()``); a plan ``px_interp_supported`` refuses is a PbError."""
+        check_interpolation(interpolation)
+        if interpolation == "nearest":
+            raise ValueError("launch_px_interp samples with 'bilinear' or 'catmull-rom': nearest sampling is launch(bytes_per_px=...)")
+        self._gated(load().pb_remap_interp_px, self._h, src_ptr, dst_ptr, int(n_frames), int(src_stride), int(dst_stride), int(channels), int(sample_bytes),
+                    TRACK_INTERP_IDS[interpolation], current_stream() if stream is None else stream)
+
+    def px_interp_supported(self, channels: int, sample_bytes: int, interpolation: str) -> bool:
+        """Whether ``launch_px_interp`` takes this plan with this format (pb_remap_interp_px_supported): a prepared plan of a camera or
+        panorama source in a tile mode with the bilinear mode's tables; three uint8 channels are the RGB call's, which every plan takes.
+        channels outside 1..4 or sample_bytes outside (1, 2) is a PbError.  Needs no GPU."""
+        check_interpolation(interpolation)
+        if interpolation == "nearest":
+            raise ValueError("px_interp_supported asks about 'bilinear' or 'catmull-rom': nearest sampling is px_supported")
+        r = load().pb_remap_interp_px_supported(self._h, int(channels), int(sample_bytes), TRACK_INTERP_IDS[interpolation])
+        if r < 0:
+            check(r)
+        return r == 1
+
+    def px_interp_route(self, channels: int, sample_bytes: int, interpolation: str) -> str:
+        """Diagnostic (pb_plan_px_interp_route): what ``launch_px_interp`` launches on this plan - "tiles" (pb_px_interp_kernel), "float64"
+        (the chain per pixel: a prepared plan whose coordinate tables cannot exist), "rgb8" (three uint8 channels) or "none"."""
+        check_interpolation(interpolation)
+        r = load().pb_plan_px_interp_route(self._h, int(channels), int(sample_bytes), TRACK_INTERP_IDS[interpolation])
+        if r < 0:
+            check(r)
+        return ("none", "tiles", "float64", "rgb8")[r]
+
+    def _remap_px_interp(self, src, out, interpolation: str):
+        """``remap_px`` with an interpolating mode: the sampler looks inside the pixel - uint8 or uint16 samples, up to four channels."""
+        sh, dh = (self.src.height, self.src.width), (self.dst.height, self.dst.width)
+        if not is_device_array(src):
+            raise PbError(f"source frames must be device arrays (CUDA tensors or DeviceArrays), got {type(src).__name__}")
+        tens = is_tensor(src)
+        shp = tuple(int(v) for v in src.shape)
+        dt = torch_dtype_np(src.dtype) if tens else np.dtype(src.dtype)
+        lead = 2 if shp[:2] == sh else 3  # (h, w[, C]), else (N, h, w[, C])
+        if len(shp) not in (lead, lead + 1) or shp[lead - 2:lead] != sh:
+            raise PbError(f"source frames must be ({sh[0]}, {sh[1]}), ({sh[0]}, {sh[1]}, C), (N, {sh[0]}, {sh[1]}) or (N, {sh[0]}, {sh[1]}, C), got {shp} {dt}")
+        tail = shp[lead:]
+        channels = tail[0] if tail else 1
+        if dt not in (np.dtype(np.uint8), np.dtype(np.uint16)) or not 1 <= channels <= 4:
+            raise PbError(f"{interpolation} sampling takes uint8 or uint16 frames of 1 to 4 channels, got {shp} {dt}")
+        n = shp[0] if lead == 3 else 1
+        oshape = ((n,) if lead == 3 else ()) + dh + tail
+        if out is not None:
+            odt = (torch_dtype_np(out.dtype) if is_tensor(out) else np.dtype(out.dtype)) if is_device_array(out) else None
+            if odt != dt or tuple(out.shape) != oshape or is_tensor(out) != tens or (tens and not out.is_contiguous()):
+                raise PbError(f"out must be a contiguous device array {oshape} {dt} of the source's kind")
+            if tens and (not out.is_cuda or out.device != src.device):
+                raise PbError(f"out must live on the source's device ({src.device}), got {out.device}")
+        require_gpu()
+        s = src.contiguous() if tens else src
+        o = empty(oshape, dt, like=s) if out is None else out
+        if n == 0:
+            return o
+        with _on(s):
+            self.ensure_bilinear()  # (as ``remap`` does for uint8 RGB: the tables are built when an interpolating mode is first used)
+            self.launch_px_interp(s.data_ptr(), o.data_ptr(), n, channels, dt.itemsize, interpolation)
+        return o
+
+    def remap_px(self, src, out=None, *, interpolation: str = "nearest"):
+        """The remap of frames of any pixel layout.  Nearest (pb_remap_px): src is a device array (h, w, *tail) or (N, h, w, *tail) of any
         dtype whose pixel - tail x itemsize - is 1, 2, 3, 4, 6 or 8 bytes (grey, grey16, RGB, RGBA, RGB16, RGBA16) -> (H, W, *tail) /
-        (N, H, W, *tail) of the same dtype and kind, in ONE launch.  A plan ``px_supported`` refuses is a PbError (no fallback)."""
+        (N, H, W, *tail) of the same dtype and kind, in ONE launch.  A plan ``px_supported`` refuses is a PbError (no fallback).
+        ``interpolation`` "bilinear" or "catmull-rom" (pb_remap_interp_px) looks inside the pixel: (h, w), (h, w, C),
+        (N, h, w) or (N, h, w, C) arrays of uint8 or uint16, C <= 4, the same kind back, in one launch of the interpolating tile kernel; the
+        bilinear mode's tables are built on first use, and a plan ``px_interp_supported`` then refuses is a PbError (no fallback)."""
+        if interpolation != "nearest":
+            check_interpolation(interpolation)
+            return self._remap_px_interp(src, out, interpolation)
         sh, dh = (self.src.height, self.src.width), (self.dst.height, self.dst.width)
         if not is_device_array(src):
             raise PbError(f"source frames must be device arrays (CUDA tensors or DeviceArrays), got {type(src).__name__}")

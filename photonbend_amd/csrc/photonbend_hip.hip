@@ -48,6 +48,7 @@
 #include "pb_kernels_stitch_video.hpp"
 #include "pb_kernels_track_stitch.hpp"
 #include "pb_kernels_track_px.hpp"
+#include "pb_kernels_px_interp.hpp"
 
 #define PB_DOUBLE_FRAMES_PER_WAVE 1  // frames a double-source wave loops over (the rest of a batch is a grid dimension)
 
@@ -634,6 +635,20 @@ static void pb_pick_px_size(int bpp, F&& f) {
         default: f(PbInt<8>()); break;
     }
 }
+// pb_px_interp_kernel's (C, S): 1 to 4 channels of 1 or 2 bytes without (3, 1), which is the RGB8 tile kernels'
+template <class F>
+static void pb_pick_px_format(int channels, int sample_bytes, F&& f) {
+    static_assert(PB_PXI_BILINEAR == PB_INTERP_BILINEAR && PB_PXI_CATMULL_ROM == PB_INTERP_CATMULL_ROM, "the kernel's FILTER is the header's constant");
+    switch (channels * 4 + sample_bytes) {
+        case 1 * 4 + 1: f(PbInt<1>(), PbInt<1>()); break;
+        case 2 * 4 + 1: f(PbInt<2>(), PbInt<1>()); break;
+        case 4 * 4 + 1: f(PbInt<4>(), PbInt<1>()); break;
+        case 1 * 4 + 2: f(PbInt<1>(), PbInt<2>()); break;
+        case 2 * 4 + 2: f(PbInt<2>(), PbInt<2>()); break;
+        case 3 * 4 + 2: f(PbInt<3>(), PbInt<2>()); break;
+        default: f(PbInt<4>(), PbInt<2>()); break;
+    }
+}
 // pb_video_hot_kernel's SUB (PB_PLANAR_444 / _422 / _420; pb_video_fmt_check has refused everything else)
 template <class F>
 static void pb_pick_subsampling(int sub, F&& f) {
@@ -1025,6 +1040,11 @@ struct PbRoute {
         SS_GENERIC,          // supersampled: frame by frame the route of n = 1 into a workspace, then pb_box_reduce_kernel
         PX,                  // nearest, pixels of bpp != 3 bytes (pb_remap_px): pb_px_hot_kernel
         PX_NONE,             // ... on a plan that kernel does not serve: nothing is launched (PB_ERR_UNSUPPORTED)
+        PX_INTERP,           // bilinear / catmull-rom, pixels of (channels, sample_bytes) != (3, 1) (pb_remap_interp_px): pb_px_interp_kernel
+        PX_INTERP_NEAREST_NONE,  // ... on a plan the nearest call refuses too - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
+        PX_INTERP_FLOAT64,   // ... on a plan prepared for the bilinear mode whose coordinate tables cannot exist (a source of one or two pixels, of 2^18 px a side
+                             // or more, a GiB of coordinates): the definition per pixel, pb_track_px_interp_kernel without a rotation per frame
+        PX_INTERP_NONE,      // ... on a plan never prepared for the bilinear mode (a cube source never is): nothing is launched
         VIDEO,               // nearest, video frames: planar 4:4:4 / 4:2:2 / 4:2:0 (pb_remap_planar) and, as PAIRS, 4:2:0 semi-planar
                              // (pb_remap_nv12): pb_video_hot_kernel
         VIDEO_NONE,          // ... on a plan those kernels do not serve - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
@@ -1036,12 +1056,14 @@ struct PbRoute {
     } kind;
     bool windows;                    // BIL_DOUBLE / bilinear INTERP_TILES: LEAN tiles gather from LDS windows
     int filter = PB_INTERP_NEAREST;  // the INTERP_* routes: PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM
-    int bpp = 3;                     // PX: bytes per pixel
+    int bpp = 3;                     // PX, PX_INTERP: bytes per pixel
     PbVideoFmt video = {};           // VIDEO*: the frames' format
+    int sample_bytes = 1;            // PX_INTERP: bytes per sample (bpp / sample_bytes channels)
 };
 static bool pb_aligned16(const void* src, unsigned long long stride) { return ((((uintptr_t)src) | stride) & 15u) == 0; }
-// video: the format of a video call's frames, null everywhere else
-static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned flags, bool aligned, int bpp = 3, const PbVideoFmt* video = nullptr) {
+// video: the format of a video call's frames, null everywhere else; sample_bytes: of a pixel of bpp != 3 bytes that an interpolating call looks into
+static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned flags, bool aligned, int bpp = 3, const PbVideoFmt* video = nullptr,
+                        int sample_bytes = 1) {
     const PbParams& P = pl->P;
     if (bpp != 3 || video) {
         // the tile kernel of the nearest plan's launch-order table, or nothing: no window, so no alignment beyond the pixel's own
@@ -1061,6 +1083,13 @@ static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned fl
             return {!served ? PbRoute::VIDEO_BIL_NEAREST_NONE : tabs ? PbRoute::VIDEO_BIL : PbRoute::VIDEO_BIL_NONE, false, PB_INTERP_BILINEAR, 3, *video};
         }
         if (video) return {px ? PbRoute::VIDEO : PbRoute::VIDEO_NONE, false, PB_INTERP_NEAREST, 3, *video};
+        if (interpolation != PB_INTERP_NEAREST) {
+            // the video frames' rule: the nearest call's plans, and of those the ones with the bilinear mode's tables.  A plan that was
+            // prepared for the mode (its tile list exists) and holds no coordinate tables cannot have them (pb_build_bilinear_list): float64
+            const bool prepared = pl->bil.tiles && !pb_is_cube(P.src.kind), tabs = prepared && pl->bil.lt.entries && pl->bil.xy && pl->bil.fix_xy;
+            return {!served ? PbRoute::PX_INTERP_NEAREST_NONE : tabs ? PbRoute::PX_INTERP : (prepared && !pl->bil.xy) ? PbRoute::PX_INTERP_FLOAT64 : PbRoute::PX_INTERP_NONE,
+                    false, interpolation, bpp, {}, sample_bytes};
+        }
         return {px ? PbRoute::PX : PbRoute::PX_NONE, false, PB_INTERP_NEAREST, bpp};
     }
     if (n > 1) {
@@ -1103,6 +1132,9 @@ static void pb_each_launch(const uint8_t* src, uint8_t* dst, int n_frames, unsig
     for (int f0 = 0; f0 < n_frames; f0 += per_launch)
         launch(src + (unsigned long long)f0 * ss, dst + (unsigned long long)f0 * ds, n_frames - f0 < per_launch ? n_frames - f0 : per_launch);
 }
+// the rotation tracks' launch loop (defined with them, below): PX_INTERP_FLOAT64 launches through it
+extern "C++" template <class LAUNCH>
+static int pb_track_launch(int n_frames, const double* rot3x3_dev, int n_rot_per_frame, const void* src, void* dst, size_t src_stride, size_t dst_stride, LAUNCH launch);
 // real workgroups per frame of a bilinear tile launch
 static unsigned pb_bil_groups(const pb_plan* pl) { return pl->bil.lt.groups * (4u / (unsigned)pl->bil.waves); }
 
@@ -1190,6 +1222,45 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
         case PbRoute::PX_NONE:
             return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_px takes prepared plans of a single source in a tile mode (not deferred, not PB_MODE_FAITHFUL, not "
                                                "double-fisheye, sources below 32768 px a side): use pb_index_map_i32 + pb_gather_px");
+        case PbRoute::PX_INTERP: {
+            // launched like VIDEO_BIL: the bilinear mode's launch-order table read with four waves per workgroup; static LDS (the regrouping planes)
+            const unsigned gpf = pl->bil.lt.groups;
+            pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
+                pb_pick_kind(P, [&](auto K) {
+                    pb_pick<PB_PXI_BILINEAR, PB_PXI_CATMULL_ROM>(r.filter == PB_INTERP_BILINEAR, [&](auto F) {
+                        pb_pick_px_format(r.bpp / r.sample_bytes, r.sample_bytes, [&](auto C, auto S) {
+                            hipLaunchKernelGGL((pb_px_interp_kernel<K.value, F.value, C.value, S.value>), dim3(gpf * (unsigned)nf), dim3(64 * PB_PXI_WAVES), 0, st,
+                                               pb_hot_of_host(P), pl->bil.lt.entries, sf, df, gpf, ss, ds, pl->bil.xy, pl->cert.fix_px, pl->bil.fix_xy);
+                        });
+                    });
+                });
+            });
+            break;
+        }
+        case PbRoute::PX_INTERP_NEAREST_NONE:
+            return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_interp_px takes prepared plans of a single source in a tile mode (not deferred, not PB_MODE_FAITHFUL, not "
+                                               "double-fisheye, sources below 32768 px a side): use pb_sample_map_bilinear_px / pb_sample_map_catmull_rom_px");
+        case PbRoute::PX_INTERP_NONE:
+            if (pb_is_cube(P.src.kind))
+                return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_interp_px takes camera and panorama sources (a cube source has no interpolating tile kernel): use "
+                                                   "pb_sample_map_bilinear_px / pb_sample_map_catmull_rom_px");
+            return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_interp_px needs the bilinear mode's tile and coordinate tables: call pb_plan_prepare(plan, PB_PLAN_BILINEAR) first");
+        case PbRoute::PX_INTERP_FLOAT64: {
+            // the float64 chain per pixel: pb_remap_track_px's interpolating launch with no rotation per frame (no table is read), frames
+            // chunked over the grid's y by the rotation tracks' launch loop
+            const int channels = r.bpp / r.sample_bytes;
+            return pb_track_launch(n_frames, nullptr, 0, src, dst, ss, ds, [&](const double* rot, const uint8_t* sf, uint8_t* df, int nf, unsigned chunks, int fpc) {
+                const auto launch = [&](auto K, auto* sample) {  // (the sample type: uint8_t or uint16_t)
+                    using SAMPLE = std::remove_pointer_t<decltype(sample)>;
+                    pb_pick_filter(r.filter, [&](auto F) {
+                        hipLaunchKernelGGL((pb_track_px_interp_kernel<K.value, decltype(F), SAMPLE>), dim3(pb_blocks(npx), chunks), dim3(PB_BLOCK), 0, st, P, rot, 0, fpc, sf, df, nf,
+                                           ss, ds, channels);
+                    });
+                };
+                if (r.sample_bytes == 1) pb_pick_kind(P, [&](auto K) { launch(K, (uint8_t*)nullptr); });
+                else pb_pick_kind(P, [&](auto K) { launch(K, (uint16_t*)nullptr); });
+            });
+        }
         case PbRoute::VIDEO: {
             // launched like PX: every plane of a tile by the tile's wave
             const unsigned gpf = pl->nearest.lt.groups;
@@ -2516,6 +2587,51 @@ int pb_remap_track_px_supported(const pb_plan* plan, int channels, int sample_by
     if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
     if (!pb_track_px_format_ok(channels, sample_bytes)) return pb_fail(PB_ERR_INVALID, pb_track_px_format_msg);
     return (plan->P.src.kind == PB_KIND_DOUBLE && sample_bytes != 1) ? 0 : 1;
+}
+
+// The interpolating modes for frames whose pixel is not uint8 RGB: pb_remap_px's frame checks with the pixel size, the
+// interpolation's, the format's, then the route - pb_px_interp_kernel on the bilinear mode's tables, or nothing.  channels 3 of one byte
+// is pb_remap_bilinear_u8 / pb_remap_catmull_rom_u8 itself, on every plan those take.
+static int pb_interp_px_check(int interpolation) {
+    if (interpolation == PB_INTERP_NEAREST)
+        return pb_fail(PB_ERR_INVALID, "pb_remap_interp_px samples with PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM: PB_INTERP_NEAREST is pb_remap_px");
+    if (interpolation != PB_INTERP_BILINEAR && interpolation != PB_INTERP_CATMULL_ROM)
+        return pb_fail(PB_ERR_INVALID, "interpolation must be PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM");
+    return PB_OK;
+}
+int pb_remap_interp_px(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, size_t src_frame_stride, size_t dst_frame_stride, int channels,
+                       int sample_bytes, int interpolation, void* stream) {
+    const bool fmt = pb_track_px_format_ok(channels, sample_bytes);
+    const int B = fmt ? channels * sample_bytes : 1;  // (a format outside the sets is refused below, in its place: the weakest alignment until then)
+    const int rc = pb_check_frames(plan, src_dev, dst_dev, n_frames, 1, src_frame_stride, dst_frame_stride, false, B);
+    if (rc != PB_OK) return rc;
+    if (int ri = pb_interp_px_check(interpolation)) return ri;
+    if (!fmt) return pb_fail(PB_ERR_INVALID, pb_track_px_format_msg);
+    if (n_frames == 0) return PB_OK;
+    const uint8_t* s = static_cast<const uint8_t*>(src_dev);
+    uint8_t* d = static_cast<uint8_t*>(dst_dev);
+    if (B == 3)
+        return interpolation == PB_INTERP_BILINEAR ? pb_remap_bilinear_u8(plan, s, d, n_frames, src_frame_stride, dst_frame_stride, stream)
+                                                   : pb_remap_catmull_rom_u8(plan, s, d, n_frames, src_frame_stride, dst_frame_stride, stream);
+    const PbRoute r = pb_route(plan, interpolation, 1, 0, false, B, nullptr, sample_bytes);
+    if ((r.kind == PbRoute::PX_INTERP || r.kind == PbRoute::PX_INTERP_FLOAT64) && !pb_px_frames_fit(plan, B))
+        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_interp_px takes frames below 2^31 bytes: use pb_sample_map_bilinear_px / pb_sample_map_catmull_rom_px");
+    return pb_launch(plan, r, s, d, n_frames, src_frame_stride, dst_frame_stride, (hipStream_t)stream);
+}
+int pb_remap_interp_px_supported(const pb_plan* plan, int channels, int sample_bytes, int interpolation) {
+    if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
+    if (int ri = pb_interp_px_check(interpolation)) return ri;
+    if (!pb_track_px_format_ok(channels, sample_bytes)) return pb_fail(PB_ERR_INVALID, pb_track_px_format_msg);
+    const int B = channels * sample_bytes;
+    if (B == 3) return 1;
+    const PbRoute::Kind k = pb_route(plan, interpolation, 1, 0, false, B, nullptr, sample_bytes).kind;
+    return (k == PbRoute::PX_INTERP || k == PbRoute::PX_INTERP_FLOAT64) && pb_px_frames_fit(plan, B);
+}
+int pb_plan_px_interp_route(const pb_plan* plan, int channels, int sample_bytes, int interpolation) {
+    const int ok = pb_remap_interp_px_supported(plan, channels, sample_bytes, interpolation);
+    if (ok != 1) return ok;
+    if (channels * sample_bytes == 3) return 3;
+    return pb_route(plan, interpolation, 1, 0, false, channels * sample_bytes, nullptr, sample_bytes).kind == PbRoute::PX_INTERP ? 1 : 2;
 }
 
 // A rotation track of video frames (bilinear: 3.19): the plain video calls' argument checks, then pb_remap_track_u8's
