@@ -522,6 +522,43 @@ pb_remap_interp_px_supported(const pb_plan* plan, int channels, int sample_bytes
 int
 pb_plan_px_interp_route(const pb_plan* plan, int channels, int sample_bytes, int interpolation);
 
+/* BILINEAR AND CATMULL-ROM SAMPLING OF FLOAT16 AND FLOAT32 FRAMES (ABI 5, additive): HDR panoramas, depth and disparity
+ * planes, flow fields, float mattes - frames of `channels` IEEE samples a pixel, channels in {1, 2, 3, 4}, sample_bytes 2 (binary16) or 4
+ * (binary32), native byte order, tightly packed rows - in ONE launch of the tile kernel pb_pxf_interp_kernel whatever n_frames, without a
+ * coordinate map.  The pixel is B = channels * sample_bytes bytes: {2, 4, 6, 8} or {4, 8, 12, 16}.
+ * The definition (tests/pxf_ref.py) is the integer modes' up to the sum: per channel V = top + ty (bot - top) with top = a + tx (b - a)
+ * (bilinear), or Keys' cubic with a = -0.5 over the 4 x 4 footprint, row sums first (Catmull-Rom); rows clamped, a panorama's columns
+ * wrapped, a camera's clamped.  V is NOT rounded to an integer and NOT clipped - the cubic's overshoot and negative lobes are kept - and is
+ * narrowed once to the sample type, round to nearest even (a half result beyond 65504 is infinity, as IEEE says).  A pixel that is not
+ * live is +0.0 in every channel (all bytes zero).  A NaN or an infinity among a pixel's taps (its clamped and wrapped 2 x 2 or 4 x 4
+ * footprint) leaves that pixel's value unspecified; it affects no other pixel and never makes a dead pixel anything but +0.0.
+ * Precision: the tile coordinates are certified to 1/1024 px per axis and all arithmetic is float32.  With a frame's samples in [L, U],
+ * D = U - L, M = max(|L|, |U|), u = 2^-24 for float32 and 2^-11 for float16 frames, every sample is within D / 512 + M 2^-20 + M u
+ * (bilinear) or 15 D / 4096 + M 2^-18 + 1.5625 M u (Catmull-Rom) of the definition's exact value.
+ * The checks, in pb_remap_interp_px's order:
+ *   pb_remap_px's frame checks and messages with bytes_per_px = channels * sample_bytes, 12 and 16 being pixel sizes for this call only
+ *   (frame pointers and strides multiples of min(4, B & -B) bytes - 4 for 12 and 16; the weakest alignment while the format is not known
+ *   to be valid);
+ *   PB_ERR_INVALID        an interpolation other than PB_INTERP_BILINEAR / PB_INTERP_CATMULL_ROM (PB_INTERP_NEAREST: the message names
+ *                         pb_remap_px, which moves float pixels of up to 8 bytes as bytes);
+ *   PB_ERR_INVALID        channels or sample_bytes outside their sets;
+ *   n_frames == 0         PB_OK, no launch;
+ *   PB_ERR_UNSUPPORTED    nothing is written and nothing launched - the plans pb_remap_px refuses (deferred plans, PB_MODE_FAITHFUL,
+ *                         double-fisheye sources, plans without device state, sources of 32768 px a side or more); frames of 2^31 bytes
+ *                         or more; plans never prepared for the bilinear mode (call pb_plan_prepare(plan, PB_PLAN_BILINEAR)); cube and
+ *                         equi-angular-cube sources; and plans that WERE prepared for it whose coordinate tables cannot exist (a source
+ *                         of one or two pixels, of 2^18 px a side or more, a GiB of coordinates): pb_remap_interp_px serves those from
+ *                         the float64 chain, and no such per-pixel kernel exists for float samples.
+ * Asynchronous on `stream`; never allocates or synchronises, so it can be captured into a graph.
+ * pb_remap_interp_pxf_supported: 1 when pb_remap_interp_pxf takes `plan` with this format and interpolation, 0 when it would return
+ * PB_ERR_UNSUPPORTED, negative on bad arguments.
+ * PB_INTERP_PXF is defined (empty) by every header that declares the two: a caller that must also build against an earlier header of
+ * ABI 5 can test for it. */
+#define PB_INTERP_PXF
+int PB_INTERP_PXF pb_remap_interp_pxf(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, size_t src_frame_stride,
+                                      size_t dst_frame_stride, int channels, int sample_bytes, int interpolation, void* stream);
+int PB_INTERP_PXF pb_remap_interp_pxf_supported(const pb_plan* plan, int channels, int sample_bytes, int interpolation);
+
 /* ROTATION TRACKS FOR 4:2:0 SEMI-PLANAR VIDEO FRAMES (ABI 5, additive): NV12 / P010 / P016 frames, every frame with rotations
  * of its own, both planes of all frames in as many launches as pb_remap_track_u8 makes.  Frame f receives exactly pb_remap_nv12's
  * definition above with idx the index map of the chain "this plan's own n_rot rotations followed by the n_rot_per_frame matrices of table

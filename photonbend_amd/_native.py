@@ -136,6 +136,8 @@ SIGNATURES = {
     "pb_remap_track_px_supported": (C.c_int, [_VP, C.c_int, C.c_int]),
     "pb_remap_interp_px": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, _VP]),
     "pb_remap_interp_px_supported": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int]),
+    "pb_remap_interp_pxf": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, _VP]),
+    "pb_remap_interp_pxf_supported": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int]),
     "pb_plan_px_interp_route": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int]),
     "pb_remap_track_nv12": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP]),
     "pb_remap_track_planar": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, _VP]),
@@ -1120,6 +1122,74 @@ class Plan:
         with _on(s):
             self.ensure_bilinear()  # (as ``remap`` does for uint8 RGB: the tables are built when an interpolating mode is first used)
             self.launch_px_interp(s.data_ptr(), o.data_ptr(), n, channels, dt.itemsize, interpolation)
+        return o
+
+    def launch_float(self, src_ptr: int, dst_ptr: int, n_frames: int, channels: int, sample_bytes: int, interpolation: str, stream: int | None = None,
+                     src_stride: int = 0, dst_stride: int = 0) -> None:
+        """The raw interpolating call for frames of ``channels`` float samples a pixel (pb_remap_interp_pxf): ``sample_bytes``
+        2 is float16, 4 float32; ``interpolation`` is "bilinear" or "catmull-rom" ("nearest" moves bytes: ``launch(bytes_per_px=...)``).
+        The plan needs the bilinear mode's tables (``Plan(..., bilinear=True)`` or ``ensure_bilinear()``); a plan ``float_supported``
+        refuses is a PbError."""
+        check_interpolation(interpolation)
+        if interpolation == "nearest":
+            raise ValueError("launch_float samples with 'bilinear' or 'catmull-rom': nearest sampling is launch(bytes_per_px=...)")
+        self._gated(load().pb_remap_interp_pxf, self._h, src_ptr, dst_ptr, int(n_frames), int(src_stride), int(dst_stride), int(channels), int(sample_bytes),
+                    TRACK_INTERP_IDS[interpolation], current_stream() if stream is None else stream)
+
+    def float_supported(self, channels: int, sample_bytes: int, interpolation: str) -> bool:
+        """Whether ``launch_float`` takes this plan with this format (pb_remap_interp_pxf_supported): a prepared plan of a camera or
+        panorama source in a tile mode with the bilinear mode's coordinate tables.  channels outside 1..4 or sample_bytes outside (2, 4)
+        is a PbError.  Needs no GPU."""
+        check_interpolation(interpolation)
+        if interpolation == "nearest":
+            raise ValueError("float_supported asks about 'bilinear' or 'catmull-rom': nearest sampling is px_supported")
+        r = load().pb_remap_interp_pxf_supported(self._h, int(channels), int(sample_bytes), TRACK_INTERP_IDS[interpolation])
+        if r < 0:
+            check(r)
+        return r == 1
+
+    def remap_float(self, src, out=None, *, interpolation: str = "bilinear"):
+        """Bilinear or Catmull-Rom sampling of float16 / float32 frames - HDR panoramas, depth, flow, mattes - in ONE launch of the
+        interpolating tile kernel (pb_remap_interp_pxf).  src: a device array (CUDA tensor or DeviceArray) (h, w), (h, w, C),
+        (N, h, w) or (N, h, w, C) of float16 or float32, C <= 4 -> the same kind, dtype and shape at the destination size.  The value is
+        the definition's sum narrowed once to the dtype: not rounded to an integer, not clipped (the cubic's overshoot is kept); +0.0 where
+        the pixel is not live.  The bilinear mode's tables are built on first use; a plan ``float_supported`` then refuses is a PbError
+        (no fallback).  "nearest" is a ValueError: ``remap_px`` moves float pixels as bytes."""
+        check_interpolation(interpolation)
+        if interpolation == "nearest":
+            raise ValueError("remap_float samples with 'bilinear' or 'catmull-rom': nearest sampling of float frames is remap_px")
+        sh, dh = (self.src.height, self.src.width), (self.dst.height, self.dst.width)
+        if not is_device_array(src):
+            raise PbError(f"source frames must be device arrays (CUDA tensors or DeviceArrays), got {type(src).__name__}")
+        tens = is_tensor(src)
+        shp = tuple(int(v) for v in src.shape)
+        name = str(src.dtype).replace("torch.", "") if tens else np.dtype(src.dtype).name  # (bfloat16 has no NumPy dtype to convert to)
+        if name not in ("float16", "float32"):
+            raise PbError(f"remap_float takes float16 or float32 frames, got {shp} {name}")
+        dt = np.dtype(name)
+        lead = 2 if shp[:2] == sh else 3  # (h, w[, C]), else (N, h, w[, C])
+        if len(shp) not in (lead, lead + 1) or shp[lead - 2:lead] != sh:
+            raise PbError(f"source frames must be ({sh[0]}, {sh[1]}), ({sh[0]}, {sh[1]}, C), (N, {sh[0]}, {sh[1]}) or (N, {sh[0]}, {sh[1]}, C), got {shp} {dt}")
+        tail = shp[lead:]
+        channels = tail[0] if tail else 1
+        if not 1 <= channels <= 4:
+            raise PbError(f"remap_float takes frames of 1 to 4 channels, got {shp} {dt}")
+        n = shp[0] if lead == 3 else 1
+        oshape = ((n,) if lead == 3 else ()) + dh + tail
+        if out is not None:
+            odt = (str(out.dtype).replace("torch.", "") if is_tensor(out) else np.dtype(out.dtype).name) if is_device_array(out) else None
+            if odt != name or tuple(out.shape) != oshape or is_tensor(out) != tens or (tens and not out.is_contiguous()):
+                raise PbError(f"out must be a contiguous device array {oshape} {dt} of the source's kind")
+            if tens and (not out.is_cuda or out.device != src.device):
+                raise PbError(f"out must live on the source's device ({src.device}), got {out.device}")
+        require_gpu()
+        s = src.contiguous() if tens else src
+        o = empty(oshape, dt, like=s) if out is None else out
+        if n == 0:
+            return o
+        with _on(s):
+            self.ensure_bilinear()  # (as ``remap_px`` does: the tables are built when an interpolating mode is first used)
+            self.launch_float(s.data_ptr(), o.data_ptr(), n, channels, dt.itemsize, interpolation)
         return o
 
     def remap_px(self, src, out=None, *, interpolation: str = "nearest"):

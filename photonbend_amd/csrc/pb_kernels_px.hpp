@@ -19,7 +19,9 @@
 // 4, 6, 8.  A pixel is loaded with EXACTLY its own bytes - u8, u16, dword, dword + u16, dwordx2 - so no load can touch a byte outside the
 // frame, the very last pixel included (the RGB8 kernels read four bytes for a three-byte pixel and special-case it; nothing of the kind
 // is needed here).  Four output pixels leave in one 4-, 8-, 16-, 24- or 32-byte store where their address is 4-byte aligned, else
-// sample by sample (a partial tile's edge, an odd row start of 1-, 2- and 6-byte pixels).
+// sample by sample (a partial tile's edge, an odd row start of 1-, 2- and 6-byte pixels).  pb_px_load, pb_px_store1 and pb_px_store4 also
+// move pixels of 12 and 16 bytes - three and four float32 channels, A = 4: three and four dwords, 48- and 64-byte stores as three and four
+// 16-byte ones - for pb_pxf_interp_kernel (pb_kernels_pxf_interp.hpp); pb_px_hot_kernel has no instantiation for them.
 //
 // Limits.  Source byte offsets are 32-bit: pb_remap_px refuses frames of B * h * w >= 2^31 bytes (source or destination) with
 // PB_ERR_UNSUPPORTED before any launch.  Sources of 32768 px a side or more are refused like the window routes (generic tiles pack row
@@ -40,7 +42,8 @@ struct PbPx {
 // exactly BPP bytes at byte offset `off` of the frame (a multiple of BPP; the frame is aligned to min(4, BPP & -BPP))
 template <int BPP>
 __device__ __forceinline__ PbPx<BPP> pb_px_load(const uint8_t* __restrict__ s, unsigned off) {
-    static_assert(BPP == 1 || BPP == 2 || BPP == 4 || BPP == 6 || BPP == 8, "pixel sizes of pb_remap_px");
+    static_assert(BPP == 1 || BPP == 2 || BPP == 4 || BPP == 6 || BPP == 8 || BPP == 12 || BPP == 16,
+                  "pixel sizes of pb_remap_px, and three and four float32 channels (pb_remap_interp_pxf)");
     PbPx<BPP> v;
     const uint8_t* p = s + off;
     if constexpr (BPP == 1) {
@@ -52,10 +55,18 @@ __device__ __forceinline__ PbPx<BPP> pb_px_load(const uint8_t* __restrict__ s, u
     } else if constexpr (BPP == 6) {
         __builtin_memcpy(&v.w[0], p, 4);  // (2-byte aligned: an unaligned dword, like the RGB8 kernels' gathers)
         v.w[1] = *reinterpret_cast<const uint16_t*>(p + 4);
-    } else {
+    } else if constexpr (BPP == 8) {
         pb_px_u32x2 t = *reinterpret_cast<const pb_px_u32x2*>(p);
         v.w[0] = t.x;
         v.w[1] = t.y;
+    } else if constexpr (BPP == 12) {
+        __builtin_memcpy(&v.w[0], __builtin_assume_aligned(p, 4), 12);  // (three dwords, 4-byte aligned: a vector of three would be read as sixteen bytes)
+    } else {
+        pb_px_u32x4 t = *reinterpret_cast<const pb_px_u32x4*>(p);
+        v.w[0] = t.x;
+        v.w[1] = t.y;
+        v.w[2] = t.z;
+        v.w[3] = t.w;
     }
     return v;
 }
@@ -85,10 +96,10 @@ __device__ __forceinline__ void pb_px_store1(uint8_t* p, const PbPx<BPP>& v) {
         q[0] = (uint16_t)v.w[0];
         q[1] = (uint16_t)(v.w[0] >> 16);
         q[2] = (uint16_t)v.w[1];
-    } else {
+    } else {  // 8, 12, 16: dword by dword
         unsigned* q = reinterpret_cast<unsigned*>(p);
-        q[0] = v.w[0];
-        q[1] = v.w[1];
+#pragma unroll
+        for (int i = 0; i < PbPx<BPP>::NW; ++i) q[i] = v.w[i];
     }
 }
 template <bool NT, class V>
@@ -114,11 +125,24 @@ __device__ __forceinline__ void pb_px_store4(uint8_t* p, const PbPx<BPP> a[4]) {
         const pb_px_u32x2 q = {a[2].w[1] | (a[3].w[0] << 16), (a[3].w[0] >> 16) | (a[3].w[1] << 16)};
         pb_px_store_vec<NT>(o, p);
         pb_px_store_vec<NT>(q, p + 16);
-    } else {
+    } else if constexpr (BPP == 8) {
         const pb_px_u32x4 o = {a[0].w[0], a[0].w[1], a[1].w[0], a[1].w[1]};
         const pb_px_u32x4 q = {a[2].w[0], a[2].w[1], a[3].w[0], a[3].w[1]};
         pb_px_store_vec<NT>(o, p);
         pb_px_store_vec<NT>(q, p + 16);
+    } else if constexpr (BPP == 12) {  // 48 bytes
+        const pb_px_u32x4 o = {a[0].w[0], a[0].w[1], a[0].w[2], a[1].w[0]};
+        const pb_px_u32x4 q = {a[1].w[1], a[1].w[2], a[2].w[0], a[2].w[1]};
+        const pb_px_u32x4 r = {a[2].w[2], a[3].w[0], a[3].w[1], a[3].w[2]};
+        pb_px_store_vec<NT>(o, p);
+        pb_px_store_vec<NT>(q, p + 16);
+        pb_px_store_vec<NT>(r, p + 32);
+    } else {  // 64 bytes
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const pb_px_u32x4 o = {a[k].w[0], a[k].w[1], a[k].w[2], a[k].w[3]};
+            pb_px_store_vec<NT>(o, p + 16 * k);
+        }
     }
 }
 // the lane's four pixels of output row y, columns x .. x + 3: clipped at the image's edge, one wide store where the address allows

@@ -49,6 +49,7 @@
 #include "pb_kernels_track_stitch.hpp"
 #include "pb_kernels_track_px.hpp"
 #include "pb_kernels_px_interp.hpp"
+#include "pb_kernels_pxf_interp.hpp"
 
 #define PB_DOUBLE_FRAMES_PER_WAVE 1  // frames a double-source wave loops over (the rest of a batch is a grid dimension)
 
@@ -649,6 +650,18 @@ static void pb_pick_px_format(int channels, int sample_bytes, F&& f) {
         default: f(PbInt<4>(), PbInt<2>()); break;
     }
 }
+// pb_pxf_interp_kernel's (C, S): 1 to 4 channels of binary16 or binary32 samples
+template <class F>
+static void pb_pick_pxf_format(int channels, int sample_bytes, F&& f) {
+    pb_pick<2, 4>(sample_bytes == 2, [&](auto S) {
+        switch (channels) {
+            case 1: f(PbInt<1>(), S); break;
+            case 2: f(PbInt<2>(), S); break;
+            case 3: f(PbInt<3>(), S); break;
+            default: f(PbInt<4>(), S); break;
+        }
+    });
+}
 // pb_video_hot_kernel's SUB (PB_PLANAR_444 / _422 / _420; pb_video_fmt_check has refused everything else)
 template <class F>
 static void pb_pick_subsampling(int sub, F&& f) {
@@ -980,14 +993,15 @@ static int pb_check_device(const pb_plan* plan) {
 // launch - callers return), the plan's device, the frame strides (0: tightly packed; the defaults are filled in here and nowhere
 // else).  n: the supersample factor - an output frame is H/n x W/n of the plan's destination.  tables: src / dst are pb_remap_u8v's
 // pointer tables, which may be null when there are no frames.  bpp: bytes per pixel (pb_remap_px; 3 everywhere else) - one of
-// PB_PX_SIZES, frames and strides aligned to pb_px_align(bpp).
+// PB_PX_SIZES, frames and strides aligned to pb_px_align(bpp).  wide: 12 and 16 are pixel sizes too (three and four float32 channels:
+// pb_remap_interp_pxf alone).
 static bool pb_px_size_ok(int bpp) { return bpp == 1 || bpp == 2 || bpp == 3 || bpp == 4 || bpp == 6 || bpp == 8; }
 static unsigned pb_px_align(int bpp) { return (unsigned)std::min(4, bpp & -bpp); }
 static int pb_check_frames(const pb_plan* plan, const void* src, const void* dst, int n_frames, int n, size_t& src_stride, size_t& dst_stride,
-                           bool tables = false, int bpp = 3) {
+                           bool tables = false, int bpp = 3, bool wide = false) {
     if (!plan || ((!src || !dst) && (n_frames > 0 || !tables))) return pb_fail(PB_ERR_INVALID, "null argument");
     if (n_frames < 0) return pb_fail(PB_ERR_INVALID, "negative frame count");
-    if (!pb_px_size_ok(bpp)) return pb_fail(PB_ERR_INVALID, "bytes_per_px outside {1, 2, 3, 4, 6, 8}");
+    if (!pb_px_size_ok(bpp) && !(wide && (bpp == 12 || bpp == 16))) return pb_fail(PB_ERR_INVALID, "bytes_per_px outside {1, 2, 3, 4, 6, 8}");
     if (n_frames == 0) return PB_OK;
     const int rc = pb_check_device(plan);
     if (rc != PB_OK) return rc;
@@ -1045,6 +1059,11 @@ struct PbRoute {
         PX_INTERP_FLOAT64,   // ... on a plan prepared for the bilinear mode whose coordinate tables cannot exist (a source of one or two pixels, of 2^18 px a side
                              // or more, a GiB of coordinates): the definition per pixel, pb_track_px_interp_kernel without a rotation per frame
         PX_INTERP_NONE,      // ... on a plan never prepared for the bilinear mode (a cube source never is): nothing is launched
+        PXF_INTERP,          // bilinear / catmull-rom, pixels of 1 to 4 float16 or float32 samples (pb_remap_interp_pxf): pb_pxf_interp_kernel
+        PXF_INTERP_NEAREST_NONE,  // ... on a plan the nearest call refuses too - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
+        PXF_INTERP_NO_TABLES,     // ... on a plan prepared for the bilinear mode whose coordinate tables cannot exist (PX_INTERP_FLOAT64's plans): there is
+                                  // no float64 per-pixel kernel for float samples, so nothing is launched
+        PXF_INTERP_NONE,     // ... on a plan never prepared for the bilinear mode (a cube source never is): nothing is launched
         VIDEO,               // nearest, video frames: planar 4:4:4 / 4:2:2 / 4:2:0 (pb_remap_planar) and, as PAIRS, 4:2:0 semi-planar
                              // (pb_remap_nv12): pb_video_hot_kernel
         VIDEO_NONE,          // ... on a plan those kernels do not serve - the plans of PX_NONE: nothing is launched (PB_ERR_UNSUPPORTED)
@@ -1058,14 +1077,15 @@ struct PbRoute {
     int filter = PB_INTERP_NEAREST;  // the INTERP_* routes: PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM
     int bpp = 3;                     // PX, PX_INTERP: bytes per pixel
     PbVideoFmt video = {};           // VIDEO*: the frames' format
-    int sample_bytes = 1;            // PX_INTERP: bytes per sample (bpp / sample_bytes channels)
+    int sample_bytes = 1;            // PX_INTERP, PXF_INTERP: bytes per sample (bpp / sample_bytes channels)
 };
 static bool pb_aligned16(const void* src, unsigned long long stride) { return ((((uintptr_t)src) | stride) & 15u) == 0; }
-// video: the format of a video call's frames, null everywhere else; sample_bytes: of a pixel of bpp != 3 bytes that an interpolating call looks into
+// video: the format of a video call's frames, null everywhere else; sample_bytes: of a pixel of bpp != 3 bytes that an interpolating call looks into;
+// float_samples: those samples are IEEE binary16 / binary32 (pb_remap_interp_pxf; a pixel of three bytes cannot be one)
 static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned flags, bool aligned, int bpp = 3, const PbVideoFmt* video = nullptr,
-                        int sample_bytes = 1) {
+                        int sample_bytes = 1, bool float_samples = false) {
     const PbParams& P = pl->P;
-    if (bpp != 3 || video) {
+    if (bpp != 3 || video || float_samples) {
         // the tile kernel of the nearest plan's launch-order table, or nothing: no window, so no alignment beyond the pixel's own
         // (pb_check_frames); fast_ready says single source, prepared, device state; generic tiles pack row and column in 16 bits each
         const bool served = n == 1 && pb_use_fast(pl) && pl->nearest.lt.entries && pl->nearest.P_dev && P.src.width < 32768 && P.src.height < 32768;
@@ -1087,6 +1107,9 @@ static PbRoute pb_route(const pb_plan* pl, int interpolation, int n, unsigned fl
             // the video frames' rule: the nearest call's plans, and of those the ones with the bilinear mode's tables.  A plan that was
             // prepared for the mode (its tile list exists) and holds no coordinate tables cannot have them (pb_build_bilinear_list): float64
             const bool prepared = pl->bil.tiles && !pb_is_cube(P.src.kind), tabs = prepared && pl->bil.lt.entries && pl->bil.xy && pl->bil.fix_xy;
+            if (float_samples)  // the same plans; where the integer samples take the float64 chain, nothing
+                return {!served ? PbRoute::PXF_INTERP_NEAREST_NONE : tabs ? PbRoute::PXF_INTERP : (prepared && !pl->bil.xy) ? PbRoute::PXF_INTERP_NO_TABLES : PbRoute::PXF_INTERP_NONE,
+                        false, interpolation, bpp, {}, sample_bytes};
             return {!served ? PbRoute::PX_INTERP_NEAREST_NONE : tabs ? PbRoute::PX_INTERP : (prepared && !pl->bil.xy) ? PbRoute::PX_INTERP_FLOAT64 : PbRoute::PX_INTERP_NONE,
                     false, interpolation, bpp, {}, sample_bytes};
         }
@@ -1261,6 +1284,31 @@ static int pb_launch(const pb_plan* pl, PbRoute r, const uint8_t* src, uint8_t* 
                 else pb_pick_kind(P, [&](auto K) { launch(K, (uint16_t*)nullptr); });
             });
         }
+        case PbRoute::PXF_INTERP: {
+            // launched like PX_INTERP; static LDS: one regrouping plane per dword of the pixel
+            const unsigned gpf = pl->bil.lt.groups;
+            pb_each_launch(src, dst, n_frames, ss, ds, gpf, [&](const uint8_t* sf, uint8_t* df, int nf) {
+                pb_pick_kind(P, [&](auto K) {
+                    pb_pick<PB_PXI_BILINEAR, PB_PXI_CATMULL_ROM>(r.filter == PB_INTERP_BILINEAR, [&](auto F) {
+                        pb_pick_pxf_format(r.bpp / r.sample_bytes, r.sample_bytes, [&](auto C, auto S) {
+                            hipLaunchKernelGGL((pb_pxf_interp_kernel<K.value, F.value, C.value, S.value>), dim3(gpf * (unsigned)nf), dim3(64 * PB_PXI_WAVES), 0, st,
+                                               pb_hot_of_host(P), pl->bil.lt.entries, sf, df, gpf, ss, ds, pl->bil.xy, pl->cert.fix_px, pl->bil.fix_xy);
+                        });
+                    });
+                });
+            });
+            break;
+        }
+        case PbRoute::PXF_INTERP_NEAREST_NONE:
+            return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_interp_pxf takes prepared plans of a single source in a tile mode (not deferred, not PB_MODE_FAITHFUL, not "
+                                               "double-fisheye, sources below 32768 px a side): float frames have no other device route");
+        case PbRoute::PXF_INTERP_NO_TABLES:
+            return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_interp_pxf needs the bilinear mode's coordinate tables, and the tables cannot exist for this source (one or two "
+                                               "pixels, 2^18 px a side or more, or a GiB of coordinates): float frames have no per-pixel route");
+        case PbRoute::PXF_INTERP_NONE:
+            if (pb_is_cube(P.src.kind))
+                return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_interp_pxf takes camera and panorama sources (a cube source has no interpolating tile kernel)");
+            return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_interp_pxf needs the bilinear mode's tile and coordinate tables: call pb_plan_prepare(plan, PB_PLAN_BILINEAR) first");
         case PbRoute::VIDEO: {
             // launched like PX: every plane of a tile by the tile's wave
             const unsigned gpf = pl->nearest.lt.groups;
@@ -2592,9 +2640,9 @@ int pb_remap_track_px_supported(const pb_plan* plan, int channels, int sample_by
 // The interpolating modes for frames whose pixel is not uint8 RGB: pb_remap_px's frame checks with the pixel size, the
 // interpolation's, the format's, then the route - pb_px_interp_kernel on the bilinear mode's tables, or nothing.  channels 3 of one byte
 // is pb_remap_bilinear_u8 / pb_remap_catmull_rom_u8 itself, on every plan those take.
-static int pb_interp_px_check(int interpolation) {
+static int pb_interp_px_check(int interpolation, const char* call = "pb_remap_interp_px") {
     if (interpolation == PB_INTERP_NEAREST)
-        return pb_fail(PB_ERR_INVALID, "pb_remap_interp_px samples with PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM: PB_INTERP_NEAREST is pb_remap_px");
+        return pb_fail(PB_ERR_INVALID, std::string(call) + " samples with PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM: PB_INTERP_NEAREST is pb_remap_px");
     if (interpolation != PB_INTERP_BILINEAR && interpolation != PB_INTERP_CATMULL_ROM)
         return pb_fail(PB_ERR_INVALID, "interpolation must be PB_INTERP_BILINEAR or PB_INTERP_CATMULL_ROM");
     return PB_OK;
@@ -2626,6 +2674,33 @@ int pb_remap_interp_px_supported(const pb_plan* plan, int channels, int sample_b
     if (B == 3) return 1;
     const PbRoute::Kind k = pb_route(plan, interpolation, 1, 0, false, B, nullptr, sample_bytes).kind;
     return (k == PbRoute::PX_INTERP || k == PbRoute::PX_INTERP_FLOAT64) && pb_px_frames_fit(plan, B);
+}
+
+// The interpolating modes for frames of float16 / float32 samples: pb_remap_interp_px's order - the frame checks with the
+// pixel size (12 and 16 bytes here alone), the interpolation's, the format's, no frames, then the route - pb_pxf_interp_kernel on the
+// bilinear mode's tables, or nothing.
+static bool pb_pxf_format_ok(int channels, int sample_bytes) { return channels >= 1 && channels <= 4 && (sample_bytes == 2 || sample_bytes == 4); }
+static const char* const pb_pxf_format_msg = "channels must be 1, 2, 3 or 4 and sample_bytes 2 (float16) or 4 (float32)";
+int pb_remap_interp_pxf(const pb_plan* plan, const void* src_dev, void* dst_dev, int n_frames, size_t src_frame_stride, size_t dst_frame_stride, int channels,
+                        int sample_bytes, int interpolation, void* stream) {
+    const bool fmt = pb_pxf_format_ok(channels, sample_bytes);
+    const int B = fmt ? channels * sample_bytes : 1;  // (a format outside the sets is refused below, in its place: the weakest alignment until then)
+    const int rc = pb_check_frames(plan, src_dev, dst_dev, n_frames, 1, src_frame_stride, dst_frame_stride, false, B, true);
+    if (rc != PB_OK) return rc;
+    if (int ri = pb_interp_px_check(interpolation, "pb_remap_interp_pxf")) return ri;
+    if (!fmt) return pb_fail(PB_ERR_INVALID, pb_pxf_format_msg);
+    if (n_frames == 0) return PB_OK;
+    const PbRoute r = pb_route(plan, interpolation, 1, 0, false, B, nullptr, sample_bytes, true);
+    if (r.kind == PbRoute::PXF_INTERP && !pb_px_frames_fit(plan, B))
+        return pb_fail(PB_ERR_UNSUPPORTED, "pb_remap_interp_pxf takes frames below 2^31 bytes");
+    return pb_launch(plan, r, static_cast<const uint8_t*>(src_dev), static_cast<uint8_t*>(dst_dev), n_frames, src_frame_stride, dst_frame_stride, (hipStream_t)stream);
+}
+int pb_remap_interp_pxf_supported(const pb_plan* plan, int channels, int sample_bytes, int interpolation) {
+    if (!plan) return pb_fail(PB_ERR_INVALID, "null argument");
+    if (int ri = pb_interp_px_check(interpolation, "pb_remap_interp_pxf")) return ri;
+    if (!pb_pxf_format_ok(channels, sample_bytes)) return pb_fail(PB_ERR_INVALID, pb_pxf_format_msg);
+    const int B = channels * sample_bytes;
+    return pb_route(plan, interpolation, 1, 0, false, B, nullptr, sample_bytes, true).kind == PbRoute::PXF_INTERP && pb_px_frames_fit(plan, B);
 }
 int pb_plan_px_interp_route(const pb_plan* plan, int channels, int sample_bytes, int interpolation) {
     const int ok = pb_remap_interp_px_supported(plan, channels, sample_bytes, interpolation);
